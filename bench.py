@@ -39,6 +39,13 @@ on the host -- with everything the engine's host side derives from the columns i
 `python bench.py --gpus N` without a launcher starts the N ranks itself (child processes, before any GPU call); under
 `python -m torch.distributed.run` it reads RANK / LOCAL_RANK / WORLD_SIZE.
 
+A plain run does only what the headline needs: the set, the warm-up, the timed steps and the line (`value`, `ms_per_step`,
+`config`, `roofline` of the timed steps).  Everything else above -- the self-check of the outputs, the legs (`packed_output`,
+`window_records*`, `six_column` / `grouped`, the pass without cuts, `placement_ab`, `e2e`, `cpu_baseline`; with several GPUs
+the other two forms and the ranks' totals against a single-GPU pass) -- runs with `--full` only.
+`--dump-outputs DIR`: after the timed steps, what the last step left on the device (the arrays of raft_hip_outputs_device,
+float64; a fixed, seeded sample of the larger ones; 64 MiB at most) and its summary as DIR/<name>.npy.
+
 Prints ONE JSON line (rank 0).
 """
 from __future__ import annotations
@@ -133,6 +140,30 @@ def cpu_baseline(args, o, p):
                    note="oracle/_ref/libraft_ref.so not present (clean checkout without the build container's prebuilt "
                         "reference harness): timing the plain-C restatement instead")
     return out, (w, res)
+
+
+DUMP_BYTES = 64 << 20       # --dump-outputs: every file of every rank together
+DUMP_SUMMARY = ("n_reads", "symmetric", "high_cov", "n_records", "n_intervals", "n_bins", "n_repeats", "n_cuts", "n_fragments",
+                "total_coverage", "total_windows", "total_repeat_length", "total_read_length")
+
+
+def dump_outputs(out_dir: str, eng, summary, seed: int, prefix: str = "", share: int = 1):
+    """--dump-outputs: the device-resident outputs of the engine's last pass (raft_hip_outputs_device: coverage, repeats,
+    cut points, fragments, CSR per read) as <out_dir>/<prefix><name>.npy in float64 (exact for these integers), and the
+    pass's summary as <prefix>summary.npy.  An array longer than its share of DUMP_BYTES is written as a sample: the same
+    sorted indices for the same length and seed, so two builds run with the same arguments are compared element for element."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    outs = eng.outputs_device()
+    cap = DUMP_BYTES // 8 // (len(outs) + 1) // share
+    for i, (name, t) in enumerate(sorted(outs.items())):
+        n = int(t.numel())
+        if n > cap:
+            idx = np.sort(np.random.default_rng([seed, i]).choice(n, cap, replace=False))
+            t = t[torch.as_tensor(idx, device=t.device)]
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), t.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, f"{prefix}summary.npy"), np.array([getattr(summary, k) for k in DUMP_SUMMARY], dtype=np.float64))
 
 
 def windows_of(read_len, reso: int) -> int:
@@ -419,7 +450,13 @@ def main():
     ap.add_argument("--plain-input-memory", action="store_true", help="leave the input columns where torch's allocator (hipMalloc) put them instead of moving them "
                     "into memory from raft_hip_device_alloc before the clock (see include/raft_hip.h: a pass's time depends on where its buffers lie)")
     ap.add_argument("--no-placement-ab", action="store_true", help="skip the extra passes that time the pileup kernel with its buffers placed the other ways")
+    ap.add_argument("--full", action="store_true", help="also the self-check, every leg beside the headline, the CPU baseline and (several GPUs) the "
+                    "other two forms and the single-GPU check of the ranks' totals; without it only the headline is set up and timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:                                 # (a plain run: the headline alone)
+        args.no_cpu_baseline = args.no_e2e = args.no_packed_leg = args.no_six_column_leg = args.no_placement_ab = True
+        args.no_extra_legs = True
     # several GPUs: which form is the headline (default: configs[3] as written, pre-split)
     args.mode = "weak" if (args.weak or args.gpus <= 1) else ("host_routed" if args.host_routed and not args.presplit else "presplit")
     args.strong = args.mode != "weak"
@@ -602,9 +639,9 @@ def main():
 
     nonlocal_form = ["coordinate columns (8 bytes per record)"]      # what the native exchange of the last pre-split run sent
 
-    def strong_run(full, presplit, warmup, steps):
+    def strong_run(full, presplit, warmup, steps, dump=False):
         """Times the strong-scaling step on this rank's share of `full`; returns (summary, elapsed, kernel s, pass s, records
-        of the whole set, totals-equal-single-GPU or None)."""
+        of the whole set, totals-equal-single-GPU or None; None as well without --full)."""
         bounds, my_len, cols = strong_shard(full, presplit)
         comm = None
         if presplit:
@@ -664,6 +701,8 @@ def main():
                 combine(s)
                 return s
         s, elapsed, pile, pass_dev = timed(step, e, warmup, steps)
+        if dump:
+            dump_outputs(args.dump_outputs, e, s, args.seed, prefix=f"rank{rank}_", share=world)
         if comm is not None:
             torch.cuda.synchronize()
             comm.close()
@@ -672,7 +711,7 @@ def main():
             dist.all_reduce(mine, op=dist.ReduceOp.SUM)
         e.close()
         ok = None
-        if rank == 0:
+        if rank == 0 and args.full:
             ok = single_gpu_totals(full) == [int(x) for x in mine[:5].tolist()]
         return s, elapsed, pile, pass_dev, [int(x) for x in mine.tolist()], ok
 
@@ -694,12 +733,12 @@ def main():
     if args.strong and world > 1:
         full = place_set(make_overlaps(n_reads, seed=args.seed, device=dev, **gen_kw))
         torch.cuda.synchronize()
-        s, elapsed, pile, pass_dev, tot, ok = strong_run(full, args.presplit, args.warmup, args.steps)
+        s, elapsed, pile, pass_dev, tot, ok = strong_run(full, args.presplit, args.warmup, args.steps, dump=bool(args.dump_outputs))
         tot_rec, tot_frag, tot_bins, tot_iv = full.n_rec, tot[0], tot[4], tot[5]
         my_rec = s.n_records
-        if rank == 0 and not ok:
+        if rank == 0 and args.full and not ok:
             raise SystemExit("bench.py: the ranks' totals differ from the single-GPU pass over the same set")
-        o, eng, check = full, None, {"ranks_totals_equal_single_gpu_pass": bool(ok)} if rank == 0 else {}
+        o, eng, check = full, None, {"ranks_totals_equal_single_gpu_pass": bool(ok)} if rank == 0 and args.full else {}
         if not args.no_extra_legs:
             # the other strong form of the SAME set ...
             other = not args.presplit
@@ -730,6 +769,8 @@ def main():
     else:
         o = place_set(make_overlaps(n_reads, seed=args.seed + rank, device=dev, **gen_kw))
         s, elapsed, pile, pass_dev, eng, sh = weak_run(o, args.warmup, args.steps)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, eng, s, args.seed, prefix=f"rank{rank}_" if world > 1 else "", share=world)
         my_rec = o.n_rec
         if dist is not None:
             cnt = torch.tensor([my_rec, s.n_fragments, s.n_bins, s.n_intervals], dtype=torch.int64, device=coll_dev)
@@ -738,24 +779,26 @@ def main():
         else:
             tot_rec, tot_frag, tot_bins, tot_iv = my_rec, s.n_fragments, s.n_bins, s.n_intervals
 
-        # ---- self-check of the last timed pass (outside the clock): size-independent invariants of the outputs
-        out = eng.outputs_device()
-        touched = ((o.qe.long() - 1) // p.reso - o.qs.long() // p.reso + 1).clamp(min=0)
-        if args.nonsym:                               # (target sides of records whose two reads differ are piled up as well)
-            touched = torch.cat([touched, (((o.te.long() - 1) // p.reso - o.ts.long() // p.reso + 1).clamp(min=0))[o.tid != o.qid]])
-        fo, fb, fe = out["frag_offset"], out["frag_begin"], out["frag_end"]
-        same = out["frag_read"][1:] == out["frag_read"][:-1]
-        check = {"sum_cov_equals_windows_touched": int(out["cov"].sum(dtype=torch.int64)) == int(touched.sum()) == s.total_coverage,
-                 "fragments_tile_reads": bool((fb[fo[:-1]] == 0).all()) and bool((fe[fo[1:] - 1] == o.read_len).all())
-                 and bool(((fe[:-1] - fb[1:])[same] == p.overlap_length).all()),
-                 "windows": s.n_bins == int(((o.read_len.long() + p.reso - 1) // p.reso).sum()),
-                 # cut points (written by the pass): every read's first is 0 and its last its length, ascending in between, and every
-                 # fragment boundary is one of them (chop.hpp:225-246, :280-321)
-                 "cut_points_span_reads": bool((out["cuts"][out["cut_offset"][:-1]] == 0).all()) and bool((out["cuts"][out["cut_offset"][1:] - 1] == o.read_len).all())
-                 and int(out["cut_offset"][-1]) == s.n_cuts}
-        del touched, out
-        if not all(check.values()) and "RAFT_BENCH_ABLATION" not in os.environ:      # (diagnostic builds with parts of the kernel switched off compute nonsense on purpose)
-            raise SystemExit(f"bench.py: self-check failed: {check}")
+        # ---- self-check of the last timed pass (outside the clock, --full): size-independent invariants of the outputs
+        check = {}
+        if args.full:
+            out = eng.outputs_device()
+            touched = ((o.qe.long() - 1) // p.reso - o.qs.long() // p.reso + 1).clamp(min=0)
+            if args.nonsym:                               # (target sides of records whose two reads differ are piled up as well)
+                touched = torch.cat([touched, (((o.te.long() - 1) // p.reso - o.ts.long() // p.reso + 1).clamp(min=0))[o.tid != o.qid]])
+            fo, fb, fe = out["frag_offset"], out["frag_begin"], out["frag_end"]
+            same = out["frag_read"][1:] == out["frag_read"][:-1]
+            check = {"sum_cov_equals_windows_touched": int(out["cov"].sum(dtype=torch.int64)) == int(touched.sum()) == s.total_coverage,
+                     "fragments_tile_reads": bool((fb[fo[:-1]] == 0).all()) and bool((fe[fo[1:] - 1] == o.read_len).all())
+                     and bool(((fe[:-1] - fb[1:])[same] == p.overlap_length).all()),
+                     "windows": s.n_bins == int(((o.read_len.long() + p.reso - 1) // p.reso).sum()),
+                     # cut points (written by the pass): every read's first is 0 and its last its length, ascending in between, and every
+                     # fragment boundary is one of them (chop.hpp:225-246, :280-321)
+                     "cut_points_span_reads": bool((out["cuts"][out["cut_offset"][:-1]] == 0).all()) and bool((out["cuts"][out["cut_offset"][1:] - 1] == o.read_len).all())
+                     and int(out["cut_offset"][-1]) == s.n_cuts}
+            del touched, out
+            if not all(check.values()) and "RAFT_BENCH_ABLATION" not in os.environ:      # (diagnostic builds with parts of the kernel switched off compute nonsense on purpose)
+                raise SystemExit(f"bench.py: self-check failed: {check}")
 
         # ---- several GPUs, weak headline (--weak): BASELINE configs[3]'s setting beside it -- the ONE set of configs[2] in `world` read ranges
         if world > 1 and not args.no_extra_legs:
@@ -994,8 +1037,9 @@ def main():
                          "pass_note": "pass_frac divides the pileup kernel's algorithmic bytes (12 I + 4 B + 4 N + 8 R) by the device time of the whole pass, "
                                       "cut points (4 M more bytes, not counted) included",
                          "kernel_source_hash": kernel_source_hash()},
-            "self_check": check,
         }
+        if args.full:
+            line["self_check"] = check
         if packed is not None:
             # the product path (what the CLI runs) next to the int32 figures: a byte per window written, no query column read
             line["roofline"].update(product_path_kernel_ms=packed["kernel_ms"], product_path_frac=packed["kernel_frac"],

@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_line_has_every_contract_field():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "60000", "--steps", "2", "--warmup", "1",
-                        "--cpu-sample-reads", "3000"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                        "--cpu-sample-reads", "3000", "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
     assert len(lines) == 1, "exactly one JSON line on stdout"
@@ -73,7 +73,7 @@ def test_bench_gpus_flag_spawns_the_ranks_itself(extra):
     (host-routed: same set, no exchange; weak: a set per rank) are legs of the same line; --host-routed / --weak swap the roles."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--reads", "30000", "--steps", "2",
-                        "--warmup", "1"] + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, env=env)
+                        "--warmup", "1", "--full"] + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, env=env)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -113,3 +113,39 @@ def test_bench_refuses_a_world_size_that_disagrees_with_gpus():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--reads", "1000"], stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=600, env=env)
     assert r.returncode != 0 and b"WORLD_SIZE" in r.stderr
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline (no legs, no self-check, no CPU baseline), --steps sets the timed steps, and
+    --dump-outputs writes what the last step computed: float64 arrays within 64 MiB, the same for two runs with the same arguments,
+    and the totals of the summary agree with the line."""
+    import numpy as np
+
+    def run(out):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "60000", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
+        assert len(lines) == 1, "exactly one JSON line on stdout"
+        return json.loads(lines[0])
+
+    d = run(tmp_path / "a")
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "int32"
+    assert abs(d["value"] - d["config"]["records_total"] / (d["ms_per_step"] / 1e3)) <= 1e-6 * d["value"]
+    for k in ("cpu_baseline", "e2e", "self_check", "packed_output", "window_records", "grouped", "six_column", "placement_ab"):
+        assert k not in d, k
+    names = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert "summary.npy" in names and "cov.npy" in names and "frag_end.npy" in names and len(names) == 12
+    assert sum((tmp_path / "a" / n).stat().st_size for n in names) <= 64 << 20
+    a = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert all(v.dtype == np.float64 for v in a.values())
+    summ = a["summary.npy"]
+    assert summ[0] == d["config"]["reads_per_gpu"] and summ[5] == d["config"]["windows_total"] and summ[8] == d["config"]["fragments_total"]
+    assert a["frag_end.npy"].size == d["config"]["fragments_total"] > 0                     # written whole
+    assert 0 < a["cov.npy"].size < d["config"]["windows_total"]                               # a sample of 3.6e7 windows
+    run(tmp_path / "b")
+    for n in names:
+        assert np.array_equal(a[n], np.load(tmp_path / "b" / n)), n
