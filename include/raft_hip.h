@@ -95,12 +95,15 @@ typedef struct raft_hip_summary {
                                    and the pileup kernel read those (4 bytes per interval) instead of coordinate columns;
                                    bit 1 -- the pass was built, without its host wait, on what the context's previous pass over a stream
                                    of the same shape had found (sizes, sorted runs), and the device confirmed it (raft_hip_run_device);
-                                   bits 2, 3 -- see RAFT_HIP_SUM_DEEP_TILES, RAFT_HIP_SUM_RERUN */
+                                   bits 2, 3, 4 -- see RAFT_HIP_SUM_DEEP_TILES, RAFT_HIP_SUM_RERUN, RAFT_HIP_SUM_KEPT_GEOMETRY.
+                                   After a re-run the bits describe the pass that produced the results (plus RERUN) */
 } raft_hip_summary;
 #define RAFT_HIP_SUM_BUCKET_WINDOWS 1
 #define RAFT_HIP_SUM_SPECULATED 2
 #define RAFT_HIP_SUM_DEEP_TILES 4   /* tiles of 2^15 intervals or more took the 32-bit side kernel (pileup_deep.hpp) */
 #define RAFT_HIP_SUM_RERUN 8        /* raft_hip_finish ran the pass more than once (a refuted guess or assumption, a list that had to grow) */
+#define RAFT_HIP_SUM_KEPT_GEOMETRY 16   /* a speculated pass that reused the per-read geometry (window / repeat-slot offsets, tile starts)
+                                           of the pass it was built on and only compared the read lengths with that pass's */
 
 /* Device-resident outputs of the last run (valid until the next run/destroy).
  * Layout is CSR per read, FASTA-index order (= reference output order):
@@ -205,7 +208,9 @@ int  raft_hip_run_host_windows(raft_hip_ctx *ctx, int32_t n_reads, const int32_t
  * the device (RAFT_HIP_ERR_READ_ID / _COORD / _FRAGMENT). */
 int  raft_hip_finish(raft_hip_ctx *ctx, raft_hip_summary *summary);
 
-/* Device pointers of the finished pass. */
+/* Device pointers of the finished pass.  They are the context's own buffers: cov_offset is also the per-read geometry a later
+ * speculated pass over the same reads may reuse, so this call marks that geometry as handed out and the next pass scans it
+ * again (no RAFT_HIP_SUM_KEPT_GEOMETRY).  Treat the arrays as read-only all the same: they are valid until the next pass. */
 int  raft_hip_outputs_device(raft_hip_ctx *ctx, raft_hip_outputs *out);
 
 /* Copies outputs of the finished pass to caller-provided host arrays sized from

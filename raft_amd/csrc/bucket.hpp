@@ -134,18 +134,26 @@ struct GuessBeside {
 
 // A speculative pass over reads whose geometry the context still holds (engine_ctx.hpp geom_id): the lengths against the copy the scan
 // that made it kept; any difference refutes the pass (kErrHint: raft_hip_finish runs it again the long way, which scans).  The repeat
-// counters are cleared on the way; `Beside`: as in scan_partials_kernel.
+// counters are cleared on the way; `Beside`: as in scan_partials_kernel.  A negative length is an error here as in the scan (kErrLen),
+// whatever the copy holds.
 constexpr int kVerifyReads = 1024;
 template <class Beside>
 __global__ __launch_bounds__(256) void verify_lengths_kernel(int32_t n_reads, const int32_t *len, const int32_t *seen, int32_t *rep_cnt, int32_t *err_flags,
-                                                             int n_blocks, Beside beside)
+                                                             long long *err_index, int n_blocks, Beside beside)
 {
     if ((int)blockIdx.x >= n_blocks) { beside((int)blockIdx.x - n_blocks); return; }
     bool bad = false;
 #pragma unroll
     for (int j = 0; j < kVerifyReads / 256; ++j) {
         const long long i = (long long)blockIdx.x * kVerifyReads + j * 256 + threadIdx.x;
-        if (i < n_reads) { bad |= len[i] != seen[i]; rep_cnt[i] = 0; }
+        if (i < n_reads) {
+            const int32_t l = len[i];
+            bad |= l != seen[i]; rep_cnt[i] = 0;
+            if (l < 0) {
+                atomicOr(err_flags, kErrLen);
+                atomicMin((unsigned long long *)err_index, (unsigned long long)i);
+            }
+        }
     }
     if (bad) atomicOr(err_flags, kErrHint);
 }

@@ -381,7 +381,7 @@ int run_pass(raft_hip_ctx *c, const raft_hip_ctx::PassArgs &in, bool verify_in_k
         d_tid = d_qid; d_ts = d_qs; d_te = d_qe;
     }
     c->ran = false; c->finished = false; c->pending_err = RAFT_HIP_OK; c->pending_err_index = -1; c->packed_width = 0; c->seq_armed = false;
-    c->cov_valid = false; c->pass_width = 4; c->n_exc = 0; c->exc_sorted = false;
+    c->cov_valid = false; c->pass_width = 4; c->n_exc = 0; c->exc_sorted = false; c->spec_scanned = false;
     c->args = in;
     const bool no_verify_env = getenv("RAFT_ALWAYS_INSPECT") != nullptr;   // (A/B measurements; bench.py times both forms)
     // (a detecting context assumes a symmetric PAF -- hifiasm's shape -- until a pass of its own has found otherwise)
@@ -475,6 +475,12 @@ int run_pass(raft_hip_ctx *c, const raft_hip_ctx::PassArgs &in, bool verify_in_k
     // (the geometry of the remembered pass, if nobody has written it since: engine_ctx.hpp geom_id.  RAFT_NO_KEEP_GEOMETRY=1: scanned again)
     const bool keep_geom = speculate && !grouped && c->geom_id != 0 && c->shape.geom_id == c->geom_id && getenv("RAFT_NO_KEEP_GEOMETRY") == nullptr;
     if (!keep_geom) ++c->geom_id;
+    else c->sum.flags |= RAFT_HIP_SUM_KEPT_GEOMETRY;
+    // (a speculative pass that scans writes the geometry of the same reads afresh: raft_hip_finish lets the passes after it keep that
+    // geometry once the pass has come through without an error flag or a re-run -- not before: a scan that met a negative length
+    // has recorded it in len_seen)
+    c->spec_scanned = speculate && !keep_geom;
+    c->spec_geom_id = c->geom_id;
     if (!known) {
         hipStream_t gst = grouped ? st : c->side_stream;
         if (!grouped) {
@@ -606,7 +612,7 @@ int run_pass(raft_hip_ctx *c, const raft_hip_ctx::PassArgs &in, bool verify_in_k
             // ONE launch: the lengths against the ones the geometry was made from (kErrHint), the repeat counters cleared; the run guess beside it
             const int vb = (int)((N + kVerifyReads - 1) / kVerifyReads);
             hipLaunchKernelGGL((verify_lengths_kernel<GuessBeside>), dim3((unsigned)(vb + (guess_too ? kGuessBlocks : 0))), dim3(256), 0, st, n_reads, d_len,
-                               c->len_seen.as<int32_t>(), c->rep_cnt.as<int32_t>(), &ctrl->err_flags, vb, gb);
+                               c->len_seen.as<int32_t>(), c->rep_cnt.as<int32_t>(), &ctrl->err_flags, &ctrl->err_index, vb, gb);
         } else {
         hipLaunchKernelGGL((scan_partials_kernel<ReadPrepLoader, 3, GuessBeside>), dim3((unsigned)(nb_scan + (guess_too ? kGuessBlocks : 0))), dim3(kScanThreads), 0, st,
                            prep_ld, N, partials, nb_scan, gb);
@@ -1136,6 +1142,9 @@ int raft_hip_finish(raft_hip_ctx *c, raft_hip_summary *summary)
                 c->pending_err = code_from_flags(hc.err_flags);
                 c->pending_err_index = hc.err_index;
             }
+            // a speculative pass that scanned the geometry afresh and came through clean: the passes after it may keep it
+            if (c->spec_scanned && n_reruns == 0 && !hc.err_flags && c->shape.valid && c->geom_id == c->spec_geom_id)
+                c->shape.geom_id = c->geom_id;
         }
         if (n_reruns > 0) c->sum.flags |= RAFT_HIP_SUM_RERUN;
         c->sum.error_index = c->pending_err ? c->pending_err_index : -1;
@@ -1240,6 +1249,7 @@ int raft_hip_outputs_device(raft_hip_ctx *c, raft_hip_outputs *o)
     if (!c->finished || c->pending_err) return RAFT_HIP_ERR_STATE;
     { const int rc = materialise_cuts(c); if (rc != RAFT_HIP_OK) return rc; }
     { const int rc = materialise_cov(c); if (rc != RAFT_HIP_OK) return rc; }
+    ++c->geom_id;                                  // (cov_offset goes out writable: the next pass scans the geometry again)
     o->cov_offset = c->cov_off.as<int64_t>(); o->cov = c->cov.as<int32_t>();
     o->rep_offset = c->rep_off.as<int64_t>(); o->rep_s = c->rep_s.as<int32_t>(); o->rep_e = c->rep_e.as<int32_t>();
     o->cut_offset = c->cut_off.as<int64_t>(); o->cuts = c->cuts.as<int32_t>();

@@ -381,6 +381,8 @@ struct raft_hip_ctx {
     unsigned long long geom_id = 0;
     bool speculated = false;           // the pass in flight was built on `shape`
     bool deep_skipped = false;         // ... and without a launch of pileup_deep_kernel (a deep tile then refutes it: kErrDeep)
+    bool spec_scanned = false;         // ... and scanned the geometry afresh (raft_hip_finish: kept by later passes if it came through clean)
+    unsigned long long spec_geom_id = 0;   // geom_id that scan wrote
     hipStream_t clean_stream = nullptr;
     bool ctrl_clean = false;           // the control block and the hand-out counters were cleared by the last pass's closing kernel, on clean_stream
 };

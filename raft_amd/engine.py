@@ -18,6 +18,8 @@ from .params import RaftParams
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libraft_hip.so")
 
 OK, ERR_PARAM, ERR_READ_ID, ERR_COORD, ERR_FRAGMENT, ERR_NOMEM, ERR_DEVICE, ERR_STATE, ERR_TOO_LARGE = range(9)
+# Summary.flags (RAFT_HIP_SUM_*)
+SUM_BUCKET_WINDOWS, SUM_SPECULATED, SUM_DEEP_TILES, SUM_RERUN, SUM_KEPT_GEOMETRY = 1, 2, 4, 8, 16
 
 EXPORTS = (
     "raft_hip_abi_version", "raft_hip_strerror", "raft_hip_last_error", "raft_hip_create", "raft_hip_destroy",
@@ -96,7 +98,7 @@ class Summary:
     total_read_length: int
     error_index: int
     n_devices_used: int = 0
-    flags: int = 0                # RAFT_HIP_SUM_*: bit 0 = the general bucketing handed the pileup kernel window records
+    flags: int = 0                # RAFT_HIP_SUM_* (SUM_* above): bit 0 = the general bucketing handed the pileup kernel window records
 
 
 class RaftError(RuntimeError):
@@ -336,10 +338,11 @@ class Engine:
         the params assert symmetric_mode = 1."""
         import torch
         cols = (read_len, qid, qs, qe, tid, ts, te)
-        # (a caller that hands over the same tensors again -- a stream of batches through fixed buffers -- is checked once)
+        # (a caller that hands over the same tensors again -- a stream of batches through fixed buffers -- is checked once; a tensor
+        # resized in place keeps its address, so the lengths are part of what must match)
         last = getattr(self, "_last_device_call", None)
         if last is not None and all(a is b for a, b in zip(last[0], cols)) and \
-                all(t is None or t.data_ptr() == q for t, q in zip(cols, last[2])) and int(qid.numel()) == last[1][2]:
+                all(t is None or (t.data_ptr(), t.numel()) == q for t, q in zip(cols, last[2])):
             args = last[1]
         else:
             for t in cols:
@@ -351,7 +354,7 @@ class Engine:
                     raise ValueError("PAF columns differ in length")
             ptr = [C.c_void_p(t.data_ptr() if (t is not None and t.numel()) else 0) for t in cols]
             args = (int(read_len.numel()), ptr[0], n_rec, *ptr[1:])
-            self._last_device_call = (cols, args, [None if t is None else t.data_ptr() for t in cols])
+            self._last_device_call = (cols, args, [None if t is None else (t.data_ptr(), t.numel()) for t in cols])
         self._keep = cols
         self.use_torch_stream()     # the tensors were produced on torch's current stream: order after it
         self._check(self._lib.raft_hip_run_device(self._ctx, *args))
@@ -680,7 +683,9 @@ class Engine:
         return res
 
     def outputs_device(self) -> dict:
-        """Zero-copy torch views of the device-resident outputs (valid until the next pass)."""
+        """Zero-copy torch views of the device-resident outputs (valid until the next pass).  Treat them as read-only: torch takes no
+        read-only CUDA array interface, so nothing stops a write, and the library scans the per-read geometry again in the next pass
+        rather than trust ``cov_offset`` after this call."""
         import torch
         o = _Outputs()
         self._check(self._lib.raft_hip_outputs_device(self._ctx, C.byref(o)))
