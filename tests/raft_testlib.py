@@ -398,3 +398,376 @@ class kernel_mode:
             else:
                 os.environ["RAFT_DEEP_MIN"] = self.old
         return False
+
+
+# ---- lattice sets: one-purpose reads at the kernels' structural boundaries and value thresholds ----------------------------------------
+# Every read of a set is independent in the reference (repeat.hpp:28-79, 111-168), so one set packs thousands of reads that each put
+# ONE run of high windows at a chosen place.  All records are self overlaps sorted by read id (tid = qid, ts = qs, te = qe): only the
+# query side piles up (chop.hpp:166), and a context with symmetric_mode = 1 given the query columns alone sees the same.  A generator
+# returns the columns together with the closed form of what must come out -- coverage per window and the repeats -- made from the
+# construction, never from code under test; tests/test_lattice_cases.py pins it to the oracle and counts, on the oracle's side, how
+# many runs end / begin on every boundary class (lattice_census), so that a sweep cannot go vacuous unnoticed.
+
+# raft_amd/csrc/engine_ctx.hpp: kTileCap = kWaveSlots - 4, wave_launch.hpp: RAFT_WAVE_SLOTS 4096.  The windows of one wave tile, and the
+# length of a piece of a read longer than that.  The sweeps below reach a row (512) and more to either side of its multiples, so they
+# keep covering the edges if the constant moves by a few slots.
+TILE_CAP = 4096 - 4
+D4_BLOCK = 1024               # raft_types.hpp kD4Block: windows per anchor of the four-bit step encoding (global window index)
+LANE, HALF_ROW, ROW = 4, 256, 512     # pileup_wave.hpp: windows of a lane, of a half-row, of a row of the LDS array
+
+
+class LatticeCase:
+    """name, p (RaftParams, symmetric_mode = 1), cols (seven columns), expect (closed form: cov_offset, cov, rep_offset, rep_s, rep_e),
+    and per read: a (first run's start window, -1: none), d (run length minus the minimum), W (windows), kind."""
+
+    def __init__(self, name, p, cols, expect, a, d, W, kind):
+        self.name, self.p, self.cols, self.expect = name, p, cols, expect
+        self.a, self.d, self.W, self.kind = a, d, W, kind
+
+    @property
+    def n_reads(self):
+        return int(self.W.size)
+
+    def query_cols(self):
+        return tuple(self.cols[:4]) + (None, None, None)
+
+    def coordinate(self, r):
+        r = int(r)
+        return (f"read {r} [{self.kind[r]}] (a={int(self.a[r])}, d={int(self.d[r])}, W={int(self.W[r])}, "
+                f"offset mod 4={int(self.expect['cov_offset'][r] % 4)})")
+
+    def oracle(self):
+        want = oracle_run(self.p, *self.cols)
+        want["symmetric"] = 1       # (asserted by the context; self overlaps add no target side whatever the detection says)
+        return want
+
+
+def lattice_first_difference(case, got, want):
+    """None, or a sentence naming the first read whose coverage or repeats differ, as a lattice coordinate."""
+    off = np.asarray(want["cov_offset"])
+    g, w = np.asarray(got["cov"]), np.asarray(want["cov"])
+    if g.shape != w.shape:
+        return f"cov has {g.size} windows, want {w.size}"
+    bad = np.flatnonzero(g != w)
+    if bad.size:
+        r = int(np.searchsorted(off, bad[0], side="right") - 1)
+        j = int(bad[0] - off[r])
+        return (f"cov differs in {bad.size} windows, first in {case.coordinate(r)} at window {j} "
+                f"(slot {j + int(off[r] % 4)} of a tile it begins, global {int(bad[0])}): got {int(g[bad[0]])} want {int(w[bad[0]])}")
+    go, wo = np.asarray(got["rep_offset"]), np.asarray(want["rep_offset"])
+    if go.shape != wo.shape:
+        return f"rep_offset has {go.size} entries, want {wo.size}"
+    for r in np.flatnonzero(np.diff(go) != np.diff(wo))[:1]:
+        return (f"repeat count differs first in {case.coordinate(r)}: got "
+                f"{list(zip(np.asarray(got['rep_s'])[go[r]:go[r + 1]].tolist(), np.asarray(got['rep_e'])[go[r]:go[r + 1]].tolist()))} want "
+                f"{list(zip(np.asarray(want['rep_s'])[wo[r]:wo[r + 1]].tolist(), np.asarray(want['rep_e'])[wo[r]:wo[r + 1]].tolist()))}")
+    for k in ("rep_s", "rep_e"):
+        bad = np.flatnonzero(np.asarray(got[k]) != np.asarray(want[k]))
+        if bad.size:
+            r = int(np.searchsorted(wo, bad[0], side="right") - 1)
+            return (f"{k} differs in {bad.size} repeats, first in {case.coordinate(r)}: got {int(np.asarray(got[k])[bad[0]])} "
+                    f"want {int(np.asarray(want[k])[bad[0]])}")
+    return None
+
+
+def assert_lattice_result(case, got, want, what):
+    """assert_same_result whose message reads as a coordinate: set, `what` (form, kernel, width) and the first differing read."""
+    msg = lattice_first_difference(case, got, want)
+    assert msg is None, f"set {case.name}, {what}: {msg}"
+    assert_same_result(got, want, f"set {case.name}, {what}")
+
+
+def _lattice_build(name, p, specs):
+    """specs: per read (W, tail, base, runs, high, a, d, kind) -- `base` records over the whole read, runs = [(s, e, k, da, db)]: k
+    coincident records whose windows are exactly [s, e) (start s*reso + da, end e*reso - db: the rounding of repeat.hpp:62-77 on both
+    edges), high = [(s, e)]: the maximal runs of windows at or above high_cov by construction, or None: taken from the closed-form
+    coverage by its threshold.  Closed form of the repeats: a run of (e - s)*reso >= repeat_length gives
+    (max(s*reso - flank, 0), min(e*reso + flank, read_len)), in order (repeat.hpp:129-140)."""
+    reso, H = p.reso, p.high_cov
+    n = len(specs)
+    W = np.array([s[0] for s in specs], np.int64)
+    tail = np.array([s[1] for s in specs], np.int64)
+    base = np.array([s[2] for s in specs], np.int64)
+    assert np.all(W >= 1) and np.all((tail >= 0) & (tail < reso))
+    rl = (W * reso - tail).astype(np.int32)
+    off = np.zeros(n + 1, np.int64)
+    np.cumsum(W, out=off[1:])
+    rr, rs, re_, rk, ws, we = [], [], [], [], [], []
+    for r, sp in enumerate(specs):
+        for (s, e, k, da, db) in sp[3]:
+            assert 0 <= s < e <= W[r] and k >= 1 and 0 <= da < reso and 0 <= db < reso, (name, r, sp)
+            st, en = s * reso + da, min(e * reso - db, int(rl[r]))
+            if st >= en or (en - 1) // reso != e - 1:
+                st, en = s * reso, min(e * reso, int(rl[r]))
+            assert st // reso == s and (en - 1) // reso == e - 1 and st < en <= rl[r], (name, r, sp)
+            rr.append(r); rs.append(st); re_.append(en); rk.append(k); ws.append(s); we.append(e)
+    rr, rk = np.array(rr, np.int64), np.array(rk, np.int64)
+    qid = np.concatenate([np.repeat(np.arange(n), base), np.repeat(rr, rk)])
+    qs = np.concatenate([np.zeros(int(base.sum()), np.int64), np.repeat(np.array(rs, np.int64), rk)])
+    qe = np.concatenate([np.repeat(rl.astype(np.int64), base), np.repeat(np.array(re_, np.int64), rk)])
+    order = np.argsort(qid, kind="stable")
+    qid, qs, qe = (x[order].astype(np.int32) for x in (qid, qs, qe))
+    diff = np.zeros(int(off[-1]) + 1, np.int64)
+    np.add.at(diff, off[:-1], base)
+    np.add.at(diff, off[1:], -base)
+    np.add.at(diff, off[rr] + np.array(ws, np.int64), rk)
+    np.add.at(diff, off[rr] + np.array(we, np.int64), -rk)
+    cov = np.cumsum(diff[:-1]).astype(np.int32)
+    rep_offset, rep_s, rep_e = np.zeros(n + 1, np.int64), [], []
+    for r, sp in enumerate(specs):
+        high = sp[4]
+        if high is None:
+            m = np.concatenate([[0], (cov[off[r]:off[r + 1]] >= H).astype(np.int8), [0]])
+            edge = np.flatnonzero(np.diff(m))
+            high = list(zip(edge[0::2].tolist(), edge[1::2].tolist()))
+        for (s, e) in high:
+            if (e - s) * reso >= p.repeat_length:
+                rep_s.append(max(s * reso - p.flanking_length, 0)); rep_e.append(min(e * reso + p.flanking_length, int(rl[r])))
+        rep_offset[r + 1] = len(rep_s)
+    expect = {"cov_offset": off, "cov": cov, "rep_offset": rep_offset, "rep_s": np.array(rep_s, np.int32), "rep_e": np.array(rep_e, np.int32)}
+    return LatticeCase(name, p, [rl, qid, qs, qe, qid.copy(), qs.copy(), qe.copy()], expect,
+                       np.array([s[5] for s in specs], np.int64), np.array([s[6] for s in specs], np.int64), W, [s[7] for s in specs])
+
+
+def _lattice_params(reso, H, m, flank):
+    return RaftParams(reso=reso, est_cov=H, cov_mul=1.0, repeat_length=m * reso, interval_length=20 * reso, read_length=40 * reso,
+                      overlap_length=0, flanking_length=flank, symmetric_mode=1)
+
+
+def run_lattice(reso, H, m, flank, a_range, W_range, seed, extra=(), name="lattice", ds=(-1, 0, 1), k_of=None, second=0):
+    """Per start window a in a_range and per d in ds one read of W windows drawn from W_range (the reads' offsets take every alignment
+    mod 4, tiles hold reads at changing slot offsets), read_len = W*reso - tail with tail in {0, 1, reso - 1}, H - 1 records over the
+    whole read (every window at high_cov - 1) and one whose windows are exactly [a, a + m + d): d = -1 is one window short of
+    repeat_length = m*reso, d = 0 exactly enough.  second > 0: the same run once more, `second` windows further on (the same place
+    relative to the next piece edge).  k_of(a, d) > 1: that many coincident records instead of one.  extra, per read variants under
+    the same closed form: "two" = two runs separated by exactly ONE low window (both qualify, their flanked intervals overlap, the
+    reference keeps both: the cut mask of chop.hpp:225-246 sees them), "first" = a run [0, m + d), "last" = a run ending on the
+    read's last, partial window, "whole" = the whole read."""
+    rng = np.random.default_rng(seed)
+    p = _lattice_params(reso, H, m, flank)
+    tails = (0, 1, reso - 1)
+    specs = []
+
+    def add(W, runs, a, d, kind, al=None):
+        da, db = int(rng.integers(0, reso)), int(rng.integers(0, reso))
+        k = 1 if k_of is None else int(k_of(a, d))
+        if al is not None and specs:                   # the read before grows by 0..3 windows: this one begins at offset mod 4 = al
+            grow = (al - sum(s[0] for s in specs)) % 4
+            specs[-1] = (specs[-1][0] + grow,) + specs[-1][1:]
+        specs.append((W, tails[len(specs) % 3] if reso > 1 else 0, H - 1, [(s, e, k, da, db) for (s, e) in runs], list(runs), a, d, kind))
+
+    for i, a in enumerate(a_range):
+        for d in ds:
+            L = m + d
+            # a run that begins or ends within a lane of a half-row boundary comes at all four alignments of its read's offset (left to
+            # chance, a given (boundary, alignment, d) is hit rarely or never: lattice_census counts them)
+            near = any(min(v % HALF_ROW, HALF_ROW - v % HALF_ROW) <= LANE for v in (a, a + L))
+            for al in ((0, 1, 2, 3) if near else (None,)):
+                W = int(rng.integers(W_range[0], W_range[1]))
+                if L < 1 or a + L + second > W:
+                    continue
+                add(W, [(a, a + L)] + ([(a + second, a + second + L)] if second else []), a, d, "run", al)
+            if "two" in extra and i % 8 == 0 and a + 2 * L + 1 <= W:
+                add(int(rng.integers(W_range[0], W_range[1])), [(a, a + L), (a + L + 1, a + 2 * L + 1)], a, d, "two")
+    for d in ds:
+        for rep in range(8):
+            W = int(rng.integers(W_range[0], W_range[1]))
+            L = m + d
+            if "first" in extra and L >= 1:
+                add(W, [(0, L)], 0, d, "first")
+            if "last" in extra and L >= 1:
+                add(W, [(W - L, W)], W - L, d, "last")
+    if "whole" in extra:
+        for rep in range(8):
+            W = int(rng.integers(W_range[0], W_range[1]))
+            add(W, [(0, W)], 0, W - m, "whole")
+    return _lattice_build(name, p, specs)
+
+
+def lattice_rows(which="r50"):
+    """A run from every window of the first two rows (and a bit): every lane, half-row and row boundary at every alignment."""
+    ex = ("two", "first", "last", "whole")
+    if which == "r50":
+        return run_lattice(50, 3, 6, 120, range(0, 1100), (1200, 1400), 11, ex, name="rows/reso 50")
+    if which == "r7":
+        return run_lattice(7, 2, 3, 0, range(0, 1100), (1200, 1400), 12, ex, name="rows/reso 7")
+    if which == "flank":
+        thin = [a for a in range(0, 1100) if a % 3 == 0 or min((a + 8) % HALF_ROW, HALF_ROW - (a + 8) % HALF_ROW) <= 12]
+        return run_lattice(50, 3, 6, 10 ** 6, thin, (1200, 1400), 13, ex, name="rows/flank beyond the read")
+    assert which == "h1"      # est_cov = 1: every covered window is high, an uncovered one low
+    return run_lattice(50, 1, 6, 120, range(0, 1100), (1200, 1400), 14, ex, name="threshold/high_cov 1")
+
+
+def lattice_tile_end():
+    """One read per tile, TILE_CAP - k windows for k from a row and more below the cap to a few above it (a read beyond the cap goes in
+    pieces), the run ending on the read's last windows: the sentinel slot and the last, partial row."""
+    rng = np.random.default_rng(21)
+    reso, H, m, flank = 50, 3, 6, 120
+    p = _lattice_params(reso, H, m, flank)
+    specs = []
+    for W in range(TILE_CAP - ROW - 8, TILE_CAP + 13):
+        near = abs(W - TILE_CAP) <= 12
+        for back in ((0, 1, 2, 3) if near else (0,)):
+            for d in (-1, 0, 1):
+                e = W - back
+                da, db = int(rng.integers(0, reso)), int(rng.integers(0, reso))
+                specs.append((W, (0, 1, reso - 1)[len(specs) % 3], H - 1, [(e - m - d, e, 1, da, db)], [(e - m - d, e)], e - m - d, d, f"end-{back}"))
+        if near:
+            specs.append((W, (0, 1, reso - 1)[len(specs) % 3], H - 1, [(0, W, 1, 7, 9)], [(0, W)], 0, W - m, "whole"))
+            specs.append((W, 0, H - 1, [(0, m, 1, 0, 0)], [(0, m)], 0, 0, "first"))
+    return _lattice_build("tile_end", p, specs)
+
+
+def lattice_pieces(between=41):
+    """Reads of three pieces (W in [9000, 9300)); the run of `rows` at every start within a row and more of the piece edges TILE_CAP and
+    2*TILE_CAP (stride 1: the short run straddles the edge in every split, 1 + 5 ... 5 + 1, neither part qualifies alone; a low window
+    exactly on either side of it), a coarser stride between; and runs of TILE_CAP - 1, TILE_CAP, TILE_CAP + 1 and 2*TILE_CAP windows
+    from swept starts: a piece that is high from end to end."""
+    near = ROW + 8
+    a_range = sorted(set(range(TILE_CAP - near, TILE_CAP + near)) | set(range(3500 - TILE_CAP, TILE_CAP - near, between))
+                     | set(range(TILE_CAP + near, 8800 - TILE_CAP, between)))
+    a_range = [a for a in a_range if a >= 0]
+    c = run_lattice(50, 3, 6, 120, a_range, (9000, 9300), 31, name="pieces", second=TILE_CAP)
+    rng = np.random.default_rng(32)
+    specs = []
+    for L in (TILE_CAP - 1, TILE_CAP, TILE_CAP + 1, 2 * TILE_CAP):
+        for s in (0, 1, 2, 3, 4, 255, 256, 511, 512, TILE_CAP - L, TILE_CAP - 1, TILE_CAP, TILE_CAP + 1, 2 * TILE_CAP - L):
+            if s < 0:
+                continue
+            W = s + L + int(rng.integers(0, 3)) * int(rng.integers(1, 700))
+            W = max(W, TILE_CAP + 2)
+            specs.append((W, (0, 1, 49)[len(specs) % 3], 2, [(s, s + L, 1, int(rng.integers(0, 50)), int(rng.integers(0, 50)))], [(s, s + L)], s, L - 6, f"long {L}"))
+    big = _lattice_build("pieces", c.p, specs)
+    return _lattice_join("pieces", c, big)
+
+
+def _lattice_join(name, x, y):
+    """Two cases of the same parameters, one after the other."""
+    assert x.p == y.p
+    nx = x.n_reads
+    cols = [np.concatenate([x.cols[0], y.cols[0]])] + [np.concatenate([x.cols[k], y.cols[k] + (nx if k in (1, 4) else 0)]).astype(np.int32) for k in range(1, 7)]
+    ex, ey = x.expect, y.expect
+    expect = {"cov_offset": np.concatenate([ex["cov_offset"], ey["cov_offset"][1:] + ex["cov_offset"][-1]]), "cov": np.concatenate([ex["cov"], ey["cov"]]),
+              "rep_offset": np.concatenate([ex["rep_offset"], ey["rep_offset"][1:] + ex["rep_offset"][-1]]),
+              "rep_s": np.concatenate([ex["rep_s"], ey["rep_s"]]), "rep_e": np.concatenate([ex["rep_e"], ey["rep_e"]])}
+    return LatticeCase(name, x.p, cols, expect, np.concatenate([x.a, y.a]), np.concatenate([x.d, y.d]), np.concatenate([x.W, y.W]), x.kind + y.kind)
+
+
+def lattice_byte_level(a_stop=600):
+    """H = 255: every window at 254, the run at 255 or, with a second coincident record, 256 -- the one-byte encoding's escape on
+    exactly the swept windows."""
+    return run_lattice(50, 255, 6, 120, range(0, a_stop), (1200, 1400), 41, ("first", "last"), name="byte_level", k_of=lambda a, d: 1 + ((a // 2 + d) & 1))
+
+
+STEP_KS = (6, 7, 8, 9, 15, 16)
+
+
+def lattice_steps():
+    """Four-bit steps: k coincident records over [a, b) on a zero baseline -- a step of +k at a and of -k at b; 7 fits, 8 is listed.
+    For k = 7 and 8 the run begins on every residue of the GLOBAL window index modulo 1024 (the anchors, the blocks' first windows; run
+    lengths vary, so the ends sweep too), for the other k on the residues next to the block edge and every 16th; and a = 0 of a read.
+    high_cov = 8: k >= 8 is high."""
+    rng = np.random.default_rng(51)
+    reso, H, m = 50, 8, 6
+    p = _lattice_params(reso, H, m, 120)
+    specs, off = [], 0
+    edge = list(range(D4_BLOCK - 9, D4_BLOCK)) + list(range(0, 10))
+    for k in STEP_KS:
+        targets = list(range(D4_BLOCK)) if k in (7, 8) else sorted(set(edge) | set(range(0, D4_BLOCK, 16)))
+        ends = set()
+        for i, t in enumerate(targets):
+            W = int(rng.integers(1200, 1400))
+            a = (t - off) % D4_BLOCK
+            d = i % 3 - 1
+            L = m + d
+            specs.append((W, (0, 1, reso - 1)[len(specs) % 3], 0, [(a, a + L, k, int(rng.integers(0, reso)), int(rng.integers(0, reso)))],
+                          [(a, a + L)] if k >= H else [], a, d, f"k={k}"))
+            ends.add((off + a + L) % D4_BLOCK)
+            off += W
+        for i, t in enumerate(t for t in targets if t not in ends):      # the step down on the residues the varying lengths left out
+            W = int(rng.integers(1200, 1400))
+            d = i % 3 - 1
+            L = m + d
+            a = (t - off - L) % D4_BLOCK
+            specs.append((W, (0, 1, reso - 1)[len(specs) % 3], 0, [(a, a + L, k, int(rng.integers(0, reso)), int(rng.integers(0, reso)))],
+                          [(a, a + L)] if k >= H else [], a, d, f"k={k}"))
+            off += W
+        for d in (-1, 0, 1):
+            W = int(rng.integers(1200, 1400))
+            specs.append((W, 0, 0, [(0, m + d, k, 3, 4)], [(0, m + d)] if k >= H else [], 0, d, f"k={k} first"))
+            off += W
+            for b in (0, -(m + d)):              # a run of each length beginning on a block's first window, and ending on its last
+                W = int(rng.integers(1200, 1400))
+                a = (b - off) % D4_BLOCK
+                specs.append((W, 0, 0, [(a, a + m + d, k, 1, 2)], [(a, a + m + d)] if k >= H else [], a, d, f"k={k} block"))
+                off += W
+    return _lattice_build("steps", p, specs)
+
+
+DEPTH_NS = (32766, 32767, 32768, 32769, 65534, 65535, 65536, 65537)
+
+
+def lattice_depth(H, Ns=DEPTH_NS):
+    """One read per tile: reads of N records -- the tile's interval count, which the wave kernel compares with 2^15 -- ALL covering one
+    common window (coverage N there: 32,767 is the largest value a 16-bit counter may hold, 65,535 the two-byte encoding's escape),
+    most of them coincident on a few windows, the rest nested around them; start and end windows on both parities (the low / high
+    half of an LDS dword) and next to a row boundary.  Every read has more than TILE_CAP / 2 windows, so that none shares its tile;
+    ordinary reads (two records over the read, a run of one more) in between.  high_cov = H."""
+    rng = np.random.default_rng(61)
+    reso, m = 50, 6
+    p = _lattice_params(reso, H, m, 120)
+    spots = [(510, 515), (511, 513), (1023, 1026), (2046, 2049), (255, 258), (3, 6), (-3, 0), (1, 2)]     # (negative: from the read's end)
+    specs = []
+
+    def ordinary():
+        W = int(rng.integers(2100, 2400))
+        a = int(rng.integers(0, W - 8))
+        specs.append((W, (0, 1, reso - 1)[len(specs) % 3], 2, [(a, a + m, 1, 5, 6)], None, a, 0, "ordinary"))
+
+    ordinary()
+    for i, N in enumerate(Ns):
+        W = 3900 + 7 * i + (i & 1)
+        s0, e0 = spots[DEPTH_NS.index(N) % len(spots)]
+        if s0 < 0:
+            s0, e0 = W + s0, W + e0
+        runs = [(s0, e0, N - 30, int(rng.integers(0, reso)), int(rng.integers(0, reso)))]
+        for j in range(1, 31):
+            runs.append((max(s0 - 2 * j - (j & 1), 0), min(e0 + 3 * j + (j >> 1 & 1), W), 1, int(rng.integers(0, reso)), int(rng.integers(0, reso))))
+        specs.append((W, (0, 1, reso - 1)[i % 3], 0, runs, None, s0, e0 - s0 - m, f"N={N}"))
+        ordinary()
+        ordinary()
+    return _lattice_build(f"depth/high_cov {H}/N {min(Ns)}..{max(Ns)}", p, specs)
+
+
+def lattice_census(case, want):
+    """From the ORACLE's arrays alone (cov, cov_offset, high_cov): for every boundary class, how many runs of high windows END on its
+    last window and how many BEGIN on its first, separately for runs one window short of repeat_length (d = -1) and exactly long
+    enough (d = 0).  Classes: the slot index s = (offset mod 4) + window of a read that begins its tile (a tile's first window sits
+    behind offset mod 4 alignment slots) modulo a lane's 4, a half-row's 256 and a row's 512 windows, per alignment; the multiples of
+    TILE_CAP inside a read (piece edges); the global window index modulo 1024 (anchors of the four-bit steps).
+    -> {(class, alignment or -1, "end" | "begin", d): count}"""
+    off, cov = np.asarray(want["cov_offset"]), np.asarray(want["cov"])
+    m = case.p.repeat_length // case.p.reso
+    high = np.concatenate([[0], (cov >= want["high_cov"]).astype(np.int8), [0]])
+    first = np.zeros(cov.size + 1, bool)
+    first[off[:-1][np.diff(off) > 0]] = True                    # a read's first window begins a run whatever lies before it
+    inner = high[1:-1].astype(bool)
+    begin = np.flatnonzero(inner & (~np.concatenate([[False], inner[:-1]]) | first[:-1]))
+    end = np.flatnonzero(inner & (~np.concatenate([inner[1:], [False]]) | np.concatenate([first[1:-1], [True]])))
+    assert begin.size == end.size
+    L = end - begin + 1
+    r = np.searchsorted(off, begin, side="right") - 1
+    al = off[r] % 4
+    out = {}
+    for d in (-1, 0):
+        sel = L == m + d
+        b, e, a4, o = begin[sel], end[sel], al[sel], off[r[sel]]
+        for B, nm in ((LANE, "lane"), (HALF_ROW, "half-row"), (ROW, "row")):
+            for x in range(4):
+                out[(nm, x, "end", d)] = int(np.sum((a4 == x) & ((e - o + a4) % B == B - 1)))
+                out[(nm, x, "begin", d)] = int(np.sum((a4 == x) & ((b - o + a4) % B == 0)))
+        out[("piece", -1, "end", d)] = int(np.sum(((e - o + 1) % TILE_CAP == 0) & (e - o + 1 < off[r[sel] + 1] - o)))
+        out[("piece", -1, "begin", d)] = int(np.sum(((b - o) % TILE_CAP == 0) & (b > o)))
+        out[("block", -1, "end", d)] = int(np.sum(e % D4_BLOCK == D4_BLOCK - 1))
+        out[("block", -1, "begin", d)] = int(np.sum(b % D4_BLOCK == 0))
+    return out

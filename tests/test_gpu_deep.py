@@ -77,7 +77,7 @@ def test_more_deep_tiles_than_the_list_holds_grow_it(monkeypatch):
 
 
 @pytest.mark.parametrize("suite", ["test_gpu_parity.py", "test_gpu_wave.py test_gpu_windows.py", "test_gpu_delta4.py test_gpu_packed_output.py",
-                                   "test_gpu_configs.py -k 'not full_size'", "test_gpu_grouped.py test_gpu_routed.py"])
+                                   "test_gpu_configs.py -k 'not full_size'", "test_gpu_grouped.py test_gpu_routed.py", "test_gpu_lattice.py"])
 def test_parity_suites_through_the_deep_kernel(suite):
     """RAFT_DEEP_MIN=40: nearly every tile of the suites' sets goes through pileup_deep_kernel -- tiles of many reads, pieces of long
     reads, coordinate columns and window records in, every coverage encoding out.  (The tests that count passes or time kernels see
