@@ -502,6 +502,42 @@ int  raft_hip_warm_up(raft_hip_ctx *ctx);
 int  raft_hip_reserve(raft_hip_ctx *ctx, int32_t n_reads, const int32_t *read_len, int64_t n_rec_estimate, int32_t n_ctx,
                       int32_t cov_width);
 
+/* ---- the estimated coverage from the data (additive; the ABI version is unchanged) -----------------------------------
+ * est_cov (-e) is the one parameter the path cannot run without -- high_cov = (int)(est_cov * cov_mul) decides which windows
+ * are repeat (repeat.hpp:89-90) -- and the reference leaves it to the user: total bases over a guessed genome size
+ * (README.md:26-30), checked afterwards against the "coverage per window/average coverage" line (repeat.hpp:173-176).  The
+ * pileup's own window coverage peaks at the sequencing depth, so a pass run under ANY est_cov holds the number: cov[] does not
+ * depend on it.
+ *
+ * Histogram of the finished pass's window coverage: hist[v] = windows with coverage v, hist[4095] = windows with coverage >= 4095.
+ * Valid where raft_hip_fetch is (after raft_hip_finish without a data error; not after the host-to-host pipelines). Leaves the
+ * pass's outputs and the context's speculation state as they are (it hands out no geometry). kernel_seconds (may be NULL): device
+ * time of the histogram launches, from HIP events on the context's stream.  The array is read on the device in the form the pass
+ * wrote (int32, or one / two bytes per window plus the listed windows; four-bit steps are decoded into int32 first): 32 KiB cross
+ * PCIe instead of cov[].  Histograms of disjoint sets of reads add. */
+#define RAFT_HIP_COV_HIST_BINS 4096
+int raft_hip_cov_histogram(raft_hip_ctx *ctx, int64_t *hist /* [RAFT_HIP_COV_HIST_BINS], host */, double *kernel_seconds);
+
+/* The estimate, in integer arithmetic on a histogram of n = n_hist bins whose last bin is the clamp bin:
+ *     c[v] = hist[v] for 1 <= v <= n-2, c[0] = c[n-1] = 0   (windows nobody overlaps, and the clamp bin, say nothing about depth)
+ *     s[v] = c[v-1] + c[v] + c[v+1]                         for 1 <= v <= n-2
+ *     est_cov = the smallest v with maximal s[v], or 0 when that maximum is 0
+ *     median  = the smallest v >= 1 with 2 * sum(hist[1..v]) >= sum(hist[1..n-1])   (clamp bin included; 0 when the sum is 0)
+ * The smoothed mode is the estimate because repeats drag the mean and the median of the covered windows up (synthetic sets of
+ * 2000 reads: median 33 at 30x, 68 at 60x; 61 at 30x for 300 reads, half of whose genome is repeat), while the mode stays within a
+ * few per cent of the depth: 8x -> 7..8, 20x -> 19..21, 30x -> 29..33, 45x -> 41..47, 60x -> 55..64 over four seeds of 4000 reads.
+ * median and mean are reported for the caller's judgement.  Very small sets whose repeats dominate the genome defeat any estimator:
+ * for 300 reads at 45x and above the mode lands on the repeat peak.
+ * Pure host arithmetic (needs no device, no context).  Errors: a NULL pointer, n_hist < 3 or a negative count ->
+ * RAFT_HIP_ERR_PARAM; counts whose sum does not fit int64 -> RAFT_HIP_ERR_TOO_LARGE. */
+typedef struct raft_hip_cov_estimate {
+    int32_t est_cov;          /* the estimate; 0 = none (no window with coverage in 1..n-2) */
+    int32_t median;           /* lower weighted median over the windows with coverage >= 1 (0 = none) */
+    int64_t windows, windows_covered, windows_clamped;   /* sum h, sum h[1..], h[n-1] */
+    double  mean;             /* sum v h[v] / sum h, clamp bin counted at n-1 (0.0 for an empty histogram) */
+} raft_hip_cov_estimate;
+int raft_hip_estimate_coverage(const int64_t *hist, int32_t n_hist, raft_hip_cov_estimate *out);
+
 /* Device seconds spent in the dominant kernel (coverage pileup + run scan) and
  * in all kernels of the last finished pass, from HIP events recorded on the
  * context's stream around them. */

@@ -8,6 +8,7 @@
 #include "device_scan.hpp"
 #include "finalize.hpp"
 #include "pack.hpp"
+#include "cov_hist.hpp"
 #include "pileup.hpp"
 #include "pileup_wave.hpp"
 #include "wave_launch.hpp"
@@ -195,12 +196,14 @@ void raft_hip_destroy(raft_hip_ctx *c)
                      &c->block_sums, &c->cov, &c->rep_cnt, &c->raw_key, &c->raw_s, &c->raw_e, &c->cut_cnt, &c->frag_cnt,
                      &c->rep_off, &c->cut_off, &c->frag_off, &c->rep_s, &c->rep_e, &c->cuts, &c->frag_read,
                      &c->frag_begin, &c->frag_end, &c->b_cnt, &c->b_off, &c->b_rid, &c->b_s, &c->b_e, &c->gs_rid, &c->gs_s, &c->gs_e, &c->gs_off, &c->gs_err, &c->rs_k0, &c->rs_k1, &c->rs_v0, &c->rs_v1, &c->gaps, &c->in_len,
-                     &c->samples, &c->exp_qid, &c->in_off, &c->m_off, &c->u_s, &c->u_e, &c->cov_anchor, &c->abs_bits, &c->exc_idx2, &c->exc_val2, &c->sort_tmp, &c->exc_pidx, &c->exc_pval, &c->exc_tile_n, &c->x_qs, &c->x_qe, &c->x_off, &c->x_raw, &c->x_send_off, &c->x_cnt, &c->cov8, &c->exc_idx, &c->exc_val, &c->exc_cnt, &c->in_col[0], &c->in_col[1], &c->in_col[2], &c->in_col[3], &c->in_col[4], &c->in_col[5]};
+                     &c->samples, &c->exp_qid, &c->in_off, &c->m_off, &c->u_s, &c->u_e, &c->cov_anchor, &c->abs_bits, &c->exc_idx2, &c->exc_val2, &c->sort_tmp, &c->exc_pidx, &c->exc_pval, &c->exc_tile_n, &c->x_qs, &c->x_qe, &c->x_off, &c->x_raw, &c->x_send_off, &c->x_cnt, &c->cov8, &c->exc_idx, &c->exc_val, &c->exc_cnt, &c->cov_hist, &c->in_col[0], &c->in_col[1], &c->in_col[2], &c->in_col[3], &c->in_col[4], &c->in_col[5]};
     for (DevBuf *b : all) b->release();
     for (DevBuf *b : c->user_bufs) { b->release(); delete b; }
     c->user_bufs.clear();
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
+    if (c->ev_hist0) (void)hipEventDestroy(c->ev_hist0);
+    if (c->ev_hist1) (void)hipEventDestroy(c->ev_hist1);
     if (c->ev_pass0) (void)hipEventDestroy(c->ev_pass0);
     if (c->ev_pass1) (void)hipEventDestroy(c->ev_pass1);
     if (c->ev_pile0) (void)hipEventDestroy(c->ev_pile0);
@@ -1396,6 +1399,91 @@ int raft_hip_fetch_packed(raft_hip_ctx *c, int64_t *cov_offset, uint8_t *cov8, i
 {
     return raft_hip_fetch_packed_w(c, 1, cov_offset, cov8, exc_cap, exc_index, exc_value, n_exc, rep_offset, rep_s, rep_e, frag_offset,
                                    frag_read, frag_begin, frag_end);
+}
+
+// hist[v] = windows of the finished pass with coverage v (cov_hist.hpp), from the form the pass holds: int32, or the codes a width-1 /
+// width-2 pass wrote plus its exception list; a delta4 pass is decoded first.  Nothing of the pass is written, no geometry goes out.
+int raft_hip_cov_histogram(raft_hip_ctx *c, int64_t *hist, double *kernel_seconds)
+{
+    static_assert(kCovHistBins == RAFT_HIP_COV_HIST_BINS, "cov_hist.hpp and raft_hip.h disagree");
+    if (!c || !hist) return RAFT_HIP_ERR_PARAM;
+    if (!c->finished || c->pending_err) return RAFT_HIP_ERR_STATE;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const long long B = c->sum.n_bins;
+    // codes as the pass wrote them (a caller that had them re-encoded in another width since holds the int32 array as well: that one then)
+    const bool codes = (c->pass_width == 1 || c->pass_width == 2) && c->packed_width == c->pass_width;
+    if (!codes) { const int rc = materialise_cov(c); if (rc != RAFT_HIP_OK) return rc; }
+    else if (c->n_exc > c->exc_cap) { c->last_error = "raft_hip_cov_histogram: the pass's exception list is incomplete"; return RAFT_HIP_ERR_DEVICE; }
+    HIP_TRY(c, c->cov_hist.ensure((size_t)kCovHistBins * 8));
+    if (kernel_seconds && !c->ev_hist0) { HIP_TRY(c, hipEventCreate(&c->ev_hist0)); HIP_TRY(c, hipEventCreate(&c->ev_hist1)); }
+    unsigned long long *d_hist = c->cov_hist.as<unsigned long long>();
+    HIP_TRY(c, hipMemsetAsync(d_hist, 0, (size_t)kCovHistBins * 8, c->stream));
+    if (kernel_seconds) HIP_TRY(c, hipEventRecord(c->ev_hist0, c->stream));
+    if (B > 0) {
+        if (!codes) {
+            hipLaunchKernelGGL(cov_hist_kernel<int32_t>, dim3(cov_hist_grid(B / kCovHistLaneWindows<int32_t>, B)), dim3(kCovHistThreads), 0, c->stream,
+                               c->cov.as<int32_t>(), B, d_hist);
+        } else {
+            if (c->pass_width == 1)
+                hipLaunchKernelGGL(cov_hist_kernel<uint8_t>, dim3(cov_hist_grid(B / kCovHistLaneWindows<uint8_t>, B)), dim3(kCovHistThreads), 0, c->stream,
+                                   c->cov8.as<uint8_t>(), B, d_hist);
+            else
+                hipLaunchKernelGGL(cov_hist_kernel<uint16_t>, dim3(cov_hist_grid(B / kCovHistLaneWindows<uint16_t>, B)), dim3(kCovHistThreads), 0, c->stream,
+                                   c->cov8.as<uint16_t>(), B, d_hist);
+            if (c->n_exc > 0)       // (complete: raft_hip_finish runs a pass whose list overflowed again)
+                hipLaunchKernelGGL(cov_hist_exc_kernel, dim3((unsigned)std::min<long long>((c->n_exc + kCovHistThreads - 1) / kCovHistThreads, kCovHistMaxBlocks)),
+                                   dim3(kCovHistThreads), 0, c->stream, c->exc_val.as<int32_t>(), c->n_exc, d_hist);
+        }
+        HIP_TRY(c, hipGetLastError());
+    }
+    if (kernel_seconds) HIP_TRY(c, hipEventRecord(c->ev_hist1, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(hist, d_hist, (size_t)kCovHistBins * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));           // (the one wait of the call: it returns host values)
+    if (kernel_seconds) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_hist0, c->ev_hist1));
+        *kernel_seconds = ms * 1e-3;
+    }
+    return RAFT_HIP_OK;
+}
+
+// The estimate read from a histogram: the mode of the covered, unclamped bins smoothed over three neighbours (see raft_hip.h).
+// Pure host arithmetic; sums are kept in 128 bits so that no count a caller can pass wraps.
+int raft_hip_estimate_coverage(const int64_t *hist, int32_t n_hist, raft_hip_cov_estimate *out)
+{
+    if (!hist || !out || n_hist < 3) return RAFT_HIP_ERR_PARAM;
+    typedef unsigned __int128 u128;
+    u128 total = 0, weighted = 0;
+    for (int32_t v = 0; v < n_hist; ++v) {
+        if (hist[v] < 0) return RAFT_HIP_ERR_PARAM;
+        total += (u128)hist[v];
+        weighted += (u128)hist[v] * (u128)v;
+    }
+    if (total > (u128)INT64_MAX) return RAFT_HIP_ERR_TOO_LARGE;
+    const int n = n_hist;
+    auto c = [&](int v) -> u128 { return v >= 1 && v <= n - 2 ? (u128)hist[v] : (u128)0; };
+    u128 best = 0;
+    int32_t est = 0;
+    for (int v = 1; v <= n - 2; ++v) {
+        const u128 s = c(v - 1) + c(v) + c(v + 1);
+        if (s > best) { best = s; est = v; }          // (strictly greater: the smallest v of a tie stays)
+    }
+    const u128 covered = total - (u128)hist[0];
+    int32_t median = 0;
+    if (covered > 0) {
+        u128 run = 0;
+        for (int v = 1; v < n; ++v) {
+            run += (u128)hist[v];
+            if (2 * run >= covered) { median = v; break; }
+        }
+    }
+    out->est_cov = est;
+    out->median = median;
+    out->windows = (int64_t)total;
+    out->windows_covered = (int64_t)covered;
+    out->windows_clamped = hist[n - 1];
+    out->mean = total > 0 ? (double)weighted / (double)total : 0.0;
+    return RAFT_HIP_OK;
 }
 
 int raft_hip_last_timing(raft_hip_ctx *c, double *pileup_seconds, double *pass_seconds)

@@ -308,6 +308,8 @@ struct raft_hip_ctx {
     DevBuf samples;                   // up to kSamples + 2 read ids at evenly spaced records (guess_runs_kernel): coarse index
     DevBuf in_len, in_col[6];         // staging for raft_hip_run_host
     DevBuf cov8, exc_idx, exc_val, exc_cnt;   // transfer encoding of cov[] (raft_hip_fetch_packed)
+    DevBuf cov_hist;                  // raft_hip_cov_histogram: RAFT_HIP_COV_HIST_BINS 64-bit counts, cleared at every call
+    hipEvent_t ev_hist0 = nullptr, ev_hist1 = nullptr;   // ... and the events around its launches (made at the first call that asks for the time)
     int packed_width = 0;             // width (bytes per window) of the encoding the buffers hold, 0 = none
     long long n_exc = 0, exc_cap = 0;
     int out_width = 4;                // raft_hip_set_output_width: 1 / 2 = the pass writes the encoding, cov[] only on request

@@ -32,8 +32,9 @@ EXPORTS = (
     "raft_hip_run_device_windows", "raft_hip_run_host_windows", "raft_hip_run_multi_windows",
     "raft_hip_fetch_delta4", "raft_hip_packed_anchor_device", "raft_hip_set_emit_cuts", "raft_hip_device_alloc", "raft_hip_device_free", "raft_hip_group_sides", "raft_hip_presplit_symmetric", "raft_hip_presplit_symmetric_local",
     "raft_hip_trim", "raft_hip_pool_bytes", "raft_hip_run_presplit_local", "raft_hip_set_placement", "raft_hip_placement_trial",
-    "raft_hip_set_placement_trial",
+    "raft_hip_set_placement_trial", "raft_hip_cov_histogram", "raft_hip_estimate_coverage",
 )
+COV_HIST_BINS = 4096              # RAFT_HIP_COV_HIST_BINS
 
 
 class _Params(C.Structure):
@@ -74,6 +75,11 @@ class _Received(C.Structure):
                 ("d_qe", C.c_void_p)]
 
 
+class _CovEstimate(C.Structure):
+    _fields_ = [("est_cov", C.c_int32), ("median", C.c_int32), ("windows", C.c_int64), ("windows_covered", C.c_int64),
+                ("windows_clamped", C.c_int64), ("mean", C.c_double)]
+
+
 class _Outputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("cov_offset", "cov", "rep_offset", "rep_s", "rep_e", "cut_offset", "cuts",
                                           "frag_offset", "frag_read", "frag_begin", "frag_end")]
@@ -99,6 +105,17 @@ class Summary:
     error_index: int
     n_devices_used: int = 0
     flags: int = 0                # RAFT_HIP_SUM_* (SUM_* above): bit 0 = the general bucketing handed the pileup kernel window records
+
+
+@dataclass
+class CoverageEstimate:
+    """raft_hip_cov_estimate: what ``estimate_coverage`` reads from a coverage histogram."""
+    est_cov: int                  # the smoothed mode of the covered, unclamped bins; 0 = none
+    median: int                   # lower weighted median over the windows with coverage >= 1 (0 = none)
+    windows: int
+    windows_covered: int
+    windows_clamped: int
+    mean: float
 
 
 class RaftError(RuntimeError):
@@ -188,6 +205,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.raft_hip_presplit_symmetric_local.argtypes = [C.POINTER(vp), i32, C.POINTER(_Records), C.POINTER(i32)]
     lib.raft_hip_packed_device.argtypes = [vp, C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
     lib.raft_hip_selftest.argtypes = [C.c_int]
+    lib.raft_hip_cov_histogram.argtypes = [vp, vp, C.POINTER(C.c_double)]
+    lib.raft_hip_estimate_coverage.argtypes = [vp, i32, C.POINTER(_CovEstimate)]
     if path is None:
         _lib = lib
     return lib
@@ -704,6 +723,29 @@ class Engine:
         return res
 
 
+    # -- the estimated coverage from the data -------------------------------------------
+    last_histogram_seconds = 0.0      # device time of the last coverage_histogram() call's launches
+
+    def coverage_histogram(self) -> np.ndarray:
+        """raft_hip_cov_histogram: int64 [4096], ``hist[v]`` = windows of the finished pass with coverage v (the last bin: >= 4095).
+        Computed on the device from the form the pass wrote; cov[] is not downloaded."""
+        hist = np.zeros(COV_HIST_BINS, np.int64)
+        secs = C.c_double(0.0)
+        self._check(self._lib.raft_hip_cov_histogram(self._ctx, C.c_void_p(hist.ctypes.data), C.byref(secs)))
+        self.last_histogram_seconds = secs.value
+        return hist
+
+    def estimate_from(self, read_len, qid, qs, qe, tid=None, ts=None, te=None) -> "CoverageEstimate":
+        """One pass over the device tensors (``run_device`` + ``finish``), its coverage histogram and the estimate read from it; when
+        there is one (``est_cov > 0``) it becomes the context's est_cov for the passes that follow."""
+        import dataclasses
+        self.run_device(read_len, qid, qs, qe, tid, ts, te)
+        self.finish()
+        est = estimate_coverage(self.coverage_histogram())
+        if est.est_cov > 0:
+            self.set_params(dataclasses.replace(self.params, est_cov=est.est_cov))
+        return est
+
     def packed_device(self) -> dict | None:
         """Zero-copy torch views of the encoding the finished pass holds (raft_hip_packed_device), or None when the pass
         wrote int32: ``cov8`` (uint8; for width 2 the uint16 codes as an int16 tensor -- same bits, ``.view(torch.uint16)`` or
@@ -851,6 +893,19 @@ class Comm:
         if self._comm.value:
             self._lib.raft_hip_comm_destroy(self._comm)
             self._comm = C.c_void_p()
+
+
+def estimate_coverage(hist) -> CoverageEstimate:
+    """raft_hip_estimate_coverage on a histogram whose last bin is the clamp bin (host arithmetic: needs no device)."""
+    h = np.ascontiguousarray(np.asarray(hist), dtype=np.int64)
+    if h.ndim != 1:
+        raise ValueError("estimate_coverage needs a one-dimensional histogram")
+    lib = load_library()
+    e = _CovEstimate()
+    rc = lib.raft_hip_estimate_coverage(C.c_void_p(h.ctypes.data if h.size else 0), int(h.size), C.byref(e))
+    if rc != OK:
+        raise RaftError(rc, lib.raft_hip_strerror(rc).decode())
+    return CoverageEstimate(int(e.est_cov), int(e.median), int(e.windows), int(e.windows_covered), int(e.windows_clamped), float(e.mean))
 
 
 def selftest(device: int = 0) -> int:

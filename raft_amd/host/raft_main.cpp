@@ -33,6 +33,7 @@ struct Params {            // param.hpp:18-31
     double cov_mul = 1.5;
     int repeat_length = 10000, interval_length = 10000, read_length = 20000, overlap_length = 500, flanking_length = 1000;
     std::string prefix = "raft";
+    bool auto_cov = false;         // -e auto: est_cov is read from the data (a survey pass and its coverage histogram) before the job
 };
 
 [[noreturn]] void print_help(const Params &p) // main.cpp:7-19
@@ -76,7 +77,7 @@ int main(int argc, char *argv[])
     while ((option = getopt(argc, argv, "r:e:m:l:i:p:f:v:o:")) != -1) {
         switch (option) {
         case 'r': p.reso = atoi(optarg); break;
-        case 'e': p.est_cov = atoi(optarg); break;
+        case 'e': p.auto_cov = strcmp(optarg, "auto") == 0; p.est_cov = p.auto_cov ? 0 : atoi(optarg); break;
         case 'm': p.cov_mul = std::stod(optarg); break;
         case 'l': p.read_length = atoi(optarg); break;
         case 'p': p.repeat_length = atoi(optarg); p.interval_length = atoi(optarg); break;
@@ -88,13 +89,14 @@ int main(int argc, char *argv[])
         }
     }
     if (argc < optind + 2) print_help(p);
-    if (p.est_cov <= 0) {
+    if (p.est_cov <= 0 && !p.auto_cov) {
         std::cout << "ERROR, main(), estimated coverage must be set properly\n";
         print_help(p);
     }
     // param.hpp:33-43
     std::cout << "INFO, printParams(), reso = " << p.reso << "\n";
-    std::cout << "INFO, printParams(), est_cov = " << p.est_cov << "\n";
+    if (p.auto_cov) std::cout << "INFO, printParams(), est_cov = auto\n";
+    else std::cout << "INFO, printParams(), est_cov = " << p.est_cov << "\n";
     std::cout << "INFO, printParams(), cov_mul = " << p.cov_mul << "\n";
     std::cout << "INFO, printParams(), repeat_length = " << p.repeat_length << "\n";
     std::cout << "INFO, printParams(), interval_length = " << p.interval_length << "\n";
@@ -112,7 +114,8 @@ int main(int argc, char *argv[])
     if (missing_or_empty(paf_fn)) die(std::string("ERROR, break_long_reads(), ") + paf_fn + " input file either does not exist or is empty");
 
     raft_hip_params hp{};
-    hp.reso = p.reso; hp.est_cov = p.est_cov; hp.cov_mul = p.cov_mul; hp.repeat_length = p.repeat_length;
+    hp.reso = p.reso; hp.est_cov = p.auto_cov ? 1 : p.est_cov;   // (-e auto: a placeholder until the survey below -- create rejects 0)
+    hp.cov_mul = p.cov_mul; hp.repeat_length = p.repeat_length;
     hp.interval_length = p.interval_length; hp.read_length = p.read_length; hp.overlap_length = p.overlap_length;
     hp.flanking_length = p.flanking_length; hp.symmetric_mode = -1;
     // stage clock on stderr when RAFT_TIMING is set (stdout stays the reference's)
@@ -242,7 +245,7 @@ int main(int argc, char *argv[])
         for (size_t d = 0; d < devices.size(); ++d) if (create_rc[d] != RAFT_HIP_OK) return;
         pin(exc_i.data(), exc_i.size() * 8); pin(exc_v.data(), exc_v.size() * 4);
         pin(cov_anchor.data(), cov_anchor.size() * 4);
-        pin(cov8.get(), ((size_t)n_win + 1) * (p.est_cov >= 40 ? 2 : 1));
+        pin(cov8.get(), ((size_t)n_win + 1) * (p.auto_cov || p.est_cov >= 40 ? 2 : 1));   // (-e auto: the depth is not known yet)
         pin(fb.get(), ((size_t)frag_cap + 1) * 4); pin(fe.get(), ((size_t)frag_cap + 1) * 4);
         pin(rep_s.get(), ((size_t)rep_cap + 1) * 4); pin(rep_e.get(), ((size_t)rep_cap + 1) * 4);
         pin(cov_off.data(), cov_off.size() * 8); pin(frag_off.data(), frag_off.size() * 8); pin(rep_off.data(), rep_off.size() * 8);
@@ -256,7 +259,7 @@ int main(int argc, char *argv[])
             const int64_t est = pf ? (int64_t)pf.tellg() * (gz ? 4 : 1) / 60 : 0;
             for (size_t d = 0; d < devices.size(); ++d)
                 (void)raft_hip_reserve(ctxs[d], n_reads, rl, est, (int32_t)devices.size(),
-                                       getenv("RAFT_NO_DELTA4") ? (p.est_cov >= 40 ? 2 : 1) : RAFT_HIP_COV_DELTA4);   // (what a hifiasm-shaped PAF will use)
+                                       getenv("RAFT_NO_DELTA4") ? (p.auto_cov || p.est_cov >= 40 ? 2 : 1) : RAFT_HIP_COV_DELTA4);   // (what a hifiasm-shaped PAF will use)
         }
     });
     g_background[3] = &out_prep;
@@ -288,6 +291,56 @@ int main(int argc, char *argv[])
     rc = raft_hip_set_params(ctx, &hp);
     if (rc != RAFT_HIP_OK) die(std::string("ERROR, raft_hip_set_params(), ") + raft_hip_strerror(rc));
     const bool sym = hp.symmetric_mode == 1 || (ranks > 0 && raft_host_paf_symmetric(paf));
+    auto engine_error = [&](int code, int64_t index) {
+        std::string m = std::string("ERROR, raft_hip, ") + raft_hip_strerror(code);
+        if (index >= 0) m += " (index " + std::to_string(index) + ")";
+        const char *d = raft_hip_last_error(ctx);
+        if (d && *d) m += std::string(" [") + d + "]";
+        return m;
+    };
+
+    // -e auto: the survey.  cov[] does not depend on est_cov, so one one-piece pass on the first context under the placeholder holds
+    // the number -e stands for: its coverage histogram is made on the device (32 KiB come back instead of cov[]) and the estimate
+    // read from it (raft_hip.h).  The pass writes two-byte codes and no cut points -- nothing of it is fetched --, and its
+    // overlap_length is 0: which fragments there are depends on the repeats, hence on the placeholder, and RAFT_HIP_ERR_FRAGMENT of
+    // the survey would not be the job's.  Every other data error (ids, coordinates, lengths) is the one the job would report, in
+    // its words.  With several devices or ranks the survey still runs in one piece on the first: one more upload of the columns.
+    if (p.auto_cov) {
+        raft_hip_params sp = hp;
+        sp.overlap_length = 0;
+        const char *we = getenv("RAFT_COV_WIDTH");           // (what the context's width was: 4 unless the test sweeps' variable chose)
+        const int was = we ? atoi(we) : 4;
+        const int width_before = (was == 1 || was == 2 || was == RAFT_HIP_COV_DELTA4) ? was : 4;
+        const bool targets = hp.symmetric_mode != 1;
+        raft_hip_summary ss{};
+        ss.error_index = -1;
+        rc = raft_hip_set_params(ctx, &sp);
+        if (rc == RAFT_HIP_OK) rc = raft_hip_set_output_width(ctx, 2);
+        if (rc == RAFT_HIP_OK) rc = raft_hip_set_emit_cuts(ctx, 0);
+        if (rc == RAFT_HIP_OK)
+            rc = raft_hip_run_host(ctx, n_reads, rl, n_rec, raft_host_paf_column(paf, 0), raft_host_paf_column(paf, 1), raft_host_paf_column(paf, 2),
+                                   targets ? raft_host_paf_column(paf, 3) : nullptr, targets ? raft_host_paf_column(paf, 4) : nullptr,
+                                   targets ? raft_host_paf_column(paf, 5) : nullptr);
+        if (rc == RAFT_HIP_OK) rc = raft_hip_finish(ctx, &ss);
+        if (rc != RAFT_HIP_OK) die(engine_error(rc, ss.error_index));
+        std::vector<int64_t> hist(RAFT_HIP_COV_HIST_BINS);
+        raft_hip_cov_estimate est{};
+        rc = raft_hip_cov_histogram(ctx, hist.data(), nullptr);
+        if (rc == RAFT_HIP_OK) rc = raft_hip_estimate_coverage(hist.data(), RAFT_HIP_COV_HIST_BINS, &est);
+        if (rc == RAFT_HIP_OK) rc = raft_hip_set_output_width(ctx, width_before);
+        if (rc == RAFT_HIP_OK) rc = raft_hip_set_emit_cuts(ctx, 1);
+        if (rc != RAFT_HIP_OK) die(engine_error(rc, -1));
+        stage("estimate");
+        if (est.est_cov <= 0) {                              // no window anybody overlaps: as for -e 0
+            std::cout << "ERROR, main(), estimated coverage must be set properly\n";
+            print_help(p);
+        }
+        fprintf(stdout, "INFO, estimate_coverage(), est_cov = %d\n", est.est_cov);
+        p.est_cov = est.est_cov;
+        hp.est_cov = est.est_cov;
+        rc = raft_hip_set_params(ctx, &hp);                  // (the first context's parameters are what every device and rank runs under)
+        if (rc != RAFT_HIP_OK) die(std::string("ERROR, raft_hip_set_params(), ") + raft_hip_strerror(rc));
+    }
 
     // hifiasm writes its PAF grouped by query (reference README.md:36-38): a symmetric stream of at most four runs sorted by
     // read id is handed over in its grouped form -- per run, where every read's records begin -- and the query column stays
@@ -385,13 +438,7 @@ int main(int argc, char *argv[])
         else if (cov_width == 1 && n_exc > n_win / 16) cov_width = 2;
         else exc_cap = n_exc;
     }
-    if (rc != RAFT_HIP_OK) {
-        std::string m = std::string("ERROR, raft_hip, ") + raft_hip_strerror(rc);
-        if (s.error_index >= 0) m += " (index " + std::to_string(s.error_index) + ")";
-        const char *d = raft_hip_last_error(ctx);
-        if (d && *d) m += std::string(" [") + d + "]";
-        die(m);
-    }
+    if (rc != RAFT_HIP_OK) die(engine_error(rc, s.error_index));
     stage("engine+fetch");
     if (timing) fprintf(stderr, "TIMING devices_used %d input %s\n", s.n_devices_used, ranks > 0 ? "pre-split slices (one exchange step)" : win ? "windows" : (n_runs > 0 ? "grouped" : (sym ? "columns (offsets and window records derived by the engine)" : "columns")));
     if (timing) fprintf(stderr, "TIMING coverage_encoding %s\n", cov_width == RAFT_HIP_COV_DELTA4 ? "delta4" : (cov_width == 2 ? "uint16" : "uint8"));

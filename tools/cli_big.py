@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """The `raft` CLI above toy size, text in -> text out, against the compiled reference on the same files (GPU box).
 
-  python tools/cli_big.py [n_reads=500000] [est_cov=30]
+  python tools/cli_big.py [n_reads=500000] [est_cov=30 | auto]
 
 tools/gen_set.cpp (built here with g++) writes SURVEY's S50k shape at ten times the reads: ~10 GB of FASTA, ~4.6e7 PAF
 records in ~2.7 GB.  Both binaries run on those files; the four output files are compared by md5; the CLI's stage clock
-(RAFT_TIMING=1) and the reference's wall time are printed.  Keep the output under profiles/."""
+(RAFT_TIMING=1) and the reference's wall time are printed.  est_cov = auto: the CLI runs with `-e auto` (stage `estimate` of its
+clock is the survey) and the reference with the N it printed.  Keep the output under profiles/."""
 import hashlib
 import os
 import shutil
@@ -15,7 +16,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 n_reads = int(sys.argv[1]) if len(sys.argv) > 1 else 500_000
-est_cov = int(sys.argv[2]) if len(sys.argv) > 2 else 30
+est_cov = sys.argv[2] if len(sys.argv) > 2 else "30"       # a number, or "auto"
 
 
 def md5_of(path):
@@ -47,6 +48,7 @@ try:
     print(f"reads.fa {os.path.getsize(fa) / 1e9:.2f} GB, overlaps.paf {os.path.getsize(paf) / 1e9:.2f} GB")
     n_rec = int(r.stderr.decode().split()[-2])
     runs = {}
+    found = None                                            # -e auto: the estimate the CLI printed
     for tag, exe, env in (("raft_amd (MI355X)", os.path.join(ROOT, "raft_amd", "bin", "raft"), {"RAFT_TIMING": "1"}),
                           ("raft_amd, second run (page cache warm)", os.path.join(ROOT, "raft_amd", "bin", "raft"), {"RAFT_TIMING": "1", "RAFT_PIPE_TRACE": "1"}),
                           ("reference (oracle/_ref/raft, 1 thread)", os.path.join(ROOT, "oracle", "_ref", "raft"), {})):
@@ -56,7 +58,10 @@ try:
         out = os.path.join(work, "out_" + ("ref" if "reference" in tag else "gpu"))
         os.makedirs(out, exist_ok=True)
         t0 = time.perf_counter()
-        p = subprocess.run([exe, "-e", str(est_cov), "-o", "x", fa, paf], cwd=out, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=dict(os.environ, **env))
+        if est_cov == "auto" and "reference" in tag and found is None:
+            print(f"{tag}: no estimate to run it with -- skipped")
+            continue
+        p = subprocess.run([exe, "-e", found if (est_cov == "auto" and "reference" in tag) else est_cov, "-o", "x", fa, paf], cwd=out, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=dict(os.environ, **env))
         wall = time.perf_counter() - t0
         t_end = time.time()
         print(f"\n== {tag}: exit {p.returncode}, wall {wall:.2f} s")
@@ -72,8 +77,10 @@ try:
                     sec = float(ln.split()[2])
                     print(f"   -> engine+fetch: {n_rec / sec:.3e} PAF records/s (upload, passes and download of every chunk overlapped)")
         for ln in p.stdout.decode().splitlines():
-            if ln.startswith(("INFO, Symmetric", "INFO, length", "high_cov", "coverage per window", "fraction_of")):
+            if ln.startswith(("INFO, Symmetric", "INFO, length", "high_cov", "coverage per window", "fraction_of", "INFO, estimate_coverage")):
                 print("   " + ln)
+            if ln.startswith("INFO, estimate_coverage(), est_cov = "):
+                found = ln.split("=")[1].strip()
         if p.returncode != 0:
             print(p.stdout.decode()[-2000:], p.stderr.decode()[-2000:])
         runs[tag] = {f: md5_of(os.path.join(out, f)) for f in sorted(os.listdir(out))}
