@@ -1,9 +1,13 @@
 // engine_ctx.hpp -- what the engine's translation units share: the context (one device + its streams and grow-only buffers), the
 // device buffers with their placement (virtual ranges over pooled 32 MiB chunks), the control block, error plumbing.
-//   engine.hip            context life cycle, one pass (run_pass), finish / fetch / encodings -- and every kernel header
+//   engine.hip            context life cycle, one pass (run_pass), finish / fetch / encodings -- and every kernel header.
+//                         run_pass is a sequence of phases over one plain PassPlan: read_switches, resolve_input, reset_and_decide,
+//                         open_pass, find_sizes, choose_quantum, ensure_buffers, launch_head, decide_source, fill_pileup_args,
+//                         interval_source (bucket_sides), launch_pileup, launch_tail; raft_hip_finish is wait_for_pass, rerun_ladder,
+//                         collect_summary
 //   engine_pipeline.hip   the host-to-host entry points: chunked upload / pass / download, several contexts, routed streams
 //   engine_exchange.hip   pre-split PAF: symmetric flag across ranks, grouped sides, the exchange (RCCL / peer copies), the pre-split job
-//   engine_placement.hip  where buffers lie: pool, trim, policy, the callers' input buffers, page-locking
+//   engine_placement.hip  where buffers lie: pool, trim, policy, the placement trial, the callers' input buffers, page-locking
 #pragma once
 #include "../../include/raft_hip.h"
 #include "raft_types.hpp"
@@ -31,7 +35,7 @@ namespace raft {
 constexpr int kTileCap = kWaveSlots - 4;
 constexpr int kWaveCounters = 32;      // tile hand-out counters of the wave kernel, 256 bytes apart (pileup_wave.hpp next_range)
 constexpr int kWinMaxRuns = 2;         // runs the window-record instantiations (pileup_wave.hpp IN = 1) take; more: unpacked to coordinate columns first
-// coverage arrays a context's placement trial compares (run_pass): off unless asked for -- RAFT_PLACEMENT_TRIALS=<k>, k >= 2, or
+// coverage arrays a context's placement trial compares (placement_trial): off unless asked for -- RAFT_PLACEMENT_TRIALS=<k>, k >= 2, or
 // raft_hip_set_placement_trial
 inline int default_trial_candidates()
 {
@@ -128,6 +132,11 @@ struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
     bool big = false;                 // may be backed by pooled chunks
+    static constexpr bool kBig = true;
+    DevBuf() = default;
+    // a context's buffer says so where it is declared: raft_hip_destroy releases what the list names.  (Only the declared object is
+    // on the list: copies and swaps move contents, `big` with them, and leave the list alone.)
+    explicit DevBuf(std::vector<DevBuf *> &owner, bool big_ = false) : big(big_) { owner.push_back(this); }
     int dev = 0;                      // device of the chunks
     std::vector<hipMemGenericAllocationHandle_t> chunks;
     std::vector<size_t> map_order;    // chunk mapped at the i-th 32 MiB of the range
@@ -279,36 +288,39 @@ using namespace raft;
 struct raft_hip_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
-    hipStream_t side_stream = nullptr;   // the general pileup kernel runs beside the fast one
+    hipStream_t side_stream = nullptr;   // the per-read geometry scan of a pass that waits for its sizes runs here, beside the look at the records (find_sizes)
     bool counted = false;                // this context is one of ChunkPool::live_ctx
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_ifork = nullptr;
+    hipEvent_t ev_ifork = nullptr, ev_gjoin = nullptr;   // ... forked from the main stream and joined to it
     raft_hip_params prm{};
     int32_t high_cov = 0, div = 0, minbins = 1;
     int32_t tile_q = 0;               // 0 = variant default
     int32_t force_bucket = 0;
     bool no_bucket_win = false;       // general bucketing: a side's windows did not fit 16 bits once (kErrWide): coordinate pairs from then on
-    size_t cov_trial_cap = 0;         // capacity of `cov` the placement trial has been run for (run_pass)
+    size_t cov_trial_cap = 0;         // capacity of `cov` the placement trial has been run for (placement_trial)
     double trial_ms[2] = {0.0, 0.0};  // that trial: the pileup kernel into `cov` as first placed / into the best of the other candidates (ms)
     int32_t trial_kept = 0;           // 0: the first placement stayed, 1: a plain hipMalloc block was kept, 2: another chunk mapping
     int32_t trial_candidates = default_trial_candidates();   // coverage arrays the placement trial compares; < 2: no trial (the default)
     std::string last_error;
 
-    // device buffers
-    DevBuf deep_list;                 // tiles too deep for 16-bit coverage (pileup_deep.hpp)
+    // device buffers: each is declared with the list (`bufs`: what raft_hip_destroy releases) and, where a pass streams through
+    // it, as kBig (see DevBuf) -- the one place that names a context's buffers
+    std::vector<DevBuf *> bufs;
+    DevBuf len_seen{bufs};            // the read lengths as the last geometry scan saw them (see geom_id below)
+    DevBuf deep_list{bufs};           // tiles too deep for 16-bit coverage (pileup_deep.hpp)
     long long deep_cap = 1024;        // its entries; grows when a pass lists more (raft_hip_finish)
-    DevBuf tail_buf;                  // the fused tail's sums (finalize.hpp FinalizeArgs::tail_part ...)
-    DevBuf wave_ctr, ctrl, scan_tmp, cov_off, rep_res_off, tile_first, tile_cuts, block_sums;
-    DevBuf cov, rep_cnt, raw_key, raw_s, raw_e, cut_cnt, frag_cnt, rep_off, cut_off, frag_off;
-    DevBuf rep_s, rep_e, cuts, frag_read, frag_begin, frag_end;
-    DevBuf b_cnt, b_off, b_rid, b_s, b_e;
-    DevBuf gs_rid, gs_s, gs_e, gs_off, gs_err;  // raft_hip_group_sides: the slice it hands back (+ its error word)
+    DevBuf tail_buf{bufs};            // the fused tail's sums (finalize.hpp FinalizeArgs::tail_part ...)
+    DevBuf wave_ctr{bufs}, ctrl{bufs}, scan_tmp{bufs}, cov_off{bufs}, rep_res_off{bufs}, tile_first{bufs}, tile_cuts{bufs}, block_sums{bufs};
+    DevBuf cov{bufs, DevBuf::kBig}, rep_cnt{bufs}, raw_key{bufs, DevBuf::kBig}, raw_s{bufs, DevBuf::kBig}, raw_e{bufs, DevBuf::kBig}, cut_cnt{bufs}, frag_cnt{bufs};
+    DevBuf rep_off{bufs}, cut_off{bufs}, frag_off{bufs};
+    DevBuf rep_s{bufs, DevBuf::kBig}, rep_e{bufs, DevBuf::kBig}, cuts{bufs, DevBuf::kBig};
+    DevBuf frag_read{bufs, DevBuf::kBig}, frag_begin{bufs, DevBuf::kBig}, frag_end{bufs, DevBuf::kBig};
+    DevBuf b_cnt{bufs}, b_off{bufs}, b_rid{bufs, DevBuf::kBig}, b_s{bufs, DevBuf::kBig}, b_e{bufs, DevBuf::kBig};
+    DevBuf gs_rid{bufs, DevBuf::kBig}, gs_s{bufs, DevBuf::kBig}, gs_e{bufs, DevBuf::kBig}, gs_off{bufs}, gs_err{bufs};  // raft_hip_group_sides: the slice it hands back (+ its error word)
     std::vector<long long> gs_off_host;
-    DevBuf rs_k0, rs_k1, rs_v0, rs_v1, gaps;   // general streams, large inputs: (read id, start | end << 32) per side, before and after the radix sort; long runs of reads without intervals
-    DevBuf samples;                   // up to kSamples + 2 read ids at evenly spaced records (guess_runs_kernel): coarse index
-    DevBuf in_len, in_col[6];         // staging for raft_hip_run_host
-    DevBuf cov8, exc_idx, exc_val, exc_cnt;   // transfer encoding of cov[] (raft_hip_fetch_packed)
-    DevBuf cov_hist;                  // raft_hip_cov_histogram: RAFT_HIP_COV_HIST_BINS 64-bit counts, cleared at every call
+    // general streams, large inputs: (read id, start | end << 32) per side, before and after the radix sort; long runs of reads without intervals
+    DevBuf rs_k0{bufs, DevBuf::kBig}, rs_k1{bufs, DevBuf::kBig}, rs_v0{bufs, DevBuf::kBig}, rs_v1{bufs, DevBuf::kBig}, gaps{bufs};
+    DevBuf in_len{bufs};              // staging for raft_hip_run_host: the read lengths (the columns: in_col below)
+    DevBuf samples{bufs};             // up to kSamples + 2 read ids at evenly spaced records (guess_runs_kernel): coarse index
     hipEvent_t ev_hist0 = nullptr, ev_hist1 = nullptr;   // ... and the events around its launches (made at the first call that asks for the time)
     int packed_width = 0;             // width (bytes per window) of the encoding the buffers hold, 0 = none
     long long n_exc = 0, exc_cap = 0;
@@ -317,7 +329,6 @@ struct raft_hip_ctx {
     bool cov_valid = false;           // c->cov holds the int32 array of the last pass
     void *pinned = nullptr;           // small pinned scratch for readbacks
     long long *pinned_dev = nullptr;  // the same block as the device addresses it
-    hipEvent_t ev_gjoin = nullptr;
     hipEvent_t ev_pass0 = nullptr, ev_pass1 = nullptr, ev_pile0 = nullptr, ev_pile1 = nullptr;
 
     // chunked host pipeline (raft_hip_run_pipelined): sub-contexts on the same device, one upload stream
@@ -337,25 +348,28 @@ struct raft_hip_ctx {
     } args{};
     bool grouped = false;              // the last pass was built on the caller's offsets (verified in its kernels)
     bool no_wait = false;              // ... and sized by the caller's window count: nothing was read back on the way
-    DevBuf exp_qid, in_off;            // grouped input without a query column: the ids rebuilt from the offsets; staged offsets
-    DevBuf m_off;                      // grouped input of more than kMaxSeg runs: offsets of the merged run
-    DevBuf u_s, u_e;                   // window records unpacked for the passes that need coordinate columns
-    DevBuf cov_anchor, abs_bits;       // delta4 encoding of cov[] (pack.hpp): block anchors; escape flags of the device-side decoder
-    DevBuf exc_idx2, exc_val2, sort_tmp;   // the exception list in ascending order (sort_exceptions)
-    DevBuf exc_pidx, exc_pval, exc_tile_n; // delta4: the windows each tile lists, kExcPerTile slots per tile (compact_exceptions_kernel)
+    DevBuf exp_qid{bufs, DevBuf::kBig}, in_off{bufs};   // grouped input without a query column: the ids rebuilt from the offsets; staged offsets
+    DevBuf m_off{bufs};                // grouped input of more than kMaxSeg runs: offsets of the merged run
+    DevBuf u_s{bufs, DevBuf::kBig}, u_e{bufs, DevBuf::kBig};   // window records unpacked for the passes that need coordinate columns
+    DevBuf cov_anchor{bufs}, abs_bits{bufs};   // delta4 encoding of cov[] (pack.hpp): block anchors; escape flags of the device-side decoder
+    DevBuf exc_idx2{bufs}, exc_val2{bufs}, sort_tmp{bufs};   // the exception list in ascending order (sort_exceptions)
+    DevBuf exc_pidx{bufs}, exc_pval{bufs}, exc_tile_n{bufs};   // delta4: the windows each tile lists, kExcPerTile slots per tile (compact_exceptions_kernel)
     bool exc_sorted = false;
     long long sizes_seq = 0;           // number of the last sizes hand-over of run_pass (publish_sizes_kernel)
     long long pass_seq = 0;            // number of the pass whose closing kernel is queued (written behind the control block when it is through)
     bool seq_armed = false;
     int d4_shift = 0;                  // delta4 on a chunk of a larger array (the host pipelines' lanes): windows of the block its first window lies in that precede it
-    DevBuf x_qs, x_qe, x_off, x_raw, x_send_off, x_cnt;   // pre-split exchange (raft_hip_exchange*): what this rank received / staged
+    DevBuf x_qs{bufs}, x_qe{bufs}, x_off{bufs}, x_raw{bufs}, x_send_off{bufs}, x_cnt{bufs};   // pre-split exchange (raft_hip_exchange*): what this rank received / staged
+    DevBuf cov8{bufs, DevBuf::kBig}, exc_idx{bufs}, exc_val{bufs}, exc_cnt{bufs};   // transfer encoding of cov[] (raft_hip_fetch_packed)
+    DevBuf cov_hist{bufs};             // raft_hip_cov_histogram: RAFT_HIP_COV_HIST_BINS 64-bit counts, cleared at every call
+    DevBuf in_col[6] = {DevBuf{bufs, DevBuf::kBig}, DevBuf{bufs, DevBuf::kBig}, DevBuf{bufs, DevBuf::kBig},
+                        DevBuf{bufs, DevBuf::kBig}, DevBuf{bufs, DevBuf::kBig}, DevBuf{bufs, DevBuf::kBig}};   // staging for raft_hip_run_host: the columns
 
     // state of the last pass
     bool ran = false, finished = false;
     int pending_err = RAFT_HIP_OK;
     long long pending_err_index = -1;
     raft_hip_summary sum{};
-    long long cap_rep = 0, cap_cut = 0;
     FinalizeArgs fa{};                // of the last pass (the cut points are materialised on demand)
     bool cuts_ready = false;
     bool is_lane = false;              // a sub-context of a host pipeline (prepare_lanes)
@@ -367,7 +381,7 @@ struct raft_hip_ctx {
     // shape is built on it without the host wait and verifies it on the device
     struct Shape {
         bool valid = false;
-        int32_t n_reads = 0, reso = 0, minbins = 0, interval_length = 0, symmetric_mode = 0, variant = 0, tile_q = 0;
+        int32_t n_reads = 0, reso = 0, minbins = 0, interval_length = 0, symmetric_mode = 0, tile_q = 0;
         int64_t n_rec = 0;
         const void *len = nullptr, *qid = nullptr;
         long long B = 0, RU = 0, CU = 0;
@@ -379,7 +393,6 @@ struct raft_hip_ctx {
     // The per-read geometry of a pass depends on the read lengths and the parameters alone.  A speculative pass over the same reads
     // keeps what the context holds (geom_id says that nobody has written the arrays since) and only compares the lengths with the copy
     // the scan left (len_seen): one kernel over 8 bytes per read where the scan's two halves ran over the reads twice.
-    DevBuf len_seen;
     unsigned long long geom_id = 0;
     bool speculated = false;           // the pass in flight was built on `shape`
     bool deep_skipped = false;         // ... and without a launch of pileup_deep_kernel (a deep tile then refutes it: kErrDeep)
@@ -438,14 +451,8 @@ inline int code_from_flags(int flags)
 // ---- what engine.hip provides to the other translation units
 void launch_rebase_ids(hipStream_t st, int32_t *ids, long long n, int32_t base);                 // ids[i] -= base (pack.hpp rebase_ids_kernel)
 void launch_add_base(hipStream_t st, long long *a, long long n, long long base);                 // a[i] += base (pack.hpp add_base_kernel)
-
-} // namespace raft
-
-// (C linkage only because their definitions sit among the ABI's entry points, inside engine.hip's extern "C" block; none of them is
-// exported: raft_amd/csrc/exports.map)
-extern "C" {
 int run_pass(raft_hip_ctx *c, const raft_hip_ctx::PassArgs &in, bool verify_in_kernels);
-raft::Ctrl host_ctrl(const raft_hip_ctx *c);       // the control block as the last pass's closing kernel handed it over
+Ctrl host_ctrl(const raft_hip_ctx *c);             // the control block as the last pass's closing kernel handed it over
 int sort_sides(raft_hip_ctx *c, hipStream_t st, long long n_rec, int32_t n_reads, int symmetric, const int32_t *d_qid, const int32_t *d_qs,
                const int32_t *d_qe, const int32_t *d_tid, const int32_t *d_ts, const int32_t *d_te, long long cap_iv, int32_t *o_rid, int32_t *o_s,
                int32_t *o_e, long long *off, int32_t *err_flags, long long *err_index);
@@ -457,4 +464,9 @@ int sort_exceptions(raft_hip_ctx *c);
 int fetch_packed_impl(raft_hip_ctx *c, int32_t width, int64_t *cov_offset, void *cov_packed, int32_t *cov_anchor, int64_t exc_cap, int64_t *exc_index,
                       int32_t *exc_value, int64_t *n_exc, int64_t *rep_offset, int32_t *rep_s, int32_t *rep_e,
                       int64_t *frag_offset, int32_t *frag_read, int32_t *frag_begin, int32_t *frag_end);
-}
+
+// ---- what engine_placement.hip provides: the pileup kernel into K candidate coverage arrays, the fastest kept (called by run_pass's
+// pileup phase between ev_pile0 and ev_pile1, with the arguments of the launch it has just made)
+int placement_trial(raft_hip_ctx *c, hipStream_t st, const PileupArgs &pa, int ow, bool win, int n_waves, long long N);
+
+} // namespace raft

@@ -1,7 +1,87 @@
 // engine_placement.hip -- where buffers lie: the per-device pool of physical chunks (trim, what it holds), the placement policy, the
-// placement trial's report, device memory for the callers' input columns, page-locking of caller memory.  The buffers themselves
+// placement trial and its report, device memory for the callers' input columns, page-locking of caller memory.  The buffers themselves
 // (DevBuf: virtual ranges over pooled chunks) are in engine_ctx.hpp; DESIGN.md I.4 says why any of this exists.
 #include "engine_ctx.hpp"
+
+namespace raft {
+
+// ---- where the coverage array lies, decided by measurement: OPT-IN (raft_hip_set_placement_trial / RAFT_PLACEMENT_TRIALS=<k>;
+// round 5 ran it by default, round 6 does not: the driver's own A/B showed 0.2 % between the policies, and a one-shot caller
+// paid 2 K - 1 extra launches and K - 1 coverage-sized allocations for nothing).  What this kernel gets from the part follows
+// the array it stores into, and not by the KIND of memory: two hipMalloc blocks of one process gave 2.24 and 2.63 ms, two chunk
+// mappings 2.49 and 2.67.  A context that asked for a trial draws K - 1 more arrays at the first pass that makes
+// a coverage array of a GiB or more -- plain blocks and chunk mappings in turn, each only while the device keeps its reserve
+// free behind it --, runs the kernel into each of them warm, and keeps the one it was fastest with.
+// Called by run_pass right behind the pass's own launch of the pileup kernel, with that launch's arguments.
+int placement_trial(raft_hip_ctx *c, hipStream_t st, const PileupArgs &pa, int ow, bool win, int n_waves, long long N)
+{
+    const int kTrials = c->trial_candidates;
+    Ctrl *ctrl = c->ctrl.as<Ctrl>();
+    c->cov_trial_cap = c->cov.cap;
+    struct TrialGuard {                       // every way out of this function releases the candidates and the events
+        std::vector<DevBuf> cand;
+        std::vector<hipEvent_t> ev;
+        ~TrialGuard()
+        {
+            for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+            for (DevBuf &b : cand) b.release();
+        }
+    } tg;
+    tg.cand.resize((size_t)kTrials - 1);
+    tg.ev.assign((size_t)2 * kTrials, nullptr);
+    std::vector<DevBuf> &cand = tg.cand;
+    std::vector<hipEvent_t> &ev = tg.ev;
+    int n_cand = 0;
+    for (int k = 0; k + 1 < kTrials; ++k) {
+        // a candidate is drawn only while an eighth of the device's memory (8 GiB at least) stays free behind it: the same
+        // reserve map_chunks keeps for its spare chunks (torch, RCCL and other processes live there)
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); break; }
+        if (free_b < c->cov.cap + std::max<size_t>(size_t(8) << 30, total_b / 8)) break;
+        cand[(size_t)k].big = (k & 1) != 0;       // plain block, chunk mapping, plain block, ...
+        if (cand[(size_t)k].ensure(c->cov.cap) != hipSuccess) { (void)hipGetLastError(); break; }
+        ++n_cand;
+    }
+    bool ok = n_cand > 0;
+    for (size_t i = 0; ok && i < ev.size(); ++i) ok = hipEventCreate(&ev[i]) == hipSuccess;
+    if (!ok) return RAFT_HIP_OK;
+    // (the pass's own launch was the context's first -- code going to the device, cold translations: 3 ms, or 200 -- and says
+    // nothing; the first run into an array pays for its first touch; the second is the measurement.  What a run leaves
+    // behind and the next must not see: the reads' repeat counters, the hand-out counters)
+    auto one_run = [&](int32_t *cov_p, hipEvent_t e0, hipEvent_t e1) -> int {
+        PileupArgs x = pa;
+        x.cov = cov_p;
+        HIP_TRY(c, hipMemsetAsync(c->rep_cnt.p, 0, (size_t)std::max(N, 1LL) * 4, st));
+        HIP_TRY(c, hipMemsetAsync(c->wave_ctr.p, 0, (size_t)kWaveCounters * kCtrStride * 4, st));
+        HIP_TRY(c, hipMemsetAsync(&ctrl->n_deep, 0, 4, st));
+        if (e0) HIP_TRY(c, hipEventRecord(e0, st));
+        launch_wave_variant(ow, win, st, x.n_seg, c->tile_cuts.p, &x, n_waves);
+        if (e1) HIP_TRY(c, hipEventRecord(e1, st));
+        return RAFT_HIP_OK;
+    };
+    int trc = RAFT_HIP_OK;
+    for (int k = 0; k < n_cand && trc == RAFT_HIP_OK; ++k) trc = one_run(cand[(size_t)k].as<int32_t>(), nullptr, nullptr);
+    if (trc == RAFT_HIP_OK) trc = one_run(c->cov.as<int32_t>(), ev[0], ev[1]);
+    for (int k = 0; k < n_cand && trc == RAFT_HIP_OK; ++k) trc = one_run(cand[(size_t)k].as<int32_t>(), ev[(size_t)2 * k + 2], ev[(size_t)2 * k + 3]);
+    if (trc != RAFT_HIP_OK) { (void)hipStreamSynchronize(st); return trc; }      // (nothing in flight may still use a candidate)
+    HIP_TRY(c, hipEventSynchronize(ev[(size_t)2 * n_cand + 1]));
+    float best = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&best, ev[0], ev[1]));
+    c->trial_ms[0] = best; c->trial_ms[1] = 0.0;
+    int keep = -1;
+    for (int k = 0; k < n_cand; ++k) {
+        float t = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&t, ev[(size_t)2 * k + 2], ev[(size_t)2 * k + 3]));
+        if (c->trial_ms[1] == 0.0 || t < c->trial_ms[1]) c->trial_ms[1] = t;
+        if (t < best * 0.985f) { best = t; keep = k; }      // (a candidate has to win by more than the noise of two launches)
+    }
+    c->trial_kept = keep >= 0 ? (cand[(size_t)keep].big ? 2 : 1) : 0;
+    if (keep >= 0) { std::swap(c->cov, cand[(size_t)keep]); c->cov_trial_cap = c->cov.cap; }
+    // (whichever array is kept holds this pass's coverage: every run wrote all of it)
+    return RAFT_HIP_OK;
+}
+
+} // namespace raft
 
 extern "C" {
 

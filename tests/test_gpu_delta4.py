@@ -154,6 +154,7 @@ def test_exception_list_overflow_and_empty_inputs():
     d4 = eng.fetch_delta4()
     check_encoding(d4, want, "one-window reads")
     assert d4["exc_index"].size == n > max(4096, n // 64)            # (more than the first list's room: the pass ran twice)
+    assert s.flags & engine.SUM_RERUN, s.flags
     assert_same_result(result_of(eng, s), want, "one-window reads, decoded on the device")
     o = make_overlaps(n_reads=1500, seed=16, mean_len=12000.0, coverage=400.0, n_families=0)
     cols = [c.numpy() for c in (o.read_len,) + o.columns()]

@@ -36,6 +36,7 @@ def result_of(eng, s):
 def grouped_runs(eng, p, rl, qid, qs, qe, off, want, what, with_host=True):
     """Every form of the grouped entry on one context; each must equal `want`."""
     import torch
+    from raft_amd import engine
     dev = "cuda:0"
     t = lambda a, dt=torch.int32: torch.as_tensor(np.ascontiguousarray(a)).to(dt).to(dev)
     d_rl, d_q, d_s, d_e, d_off = t(rl), t(qid), t(qs), t(qe), t(off, torch.int64)
@@ -46,6 +47,7 @@ def grouped_runs(eng, p, rl, qid, qs, qe, off, want, what, with_host=True):
         eng.run_device_grouped(d_rl, d_off, kw["qid"], d_s, d_e, n_bins=kw["n_bins"])
         s = eng.finish()
         assert_same_result(result_of(eng, s), want, f"{what}: {form}")
+        assert kw["n_bins"] in (B, -1) or s.flags & engine.SUM_RERUN, (what, form, s.flags)   # a wrong count: the pass again, sized by the device
         assert s.interval_path == 0 and s.n_segments == off.shape[0] and s.n_bins == B
     if with_host:
         eng.run_host_grouped(rl, off, qs, qe)
@@ -144,6 +146,7 @@ def test_offsets_that_disagree_with_the_query_column_and_bad_offsets():
         eng.run_device_grouped(d[0], t(wrong, torch.int64), d[1], d[2], d[3], n_bins=hint)
         s = eng.finish()
         assert_same_result(result_of(eng, s), want, f"wrong offsets, hint {hint}")
+        assert s.flags & engine.SUM_RERUN, (hint, s.flags)
     # (b) offsets that step back / do not start at 0 / do not end at n_rec
     for what, mut in (("step back", lambda x: x.__setitem__((0, 100), x[0, 101] + 5)),
                       ("start", lambda x: x.__setitem__((0, 0), 1)),

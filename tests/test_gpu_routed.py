@@ -162,6 +162,7 @@ def test_large_shuffled_stream_buckets_window_records_or_coordinate_pairs(shape,
             got.update(symmetric=s.symmetric, high_cov=s.high_cov, total_coverage=s.total_coverage, total_windows=s.total_windows,
                        total_repeat_length=s.total_repeat_length, total_read_length=s.total_read_length)
             assert_same_result(got, want, f"{shape} pairs={force_pairs} pass {rep}")
+            assert not (wide and not force_pairs and rep == 0) or s.flags & engine.SUM_RERUN, s.flags   # kErrWide: run again with pairs
             assert s.interval_path == 1 and s.n_intervals == int((qid != tid).sum()) + n
         if shape == "errors":
             b2 = tb.copy(); b2[4242] = rl[tid[4242]] + 9000

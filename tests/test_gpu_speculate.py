@@ -106,6 +106,7 @@ def test_a_stream_that_is_not_what_was_assumed_is_run_the_long_way(what):
         # (lengths that leave every window count alone refute the pass only where it kept the geometry it held: with
         # RAFT_NO_KEEP_GEOMETRY=1 the scan runs over the new lengths and the pass stands)
         assert what == "same_windows" or not (s.flags & SPECULATED)
+        assert bool(s.flags & engine.SUM_RERUN) != bool(s.flags & SPECULATED), (what, s.flags)   # refuted: run again, nothing remembered
         assert_same_result(_result(eng, s), want, what)
         # ... and the context is itself again afterwards
         eng.run_device(*dev); s = eng.finish()
