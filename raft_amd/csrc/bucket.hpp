@@ -82,6 +82,17 @@ __global__ __launch_bounds__(256) void inspect_kernel(long long n_rec, int32_t n
     }
 }
 
+// inspect_kernel reads the target column only beside a query that matches tid[0].  Once it has named a record whose QUERY id is out of
+// range, this looks at the targets of the n records before it: the error's index is the first record with either id out of range,
+// as in the oracle (and as the bucketing kernels report it, which look at both sides).  The error path only.
+__global__ __launch_bounds__(256) void first_bad_target_kernel(long long n, int32_t n_reads, const int32_t *tid, long long *err_index)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int32_t t = tid[i];
+        if (t < 0 || t >= n_reads) atomicMin((unsigned long long *)err_index, (unsigned long long)i);
+    }
+}
+
 // Sorted runs of the record stream as up to 256 k evenly spaced samples show them: where one sample is smaller than the one
 // before, a run ends in between, and a bisection (left part >= the earlier sample, right part below it) finds the first
 // record of the next run.  inspect_kernel, which looks at every record, confirms or refutes it.

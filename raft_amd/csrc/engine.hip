@@ -621,7 +621,8 @@ static void launch_head(raft_hip_ctx *c, const raft_hip_ctx::PassArgs &in, PassP
 
 // Where the pileup kernel's intervals will come from, as far as the host can say: the runs of the stream (as the offsets, the
 // remembered shape, the samples or inspect_kernel name them), whether the targets' sides exist -- and what the context remembers of
-// it for the next pass.  No launch; an input error inspect_kernel reported ends the pass here.
+// it for the next pass.  No launch on a clean stream; an input error inspect_kernel reported ends the pass here (an id out of range:
+// after one look at the targets of the records before it, first_bad_target_kernel).
 static int decide_source(raft_hip_ctx *c, PassPlan &P)
 {
     const InspectOut *hi = P.hi();
@@ -640,7 +641,18 @@ static int decide_source(raft_hip_ctx *c, PassPlan &P)
             return RAFT_HIP_OK;
         }
     } else if (P.n_rec > 0) {
-        if (hi->err_flags) return park_input_error(c, P, hi->err_flags, hi->err_index);
+        if (hi->err_flags) {
+            long long index = hi->err_index;
+            // inspect_kernel has looked at the query ids alone: unless the caller says the targets' sides do not exist, an earlier
+            // record may name a target out of range (the control block's word still holds the index; the next pass clears it)
+            if ((hi->err_flags & kErrReadId) && c->prm.symmetric_mode != 1 && index > 0 && index <= (long long)P.n_rec) {
+                hipLaunchKernelGGL(first_bad_target_kernel, dim3(grid_for(index, 256, 1024)), dim3(256), 0, P.st, index, P.n_reads, P.d_tid, &P.ctrl->insp.err_index);
+                HIP_TRY(c, hipGetLastError());
+                HIP_TRY(c, hipMemcpyAsync(&index, &P.ctrl->insp.err_index, 8, hipMemcpyDeviceToHost, P.st));
+                HIP_TRY(c, hipStreamSynchronize(P.st));
+            }
+            return park_input_error(c, P, hi->err_flags, index);
+        }
         if (c->prm.symmetric_mode < 0) { P.symmetric = hi->sym_found ? 1 : 0; c->assume_sym = P.symmetric != 0; }
         P.n_desc = hi->n_desc;
         for (int i = 0; i < std::min(P.n_desc, kMaxSeg); ++i) P.desc[i] = hi->desc_pos[i];

@@ -771,3 +771,499 @@ def lattice_census(case, want):
         out[("block", -1, "end", d)] = int(np.sum(e % D4_BLOCK == D4_BLOCK - 1))
         out[("block", -1, "begin", d)] = int(np.sum(b % D4_BLOCK == 0))
     return out
+
+
+# ---- the general bucketing's sorts: sides of a record stream by read id (sort_pairs.hpp:101-423, bucket.hpp:353-604) -------------------
+# A shuffled, non-symmetric or many-file stream reaches the pileup kernels through engine.hip bucket_sides: a counting sort below
+# SORT_THRESHOLD interval slots, above it the LSD radix sort of (key, 64-bit value) pairs in PAIR_TILE-pair tiles or of 64-bit window
+# records in ITEM_TILE-item tiles; unzip_*_kernel then rebuilds the reads' offsets, a run of more than GAP_INLINE - 1 reads without
+# sides through a list of GAP_LIST entries.  The constants below are what the cases are laid on; tests/test_bucket_sort_cases.py reads
+# them back from the sources, so that a retune fails there instead of moving the edges away from the cases.
+RS_WAVES, PAIR_IPT, ITEM_IPT = 4, 16, 32
+PAIR_TILE = 64 * RS_WAVES * PAIR_IPT          # 4096 pairs: a tile of radix_sort_by_key<64-bit value> (Engine.group_sides, sort_sides)
+ITEM_TILE = 64 * RS_WAVES * ITEM_IPT          # 8192 items: a tile of radix_sort_items (sort_sides_win)
+RS_SEGS = 256                                 # segments of the digit table's scan: L = ceil(tiles / RS_SEGS) tiles per segment
+GAP_INLINE, GAP_LIST = 32, 1024               # a gap of GAP_INLINE reads or more is listed while the list has room
+SORT_THRESHOLD = 1 << 20                      # interval slots (2 per record, 1 when symmetric) from which a pass sorts
+
+
+def side_keys(n_reads, qid, tid, symmetric):
+    """The sort's key of every slot, in input order: slot j < n_rec is the query side of record j, slot n_rec + i the target side of
+    record i (not symmetric only), which exists when tid[i] != qid[i]; a slot without a side carries the key n_reads."""
+    qid = np.asarray(qid, np.int64)
+    if symmetric:
+        return qid
+    tid = np.asarray(tid, np.int64)
+    return np.concatenate([qid, np.where(tid != qid, tid, n_reads)])
+
+
+def sides_reference(n_reads, qid, qs, qe, tid, ts, te, symmetric):
+    """What bucketing by read id must produce: the existing sides in stable order of their read id.
+    -> (off int64 [n_reads + 1], start, end): read r's sides are [off[r], off[r + 1]), off[n_reads] the number of sides."""
+    key = side_keys(n_reads, qid, tid, symmetric)
+    start = np.asarray(qs) if symmetric else np.concatenate([np.asarray(qs), np.asarray(ts)])
+    end = np.asarray(qe) if symmetric else np.concatenate([np.asarray(qe), np.asarray(te)])
+    exists = key < n_reads
+    key, start, end = key[exists], start[exists], end[exists]
+    order = np.argsort(key, kind="stable")
+    off = np.searchsorted(key[order], np.arange(n_reads + 1)).astype(np.int64)
+    return off, start[order], end[order]
+
+
+def sort_passes(n_reads):
+    """Digit passes of the sort: keys run from 0 to n_reads inclusive (engine.hip sides_begin)."""
+    bits = 1
+    while bits < 32 and (1 << bits) <= n_reads:
+        bits += 1
+    return (bits + 7) // 8
+
+
+def side_tags(n_ent):
+    """Coordinate columns that are tags (group_sides does not interpret them): start = the slot's own index, the top bit set on odd
+    slots (a sign extension of the 64-bit value's low half shows), end = a 32-bit hash of the index."""
+    j = np.arange(n_ent, dtype=np.uint64)
+    start = (j | ((j & np.uint64(1)) << np.uint64(31))).astype(np.uint32)
+    h = (j * np.uint64(0x9E3779B1) + np.uint64(0x7F4A7C15)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(15)
+    h = (h * np.uint64(0x85EBCA6B)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(13)
+    return start.view(np.int32), h.astype(np.uint32).view(np.int32)
+
+
+class SortCase:
+    """(name, n_reads, columns, symmetric) of the direct test; the columns (qid, qs, qe, tid, ts, te) are made when asked for and not
+    kept (the lattice holds some 3e7 slots).  group: the cases that share one context, in the order they run."""
+
+    def __init__(self, group, name, n_reads, n_rec, symmetric, ids):
+        self.group, self.name, self.n_reads, self.n_rec, self.symmetric, self._ids = group, name, int(n_reads), int(n_rec), bool(symmetric), ids
+
+    @property
+    def n_ent(self):
+        return self.n_rec * (1 if self.symmetric else 2)
+
+    @property
+    def columns(self):
+        qid, tid = self._ids()
+        qid, tid = _i32(qid), _i32(tid)
+        assert qid.size == tid.size == self.n_rec and (qid.size == 0 or (0 <= min(qid.min(), tid.min()) and max(qid.max(), tid.max()) < self.n_reads)), self.name
+        s, e = side_tags(self.n_ent)
+        n = self.n_rec
+        if self.symmetric:
+            return qid, s, e, tid, s.copy(), e.copy()
+        return qid, s[:n].copy(), e[:n].copy(), tid, s[n:].copy(), e[n:].copy()
+
+    def __iter__(self):
+        return iter((self.name, self.n_reads, self.columns, self.symmetric))
+
+
+def _large_small_large(cases, size):
+    """Largest, smallest, second largest, ...: a context's ping-pong buffers and gap list are reused across sizes in both directions."""
+    asc = sorted(cases, key=size)
+    out = []
+    while asc:
+        out.append(asc.pop())
+        if asc:
+            out.append(asc.pop(0))
+    return out
+
+
+SORT_SIZES = ([0, 1, 2, 63, 64, 65, PAIR_TILE // 4 - 1, PAIR_TILE // 4, PAIR_TILE // 4 + 1, PAIR_TILE - 1, PAIR_TILE, PAIR_TILE + 1]
+              + [t * PAIR_TILE + d for t in (7, 8, 9, RS_SEGS - 1, RS_SEGS, RS_SEGS + 1) for d in (-1, 0, 1)] + [(2 * RS_SEGS + 1) * PAIR_TILE])
+SORT_WIDTHS = (1, 2, 255, 256, 257, 65535, 65536, 65537, (1 << 24) - 1, 1 << 24)
+SORT_DIST_WIDTHS = (255, 65535, 65537)        # one, two and three digit passes
+SORT_DISTS = ("uniform", "one_read", "ascending", "descending", "top_digit", "low_digit", "self", "no_self")
+
+
+def _dist_ids(dist, n_reads, n_rec, seed):
+    """Read ids of a key distribution -> (qid, tid, symmetric)."""
+    rng = np.random.default_rng(seed)
+    j = np.arange(n_rec, dtype=np.int64)
+    passes = sort_passes(n_reads)
+    if dist == "uniform":
+        return rng.integers(0, n_reads, n_rec), rng.integers(0, n_reads, n_rec), False
+    if dist == "one_read":                        # one digit takes whole tiles, all 64 lanes of a step are peers
+        q = np.full(n_rec, n_reads - 1 - (n_reads > 2), np.int64)
+        return q, q.copy(), True
+    if dist in ("ascending", "descending"):
+        q = j * n_reads // max(n_rec, 1)
+        t = (q + 1) % n_reads
+        return (q, t, False) if dist == "ascending" else (q[::-1].copy(), t[::-1].copy(), False)
+    if dist == "top_digit":                       # two interleaved reads whose ids differ in the top digit alone
+        top = 1 << (8 * (passes - 1))
+        a = 5 if 5 + top < n_reads else 0
+        m = 1
+        while a + 2 * m * top < n_reads and 2 * m < 256:
+            m *= 2
+        b = a + m * top
+        assert b < n_reads and (a ^ b) >> (8 * (passes - 1)) and ((a ^ b) & (top - 1)) == 0
+        q = np.where(j & 1, b, a)
+        return q, np.where(j & 1, a, b), False
+    if dist == "low_digit":                       # ids that differ in the low digit alone
+        base = max((n_reads - 256) // 256 * 256, 0)
+        span = min(256, n_reads - base)
+        return base + rng.integers(0, span, n_rec), base + rng.integers(0, span, n_rec), False
+    if dist == "self":                            # tid == qid on every record: half of all slots carry the key n_reads
+        q = rng.integers(0, n_reads, n_rec)
+        return q, q.copy(), False
+    assert dist == "no_self" and n_reads >= 2     # tid == qid on none
+    q = rng.integers(0, n_reads, n_rec)
+    return q, (q + 1 + rng.integers(0, n_reads - 1, n_rec)) % n_reads, False
+
+
+def _present_ids(present, n_rec, seed):
+    """n_rec ids over the reads `present`, each of them at least once, in random order."""
+    present = np.asarray(present, np.int64)
+    rng = np.random.default_rng(seed)
+    assert n_rec >= present.size
+    q = np.concatenate([present, present[rng.integers(0, present.size, n_rec - present.size)]])
+    return rng.permutation(q)
+
+
+def bucket_sort_cases(group=None):
+    """The direct test's lattice (Engine.group_sides: expand_sides_kernel, radix_sort_by_key, unzip_sorted_kernel, fill_gaps_kernel):
+    deterministic SortCases, each unpacking to (name, n_reads, columns, symmetric).  Slot counts n_ent at every edge of a PAIR_TILE
+    tile, of the table scan's segments and of rs_tile_of_block's eighths; key widths of one to four digit passes; key distributions;
+    runs of reads without sides on either side of GAP_INLINE and GAP_LIST.  A stream that is not symmetric has two slots per record:
+    the odd slot counts come as symmetric streams only."""
+    out = []
+
+    def add(grp, name, n_reads, n_rec, symmetric, ids):
+        out.append(SortCase(grp, f"{grp}/{name}", n_reads, n_rec, symmetric, ids))
+
+    def uniform(n_reads, n_rec, seed, force_self=False):
+        def ids():
+            rng = np.random.default_rng(seed)
+            q, t = rng.integers(0, n_reads, n_rec), rng.integers(0, n_reads, n_rec)
+            if force_self:
+                t[::7] = q[::7]                   # slots that carry n_reads itself: a key whose only set bit may be the top one
+            return q, t
+        return ids
+
+    # slot counts, ids uniform over 3000 reads (two passes)
+    for sym in (True, False):
+        grp = "sizes_sym" if sym else "sizes_nonsym"
+        for n_ent in SORT_SIZES:
+            if sym or n_ent % 2 == 0:
+                n_rec = n_ent if sym else n_ent // 2
+                add(grp, f"n_ent={n_ent}", 3000, n_rec, sym, uniform(3000, n_rec, 100 + n_ent % 9973, force_self=not sym))
+    # key widths
+    for n_reads in SORT_WIDTHS:
+        n_rec = 5000 if n_reads >= (1 << 24) - 1 else 3 * PAIR_TILE + 17
+        add("widths", f"n_reads={n_reads}", n_reads, n_rec, False, uniform(n_reads, n_rec, 200 + n_reads % 9973, force_self=True))
+    # key distributions x digit passes, ten tiles and a partial one (five where the stream is symmetric)
+    for dist in SORT_DISTS:
+        for n_reads in SORT_DIST_WIDTHS:
+            n_rec = 5 * PAIR_TILE + 123
+            sym = _dist_ids(dist, n_reads, 4, 0)[2]
+            add("dists", f"{dist}/n_reads={n_reads}", n_reads, n_rec, sym, (lambda d=dist, nr=n_reads, n=n_rec: _dist_ids(d, nr, n, 300 + nr % 97)[:2]))
+    # reads without sides
+    n_rec = 3 * PAIR_TILE + 5
+
+    def gap(name, present, n_reads, sym=True, n=n_rec):
+        present = np.asarray(present, np.int64)
+        if sym:
+            add("gaps", name, n_reads, n, True, lambda: (lambda q: (q, q.copy()))(_present_ids(present, n, 400 + present.size)))
+        else:
+            add("gaps", name, n_reads, n, False, lambda: (_present_ids(present, n, 400 + present.size), _present_ids(present, n, 401 + present.size)))
+
+    gap("between=31,32", [0, 32, 65, 66, 98, 131], 132)                   # 31, 32, 0, 31, 32 reads without sides between two with
+    gap("between=31,32/nonsym", [0, 32, 65, 66, 98, 131], 132, sym=False)
+    for g in (GAP_INLINE - 1, GAP_INLINE):
+        gap(f"leading={g}", [g, g + 1, g + 3], g + 4)
+        gap(f"trailing={g}", [0, 2, 3], 4 + g)
+        gap(f"trailing={g}/nonsym", [0, 2, 3], 4 + g, sym=False)
+    for G in (GAP_LIST - 1, GAP_LIST, GAP_LIST + 76):                     # the list one short of full, full, overflowing to inline fills
+        gap(f"gaps_of_40={G}", 41 * np.arange(G + 1), 41 * G + 1)
+    gap("gaps_of_40=1100/nonsym", 41 * np.arange(GAP_LIST + 77), 41 * (GAP_LIST + 76) + 1, sym=False)
+    gap("one_gap=1e6", [0, 10 ** 6 + 1], 10 ** 6 + 2)
+    gap("last_read_only", [69999], 70000)
+    gap("first_read_only", [0], 70000)
+    gap("first_read_only/nonsym", [0, 0], 70000, sym=False, n=2 * PAIR_TILE)   # (tid == qid: every target slot carries 70000)
+    gap("no_gaps", np.arange(50), 50)
+    groups = {}
+    for c in out:
+        groups.setdefault(c.group, []).append(c)
+    out = [c for g in groups.values() for c in _large_small_large(g, lambda c: (c.n_ent, c.n_reads))]
+    return out if group is None else [c for c in out if c.group == group]
+
+
+SORT_GROUPS = ("sizes_sym", "sizes_nonsym", "widths", "dists", "gaps")
+
+
+def gap_runs(n_reads, keys):
+    """Runs of reads without sides as unzip_*_kernel meets them -> (leading, between [array], trailing) lengths; `keys`: side_keys."""
+    present = np.unique(keys[keys < n_reads])
+    if present.size == 0:
+        return n_reads, np.empty(0, np.int64), 0
+    return int(present[0]), np.diff(present) - 1, int(n_reads - 1 - present[-1])
+
+
+def sort_census(n_reads, keys, tile):
+    """The structural classes a sort input of `keys` (side_keys: one per slot, input order) falls in, from the input alone."""
+    n_ent = int(keys.size)
+    n_tiles = -(-n_ent // tile)
+    lead, between, trail = gap_runs(n_reads, keys)
+    listed = int((between >= GAP_INLINE).sum()) + (lead >= GAP_INLINE) + (trail >= GAP_INLINE)
+    whole = False
+    if n_ent >= tile:
+        d = (keys[: n_ent // tile * tile] & 255).reshape(-1, tile)
+        whole = bool(np.any(np.all(d == d[:, :1], axis=1)))
+    return {"n_ent": n_ent, "n_tiles": n_tiles, "n_valid_last": n_ent - (n_tiles - 1) * tile if n_tiles else 0, "tiles_mod8": n_tiles % 8,
+            "L": -(-n_tiles // RS_SEGS), "passes": sort_passes(n_reads), "whole_tile_one_digit": whole,
+            "absent_share": float((keys == n_reads).mean()) if n_ent else 0.0, "leading": lead, "trailing": trail,
+            "between": set(between.tolist()) if between.size < 10000 else set(np.unique(between).tolist()), "listed": listed}
+
+
+def census_classes(censuses, full):
+    """-> {class: names of the cases in it}; `censuses`: {case name: sort_census}; full: the tile size."""
+    cls = {}
+
+    def put(k, name):
+        cls.setdefault(k, []).append(name)
+    for name, c in censuses.items():
+        put(("n_valid_last", "full" if c["n_valid_last"] == full else c["n_valid_last"]), name)
+        if c["tiles_mod8"]:
+            put(("tiles_mod8", "nonzero"), name)
+        put(("L", c["L"]), name)
+        put(("passes", c["passes"]), name)
+        if c["whole_tile_one_digit"]:
+            put(("whole_tile_one_digit", True), name)
+        if c["absent_share"] >= 0.5:
+            put(("absent_share", ">=0.5"), name)
+        for g in c["between"]:
+            put(("between", g), name)
+        put(("leading", c["leading"]), name)
+        put(("trailing", c["trailing"]), name)
+        if c["listed"] >= 1:
+            put(("listed", "<=1024" if c["listed"] <= GAP_LIST else ">1024"), name)
+    return cls
+
+
+def sides_first_difference(name, n_reads, cols, symmetric, got, want, tile=PAIR_TILE):
+    """None, or a sentence naming the case and the first side that differs -- its place in the sorted order and that place's tile, its
+    key (the read), the slot it came from (its tag) and that slot's tile.  got / want: (off, start, end)."""
+    g_off, g_s, g_e = (np.asarray(a) for a in got)
+    w_off, w_s, w_e = (np.asarray(a) for a in want)
+    if g_off.shape != w_off.shape:
+        return f"case {name}: off has {g_off.size} entries, want {w_off.size}"
+    pos, why = None, ""
+    bad = np.flatnonzero(g_off != w_off)
+    if bad.size:
+        r = int(bad[0])
+        pos = int(min(g_off[r], w_off[r]))
+        why = f"off[{r}] is {int(g_off[r])}, want {int(w_off[r])} ({bad.size} entries differ)"
+    n = min(g_s.size, w_s.size)
+    col = np.flatnonzero((g_s[:n] != w_s[:n]) | (g_e[:n] != w_e[:n]))
+    if col.size and (pos is None or col[0] < pos):
+        pos = int(col[0])
+        why = (f"got (start, end) = ({int(g_s[pos]) & 0xFFFFFFFF:#x}, {int(g_e[pos]) & 0xFFFFFFFF:#x}) = slot {int(g_s[pos]) & 0x7FFFFFFF}, "
+               f"want ({int(w_s[pos]) & 0xFFFFFFFF:#x}, {int(w_e[pos]) & 0xFFFFFFFF:#x}); {col.size} sides differ")
+    if pos is None and g_s.size != w_s.size:
+        pos, why = n, f"{g_s.size} sides, want {w_s.size}"
+    if pos is None:
+        return None
+    if pos >= w_s.size:
+        return f"case {name}: first differing side at sorted place {pos} (tile {pos // tile}), past the {w_s.size} sides there are: {why}"
+    key = int(np.searchsorted(w_off, pos, side="right") - 1)
+    slot = int(w_s[pos]) & 0x7FFFFFFF
+    n_rec = int(np.asarray(cols[0]).size)
+    what = f"query side of record {slot}" if slot < n_rec or symmetric else f"target side of record {slot - n_rec}"
+    return (f"case {name}: first differing side at sorted place {pos} (tile {pos // tile}), key {key} of {n_reads} reads, "
+            f"slot {slot} (tile {slot // tile}: the {what}): {why}")
+
+
+def assert_same_sides(name, n_reads, cols, symmetric, got, want, tile=PAIR_TILE):
+    msg = sides_first_difference(name, n_reads, cols, symmetric, got, want, tile)
+    assert msg is None, msg
+
+
+# ---- pass-level sets for the three routes of bucket_sides (counting sort, coordinate pairs, window records) ----------------------------
+
+class PassCase:
+    """(name, params, columns) of the pass-level test: a whole record stream with real coordinates; columns = the seven of oracle_run.
+    wide: a side whose windows do not fit 16 bits (the window-record route gives way to coordinate pairs)."""
+
+    def __init__(self, name, make, symmetric=False, wide=False, conditions=True):
+        self.name, self._make, self.symmetric, self.wide, self.conditions = name, make, symmetric, wide, conditions
+
+    def build(self):
+        p, cols = self._make()
+        return p, [_i32(c) for c in cols]
+
+    def __iter__(self):
+        p, cols = self.build()
+        return iter((self.name, p, cols))
+
+
+def _pass_ids(rng, n, pool, hot=True):
+    """n read ids from `pool`; hot: a third of them on 2 % of the pool (uniform ids leave the coverage flat: no repeats)."""
+    m = pool.size
+    pick = rng.integers(0, m, n)
+    if hot and m >= 50:
+        hot_ids = rng.permutation(m)[: m // 50]
+        sel = rng.random(n) < 1.0 / 3.0
+        pick[sel] = hot_ids[rng.integers(0, hot_ids.size, int(sel.sum()))]
+    return pool[pick]
+
+
+def _pass_coords(rng, length, period):
+    """An interval per entry of `length` (its read's length): centred near the middle of one of the read's stretches of `period` bases,
+    up to 0.3 periods long -- coverage in peaks with empty valleys between, several runs of high windows per read."""
+    n = length.size
+    L = length.astype(np.int64)
+    c = (rng.random(n) * np.maximum(L // period, 1)).astype(np.int64)
+    centre = c * period + period // 2 + ((rng.random(n) - 0.5) * 0.2 * period).astype(np.int64)
+    ln = 1 + (rng.random(n) * 0.3 * period).astype(np.int64)
+    s = np.clip(centre - ln // 2, 0, L - 1)
+    return s, np.minimum(s + ln, L)
+
+
+def _pass_params(reso, cols, period, est_cov=None):
+    """est_cov: the mean coverage of a window that the sides (both of every record) give, so that high_cov = 1.5 est_cov lies between
+    the valleys and the peaks whatever the depth of the set."""
+    if est_cov is None:
+        rl, qid, qs, qe, tid, ts, te = cols
+        touched = int(((qe - 1) // reso - qs // reso + 1).sum()) + int((((te - 1) // reso - ts // reso + 1) * (tid != qid)).sum())
+        est_cov = max(1, touched // max(int(((rl.astype(np.int64) + reso - 1) // reso).sum()), 1))
+    return RaftParams(reso=reso, est_cov=int(est_cov), cov_mul=1.5, repeat_length=max(period // 10, 6 * reso), interval_length=period // 4,
+                      read_length=3 * (period // 4), overlap_length=period // 40, flanking_length=period // 80)
+
+
+def _pass_stream(seed, rl, n_rec, period=4000, pool=None, hot=True, self_only=False):
+    """n_rec records over the reads `pool` (default: all), both sides by _pass_ids / _pass_coords -> the six record columns (int64)."""
+    rng = np.random.default_rng(seed)
+    rl = np.asarray(rl, np.int64)
+    pool = np.arange(rl.size) if pool is None else np.asarray(pool, np.int64)
+    qid = _pass_ids(rng, n_rec, pool, hot)
+    tid = qid.copy() if self_only else _pass_ids(rng, n_rec, pool, hot)
+    qs, qe = _pass_coords(rng, rl[qid], period)
+    ts, te = _pass_coords(rng, rl[tid], period)
+    return [qid, qs, qe, tid, ts, te]
+
+
+def _mirrored(seed, cols6):
+    """Every record and its mirror (query and target swapped), permuted: a symmetric stream in any order (chop.hpp:171-184)."""
+    qid, qs, qe, tid, ts, te = cols6
+    both = [np.concatenate(x) for x in ((qid, tid), (qs, ts), (qe, te), (tid, qid), (ts, qs), (te, qe))]
+    order = np.random.default_rng(seed).permutation(both[0].size)
+    return [x[order] for x in both]
+
+
+def bucket_pass_cases():
+    """The pass-level sets: PassCases, each unpacking to (name, params, columns).  Record counts on either side of SORT_THRESHOLD interval
+    slots, ITEM_TILE tiles with short last tiles and a 257th, one to four digit passes, runs of reads without sides, a stream of self
+    overlaps, every side on one read, window indices up to and beyond 16 bits.  reso 50 unless stated."""
+    out = []
+
+    def plain(name, seed, n_reads, n_rec, lo, hi, **kw):
+        def make():
+            rl = np.random.default_rng(seed).integers(lo, hi, n_reads)
+            cols6 = _pass_stream(seed + 1, rl, n_rec, **kw)
+            cols = [rl] + cols6
+            return _pass_params(50, [np.asarray(c, np.int64) for c in cols], 4000), cols
+        out.append(PassCase(name, make))
+
+    half = SORT_THRESHOLD // 2
+    plain("thr_below", 500, 9000, half - 1, 2000, 40000)                  # cap_iv = 2^20 - 2: the counting sort on every route
+    plain("thr_at", 502, 9000, half, 2000, 40000)                         # cap_iv = 2^20: 128 item tiles, 256 pair tiles
+    for name, n_rec in (("sym_below", SORT_THRESHOLD - 2), ("sym_at", SORT_THRESHOLD)):
+        def make(n_rec=n_rec):
+            rl = np.random.default_rng(510).integers(2000, 40000, 9000)
+            cols = [rl] + _mirrored(512, _pass_stream(511 + n_rec % 7, rl, n_rec // 2))
+            return _pass_params(50, [np.asarray(c, np.int64) for c in cols], 4000), cols
+        out.append(PassCase(name, make, symmetric=True))
+    plain("tiles257", 520, 9000, SORT_THRESHOLD + 1, 2000, 40000)         # cap_iv = 256 * 8192 + 2: L = 2, a last tile of 2 items
+    for k in (32, 33):
+        plain(f"tile_tail/{2 * k}", 530 + k, 9000, 64 * ITEM_TILE + k, 2000, 40000)    # cap_iv = 128 * 8192 + 2 k
+    for passes, n_reads in ((1, 255), (2, 256), (2, 65535), (3, 65536), (3, 70000)):
+        assert sort_passes(n_reads) == passes
+        lo, hi = (20000, 60000) if n_reads < 1000 else (1000, 12000)
+        plain(f"pass{passes}/{n_reads}", 540 + n_reads % 89, n_reads, half, lo, hi)
+
+    def pass4():
+        rng = np.random.default_rng(550)
+        n_reads = 1 << 24
+        rl = rng.integers(1, 51, n_reads)
+        qid, tid = rng.integers(0, n_reads, half), rng.integers(0, n_reads, half)
+        qs = (rng.random(half) * rl[qid]).astype(np.int64)
+        ts = (rng.random(half) * rl[tid]).astype(np.int64)
+        qe = np.minimum(qs + 1 + (rng.random(half) * 50).astype(np.int64), rl[qid])
+        te = np.minimum(ts + 1 + (rng.random(half) * 50).astype(np.int64), rl[tid])
+        return _pass_params(50, None, 4000, est_cov=1), [rl, qid, qs, qe, tid, ts, te]
+    out.append(PassCase("pass4", pass4, conditions=False))
+
+    def named_reads(seed, n_reads, named, n_rec):
+        rng = np.random.default_rng(seed)
+        rl = rng.integers(200, 2000, n_reads)
+        rl[named] = rng.integers(5000, 30000, named.size)
+        cols = [rl] + _pass_stream(seed + 1, rl, n_rec, pool=named)
+        return _pass_params(50, [np.asarray(c, np.int64) for c in cols], 4000), cols
+
+    def gaps():
+        n_reads = 200000
+        rng = np.random.default_rng(560)
+        mid = np.sort(rng.choice(np.arange(1000, n_reads - 1000), 2994, replace=False))
+        # a leading gap of 32 reads, runs of 31 and of 32 reads without sides between two with, a trailing gap of 31
+        named = np.unique(np.concatenate([[32, 100, 132, 165], mid, [n_reads - 40, n_reads - 32]]))
+        assert named.size == 3000
+        return named_reads(561, n_reads, named, half)
+    out.append(PassCase("gaps", gaps))
+
+    def many_gaps():
+        named = 31 + 40 * np.arange(1100)                                  # leading 31, 1099 gaps of 39, trailing 32: 1100 listed
+        return named_reads(570, int(named[-1]) + 1 + 32, named, half)
+    out.append(PassCase("many_gaps", many_gaps, conditions=False))
+    plain("self_only", 580, 9000, half, 2000, 40000, self_only=True)
+
+    def one_read():
+        """Every side on read 7 of 60,000 bases among 300 reads: 100,000 records over the whole read, the others on 200 stripes of
+        three windows (some 2,100 each) with high_cov between the two -- 2^19 intervals in one tile (the deep kernel's), 200 repeats
+        of 150 bases."""
+        rng = np.random.default_rng(590)
+        rl = rng.integers(20000, 60000, 300)
+        rl[7] = 60000
+        k = rng.integers(0, 200, half)
+        qs = 300 * k + rng.integers(0, 50, half)
+        qe = 300 * k + 101 + rng.integers(0, 50, half)
+        whole = rng.permutation(half)[:100000]
+        qs[whole], qe[whole] = 0, 60000
+        qid = np.full(half, 7)
+        ts, te = _pass_coords(rng, rl[qid], 4000)
+        p = RaftParams(reso=50, est_cov=101000, cov_mul=1.0, repeat_length=150, interval_length=1000, read_length=3000, overlap_length=100, flanking_length=0)
+        return p, [rl, qid, qs, qe, qid.copy(), ts, te]
+    out.append(PassCase("one_read", one_read))
+
+    def edge16(wide):
+        """reso 1: a window is a base.  Reads of 65,534 and 65,535 bases; sides that end exactly at base 65,535 (one past the last
+        window = 65,535: the largest that fits) and sides that start in window 65,534; wide: one read of 65,536 bases more, with one
+        side that ends at 65,536."""
+        rng = np.random.default_rng(600)
+        rl = np.where(np.arange(160) & 1, 65535, 65534)
+        qid, qs, qe, tid, ts, te = _pass_stream(601, rl, half, hot=False)
+        at = np.flatnonzero(rl[qid] == 65535)[:200]
+        qe[at[:100]] = 65535; qs[at[:100]] = 65535 - 1 - 13 * np.arange(100)
+        qs[at[100:]] = 65534; qe[at[100:]] = 65535
+        at = np.flatnonzero((rl[tid] == 65535) & (tid != qid))[-200:]
+        te[at[:100]] = 65535; ts[at[:100]] = 65535 - 1 - 17 * np.arange(100)
+        ts[at[100:]] = 65534; te[at[100:]] = 65535
+        cols = [rl, qid, qs, qe, tid, ts, te]
+        if wide:
+            add = [65536, 160, 65000, 65536, 3, 100, 900]
+            cols = [np.concatenate([c, [v]]) for c, v in zip(cols, add)]
+        return _pass_params(1, [np.asarray(c, np.int64) for c in cols], 4000), cols
+    out.append(PassCase("edge16_fits", lambda: edge16(False)))
+    out.append(PassCase("edge16_wide", lambda: edge16(True), wide=True))
+    return out
+
+
+def sides_pileup(reso, read_len, off, start, end):
+    """Coverage per window from bucketed sides (sides_reference), a difference array per read: a side adds one to the windows
+    start // reso .. (end - 1) // reso (repeat.hpp:62-77, for end > start >= 0).  -> cov (the oracle's layout)."""
+    nb = (np.asarray(read_len, np.int64) + reso - 1) // reso
+    cov_off = np.zeros(nb.size + 1, np.int64)
+    np.cumsum(nb, out=cov_off[1:])
+    rid = np.repeat(np.arange(nb.size), np.diff(off))
+    diff = np.zeros(int(cov_off[-1]) + 1, np.int64)
+    np.add.at(diff, cov_off[rid] + np.asarray(start, np.int64) // reso, 1)
+    np.add.at(diff, cov_off[rid] + (np.asarray(end, np.int64) - 1) // reso + 1, -1)
+    return np.cumsum(diff[:-1]).astype(np.int32)
