@@ -538,6 +538,54 @@ typedef struct raft_hip_cov_estimate {
 } raft_hip_cov_estimate;
 int raft_hip_estimate_coverage(const int64_t *hist, int32_t n_hist, raft_hip_cov_estimate *out);
 
+/* ---- the per-read table (additive; the ABI version is unchanged) ------------------------------------------------------
+ * What people open coverage.txt for, read by read, answered on the device from what a finished pass and its record stream
+ * already hold there: 20 bytes per read cross PCIe instead of cov[].
+ *
+ * Coverage summary of every read of the finished pass, over the read's windows cov_offset[r] <= w < cov_offset[r + 1]:
+ *     cov_sum[r]      = sum of cov[w]
+ *     cov_max[r]      = max of cov[w]; 0 for a read without windows
+ *     high_windows[r] = windows with cov[w] >= threshold
+ * All three are host arrays of n_reads entries; any may be NULL (it is then not copied).  threshold is an argument and not the
+ * context's high_cov: cov[] does not depend on est_cov, so a survey pass run under a placeholder can serve the call;
+ * threshold < 1 -> RAFT_HIP_ERR_PARAM.  Valid exactly where raft_hip_cov_histogram is (after raft_hip_finish without a data
+ * error; not after the host-to-host pipelines), otherwise RAFT_HIP_ERR_STATE.  Like the histogram it writes nothing of the
+ * pass, hands out no geometry (a later speculated pass still reports RAFT_HIP_SUM_KEPT_GEOMETRY), reads the array in the form
+ * the pass wrote (int32; one / two bytes per window plus the listed windows; four-bit steps decoded into int32 first) and waits
+ * for the stream once, at its end.  A pass whose exception list is incomplete -> RAFT_HIP_ERR_DEVICE, as the histogram.
+ * kernel_seconds (may be NULL): device time of the launches, from HIP events on the context's stream.
+ * sum(cov_sum) = summary.total_coverage. */
+int raft_hip_read_stats(raft_hip_ctx *ctx, int32_t threshold, int64_t *cov_sum, int32_t *cov_max, int32_t *high_windows,
+                        double *kernel_seconds);
+
+/* Census of a record stream, independent of any pass (the context lends its stream and buffers); the columns may be in any
+ * order.  With len[] = read_len[] (the FASTA lengths: the engine never sees PAF columns 2 and 7):
+ *     intervals[r] = the intervals a pass piles up on read r under the final flag `symmetric`: one per record with qid == r and,
+ *                    when symmetric == 0, one per record with tid == r and tid != qid (chop.hpp:165-169 with repeat.hpp:48-58);
+ *                    their sum is summary.n_intervals of a pass over the same stream
+ *     contained[r]   bit 0: some record has qid == r, qs == 0, qe == len[r] and len[tid] > len[r]
+ *                    bit 1: some record has tid == r, ts == 0, te == len[r] and len[qid] > len[r]; looked at only when symmetric == 0
+ *     *n_contained = reads with contained[r] != 0
+ * This is the awk of the reference's bash_scripts/map_mm_noncontained.sh:15-16 WITHOUT its identity filter: PAF columns 10 and 11
+ * are not tokenised, so a read is flagged whatever the identity of the overlap that contains it.  A record of a read with itself
+ * counts once and never flags (the lengths are equal).
+ * intervals, contained: host arrays [n_reads], either may be NULL; n_contained, error_index, kernel_seconds may be NULL.
+ * d_tid is required whenever n_rec > 0 (containment compares the two reads' lengths in either mode); d_ts and d_te may be NULL
+ * when symmetric != 0.  A missing column, n_reads < 0 or n_rec < 0 -> RAFT_HIP_ERR_PARAM.
+ * An id outside [0, n_reads) in the query or the target column -> RAFT_HIP_ERR_READ_ID with *error_index = the first such record
+ * (within one record the query column is looked at first); the output arrays are then not written.  Otherwise *error_index = -1.
+ * Valid in any state of the context; a pass in flight on the context's stream is waited for. */
+int raft_hip_census_device(raft_hip_ctx *ctx, int32_t n_reads, const int32_t *d_read_len, int64_t n_rec,
+                           const int32_t *d_qid, const int32_t *d_qs, const int32_t *d_qe,
+                           const int32_t *d_tid, const int32_t *d_ts, const int32_t *d_te, int32_t symmetric,
+                           int32_t *intervals /* host [n_reads] */, uint8_t *contained /* host [n_reads] */,
+                           int64_t *n_contained, int64_t *error_index, double *kernel_seconds);
+/* The same from host columns, staged through buffers of the context that no pass uses. */
+int raft_hip_census_host(raft_hip_ctx *ctx, int32_t n_reads, const int32_t *read_len, int64_t n_rec,
+                         const int32_t *qid, const int32_t *qs, const int32_t *qe,
+                         const int32_t *tid, const int32_t *ts, const int32_t *te, int32_t symmetric,
+                         int32_t *intervals, uint8_t *contained, int64_t *n_contained, int64_t *error_index, double *kernel_seconds);
+
 /* Device seconds spent in the dominant kernel (coverage pileup + run scan) and
  * in all kernels of the last finished pass, from HIP events recorded on the
  * context's stream around them. */

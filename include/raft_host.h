@@ -120,6 +120,16 @@ int raft_host_write_repeats(const char *txt_path, const char *bed_path, const ra
 int raft_host_write_fasta(const char *path, const raft_host_reads *reads, const int64_t *frag_offset,
                           const int32_t *frag_begin, const int32_t *frag_end);
 
+/* The per-read table of `raft --read-stats` (PREFIX.read_stats.tsv): one header line, then one line per read, tab-separated,
+ * integers only apart from the name:
+ *     read  name  length  windows  intervals  contained  cov_sum  cov_max  high_windows  repeats  fragments
+ * read = the FASTA index, name = names[read], windows = ceil(length / reso); intervals and contained as raft_hip_census_* gives
+ * them, cov_sum / cov_max / high_windows as raft_hip_read_stats does (include/raft_hip.h); repeats and fragments are the
+ * differences of rep_offset and frag_offset (CSR offsets as returned by raft_hip_fetch, n_reads + 1 entries each). */
+int raft_host_write_read_stats(const char *path, int32_t n_reads, const char *const *names, const int32_t *length, int32_t reso,
+                               const int32_t *intervals, const uint8_t *contained, const int64_t *cov_sum, const int32_t *cov_max,
+                               const int32_t *high_windows, const int64_t *rep_offset, const int64_t *frag_offset);
+
 /* The reference's stand-alone comparator tool (split_naive.cpp:10-44): every read of in_path cut into consecutive
  * pieces of split_len bases, written to out_path as ">name_k" records, k from 1.  n_reads (may be NULL) receives the
  * number of input records. */

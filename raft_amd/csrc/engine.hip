@@ -9,6 +9,8 @@
 #include "finalize.hpp"
 #include "pack.hpp"
 #include "cov_hist.hpp"
+#include "read_stats.hpp"
+#include "census.hpp"
 #include "pileup.hpp"
 #include "pileup_wave.hpp"
 #include "wave_launch.hpp"
@@ -1598,6 +1600,146 @@ int raft_hip_cov_histogram(raft_hip_ctx *c, int64_t *hist, double *kernel_second
         *kernel_seconds = ms * 1e-3;
     }
     return RAFT_HIP_OK;
+}
+
+// Per read: sum and maximum of cov[] over the read's windows and the windows at or above `threshold` (read_stats.hpp), from the form
+// the pass holds, as the histogram above.  Nothing of the pass is written, no geometry goes out.
+int raft_hip_read_stats(raft_hip_ctx *c, int32_t threshold, int64_t *cov_sum, int32_t *cov_max, int32_t *high_windows, double *kernel_seconds)
+{
+    if (!c || threshold < 1) return RAFT_HIP_ERR_PARAM;
+    if (!c->finished || c->pending_err) return RAFT_HIP_ERR_STATE;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const long long B = c->sum.n_bins;
+    const int32_t n_reads = c->sum.n_reads;
+    const bool codes = (c->pass_width == 1 || c->pass_width == 2) && c->packed_width == c->pass_width;
+    if (!codes) { const int rc = materialise_cov(c); if (rc != RAFT_HIP_OK) return rc; }
+    else if (c->n_exc > c->exc_cap) { c->last_error = "raft_hip_read_stats: the pass's exception list is incomplete"; return RAFT_HIP_ERR_DEVICE; }
+    const size_t n = (size_t)std::max(n_reads, 1);
+    HIP_TRY(c, c->rs_sum.ensure(n * 8));
+    HIP_TRY(c, c->rs_max.ensure(n * 4));
+    HIP_TRY(c, c->rs_high.ensure(n * 4));
+    if (kernel_seconds && !c->ev_hist0) { HIP_TRY(c, hipEventCreate(&c->ev_hist0)); HIP_TRY(c, hipEventCreate(&c->ev_hist1)); }
+    ReadStatsOut out{c->rs_sum.as<unsigned long long>(), c->rs_max.as<int32_t>(), c->rs_high.as<int32_t>()};
+    HIP_TRY(c, hipMemsetAsync(out.sum, 0, n * 8, c->stream));
+    HIP_TRY(c, hipMemsetAsync(out.max, 0, n * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(out.high, 0, n * 4, c->stream));
+    if (kernel_seconds) HIP_TRY(c, hipEventRecord(c->ev_hist0, c->stream));
+    if (B > 0 && n_reads > 0) {
+        const long long *off = c->cov_off.as<long long>();
+        const unsigned thr = (unsigned)threshold;
+        if (!codes) {
+            hipLaunchKernelGGL(read_stats_kernel<int32_t>, dim3(read_stats_grid(B, kReadStatsLaneWindows<int32_t>)), dim3(kReadStatsThreads), 0, c->stream,
+                               c->cov.as<int32_t>(), B, off, n_reads, thr, out);
+        } else {
+            const unsigned limit = c->pass_width == 1 ? ReadStatsIn<uint8_t>::limit : ReadStatsIn<uint16_t>::limit;
+            if (c->pass_width == 1)
+                hipLaunchKernelGGL(read_stats_kernel<uint8_t>, dim3(read_stats_grid(B, kReadStatsLaneWindows<uint8_t>)), dim3(kReadStatsThreads), 0, c->stream,
+                                   c->cov8.as<uint8_t>(), B, off, n_reads, thr, out);
+            else
+                hipLaunchKernelGGL(read_stats_kernel<uint16_t>, dim3(read_stats_grid(B, kReadStatsLaneWindows<uint16_t>)), dim3(kReadStatsThreads), 0, c->stream,
+                                   c->cov8.as<uint16_t>(), B, off, n_reads, thr, out);
+            if (c->n_exc > 0)       // (complete: raft_hip_finish runs a pass whose list overflowed again)
+                hipLaunchKernelGGL(read_stats_exc_kernel, dim3((unsigned)std::min<long long>((c->n_exc + 255) / 256, 4096)), dim3(256), 0, c->stream,
+                                   c->exc_idx.as<long long>(), c->exc_val.as<int32_t>(), c->n_exc, off, n_reads, limit, thr, out);
+        }
+        HIP_TRY(c, hipGetLastError());
+    }
+    if (kernel_seconds) HIP_TRY(c, hipEventRecord(c->ev_hist1, c->stream));
+    PHASE(queue_copies(c, {{cov_sum, out.sum, (size_t)n_reads * 8}, {cov_max, out.max, (size_t)n_reads * 4}, {high_windows, out.high, (size_t)n_reads * 4}}));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));           // (the one wait of the call)
+    if (kernel_seconds) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_hist0, c->ev_hist1));
+        *kernel_seconds = ms * 1e-3;
+    }
+    return RAFT_HIP_OK;
+}
+
+// What the record stream says about each read (census.hpp): intervals per read under the final flag `symmetric`, contained flags.
+// Independent of any pass: the call reads its arguments and writes buffers of its own.
+static int census_run(raft_hip_ctx *c, int32_t n_reads, const int32_t *d_len, int64_t n_rec, const int32_t *const d_col[6], int32_t symmetric,
+                      int32_t *intervals, uint8_t *contained, int64_t *n_contained, int64_t *error_index, double *kernel_seconds)
+{
+    const size_t n = (size_t)std::max(n_reads, 1);
+    HIP_TRY(c, c->cen_cnt.ensure(n * 4));
+    HIP_TRY(c, c->cen_flags.ensure(n * 4));
+    HIP_TRY(c, c->cen_out.ensure(n));
+    HIP_TRY(c, c->cen_ctl.ensure(16));
+    if (kernel_seconds && !c->ev_hist0) { HIP_TRY(c, hipEventCreate(&c->ev_hist0)); HIP_TRY(c, hipEventCreate(&c->ev_hist1)); }
+    unsigned long long *ctl = c->cen_ctl.as<unsigned long long>();        // [0] first bad record, [1] reads with a flag
+    HIP_TRY(c, hipMemsetAsync(c->cen_cnt.p, 0, n * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->cen_flags.p, 0, n * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(ctl, 0xFF, 8, c->stream));
+    HIP_TRY(c, hipMemsetAsync(ctl + 1, 0, 8, c->stream));
+    if (kernel_seconds) HIP_TRY(c, hipEventRecord(c->ev_hist0, c->stream));
+    if (n_rec > 0) {
+        CensusArgs A{d_len, d_col[0], d_col[1], d_col[2], d_col[3], symmetric ? nullptr : d_col[4], symmetric ? nullptr : d_col[5], (long long)n_rec, n_reads,
+                     symmetric ? 1 : 0, c->cen_cnt.as<unsigned>(), c->cen_flags.as<unsigned>(), ctl};
+        uintptr_t bits = 0;
+        for (int k = 0; k < (symmetric ? 4 : 6); ++k) bits |= reinterpret_cast<uintptr_t>(d_col[k]);
+        if (bits & 15) hipLaunchKernelGGL(census_kernel<false>, dim3(census_grid(n_rec)), dim3(kCensusThreads), 0, c->stream, A);
+        else hipLaunchKernelGGL(census_kernel<true>, dim3(census_grid(n_rec)), dim3(kCensusThreads), 0, c->stream, A);
+    }
+    if (n_reads > 0)
+        hipLaunchKernelGGL(census_pack_kernel, dim3((unsigned)std::min<long long>(((long long)n_reads + 255) / 256, 1024)), dim3(256), 0, c->stream,
+                           c->cen_flags.as<unsigned>(), n_reads, c->cen_out.as<uint8_t>(), ctl + 1);
+    HIP_TRY(c, hipGetLastError());
+    if (kernel_seconds) HIP_TRY(c, hipEventRecord(c->ev_hist1, c->stream));
+    unsigned long long h_ctl[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(h_ctl, ctl, 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (kernel_seconds) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_hist0, c->ev_hist1));
+        *kernel_seconds = ms * 1e-3;
+    }
+    if (h_ctl[0] != ~0ull) {
+        if (error_index) *error_index = (int64_t)h_ctl[0];
+        c->last_error = "census: a record names a read id outside [0, n_reads)";
+        return RAFT_HIP_ERR_READ_ID;
+    }
+    if (error_index) *error_index = -1;
+    if (n_contained) *n_contained = (int64_t)h_ctl[1];
+    PHASE(queue_copies(c, {{intervals, c->cen_cnt.p, (size_t)n_reads * 4}, {contained, c->cen_out.p, (size_t)n_reads}}));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return RAFT_HIP_OK;
+}
+
+static bool census_args_ok(const raft_hip_ctx *c, int32_t n_reads, const int32_t *len, int64_t n_rec, const int32_t *qid, const int32_t *qs,
+                           const int32_t *qe, const int32_t *tid, const int32_t *ts, const int32_t *te, int32_t symmetric)
+{
+    if (!c || n_reads < 0 || n_rec < 0 || (n_reads > 0 && !len)) return false;
+    if (n_rec > 0 && (!qid || !qs || !qe || !tid)) return false;
+    if (n_rec > 0 && !symmetric && (!ts || !te)) return false;
+    return true;
+}
+
+int raft_hip_census_device(raft_hip_ctx *c, int32_t n_reads, const int32_t *d_read_len, int64_t n_rec, const int32_t *d_qid, const int32_t *d_qs,
+                           const int32_t *d_qe, const int32_t *d_tid, const int32_t *d_ts, const int32_t *d_te, int32_t symmetric,
+                           int32_t *intervals, uint8_t *contained, int64_t *n_contained, int64_t *error_index, double *kernel_seconds)
+{
+    if (!census_args_ok(c, n_reads, d_read_len, n_rec, d_qid, d_qs, d_qe, d_tid, d_ts, d_te, symmetric)) return RAFT_HIP_ERR_PARAM;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int32_t *col[6] = {d_qid, d_qs, d_qe, d_tid, d_ts, d_te};
+    return census_run(c, n_reads, d_read_len, n_rec, col, symmetric, intervals, contained, n_contained, error_index, kernel_seconds);
+}
+
+int raft_hip_census_host(raft_hip_ctx *c, int32_t n_reads, const int32_t *read_len, int64_t n_rec, const int32_t *qid, const int32_t *qs,
+                         const int32_t *qe, const int32_t *tid, const int32_t *ts, const int32_t *te, int32_t symmetric,
+                         int32_t *intervals, uint8_t *contained, int64_t *n_contained, int64_t *error_index, double *kernel_seconds)
+{
+    if (!census_args_ok(c, n_reads, read_len, n_rec, qid, qs, qe, tid, ts, te, symmetric)) return RAFT_HIP_ERR_PARAM;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int32_t *h[6] = {qid, qs, qe, tid, ts, te};
+    const int32_t *col[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    HIP_TRY(c, c->cen_len.ensure((size_t)std::max(n_reads, 1) * 4));
+    if (n_reads > 0) HIP_TRY(c, hipMemcpyAsync(c->cen_len.p, read_len, (size_t)n_reads * 4, hipMemcpyHostToDevice, c->stream));
+    for (int k = 0; k < (symmetric ? 4 : 6); ++k) {
+        HIP_TRY(c, c->cen_col[k].ensure((size_t)std::max<int64_t>(n_rec, 1) * 4));
+        if (n_rec > 0) HIP_TRY(c, hipMemcpyAsync(c->cen_col[k].p, h[k], (size_t)n_rec * 4, hipMemcpyHostToDevice, c->stream));
+        col[k] = c->cen_col[k].as<int32_t>();
+    }
+    return census_run(c, n_reads, c->cen_len.as<int32_t>(), n_rec, col, symmetric, intervals, contained, n_contained, error_index, kernel_seconds);
 }
 
 // The estimate read from a histogram: the mode of the covered, unclamped bins smoothed over three neighbours (see raft_hip.h).

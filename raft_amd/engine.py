@@ -33,6 +33,7 @@ EXPORTS = (
     "raft_hip_fetch_delta4", "raft_hip_packed_anchor_device", "raft_hip_set_emit_cuts", "raft_hip_device_alloc", "raft_hip_device_free", "raft_hip_group_sides", "raft_hip_presplit_symmetric", "raft_hip_presplit_symmetric_local",
     "raft_hip_trim", "raft_hip_pool_bytes", "raft_hip_run_presplit_local", "raft_hip_set_placement", "raft_hip_placement_trial",
     "raft_hip_set_placement_trial", "raft_hip_cov_histogram", "raft_hip_estimate_coverage",
+    "raft_hip_read_stats", "raft_hip_census_device", "raft_hip_census_host",
 )
 COV_HIST_BINS = 4096              # RAFT_HIP_COV_HIST_BINS
 
@@ -207,6 +208,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     lib.raft_hip_selftest.argtypes = [C.c_int]
     lib.raft_hip_cov_histogram.argtypes = [vp, vp, C.POINTER(C.c_double)]
     lib.raft_hip_estimate_coverage.argtypes = [vp, i32, C.POINTER(_CovEstimate)]
+    lib.raft_hip_read_stats.argtypes = [vp, i32, vp, vp, vp, C.POINTER(C.c_double)]
+    lib.raft_hip_census_device.argtypes = [vp, i32, vp, i64] + [vp] * 6 + [i32, vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_double)]
+    lib.raft_hip_census_host.argtypes = lib.raft_hip_census_device.argtypes
     if path is None:
         _lib = lib
     return lib
@@ -745,6 +749,61 @@ class Engine:
         if est.est_cov > 0:
             self.set_params(dataclasses.replace(self.params, est_cov=est.est_cov))
         return est
+
+    # -- the per-read table ------------------------------------------------------------
+    last_read_stats_seconds = 0.0     # device time of the last read_stats() call's launches
+    last_census_seconds = 0.0         # ... and of the last census()
+
+    def read_stats(self, threshold: int | None = None) -> dict:
+        """raft_hip_read_stats: per read of the finished pass ``cov_sum`` (int64), ``cov_max`` and ``high_windows`` (int32; windows
+        with coverage >= ``threshold``, by default the context's high_cov = int(est_cov * cov_mul)).  Reduced on the device from the
+        form the pass wrote; cov[] is not downloaded."""
+        if threshold is None:
+            threshold = int(self.params.est_cov * self.params.cov_mul)
+        last = getattr(self, "summary", None)
+        n = max(int(last.n_reads), 0) if last is not None else 0
+        out = {"cov_sum": np.zeros(n, np.int64), "cov_max": np.zeros(n, np.int32), "high_windows": np.zeros(n, np.int32)}
+        secs = C.c_double(0.0)
+        self._check(self._lib.raft_hip_read_stats(self._ctx, int(threshold), *(C.c_void_p(a.ctypes.data if a.size else 0) for a in out.values()),
+                                                  C.byref(secs)))
+        self.last_read_stats_seconds = secs.value
+        return out
+
+    def census(self, read_len, qid, qs, qe, tid, ts=None, te=None, symmetric: bool = False) -> dict:
+        """raft_hip_census_device / _host: ``intervals`` (int32 [n_reads]: what a pass piles up on each read under ``symmetric``),
+        ``contained`` (uint8 flags: bit 0 through a query side, bit 1 through a target side) and ``n_contained``.  The columns are
+        int32 torch tensors on this engine's device, or numpy arrays (staged by the library); ts / te may be None when
+        ``symmetric``.  Independent of any pass."""
+        cols = [read_len, qid, qs, qe, tid] + ([] if symmetric else [ts, te])
+        if any(x is None for x in cols[:4]) or (not symmetric and (ts is None or te is None)):
+            raise ValueError("census needs read_len, qid, qs, qe (and ts, te unless symmetric)")
+        on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in cols if x is not None)
+        if on_device:
+            import torch
+            for t in cols:
+                if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()):
+                    raise TypeError("census needs contiguous int32 CUDA tensors")
+            self.use_torch_stream()
+            size = lambda t: int(t.numel())
+            P = lambda t: C.c_void_p(t.data_ptr() if (t is not None and t.numel()) else 0)
+            fn = self._lib.raft_hip_census_device
+        else:
+            cols = [None if x is None else np.ascontiguousarray(np.asarray(x.cpu() if hasattr(x, "is_cuda") else x), dtype=np.int32) for x in cols]
+            size = lambda a: int(a.size)
+            P = lambda a: C.c_void_p(a.ctypes.data if (a is not None and a.size) else 0)
+            fn = self._lib.raft_hip_census_host
+        n_reads, n_rec = size(cols[0]), size(cols[1])
+        for x in cols[2:]:
+            if x is not None and size(x) != n_rec:
+                raise ValueError("PAF columns differ in length")
+        ptr = [P(x) for x in cols] + ([C.c_void_p(0)] * 2 if symmetric else [])
+        intervals, contained = np.zeros(n_reads, np.int32), np.zeros(n_reads, np.uint8)
+        n_cont, err, secs = C.c_int64(0), C.c_int64(-1), C.c_double(0.0)
+        rc = fn(self._ctx, n_reads, ptr[0], n_rec, *ptr[1:], 1 if symmetric else 0, C.c_void_p(intervals.ctypes.data if n_reads else 0),
+                C.c_void_p(contained.ctypes.data if n_reads else 0), C.byref(n_cont), C.byref(err), C.byref(secs))
+        self._check(rc, err.value)
+        self.last_census_seconds = secs.value
+        return {"intervals": intervals, "contained": contained, "n_contained": int(n_cont.value)}
 
     def packed_device(self) -> dict | None:
         """Zero-copy torch views of the encoding the finished pass holds (raft_hip_packed_device), or None when the pass

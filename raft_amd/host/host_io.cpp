@@ -1346,6 +1346,28 @@ int raft_host_write_fasta(const char *path, const raft_host_reads *reads, const 
     return write_ordered(path, n, 8 << 20, [&](long long i) { return (long long)reads->lens[(size_t)i] + 64; }, one_read);
 }
 
+// The per-read table of `raft --read-stats`: a header line, then one line per read, tab-separated, integers only (see raft_host.h)
+int raft_host_write_read_stats(const char *path, int32_t n_reads, const char *const *names, const int32_t *length, int32_t reso,
+                               const int32_t *intervals, const uint8_t *contained, const int64_t *cov_sum, const int32_t *cov_max,
+                               const int32_t *high_windows, const int64_t *rep_offset, const int64_t *frag_offset)
+{
+    if (!path || n_reads < 0 || reso <= 0 || (n_reads > 0 && (!names || !length || !intervals || !contained || !cov_sum || !cov_max ||
+                                                               !high_windows || !rep_offset || !frag_offset)))
+        return RAFT_HOST_ERR_ARG;
+    Out t(path);
+    if (!t.ok()) return RAFT_HOST_ERR_IO;
+    static const char head[] = "read\tname\tlength\twindows\tintervals\tcontained\tcov_sum\tcov_max\thigh_windows\trepeats\tfragments\n";
+    t.str(head, sizeof head - 1);
+    for (int32_t i = 0; i < n_reads; ++i) {
+        t.num(i); t.ch('\t'); t.str(names[i], strlen(names[i])); t.ch('\t');
+        t.num(length[i]); t.ch('\t'); t.num(((long long)length[i] + reso - 1) / reso); t.ch('\t');
+        t.num(intervals[i]); t.ch('\t'); t.num((int)contained[i]); t.ch('\t');
+        t.num((long long)cov_sum[i]); t.ch('\t'); t.num(cov_max[i]); t.ch('\t'); t.num(high_windows[i]); t.ch('\t');
+        t.num((long long)(rep_offset[i + 1] - rep_offset[i])); t.ch('\t'); t.num((long long)(frag_offset[i + 1] - frag_offset[i])); t.ch('\n');
+    }
+    return t.close() ? RAFT_HOST_OK : RAFT_HOST_ERR_IO;
+}
+
 // split_naive.cpp:10-44: every read is cut into consecutive pieces of split_len bases, no overlaps, written as
 // ">name_k\n<piece>\n" with k counting from 1; a read without bases writes nothing.
 int raft_host_split_naive(const char *in_path, const char *out_path, int32_t split_len, int32_t *n_reads_out)

@@ -10,6 +10,7 @@
 #include "../../include/raft_hip.h"
 #include "../../include/raft_host.h"
 
+#include <getopt.h>
 #include <unistd.h>
 
 #include <chrono>
@@ -34,6 +35,7 @@ struct Params {            // param.hpp:18-31
     int repeat_length = 10000, interval_length = 10000, read_length = 20000, overlap_length = 500, flanking_length = 1000;
     std::string prefix = "raft";
     bool auto_cov = false;         // -e auto: est_cov is read from the data (a survey pass and its coverage histogram) before the job
+    bool read_stats = false;       // --read-stats: PREFIX.read_stats.tsv, the per-read table (raft_hip_read_stats, raft_hip_census_host)
 };
 
 [[noreturn]] void print_help(const Params &p) // main.cpp:7-19
@@ -74,8 +76,11 @@ int main(int argc, char *argv[])
 {
     Params p;
     int option;
-    while ((option = getopt(argc, argv, "r:e:m:l:i:p:f:v:o:")) != -1) {
+    // (the short options and their quirks are the reference's; the one long option is this program's own)
+    static const struct option long_options[] = {{"read-stats", no_argument, nullptr, 1000}, {nullptr, 0, nullptr, 0}};
+    while ((option = getopt_long(argc, argv, "r:e:m:l:i:p:f:v:o:", long_options, nullptr)) != -1) {
         switch (option) {
+        case 1000: p.read_stats = true; break;
         case 'r': p.reso = atoi(optarg); break;
         case 'e': p.auto_cov = strcmp(optarg, "auto") == 0; p.est_cov = p.auto_cov ? 0 : atoi(optarg); break;
         case 'm': p.cov_mul = std::stod(optarg); break;
@@ -305,7 +310,16 @@ int main(int argc, char *argv[])
     // overlap_length is 0: which fragments there are depends on the repeats, hence on the placeholder, and RAFT_HIP_ERR_FRAGMENT of
     // the survey would not be the job's.  Every other data error (ids, coordinates, lengths) is the one the job would report, in
     // its words.  With several devices or ranks the survey still runs in one piece on the first: one more upload of the columns.
-    if (p.auto_cov) {
+    //
+    // --read-stats: the per-read table.  Its coverage summary (raft_hip_read_stats) is taken from the same survey pass, right behind
+    // the histogram, under threshold = (int)(est_cov * cov_mul); without -e auto one such pass -- the survey's recipe -- runs here for
+    // it.  The census of the record stream (raft_hip_census_host) reads the tokenised columns under the job's symmetric flag, before
+    // anything below writes window records over the query column.  The job itself runs as it does without the option.
+    std::vector<int64_t> rs_sum;
+    std::vector<int32_t> rs_max, rs_high, cen_intervals;
+    std::vector<uint8_t> cen_contained;
+    int64_t n_contained = 0;
+    if (p.auto_cov || p.read_stats) {
         raft_hip_params sp = hp;
         sp.overlap_length = 0;
         const char *we = getenv("RAFT_COV_WIDTH");           // (what the context's width was: 4 unless the test sweeps' variable chose)
@@ -323,23 +337,44 @@ int main(int argc, char *argv[])
                                    targets ? raft_host_paf_column(paf, 5) : nullptr);
         if (rc == RAFT_HIP_OK) rc = raft_hip_finish(ctx, &ss);
         if (rc != RAFT_HIP_OK) die(engine_error(rc, ss.error_index));
-        std::vector<int64_t> hist(RAFT_HIP_COV_HIST_BINS);
         raft_hip_cov_estimate est{};
-        rc = raft_hip_cov_histogram(ctx, hist.data(), nullptr);
-        if (rc == RAFT_HIP_OK) rc = raft_hip_estimate_coverage(hist.data(), RAFT_HIP_COV_HIST_BINS, &est);
+        est.est_cov = p.est_cov;
+        if (p.auto_cov) {
+            std::vector<int64_t> hist(RAFT_HIP_COV_HIST_BINS);
+            rc = raft_hip_cov_histogram(ctx, hist.data(), nullptr);
+            if (rc == RAFT_HIP_OK) rc = raft_hip_estimate_coverage(hist.data(), RAFT_HIP_COV_HIST_BINS, &est);
+        }
+        if (rc == RAFT_HIP_OK && p.read_stats && est.est_cov > 0) {
+            rs_sum.resize((size_t)n_reads); rs_max.resize((size_t)n_reads); rs_high.resize((size_t)n_reads);
+            const int32_t high_cov = (int32_t)(est.est_cov * p.cov_mul);          // (the job's: repeat.hpp:89-90)
+            rc = raft_hip_read_stats(ctx, std::max(high_cov, 1), rs_sum.data(), rs_max.data(), rs_high.data(), nullptr);
+            if (high_cov < 1)                                                      // (every window is at or above a threshold below 1)
+                for (int32_t i = 0; i < n_reads; ++i) rs_high[(size_t)i] = (int32_t)(((int64_t)rl[i] + p.reso - 1) / p.reso);
+        }
         if (rc == RAFT_HIP_OK) rc = raft_hip_set_output_width(ctx, width_before);
         if (rc == RAFT_HIP_OK) rc = raft_hip_set_emit_cuts(ctx, 1);
         if (rc != RAFT_HIP_OK) die(engine_error(rc, -1));
         stage("estimate");
-        if (est.est_cov <= 0) {                              // no window anybody overlaps: as for -e 0
-            std::cout << "ERROR, main(), estimated coverage must be set properly\n";
-            print_help(p);
+        if (p.auto_cov) {
+            if (est.est_cov <= 0) {                              // no window anybody overlaps: as for -e 0
+                std::cout << "ERROR, main(), estimated coverage must be set properly\n";
+                print_help(p);
+            }
+            fprintf(stdout, "INFO, estimate_coverage(), est_cov = %d\n", est.est_cov);
+            p.est_cov = est.est_cov;
+            hp.est_cov = est.est_cov;
         }
-        fprintf(stdout, "INFO, estimate_coverage(), est_cov = %d\n", est.est_cov);
-        p.est_cov = est.est_cov;
-        hp.est_cov = est.est_cov;
         rc = raft_hip_set_params(ctx, &hp);                  // (the first context's parameters are what every device and rank runs under)
         if (rc != RAFT_HIP_OK) die(std::string("ERROR, raft_hip_set_params(), ") + raft_hip_strerror(rc));
+    }
+    if (p.read_stats) {
+        cen_intervals.resize((size_t)n_reads); cen_contained.resize((size_t)n_reads);
+        int64_t bad_index = -1;
+        rc = raft_hip_census_host(ctx, n_reads, rl, n_rec, raft_host_paf_column(paf, 0), raft_host_paf_column(paf, 1), raft_host_paf_column(paf, 2),
+                                  raft_host_paf_column(paf, 3), sym ? nullptr : raft_host_paf_column(paf, 4), sym ? nullptr : raft_host_paf_column(paf, 5),
+                                  sym ? 1 : 0, cen_intervals.data(), cen_contained.data(), &n_contained, &bad_index, nullptr);
+        if (rc != RAFT_HIP_OK) die(engine_error(rc, bad_index));
+        stage("census");
     }
 
     // hifiasm writes its PAF grouped by query (reference README.md:36-38): a symmetric stream of at most four runs sorted by
@@ -460,6 +495,13 @@ int main(int argc, char *argv[])
                                 rep_off.data(), rep_s.get(), rep_e.get()) != RAFT_HOST_OK) {
         die("ERROR, repeat_annotate(), cannot write output files");
     }
+    if (p.read_stats) {
+        std::vector<const char *> names((size_t)n_reads);
+        for (int32_t i = 0; i < n_reads; ++i) names[(size_t)i] = raft_host_reads_name(reads, i);
+        if (raft_host_write_read_stats((p.prefix + ".read_stats.tsv").c_str(), n_reads, names.data(), rl, p.reso, cen_intervals.data(), cen_contained.data(),
+                                       rs_sum.data(), rs_max.data(), rs_high.data(), rep_off.data(), frag_off.data()) != RAFT_HOST_OK)
+            die("ERROR, read_stats(), cannot write output files");
+    }
     stage("write_tables");
     // repeat.hpp:173-178 (total_windows is an int in the reference; identical below 2^31 windows)
     const double cpw = (double)s.total_coverage / (double)s.total_windows;
@@ -479,6 +521,7 @@ int main(int argc, char *argv[])
     for (int i = 0; i < argc; ++i) fprintf(stdout, " %s", argv[i]);
     fflush(stdout);
     std::cout << "\n";
+    if (p.read_stats) std::cout << "INFO, read_stats(), contained reads = " << n_contained << " of " << n_reads << "\n";
     stage("stdout");
     if (timing) {
         timespec ts{};

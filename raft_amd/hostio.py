@@ -16,7 +16,7 @@ EXPORTS = ("raft_host_reads_load", "raft_host_reads_free", "raft_host_reads_coun
            "raft_host_paf_symmetric", "raft_host_unpack_coverage", "raft_host_write_coverage_packed",
            "raft_host_unpack_coverage_w", "raft_host_write_coverage_packed_w", "raft_host_text_read", "raft_host_text_free",
            "raft_host_paf_parse", "raft_host_group_offsets", "raft_host_pack_windows", "raft_host_unpack_coverage_d4",
-           "raft_host_write_coverage_d4")
+           "raft_host_write_coverage_d4", "raft_host_write_read_stats")
 
 
 class HostError(RuntimeError):
@@ -66,6 +66,7 @@ def load_library():
         lib.raft_host_unpack_coverage_d4.argtypes = [C.c_int64, vp, vp, C.c_int64, vp, vp, vp]
         lib.raft_host_write_coverage_d4.argtypes = [C.c_char_p, C.c_int32, C.c_int32, vp, vp, vp, C.c_int64, vp, vp]
         lib.raft_host_pack_windows.argtypes = [C.c_int64, vp, vp, C.c_int32, vp, C.POINTER(C.c_int64)]
+        lib.raft_host_write_read_stats.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), vp, C.c_int32] + [vp] * 7
         _lib = lib
     return _lib
 
