@@ -6,6 +6,10 @@
 //                         interval_source (bucket_sides), launch_pileup, launch_tail; raft_hip_finish is wait_for_pass, rerun_ladder,
 //                         collect_summary
 //   engine_pipeline.hip   the host-to-host entry points: chunked upload / pass / download, several contexts, routed streams
+//                         run_multi_impl is a sequence of phases over one plain PipelinePlan: check_arguments, choose_route, decide_derive,
+//                         plan_chunks, place_jobs, prepare_contexts, make_rings, run_lanes (Lane: a method per stage of a chunk),
+//                         drain_and_collect, reorder_exceptions, close_gaps
+//   pipeline_plan.hpp     its arithmetic, free of HIP: WindowDiv, the sorted runs, the chunk plan, the jobs' places, derive_slice
 //   engine_exchange.hip   pre-split PAF: symmetric flag across ranks, grouped sides, the exchange (RCCL / peer copies), the pre-split job
 //   engine_placement.hip  where buffers lie: pool, trim, policy, the placement trial, the callers' input buffers, page-locking
 #pragma once
