@@ -1,0 +1,160 @@
+// cli_plan.hpp -- what the `raft` command line (raft_main.cpp) decides, as plain functions over plain values: which devices a job
+// runs on, how large the arrays are that its results come back in, which coverage encoding it asks for first and what it asks for
+// after an overflow of the exception list, and the two descriptions on the stage clock.  No getenv, no file, no thread, nothing
+// of raft_hip.h but its constants: a host compiler alone builds it (tests/cli_plan_check.cpp does, under the sanitizers).
+#pragma once
+#include "../../include/raft_hip.h"
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace raft_cli {
+
+// RAFT_DEVICES=0,1,...: the GPUs of the node that share the job (reads shard across them, host-routed, no collective;
+// SURVEY.md §8e); RAFT_DEVICE=n: a single one; default: device 0.  A device may be named twice.  The list ends at the first
+// thing that is not a number, a trailing comma included.
+// RAFT_RANKS=N: the PRE-SPLIT job (BASELINE configs[3]): the record stream is cut into N contiguous slices, rank r
+// -- a context on device r modulo the devices named -- holds slice r, and ONE exchange step routes every interval to the rank
+// that owns its read (raft_hip_run_presplit_local).  Outputs are the single-rank run's, byte for byte.  ranks = 0: not such a job.
+struct DeviceList {
+    std::vector<int> devices;
+    int ranks = 0;
+};
+
+inline DeviceList device_list(const char *devices_text, const char *device_text, const char *ranks_text)
+{
+    DeviceList l;
+    if (const char *e = devices_text) {
+        for (const char *q = e; *q;) {
+            char *end = nullptr;
+            const long v = strtol(q, &end, 10);
+            if (end == q) break;
+            l.devices.push_back((int)v);
+            q = (*end == ',') ? end + 1 : end;
+            if (*end != ',' && *end != '\0') break;
+        }
+    }
+    if (l.devices.empty()) l.devices.push_back(device_text ? atoi(device_text) : 0);
+    l.ranks = ranks_text ? std::max(1, std::min(64, atoi(ranks_text))) : 0;
+    if (l.ranks > 0) {
+        const std::vector<int> named = l.devices;
+        l.devices.clear();
+        for (int r = 0; r < l.ranks; ++r) l.devices.push_back(named[(size_t)r % named.size()]);
+    }
+    return l;
+}
+
+// Host arrays for everything that comes back, sized by the bounds of raft_hip.h (from the read lengths alone): windows, repeats,
+// fragments, the first size of the exception list, the block anchors of the four-bit step encoding, and the bytes of the coverage
+// array (two per window: room for either byte encoding).
+struct Capacities {
+    int64_t n_win = 0, rep_cap = 0, frag_cap = 0, exc_cap0 = 0, n_anchor = 0, cov8_bytes = 0;
+};
+
+inline Capacities output_capacities(int32_t n_reads, const int32_t *read_len, int reso, int repeat_length, int interval_length)
+{
+    Capacities c;
+    const int64_t minw = std::max<int64_t>(((int64_t)repeat_length + reso - 1) / reso, 1);
+    int64_t sum_len = 0;
+    for (int32_t i = 0; i < n_reads; ++i) { c.n_win += ((int64_t)read_len[i] + reso - 1) / reso; sum_len += read_len[i]; }
+    c.rep_cap = (c.n_win + n_reads) / (minw + 1);
+    c.frag_cap = sum_len / interval_length + 2 * (int64_t)n_reads;
+    c.exc_cap0 = std::max<int64_t>(1 << 16, c.n_win / 64);
+    c.n_anchor = c.n_win / 1024 + 2;
+    c.cov8_bytes = (c.n_win + 1) * 2;
+    return c;
+}
+
+// The record count to within a few per cent from the size of the overlaps file: a PAF line of hifiasm's has ~63 bytes; .gz: ~4x
+// that when inflated.
+inline int64_t record_estimate(int64_t file_size, const std::string &name)
+{
+    const bool gz = name.size() > 3 && name.compare(name.size() - 3, 3, ".gz") == 0;
+    return file_size * (gz ? 4 : 1) / 60;
+}
+
+// Handing over the plain columns, the CLI does not know the stream's shape exactly; 8 k samples tell a handful of sorted runs --
+// which the engine cuts into chunks wherever it likes -- from a shuffled stream, whose routed chunks end where the host's buckets
+// do and keep the byte encodings.  A sample is compared with the sample before it; few: fewer than four descents.
+inline bool few_sorted_runs(const int32_t *qid, int64_t n_rec)
+{
+    const int64_t S = std::min<int64_t>(n_rec, 8192);
+    int descents = 0;
+    int64_t prev = 0;
+    for (int64_t i = 1; i < S; ++i) {
+        const int64_t pos = i * (n_rec - 1) / (S - 1);
+        if (qid[pos] < qid[prev]) ++descents;
+        prev = pos;
+    }
+    return descents < 4;
+}
+
+// One byte per window unless the expected coverage lets repeats pile up beyond it (from 40x on: two); -e auto, while the depth
+// is not known yet: two.
+inline int byte_width(bool auto_cov, int est_cov) { return auto_cov || est_cov >= 40 ? 2 : 1; }
+
+// What the device buffers are reserved for before the overlaps are tokenised: what a hifiasm-shaped PAF will use.
+inline int reserve_cov_width(bool no_delta4, bool auto_cov, int est_cov) { return no_delta4 ? byte_width(auto_cov, est_cov) : RAFT_HIP_COV_DELTA4; }
+
+// The job's first encoding.  Grouped input (whose chunks the pipelines can cut where they like) brings the coverage back as
+// four-bit steps: the step from one window to the next is the pileup's own difference array, within +-7 for all but a few windows
+// in a thousand whatever the depth -- half of a byte per window, a quarter of two.  Any other stream: the byte encodings.
+inline int first_cov_width(int n_runs, bool few_runs, bool no_delta4, int ranks, int est_cov)
+{
+    return ((n_runs > 0 || few_runs) && !no_delta4 && ranks == 0) ? RAFT_HIP_COV_DELTA4 : byte_width(false, est_cov);
+}
+
+// The width a context has outside the survey: 4 unless RAFT_COV_WIDTH (the test sweeps' variable, read by the engine) chose.
+inline int context_cov_width(const char *cov_width_text)
+{
+    const int was = cov_width_text ? atoi(cov_width_text) : 4;
+    return (was == 1 || was == 2 || was == RAFT_HIP_COV_DELTA4) ? was : 4;
+}
+
+// The ladder: an attempt that met more windows at or above the limit than the list holds (n_exc says how many) is followed by
+// one with two bytes per window when a byte leaves more than one window in 16 on the list (four-bit steps: one in 8 -- steps that
+// mostly do not fit are not a coverage profile), else by one with room for exactly those.  Three attempts at the most.
+struct Attempt {
+    int cov_width;
+    int64_t exc_cap;
+};
+
+inline bool ladder_stops(int rc, int attempt, int64_t n_exc, int64_t exc_cap)
+{
+    return rc != RAFT_HIP_ERR_TOO_LARGE || attempt == 2 || n_exc <= exc_cap;
+}
+
+inline Attempt next_attempt(int cov_width, int64_t exc_cap, int64_t n_exc, int64_t n_win)
+{
+    if (cov_width == RAFT_HIP_COV_DELTA4 && n_exc > n_win / 8) return {2, exc_cap};
+    if (cov_width == 1 && n_exc > n_win / 16) return {2, exc_cap};
+    return {cov_width, n_exc};
+}
+
+// starttime of /proc/self/stat, in clock ticks since boot: field 22, counted behind the LAST ')' (state is field 3), so that a
+// command name with blanks or parentheses does not shift the fields.  0: not there.
+inline unsigned long long stat_start_time(const char *stat_text)
+{
+    unsigned long long start = 0;
+    if (const char *q = strrchr(stat_text, ')')) {
+        int field = 2;
+        for (const char *t = q + 1; *t && field < 22; ++t)
+            if (*t == ' ') { ++field; if (field == 22) start = strtoull(t + 1, nullptr, 10); }
+    }
+    return start;
+}
+
+// `TIMING devices_used N input ...` and `TIMING coverage_encoding ...`
+inline const char *input_label(int ranks, bool windows, int n_runs, bool sym)
+{
+    return ranks > 0 ? "pre-split slices (one exchange step)"
+                     : windows ? "windows" : (n_runs > 0 ? "grouped" : (sym ? "columns (offsets and window records derived by the engine)" : "columns"));
+}
+
+inline const char *encoding_label(int cov_width) { return cov_width == RAFT_HIP_COV_DELTA4 ? "delta4" : (cov_width == 2 ? "uint16" : "uint8"); }
+
+} // namespace raft_cli

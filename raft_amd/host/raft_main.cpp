@@ -7,8 +7,14 @@
 // interval_length (main.cpp:44-47); -v falls through into -o (main.cpp:51-55); -i is accepted by getopt but has
 // no case, so it prints the usage and exits 1 (main.cpp:56-57); PREFIX.reads.fasta is created before the inputs
 // are validated (chop.hpp:333-349); messages go to stdout.
+//
+// main() is a list of phases over one Job.  What a phase decides from plain values is in cli_plan.hpp; the environment is read
+// in read_switches() and nowhere else (but for the exit block of main()).  Four helper threads run beside the main thread:
+// bring_up (the device contexts), paf_reader (the bytes of the overlaps file), out_prep (the arrays the results come back in)
+// and fasta_writer; where each is joined is part of what a phase does, and die() joins whatever still runs.
 #include "../../include/raft_hip.h"
 #include "../../include/raft_host.h"
+#include "cli_plan.hpp"
 
 #include <getopt.h>
 #include <unistd.h>
@@ -38,6 +44,63 @@ struct Params {            // param.hpp:18-31
     bool read_stats = false;       // --read-stats: PREFIX.read_stats.tsv, the per-read table (raft_hip_read_stats, raft_hip_census_host)
 };
 
+struct Switches {                  // the environment, as read_switches() found it
+    bool timing = false, no_warm_up = false, no_pin = false, no_delta4 = false, cli_prepare = false, no_grouped = false, no_windows = false;
+    int context_width = 4;         // the width the first context has outside the survey
+    int chunks = 0;                // 0: the engine decides (one piece for small inputs)
+};
+
+struct Job {
+    Params p;
+    const char *reads_fn = nullptr, *paf_fn = nullptr;
+    std::string fasta_out;
+    raft_hip_params hp{};
+    Switches sw;
+    std::chrono::system_clock::time_point t_start;              // the reference's timer
+    std::chrono::steady_clock::time_point t_main, t_prev;       // the stage clock
+    // the devices: context d is on devices[d]; ranks > 0: the pre-split job
+    std::vector<int> devices;
+    int ranks = 0;
+    std::vector<raft_hip_ctx *> ctxs;
+    std::vector<int> create_rc;
+    std::promise<void> devices_up_p;
+    std::shared_future<void> devices_up;
+    // the inputs
+    raft_host_text *paf_text = nullptr;
+    int paf_text_rc = RAFT_HOST_OK;
+    raft_host_reads *reads = nullptr;
+    int32_t n_reads = 0;
+    const int32_t *rl = nullptr;
+    raft_host_paf *paf = nullptr;
+    int64_t n_rec = 0;
+    const int32_t *col[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};    // qid, qs, qe, tid, ts, te
+    // the arrays everything comes back in (made and page-locked on out_prep)
+    raft_cli::Capacities cap;
+    std::vector<int64_t> cov_off, rep_off, frag_off;
+    std::unique_ptr<uint8_t[]> cov8;
+    std::unique_ptr<int32_t[]> rep_s, rep_e, fb, fe;
+    std::vector<int64_t> exc_i;
+    std::vector<int32_t> exc_v;
+    std::vector<int32_t> cov_anchor;          // the four-bit step encoding's block anchors (cov_width = RAFT_HIP_COV_DELTA4)
+    // --read-stats: the survey's coverage summary and the census of the record stream
+    std::vector<int64_t> rs_sum;
+    std::vector<int32_t> rs_max, rs_high, cen_intervals;
+    std::vector<uint8_t> cen_contained;
+    int64_t n_contained = 0;
+    // the form the job is handed over in, and what it brought back
+    std::unique_ptr<int64_t[]> rec_off;
+    int32_t n_runs = 0;
+    const uint32_t *win = nullptr;
+    bool sym = false;
+    int cov_width = 1;
+    raft_hip_summary s{};
+    int64_t n_exc = 0;
+    int fasta_rc = RAFT_HOST_OK;
+    std::thread bring_up, paf_reader, out_prep, fasta_writer;
+};
+
+Job *g_job = nullptr;      // for die()
+
 [[noreturn]] void print_help(const Params &p) // main.cpp:7-19
 {
     std::cout << "Usage: raft [options] <input-reads.fa> <in.paf>\n";
@@ -59,22 +122,45 @@ bool missing_or_empty(const char *fn) // chop.hpp:326-329,336-349
     return !f || f.peek() == std::ifstream::traits_type::eof();
 }
 
-std::thread *g_background[4] = {nullptr, nullptr, nullptr, nullptr};   // helpers that must be finished before the process exits
-
+// Main thread only.  The helpers must be finished before the process exits.
 [[noreturn]] void die(const std::string &msg)
 {
-    for (std::thread *t : g_background)
-        if (t && t->joinable()) t->join();
+    if (g_job)
+        for (std::thread *t : {&g_job->bring_up, &g_job->fasta_writer, &g_job->paf_reader, &g_job->out_prep})
+            if (t->joinable()) t->join();
     std::cout << msg << "\n";
     std::cout.flush();
     exit(1);
 }
 
-} // namespace
-
-int main(int argc, char *argv[])
+std::string engine_error(const Job &j, int code, int64_t index)
 {
-    Params p;
+    std::string m = std::string("ERROR, raft_hip, ") + raft_hip_strerror(code);
+    if (index >= 0) m += " (index " + std::to_string(index) + ")";
+    const char *d = raft_hip_last_error(j.ctxs[0]);
+    if (d && *d) m += std::string(" [") + d + "]";
+    return m;
+}
+
+// stage clock on stderr when RAFT_TIMING is set (stdout stays the reference's)
+void stage(Job &j, const char *what)
+{
+    const auto now = std::chrono::steady_clock::now();
+    if (j.sw.timing) fprintf(stderr, "TIMING %-16s %8.3f s\n", what, std::chrono::duration<double>(now - j.t_prev).count());
+    j.t_prev = now;
+}
+
+// Arrays that cross PCIe are page-locked once the runtime is up (raft_hip_host_register: the link's 53 GB/s instead of
+// the runtime's staging of pageable memory); not worth the calls for small inputs.  A failed registration is not an
+// error: the copy then takes the pageable path.
+void pin(const Job &j, const void *ptr, size_t bytes)
+{
+    if (!j.sw.no_pin && ptr && bytes >= (size_t)(64u << 10)) (void)raft_hip_host_register(const_cast<void *>(ptr), bytes);
+}
+
+void parse_options(Job &j, int argc, char *argv[])
+{
+    Params &p = j.p;
     int option;
     // (the short options and their quirks are the reference's; the one long option is this program's own)
     static const struct option long_options[] = {{"read-stats", no_argument, nullptr, 1000}, {nullptr, 0, nullptr, 0}};
@@ -98,7 +184,14 @@ int main(int argc, char *argv[])
         std::cout << "ERROR, main(), estimated coverage must be set properly\n";
         print_help(p);
     }
-    // param.hpp:33-43
+    j.reads_fn = argv[optind];
+    j.paf_fn = argv[optind + 1];
+    j.fasta_out = p.prefix + ".reads.fasta";
+}
+
+void print_params(Job &j) // param.hpp:33-43, and main.cpp's timer
+{
+    const Params &p = j.p;
     std::cout << "INFO, printParams(), reso = " << p.reso << "\n";
     if (p.auto_cov) std::cout << "INFO, printParams(), est_cov = auto\n";
     else std::cout << "INFO, printParams(), est_cov = " << p.est_cov << "\n";
@@ -109,426 +202,483 @@ int main(int argc, char *argv[])
     std::cout << "INFO, printParams(), overlap_length = " << p.overlap_length << "\n";
     std::cout << "INFO, printParams(), flanking_length = " << p.flanking_length << "\n";
 
-    const auto t_start = std::chrono::system_clock::now();
+    j.t_start = std::chrono::system_clock::now();
     std::cout << "INFO, main(), started timer\n";
+}
 
-    const char *reads_fn = argv[optind], *paf_fn = argv[optind + 1];
-    const std::string fasta_out = p.prefix + ".reads.fasta";
-    { std::ofstream touch(fasta_out); }               // chop.hpp:333: created before any validation
-    if (missing_or_empty(reads_fn)) die(std::string("ERROR, break_long_reads(), ") + reads_fn + " input file either does not exist or is empty");
-    if (missing_or_empty(paf_fn)) die(std::string("ERROR, break_long_reads(), ") + paf_fn + " input file either does not exist or is empty");
+void check_inputs(Job &j)
+{
+    { std::ofstream touch(j.fasta_out); }               // chop.hpp:333: created before any validation
+    if (missing_or_empty(j.reads_fn)) die(std::string("ERROR, break_long_reads(), ") + j.reads_fn + " input file either does not exist or is empty");
+    if (missing_or_empty(j.paf_fn)) die(std::string("ERROR, break_long_reads(), ") + j.paf_fn + " input file either does not exist or is empty");
+}
 
-    raft_hip_params hp{};
-    hp.reso = p.reso; hp.est_cov = p.auto_cov ? 1 : p.est_cov;   // (-e auto: a placeholder until the survey below -- create rejects 0)
+// what the contexts are created under; symmetric_mode follows once the overlaps are tokenised (hand_over_symmetric_flag)
+void fill_engine_params(Job &j)
+{
+    const Params &p = j.p;
+    raft_hip_params &hp = j.hp;
+    hp.reso = p.reso; hp.est_cov = p.auto_cov ? 1 : p.est_cov;   // (-e auto: a placeholder until the survey -- create rejects 0)
     hp.cov_mul = p.cov_mul; hp.repeat_length = p.repeat_length;
     hp.interval_length = p.interval_length; hp.read_length = p.read_length; hp.overlap_length = p.overlap_length;
     hp.flanking_length = p.flanking_length; hp.symmetric_mode = -1;
-    // stage clock on stderr when RAFT_TIMING is set (stdout stays the reference's)
-    const bool timing = getenv("RAFT_TIMING") != nullptr;
-    auto t_prev = std::chrono::steady_clock::now();
-    const auto t_main = t_prev;
-    auto stage = [&](const char *what) {
-        const auto now = std::chrono::steady_clock::now();
-        if (timing) fprintf(stderr, "TIMING %-16s %8.3f s\n", what, std::chrono::duration<double>(now - t_prev).count());
-        t_prev = now;
-    };
-    if (timing) {
-        // what the stage clock cannot see from inside (1.4 s of a 4.8 s run appeared in no stage): how old the process was
-        // when main() got here -- the loader mapping libamdhip64 and friends -- and, at the end, the moment main() leaves, so that
-        // whoever started the process can tell what the teardown behind _exit took (tools/cli_big.py prints both)
-        double age = -1.0;
-        if (FILE *f = fopen("/proc/self/stat", "r")) {
-            char buf[1024];
-            const size_t n = fread(buf, 1, sizeof buf - 1, f);
-            fclose(f);
-            buf[n] = 0;
-            if (const char *q = strrchr(buf, ')')) {           // (fields behind the command name: state is field 3, starttime field 22)
-                unsigned long long start = 0;
-                int field = 2;
-                for (const char *t = q + 1; *t && field < 22; ++t)
-                    if (*t == ' ') { ++field; if (field == 22) start = strtoull(t + 1, nullptr, 10); }
-                double up = 0.0;
-                if (FILE *u = fopen("/proc/uptime", "r")) { if (fscanf(u, "%lf", &up) != 1) up = 0.0; fclose(u); }
-                if (start && up > 0.0) age = up - (double)start / (double)sysconf(_SC_CLK_TCK);
-            }
-        }
-        fprintf(stderr, "TIMING %-16s %8.3f s\n", "process->main", age);
-    }
+}
 
-    // The device contexts come up (runtime init, first allocations) while the host tokenises the inputs.
-    // RAFT_DEVICES=0,1,...: the GPUs of the node that share the job (reads shard across them, host-routed, no collective;
-    // SURVEY.md §8e); RAFT_DEVICE=n: a single one; default: device 0.  A device may be named twice.
-    std::vector<int> devices;
-    if (const char *e = getenv("RAFT_DEVICES")) {
-        for (const char *q = e; *q;) {
-            char *end = nullptr;
-            const long v = strtol(q, &end, 10);
-            if (end == q) break;
-            devices.push_back((int)v);
-            q = (*end == ',') ? end + 1 : end;
-            if (*end != ',' && *end != '\0') break;
-        }
-    }
-    if (devices.empty()) { const char *e = getenv("RAFT_DEVICE"); devices.push_back(e ? atoi(e) : 0); }
-    // RAFT_RANKS=N: the PRE-SPLIT job (BASELINE configs[3]): the record stream is cut into N contiguous slices, rank r
-    // -- a context on device r modulo the devices named -- holds slice r, and ONE exchange step routes every interval to the rank
-    // that owns its read (raft_hip_run_presplit_local).  Outputs are the single-rank run's, byte for byte.
-    const int ranks = getenv("RAFT_RANKS") ? std::max(1, std::min(64, atoi(getenv("RAFT_RANKS")))) : 0;
-    if (ranks > 0) {
-        const std::vector<int> named = devices;
-        devices.clear();
-        for (int r = 0; r < ranks; ++r) devices.push_back(named[(size_t)r % named.size()]);
-    }
-    std::vector<raft_hip_ctx *> ctxs(devices.size(), nullptr);
-    std::vector<int> create_rc(devices.size(), RAFT_HIP_OK);
-    std::promise<void> devices_up_p;
-    std::shared_future<void> devices_up = devices_up_p.get_future().share();
-    std::thread bring_up([&] {
+// The one place that reads the environment (the exit block of main() apart).
+void read_switches(Job &j)
+{
+    Switches &sw = j.sw;
+    sw.timing = getenv("RAFT_TIMING") != nullptr;              // the stage clock on stderr
+    // which devices share the job, and whether it is the pre-split job of N ranks (cli_plan.hpp device_list)
+    const raft_cli::DeviceList l = raft_cli::device_list(getenv("RAFT_DEVICES"), getenv("RAFT_DEVICE"), getenv("RAFT_RANKS"));
+    j.devices = l.devices;
+    j.ranks = l.ranks;
+    sw.no_warm_up = getenv("RAFT_NO_WARM_UP") != nullptr;      // contexts are not warmed up, device buffers not reserved ahead of the job
+    sw.no_pin = getenv("RAFT_NO_PIN") != nullptr;              // host arrays stay pageable
+    sw.no_delta4 = getenv("RAFT_NO_DELTA4") != nullptr;        // coverage comes back in a byte encoding whatever the input's shape
+    sw.context_width = raft_cli::context_cov_width(getenv("RAFT_COV_WIDTH"));   // read by the engine at create: what the survey puts back
+    sw.cli_prepare = getenv("RAFT_CLI_PREPARE") != nullptr;    // group offsets and window records are made here, not by the engine
+    sw.no_grouped = getenv("RAFT_NO_GROUPED") != nullptr;      // ... but no group offsets: the plain columns go up
+    sw.no_windows = getenv("RAFT_NO_WINDOWS") != nullptr;      // ... but no window records: the coordinate columns go up
+    const char *chunks = getenv("RAFT_CHUNKS");                // pieces of the chunked pipeline; 0 / unset: the engine decides
+    sw.chunks = chunks ? atoi(chunks) : 0;
+}
+
+// What the stage clock cannot see from inside (1.4 s of a 4.8 s run appeared in no stage): how old the process was
+// when main() got here -- the loader mapping libamdhip64 and friends -- and, at the end, the moment main() leaves, so that
+// whoever started the process can tell what the teardown behind _exit took (tools/cli_big.py prints both).  -1: not known.
+double process_age()
+{
+    FILE *f = fopen("/proc/self/stat", "r");
+    if (!f) return -1.0;
+    char buf[1024];
+    const size_t n = fread(buf, 1, sizeof buf - 1, f);
+    fclose(f);
+    buf[n] = 0;
+    const unsigned long long start = raft_cli::stat_start_time(buf);
+    if (!start) return -1.0;
+    double up = 0.0;
+    if (FILE *u = fopen("/proc/uptime", "r")) { if (fscanf(u, "%lf", &up) != 1) up = 0.0; fclose(u); }
+    return up > 0.0 ? up - (double)start / (double)sysconf(_SC_CLK_TCK) : -1.0;
+}
+
+void start_clock(Job &j)
+{
+    j.t_prev = std::chrono::steady_clock::now();
+    j.t_main = j.t_prev;
+    if (j.sw.timing) fprintf(stderr, "TIMING %-16s %8.3f s\n", "process->main", process_age());
+}
+
+// The device contexts come up (runtime init, first allocations) while the host tokenises the inputs: created and warmed up --
+// the engine's code goes to the device, the pipeline's lanes come up: 70-80 ms that would otherwise sit inside the first job.
+// j.hp is read by these threads: nobody writes it before bring_up is joined.
+void start_devices(Job &j)
+{
+    j.ctxs.assign(j.devices.size(), nullptr);
+    j.create_rc.assign(j.devices.size(), RAFT_HIP_OK);
+    j.devices_up = j.devices_up_p.get_future().share();
+    j.bring_up = std::thread([&j] {
         std::vector<std::thread> th;
-        // (created and warmed up: the engine's code goes to the device, the pipeline's lanes come up -- 70-80 ms that would
-        // otherwise sit inside the first job)
-        auto up = [&](size_t d) {
-            create_rc[d] = raft_hip_create(devices[d], &hp, &ctxs[d]);
-            if (create_rc[d] == RAFT_HIP_OK && !getenv("RAFT_NO_WARM_UP")) create_rc[d] = raft_hip_warm_up(ctxs[d]);
+        auto up = [&j](size_t d) {
+            j.create_rc[d] = raft_hip_create(j.devices[d], &j.hp, &j.ctxs[d]);
+            if (j.create_rc[d] == RAFT_HIP_OK && !j.sw.no_warm_up) j.create_rc[d] = raft_hip_warm_up(j.ctxs[d]);
         };
-        for (size_t d = 1; d < devices.size(); ++d) th.emplace_back([&, d] { up(d); });
+        for (size_t d = 1; d < j.devices.size(); ++d) th.emplace_back([&up, d] { up(d); });
         up(0);
         for (auto &t : th) t.join();
-        devices_up_p.set_value();
+        j.devices_up_p.set_value();
     });
-    g_background[0] = &bring_up;
-    // Arrays that cross PCIe are page-locked once the runtime is up (raft_hip_host_register: the link's 53 GB/s instead of
-    // the runtime's staging of pageable memory); not worth the calls for small inputs.  A failed registration is not an
-    // error: the copy then takes the pageable path.
-    const bool no_pin = getenv("RAFT_NO_PIN") != nullptr;
-    auto pin = [&](const void *ptr, size_t bytes) {
-        if (!no_pin && ptr && bytes >= (size_t)(64u << 10)) (void)raft_hip_host_register(const_cast<void *>(ptr), bytes);
-    };
+}
 
-    // The overlaps file's bytes need nothing of the reads: they are read -- inflated, for a .gz -- beside the loading of
-    // the reads (on gz inputs, the reference's own quick-start shape, the two inflations are most of the run).
-    raft_host_text *paf_text = nullptr;
-    int paf_text_rc = RAFT_HOST_OK;
-    std::thread paf_reader([&] { paf_text_rc = raft_host_text_read(paf_fn, &paf_text); });
-    g_background[2] = &paf_reader;
+// The overlaps file's bytes need nothing of the reads: they are read -- inflated, for a .gz -- beside the loading of
+// the reads (on gz inputs, the reference's own quick-start shape, the two inflations are most of the run).
+void start_paf_read(Job &j)
+{
+    j.paf_reader = std::thread([&j] { j.paf_text_rc = raft_host_text_read(j.paf_fn, &j.paf_text); });
+}
 
-    raft_host_reads *reads = nullptr;
-    int rc = raft_host_reads_load(reads_fn, &reads);
-    stage("reads_load");
+void load_reads(Job &j)
+{
+    const int rc = raft_host_reads_load(j.reads_fn, &j.reads);
+    stage(j, "reads_load");
     if (rc == RAFT_HOST_ERR_DUP_NAME) die("ERROR, loadFASTA(), two reads share a name");
-    if (rc != RAFT_HOST_OK) die(std::string("ERROR, loadFASTA(), cannot read ") + reads_fn);
-    const int32_t n_reads = raft_host_reads_count(reads);
+    if (rc != RAFT_HOST_OK) die(std::string("ERROR, loadFASTA(), cannot read ") + j.reads_fn);
+    j.n_reads = raft_host_reads_count(j.reads);
+    j.rl = raft_host_reads_lengths(j.reads);
     std::cout.flush();
-    if (n_reads > 0) fprintf(stdout, "Real Reads %d \n", raft_host_reads_real(reads)); // chop.hpp:105
+    if (j.n_reads > 0) fprintf(stdout, "Real Reads %d \n", raft_host_reads_real(j.reads)); // chop.hpp:105
+}
 
-    // Host arrays for everything that comes back, sized by the bounds of raft_hip.h (from the read lengths alone).
-    // Coverage returns in its transfer encoding (a byte per window + the windows at or above 255): a quarter of the
-    // int32 array's bytes over PCIe, and the formatter below reads it as it is.  They are allocated and page-locked beside
-    // the tokenising of the overlaps (pinning untouched pages costs their first touch: 0.1 s for the 2 GB of a human set).
-    const int32_t *rl = raft_host_reads_lengths(reads);
-    int64_t n_win = 0, rep_cap = 0, frag_cap = 0;
-    std::vector<int64_t> cov_off((size_t)n_reads + 1), rep_off((size_t)n_reads + 1), frag_off((size_t)n_reads + 1);
-    std::unique_ptr<uint8_t[]> cov8;
-    std::unique_ptr<int32_t[]> rep_s, rep_e, fb, fe;
-    std::vector<int64_t> exc_i;
-    std::vector<int32_t> exc_v;
-    std::vector<int32_t> cov_anchor;          // the four-bit step encoding's block anchors (cov_width = RAFT_HIP_COV_DELTA4)
-    int64_t exc_cap0 = 0;
-    std::thread out_prep([&] {
-        const int64_t minw = std::max<int64_t>(((int64_t)p.repeat_length + p.reso - 1) / p.reso, 1);
-        int64_t sum_len = 0;
-        for (int32_t i = 0; i < n_reads; ++i) { n_win += ((int64_t)rl[i] + p.reso - 1) / p.reso; sum_len += rl[i]; }
-        rep_cap = (n_win + n_reads) / (minw + 1);
-        frag_cap = sum_len / p.interval_length + 2 * (int64_t)n_reads;
-        cov8.reset(new uint8_t[((size_t)n_win + 1) * 2]);                         // (not value-initialised: no zero fill)
-        rep_s.reset(new int32_t[(size_t)rep_cap + 1]); rep_e.reset(new int32_t[(size_t)rep_cap + 1]);
-        fb.reset(new int32_t[(size_t)frag_cap + 1]); fe.reset(new int32_t[(size_t)frag_cap + 1]);
-        exc_cap0 = std::max<int64_t>(1 << 16, n_win / 64);
-        exc_i.resize((size_t)exc_cap0); exc_v.resize((size_t)exc_cap0);
-        cov_anchor.resize((size_t)n_win / 1024 + 2);
-        devices_up.wait();
-        for (size_t d = 0; d < devices.size(); ++d) if (create_rc[d] != RAFT_HIP_OK) return;
-        pin(exc_i.data(), exc_i.size() * 8); pin(exc_v.data(), exc_v.size() * 4);
-        pin(cov_anchor.data(), cov_anchor.size() * 4);
-        pin(cov8.get(), ((size_t)n_win + 1) * (p.auto_cov || p.est_cov >= 40 ? 2 : 1));   // (-e auto: the depth is not known yet)
-        pin(fb.get(), ((size_t)frag_cap + 1) * 4); pin(fe.get(), ((size_t)frag_cap + 1) * 4);
-        pin(rep_s.get(), ((size_t)rep_cap + 1) * 4); pin(rep_e.get(), ((size_t)rep_cap + 1) * 4);
-        pin(cov_off.data(), cov_off.size() * 8); pin(frag_off.data(), frag_off.size() * 8); pin(rep_off.data(), rep_off.size() * 8);
-        pin(rl, (size_t)n_reads * 4);
-        // the job's device buffers, sized from what is known by now: the reads' lengths, and the record count to within a few
-        // per cent from the size of the overlaps file (a PAF line of hifiasm's has ~63 bytes; .gz: ~4x that when inflated)
-        if (!getenv("RAFT_NO_WARM_UP")) {
-            std::ifstream pf(paf_fn, std::ios::binary | std::ios::ate);
-            const std::string pn(paf_fn);
-            const bool gz = pn.size() > 3 && pn.compare(pn.size() - 3, 3, ".gz") == 0;
-            const int64_t est = pf ? (int64_t)pf.tellg() * (gz ? 4 : 1) / 60 : 0;
-            for (size_t d = 0; d < devices.size(); ++d)
-                (void)raft_hip_reserve(ctxs[d], n_reads, rl, est, (int32_t)devices.size(),
-                                       getenv("RAFT_NO_DELTA4") ? (p.auto_cov || p.est_cov >= 40 ? 2 : 1) : RAFT_HIP_COV_DELTA4);   // (what a hifiasm-shaped PAF will use)
-        }
-    });
-    g_background[3] = &out_prep;
+// On out_prep.  Host arrays for everything that comes back, sized by the bounds of raft_hip.h (from the read lengths alone).
+// Coverage returns in its transfer encoding (a byte per window + the windows at or above 255): a quarter of the
+// int32 array's bytes over PCIe, and the formatter reads it as it is.  They are allocated and page-locked beside
+// the tokenising of the overlaps (pinning untouched pages costs their first touch: 0.1 s for the 2 GB of a human set);
+// page-locking and reserving wait for the contexts and are left out when one of them did not come up.
+void prepare_outputs(Job &j)
+{
+    const Params &p = j.p;
+    j.cap = raft_cli::output_capacities(j.n_reads, j.rl, p.reso, p.repeat_length, p.interval_length);
+    const raft_cli::Capacities &c = j.cap;
+    j.cov8.reset(new uint8_t[(size_t)c.cov8_bytes]);                              // (not value-initialised: no zero fill)
+    j.rep_s.reset(new int32_t[(size_t)c.rep_cap + 1]); j.rep_e.reset(new int32_t[(size_t)c.rep_cap + 1]);
+    j.fb.reset(new int32_t[(size_t)c.frag_cap + 1]); j.fe.reset(new int32_t[(size_t)c.frag_cap + 1]);
+    j.exc_i.resize((size_t)c.exc_cap0); j.exc_v.resize((size_t)c.exc_cap0);
+    j.cov_anchor.resize((size_t)c.n_anchor);
+    j.devices_up.wait();
+    for (size_t d = 0; d < j.devices.size(); ++d) if (j.create_rc[d] != RAFT_HIP_OK) return;
+    pin(j, j.exc_i.data(), j.exc_i.size() * 8); pin(j, j.exc_v.data(), j.exc_v.size() * 4);
+    pin(j, j.cov_anchor.data(), j.cov_anchor.size() * 4);
+    pin(j, j.cov8.get(), ((size_t)c.n_win + 1) * raft_cli::byte_width(p.auto_cov, p.est_cov));
+    pin(j, j.fb.get(), ((size_t)c.frag_cap + 1) * 4); pin(j, j.fe.get(), ((size_t)c.frag_cap + 1) * 4);
+    pin(j, j.rep_s.get(), ((size_t)c.rep_cap + 1) * 4); pin(j, j.rep_e.get(), ((size_t)c.rep_cap + 1) * 4);
+    pin(j, j.cov_off.data(), j.cov_off.size() * 8); pin(j, j.frag_off.data(), j.frag_off.size() * 8); pin(j, j.rep_off.data(), j.rep_off.size() * 8);
+    pin(j, j.rl, (size_t)j.n_reads * 4);
+    // the job's device buffers, sized from what is known by now: the reads' lengths, and the record count from the size of the
+    // overlaps file (cli_plan.hpp record_estimate)
+    if (!j.sw.no_warm_up) {
+        std::ifstream pf(j.paf_fn, std::ios::binary | std::ios::ate);
+        const int64_t est = pf ? raft_cli::record_estimate((int64_t)pf.tellg(), j.paf_fn) : 0;
+        for (size_t d = 0; d < j.devices.size(); ++d)
+            (void)raft_hip_reserve(j.ctxs[d], j.n_reads, j.rl, est, (int32_t)j.devices.size(), raft_cli::reserve_cov_width(j.sw.no_delta4, p.auto_cov, p.est_cov));
+    }
+}
 
-    raft_host_paf *paf = nullptr;
+void start_output_prep(Job &j)
+{
+    j.cov_off.resize((size_t)j.n_reads + 1); j.rep_off.resize((size_t)j.n_reads + 1); j.frag_off.resize((size_t)j.n_reads + 1);
+    j.out_prep = std::thread([&j] { prepare_outputs(j); });
+}
+
+void parse_paf(Job &j)
+{
     char bad[256] = {0};
-    paf_reader.join();
-    stage("paf_read (rest)");
-    rc = paf_text_rc;
-    if (rc == RAFT_HOST_OK) rc = raft_host_paf_parse(paf_text, reads, &paf, bad, sizeof bad);
-    if (raft_host_paf_count(paf) < (1 << 22)) { raft_host_text_free(paf_text); paf_text = nullptr; }   // (a big file's GBs of touched pages are left to the process exit: unmapping them here -- or beside
-                                                                                   // the pass, where it holds the address space's lock against the page-locking -- cost 0.3 s of a 4 s run)
+    j.paf_reader.join();
+    stage(j, "paf_read (rest)");
+    int rc = j.paf_text_rc;
+    if (rc == RAFT_HOST_OK) rc = raft_host_paf_parse(j.paf_text, j.reads, &j.paf, bad, sizeof bad);
+    // (a big file's GBs of touched pages are left to the process exit: unmapping them here -- or beside the pass, where it holds
+    // the address space's lock against the page-locking -- cost 0.3 s of a 4 s run)
+    if (raft_host_paf_count(j.paf) < (1 << 22)) { raft_host_text_free(j.paf_text); j.paf_text = nullptr; }
     if (rc == RAFT_HOST_ERR_UNKNOWN_NAME) die(std::string("ERROR, create_pileup(), read ") + bad + " of the overlaps file is not in the reads file");
-    if (rc != RAFT_HOST_OK) die(std::string("ERROR, create_pileup(), cannot read ") + paf_fn);
-    const int64_t n_rec = raft_host_paf_count(paf);
-    stage("paf_load");
-    bring_up.join();
-    for (size_t d = 0; d < devices.size(); ++d)
-        if (create_rc[d] != RAFT_HIP_OK)
-            die(std::string("ERROR, raft_hip_create(), device ") + std::to_string(devices[d]) + ": " + raft_hip_strerror(create_rc[d]));
-    raft_hip_ctx *ctx = ctxs[0];
-    stage("device_wait");
+    if (rc != RAFT_HOST_OK) die(std::string("ERROR, create_pileup(), cannot read ") + j.paf_fn);
+    j.n_rec = raft_host_paf_count(j.paf);
+    for (int k = 0; k < 6; ++k) j.col[k] = raft_host_paf_column(j.paf, k);
+    stage(j, "paf_load");
+}
 
-    // The tokeniser already knows whether the PAF is symmetric (chop.hpp:171-184, found while the lines were in
-    // registers): the engine is told, so it neither scans for the mirror of record 0 nor -- for a symmetric PAF -- is
-    // handed the target columns at all (half of the upload).
-    hp.symmetric_mode = ranks > 0 ? -1 : (raft_host_paf_symmetric(paf) ? 1 : 0);   // (a pre-split job finds the flag across its ranks)
-    out_prep.join();                                  // (its raft_hip_reserve reads the contexts' parameters: done before they change)
-    rc = raft_hip_set_params(ctx, &hp);
+void await_devices(Job &j)
+{
+    j.bring_up.join();
+    for (size_t d = 0; d < j.devices.size(); ++d)
+        if (j.create_rc[d] != RAFT_HIP_OK)
+            die(std::string("ERROR, raft_hip_create(), device ") + std::to_string(j.devices[d]) + ": " + raft_hip_strerror(j.create_rc[d]));
+    stage(j, "device_wait");
+}
+
+// The tokeniser already knows whether the PAF is symmetric (chop.hpp:171-184, found while the lines were in
+// registers): the engine is told, so it neither scans for the mirror of record 0 nor -- for a symmetric PAF -- is
+// handed the target columns at all (half of the upload).  bring_up is joined: j.hp may be written.
+void hand_over_symmetric_flag(Job &j)
+{
+    j.hp.symmetric_mode = j.ranks > 0 ? -1 : (raft_host_paf_symmetric(j.paf) ? 1 : 0);   // (a pre-split job finds the flag across its ranks)
+    j.out_prep.join();                                  // (its raft_hip_reserve reads the contexts' parameters: done before they change)
+    const int rc = raft_hip_set_params(j.ctxs[0], &j.hp);
     if (rc != RAFT_HIP_OK) die(std::string("ERROR, raft_hip_set_params(), ") + raft_hip_strerror(rc));
-    const bool sym = hp.symmetric_mode == 1 || (ranks > 0 && raft_host_paf_symmetric(paf));
-    auto engine_error = [&](int code, int64_t index) {
-        std::string m = std::string("ERROR, raft_hip, ") + raft_hip_strerror(code);
-        if (index >= 0) m += " (index " + std::to_string(index) + ")";
-        const char *d = raft_hip_last_error(ctx);
-        if (d && *d) m += std::string(" [") + d + "]";
-        return m;
-    };
+    j.sym = j.hp.symmetric_mode == 1 || (j.ranks > 0 && raft_host_paf_symmetric(j.paf));
+}
 
-    // -e auto: the survey.  cov[] does not depend on est_cov, so one one-piece pass on the first context under the placeholder holds
-    // the number -e stands for: its coverage histogram is made on the device (32 KiB come back instead of cov[]) and the estimate
-    // read from it (raft_hip.h).  The pass writes two-byte codes and no cut points -- nothing of it is fetched --, and its
-    // overlap_length is 0: which fragments there are depends on the repeats, hence on the placeholder, and RAFT_HIP_ERR_FRAGMENT of
-    // the survey would not be the job's.  Every other data error (ids, coordinates, lengths) is the one the job would report, in
-    // its words.  With several devices or ranks the survey still runs in one piece on the first: one more upload of the columns.
-    //
-    // --read-stats: the per-read table.  Its coverage summary (raft_hip_read_stats) is taken from the same survey pass, right behind
-    // the histogram, under threshold = (int)(est_cov * cov_mul); without -e auto one such pass -- the survey's recipe -- runs here for
-    // it.  The census of the record stream (raft_hip_census_host) reads the tokenised columns under the job's symmetric flag, before
-    // anything below writes window records over the query column.  The job itself runs as it does without the option.
-    std::vector<int64_t> rs_sum;
-    std::vector<int32_t> rs_max, rs_high, cen_intervals;
-    std::vector<uint8_t> cen_contained;
-    int64_t n_contained = 0;
-    if (p.auto_cov || p.read_stats) {
-        raft_hip_params sp = hp;
-        sp.overlap_length = 0;
-        const char *we = getenv("RAFT_COV_WIDTH");           // (what the context's width was: 4 unless the test sweeps' variable chose)
-        const int was = we ? atoi(we) : 4;
-        const int width_before = (was == 1 || was == 2 || was == RAFT_HIP_COV_DELTA4) ? was : 4;
-        const bool targets = hp.symmetric_mode != 1;
-        raft_hip_summary ss{};
-        ss.error_index = -1;
-        rc = raft_hip_set_params(ctx, &sp);
+// What the survey changes on the first context, and the way back: its own parameters, two-byte codes and no cut points for the
+// pass; then the width the context had and the cut points again (restore_outputs), and the job's parameters (restore_params).
+// Both restores are calls whose codes the survey reports.
+struct SurveySettings {
+    raft_hip_ctx *ctx;
+    int width_before;
+    int apply(const raft_hip_params &sp)
+    {
+        int rc = raft_hip_set_params(ctx, &sp);
         if (rc == RAFT_HIP_OK) rc = raft_hip_set_output_width(ctx, 2);
         if (rc == RAFT_HIP_OK) rc = raft_hip_set_emit_cuts(ctx, 0);
-        if (rc == RAFT_HIP_OK)
-            rc = raft_hip_run_host(ctx, n_reads, rl, n_rec, raft_host_paf_column(paf, 0), raft_host_paf_column(paf, 1), raft_host_paf_column(paf, 2),
-                                   targets ? raft_host_paf_column(paf, 3) : nullptr, targets ? raft_host_paf_column(paf, 4) : nullptr,
-                                   targets ? raft_host_paf_column(paf, 5) : nullptr);
-        if (rc == RAFT_HIP_OK) rc = raft_hip_finish(ctx, &ss);
-        if (rc != RAFT_HIP_OK) die(engine_error(rc, ss.error_index));
-        raft_hip_cov_estimate est{};
-        est.est_cov = p.est_cov;
-        if (p.auto_cov) {
-            std::vector<int64_t> hist(RAFT_HIP_COV_HIST_BINS);
-            rc = raft_hip_cov_histogram(ctx, hist.data(), nullptr);
-            if (rc == RAFT_HIP_OK) rc = raft_hip_estimate_coverage(hist.data(), RAFT_HIP_COV_HIST_BINS, &est);
-        }
-        if (rc == RAFT_HIP_OK && p.read_stats && est.est_cov > 0) {
-            rs_sum.resize((size_t)n_reads); rs_max.resize((size_t)n_reads); rs_high.resize((size_t)n_reads);
-            const int32_t high_cov = (int32_t)(est.est_cov * p.cov_mul);          // (the job's: repeat.hpp:89-90)
-            rc = raft_hip_read_stats(ctx, std::max(high_cov, 1), rs_sum.data(), rs_max.data(), rs_high.data(), nullptr);
-            if (high_cov < 1)                                                      // (every window is at or above a threshold below 1)
-                for (int32_t i = 0; i < n_reads; ++i) rs_high[(size_t)i] = (int32_t)(((int64_t)rl[i] + p.reso - 1) / p.reso);
-        }
-        if (rc == RAFT_HIP_OK) rc = raft_hip_set_output_width(ctx, width_before);
-        if (rc == RAFT_HIP_OK) rc = raft_hip_set_emit_cuts(ctx, 1);
-        if (rc != RAFT_HIP_OK) die(engine_error(rc, -1));
-        stage("estimate");
-        if (p.auto_cov) {
-            if (est.est_cov <= 0) {                              // no window anybody overlaps: as for -e 0
-                std::cout << "ERROR, main(), estimated coverage must be set properly\n";
-                print_help(p);
-            }
-            fprintf(stdout, "INFO, estimate_coverage(), est_cov = %d\n", est.est_cov);
-            p.est_cov = est.est_cov;
-            hp.est_cov = est.est_cov;
-        }
-        rc = raft_hip_set_params(ctx, &hp);                  // (the first context's parameters are what every device and rank runs under)
-        if (rc != RAFT_HIP_OK) die(std::string("ERROR, raft_hip_set_params(), ") + raft_hip_strerror(rc));
+        return rc;
     }
-    if (p.read_stats) {
-        cen_intervals.resize((size_t)n_reads); cen_contained.resize((size_t)n_reads);
-        int64_t bad_index = -1;
-        rc = raft_hip_census_host(ctx, n_reads, rl, n_rec, raft_host_paf_column(paf, 0), raft_host_paf_column(paf, 1), raft_host_paf_column(paf, 2),
-                                  raft_host_paf_column(paf, 3), sym ? nullptr : raft_host_paf_column(paf, 4), sym ? nullptr : raft_host_paf_column(paf, 5),
-                                  sym ? 1 : 0, cen_intervals.data(), cen_contained.data(), &n_contained, &bad_index, nullptr);
-        if (rc != RAFT_HIP_OK) die(engine_error(rc, bad_index));
-        stage("census");
+    int restore_outputs()
+    {
+        const int rc = raft_hip_set_output_width(ctx, width_before);
+        return rc == RAFT_HIP_OK ? raft_hip_set_emit_cuts(ctx, 1) : rc;
     }
+    int restore_params(const raft_hip_params &hp) { return raft_hip_set_params(ctx, &hp); }   // (the first context's parameters are what every device and rank runs under)
+};
 
-    // hifiasm writes its PAF grouped by query (reference README.md:36-38): a symmetric stream of at most four runs sorted by
-    // read id is handed over in its grouped form -- per run, where every read's records begin -- and the query column stays
-    // on the host (a third of the upload); any other stream goes up as it is.
-    // Round 4: by default neither is prepared here any more.  The engine's host pipeline derives both from the plain columns of a
-    // symmetric stream itself, chunk by chunk, beside the uploads of the chunks before (raft_hip.h "derived input"): the two
-    // stages below were a second and a third pass over the columns between the parse and the engine (19 ms for 4.4e7 records).
-    // RAFT_CLI_PREPARE=1 keeps them (A/B, and the grouped / window-record entry points through the CLI).
-    std::unique_ptr<int64_t[]> rec_off;
-    int32_t n_runs = 0;
-    const bool prepare = getenv("RAFT_CLI_PREPARE") != nullptr && ranks == 0;
-    if (prepare && sym && n_rec > 0 && !getenv("RAFT_NO_GROUPED")) {
-        rec_off.reset(new int64_t[(size_t)4 * ((size_t)n_reads + 1)]);
-        if (raft_host_group_offsets(n_reads, n_rec, raft_host_paf_column(paf, 0), 4, &n_runs, rec_off.get()) != RAFT_HOST_OK) n_runs = 0;
-        if (n_runs == 0 && devices.size() == 1 && n_rec < ((int64_t)1 << 29)) {
+// --read-stats: the coverage summary of the pass that has just run, under threshold = (int)(est_cov * cov_mul)
+int survey_read_stats(Job &j, int est_cov)
+{
+    j.rs_sum.resize((size_t)j.n_reads); j.rs_max.resize((size_t)j.n_reads); j.rs_high.resize((size_t)j.n_reads);
+    const int32_t high_cov = (int32_t)(est_cov * j.p.cov_mul);          // (the job's: repeat.hpp:89-90)
+    const int rc = raft_hip_read_stats(j.ctxs[0], std::max(high_cov, 1), j.rs_sum.data(), j.rs_max.data(), j.rs_high.data(), nullptr);
+    if (high_cov < 1)                                                    // (every window is at or above a threshold below 1)
+        for (int32_t i = 0; i < j.n_reads; ++i) j.rs_high[(size_t)i] = (int32_t)(((int64_t)j.rl[i] + j.p.reso - 1) / j.p.reso);
+    return rc;
+}
+
+// -e auto: the survey.  cov[] does not depend on est_cov, so one one-piece pass on the first context under the placeholder holds
+// the number -e stands for: its coverage histogram is made on the device (32 KiB come back instead of cov[]) and the estimate
+// read from it (raft_hip.h).  The pass writes two-byte codes and no cut points -- nothing of it is fetched --, and its
+// overlap_length is 0: which fragments there are depends on the repeats, hence on the placeholder, and RAFT_HIP_ERR_FRAGMENT of
+// the survey would not be the job's.  Every other data error (ids, coordinates, lengths) is the one the job would report, in
+// its words.  With several devices or ranks the survey still runs in one piece on the first: one more upload of the columns.
+//
+// --read-stats: the per-read table.  Its coverage summary (raft_hip_read_stats) is taken from the same survey pass, right behind
+// the histogram; without -e auto one such pass -- the survey's recipe -- runs here for it.  The job itself runs as it does
+// without the option.
+void survey(Job &j)
+{
+    Params &p = j.p;
+    if (!p.auto_cov && !p.read_stats) return;
+    raft_hip_ctx *ctx = j.ctxs[0];
+    SurveySettings settings{ctx, j.sw.context_width};
+    raft_hip_params sp = j.hp;
+    sp.overlap_length = 0;
+    const bool targets = j.hp.symmetric_mode != 1;
+    raft_hip_summary ss{};
+    ss.error_index = -1;
+    int rc = settings.apply(sp);
+    if (rc == RAFT_HIP_OK)
+        rc = raft_hip_run_host(ctx, j.n_reads, j.rl, j.n_rec, j.col[0], j.col[1], j.col[2], targets ? j.col[3] : nullptr, targets ? j.col[4] : nullptr,
+                               targets ? j.col[5] : nullptr);
+    if (rc == RAFT_HIP_OK) rc = raft_hip_finish(ctx, &ss);
+    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, ss.error_index));
+    raft_hip_cov_estimate est{};
+    est.est_cov = p.est_cov;
+    if (p.auto_cov) {
+        std::vector<int64_t> hist(RAFT_HIP_COV_HIST_BINS);
+        rc = raft_hip_cov_histogram(ctx, hist.data(), nullptr);
+        if (rc == RAFT_HIP_OK) rc = raft_hip_estimate_coverage(hist.data(), RAFT_HIP_COV_HIST_BINS, &est);
+    }
+    if (rc == RAFT_HIP_OK && p.read_stats && est.est_cov > 0) rc = survey_read_stats(j, est.est_cov);
+    if (rc == RAFT_HIP_OK) rc = settings.restore_outputs();
+    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, -1));
+    stage(j, "estimate");
+    if (p.auto_cov) {
+        if (est.est_cov <= 0) {                              // no window anybody overlaps: as for -e 0
+            std::cout << "ERROR, main(), estimated coverage must be set properly\n";
+            print_help(p);
+        }
+        fprintf(stdout, "INFO, estimate_coverage(), est_cov = %d\n", est.est_cov);
+        p.est_cov = est.est_cov;
+        j.hp.est_cov = est.est_cov;
+    }
+    rc = settings.restore_params(j.hp);
+    if (rc != RAFT_HIP_OK) die(std::string("ERROR, raft_hip_set_params(), ") + raft_hip_strerror(rc));
+}
+
+// --read-stats: the census of the record stream (raft_hip_census_host) reads the tokenised columns under the job's symmetric
+// flag, before prepare_input() writes window records over the query column.
+void census(Job &j)
+{
+    if (!j.p.read_stats) return;
+    j.cen_intervals.resize((size_t)j.n_reads); j.cen_contained.resize((size_t)j.n_reads);
+    int64_t bad_index = -1;
+    const int rc = raft_hip_census_host(j.ctxs[0], j.n_reads, j.rl, j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.sym ? nullptr : j.col[4],
+                                        j.sym ? nullptr : j.col[5], j.sym ? 1 : 0, j.cen_intervals.data(), j.cen_contained.data(), &j.n_contained, &bad_index, nullptr);
+    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
+    stage(j, "census");
+}
+
+// hifiasm writes its PAF grouped by query (reference README.md:36-38): a symmetric stream of at most four runs sorted by
+// read id is handed over in its grouped form -- per run, where every read's records begin -- and the query column stays
+// on the host (a third of the upload); any other stream goes up as it is.
+// By default neither that nor the window records are prepared here: the engine's host pipeline derives both from the plain columns
+// of a symmetric stream itself, chunk by chunk, beside the uploads of the chunks before (raft_hip.h "derived input"); made here
+// they are a second and a third pass over the columns between the parse and the engine (19 ms for 4.4e7 records).
+// RAFT_CLI_PREPARE=1 keeps them (A/B, and the grouped / window-record entry points through the CLI).
+void prepare_input(Job &j)
+{
+    const bool prepare = j.sw.cli_prepare && j.ranks == 0;
+    if (prepare && j.sym && j.n_rec > 0 && !j.sw.no_grouped) {
+        j.rec_off.reset(new int64_t[(size_t)4 * ((size_t)j.n_reads + 1)]);
+        if (raft_host_group_offsets(j.n_reads, j.n_rec, j.col[0], 4, &j.n_runs, j.rec_off.get()) != RAFT_HOST_OK) j.n_runs = 0;
+        if (j.n_runs == 0 && j.devices.size() == 1 && j.n_rec < ((int64_t)1 << 29)) {
             // more than four runs (a PAF concatenated from more than two pairs of files): up to sixteen are still grouped input
             // for one device -- merged into one run on the device instead of falling to the counting sort
-            rec_off.reset(new int64_t[(size_t)16 * ((size_t)n_reads + 1)]);
-            if (raft_host_group_offsets(n_reads, n_rec, raft_host_paf_column(paf, 0), 16, &n_runs, rec_off.get()) != RAFT_HOST_OK) n_runs = 0;
+            j.rec_off.reset(new int64_t[(size_t)16 * ((size_t)j.n_reads + 1)]);
+            if (raft_host_group_offsets(j.n_reads, j.n_rec, j.col[0], 16, &j.n_runs, j.rec_off.get()) != RAFT_HOST_OK) j.n_runs = 0;
         }
     }
-    stage("group_offsets");
+    stage(j, "group_offsets");
     // ... and its records as window records: what profileCoverage uses of an interval is the windows it touches
     // (repeat.hpp:69-72), two 16-bit indices where reads stay below 65,535 windows -- one word per record goes up instead
     // of two.  They are written over the query column, which grouped input no longer needs.
-    const uint32_t *win = nullptr;
-    if (n_runs > 0 && p.reso <= 32767 && !getenv("RAFT_NO_WINDOWS")) {
-        uint32_t *w = reinterpret_cast<uint32_t *>(const_cast<int32_t *>(raft_host_paf_column(paf, 0)));
+    if (j.n_runs > 0 && j.p.reso <= 32767 && !j.sw.no_windows) {
+        uint32_t *w = reinterpret_cast<uint32_t *>(const_cast<int32_t *>(j.col[0]));
         int64_t bad = -1;
-        if (raft_host_pack_windows(n_rec, raft_host_paf_column(paf, 1), raft_host_paf_column(paf, 2), p.reso, w, &bad) == RAFT_HOST_OK) win = w;
+        if (raft_host_pack_windows(j.n_rec, j.col[1], j.col[2], j.p.reso, w, &bad) == RAFT_HOST_OK) j.win = w;
         // (a negative coordinate or a window index beyond 16 bits: the coordinate columns go up, and the engine reports the former)
     }
-    stage("pack_windows");
-    if (n_runs > 0) pin(rec_off.get(), (size_t)n_runs * ((size_t)n_reads + 1) * 8);
-    if (win) pin(const_cast<uint32_t *>(win), (size_t)n_rec * 4);
-    else for (int k = n_runs > 0 ? 1 : 0; k < (sym ? 3 : 6); ++k) pin(raft_host_paf_column(paf, k), (size_t)n_rec * 4);
-    stage("page-lock");
-    // one byte per window unless the expected coverage lets repeats pile up beyond it (from 40x on: two), and two in any
-    // case when the first attempt meets more windows at or above 255 than the exception list holds
-    // ... but grouped input (whose chunks the pipelines can cut where they like) brings the coverage back as four-bit steps: the
-    // step from one window to the next is the pileup's own difference array, within +-7 for all but a few windows in a
-    // thousand whatever the depth -- half of a byte per window, a quarter of two
-    // (handing over the plain columns, the CLI does not know the stream's shape exactly; 8 k samples tell a handful of sorted runs
-    // -- which the engine cuts into chunks wherever it likes -- from a shuffled stream, whose routed chunks end where the host's
-    // buckets do and keep the byte encodings)
-    bool few_runs = false;
-    if (sym && !prepare && n_rec > 0) {
-        const int32_t *q = raft_host_paf_column(paf, 0);
-        const int64_t S = std::min<int64_t>(n_rec, 8192);
-        int descents = 0;
-        int64_t prev = 0;
-        for (int64_t i = 1; i < S; ++i) {
-            const int64_t pos = S > 1 ? i * (n_rec - 1) / (S - 1) : 0;
-            if (q[pos] < q[prev]) ++descents;
-            prev = pos;
-        }
-        few_runs = descents < 4;
-    }
-    int cov_width = ((n_runs > 0 || few_runs) && !getenv("RAFT_NO_DELTA4") && ranks == 0) ? RAFT_HIP_COV_DELTA4 : (p.est_cov >= 40 ? 2 : 1);
-    raft_hip_summary s{};
-    int64_t n_exc = 0;
-    const char *chunks_env = getenv("RAFT_CHUNKS");   // 0 / unset: the engine decides (one piece for small inputs)
-    for (int64_t exc_cap = exc_cap0, attempt = 0; attempt < 3; ++attempt) {
-        if ((int64_t)exc_i.size() != exc_cap) {          // (a retry with more room: the first size was made and page-locked beside the tokenising)
-            if (!no_pin) { (void)raft_hip_host_unregister(exc_i.data()); (void)raft_hip_host_unregister(exc_v.data()); }
-            exc_i.resize((size_t)exc_cap); exc_v.resize((size_t)exc_cap);
-            pin(exc_i.data(), exc_i.size() * 8); pin(exc_v.data(), exc_v.size() * 4);
+    stage(j, "pack_windows");
+}
+
+// the inputs are page-locked in the form they go up in
+void lock_inputs(Job &j)
+{
+    if (j.n_runs > 0) pin(j, j.rec_off.get(), (size_t)j.n_runs * ((size_t)j.n_reads + 1) * 8);
+    if (j.win) pin(j, j.win, (size_t)j.n_rec * 4);
+    else for (int k = j.n_runs > 0 ? 1 : 0; k < (j.sym ? 3 : 6); ++k) pin(j, j.col[k], (size_t)j.n_rec * 4);
+    stage(j, "page-lock");
+}
+
+// The first attempt's coverage encoding (cli_plan.hpp first_cov_width; p.est_cov is the survey's by now): four-bit steps for
+// grouped input and for plain columns that look like a handful of sorted runs, else one byte per window, or two from 40x on.
+void choose_encoding(Job &j)
+{
+    const bool prepare = j.sw.cli_prepare && j.ranks == 0;
+    const bool few_runs = j.sym && !prepare && j.n_rec > 0 && raft_cli::few_sorted_runs(j.col[0], j.n_rec);
+    j.cov_width = raft_cli::first_cov_width(j.n_runs, few_runs, j.sw.no_delta4, j.ranks, j.p.est_cov);
+}
+
+// upload, pass and download of consecutive read ranges overlap, on every device named (one piece for small inputs)
+int call_engine(Job &j, raft_hip_host_outputs *ho)
+{
+    raft_hip_ctx **ctxs = j.ctxs.data();
+    const int32_t n_ctx = (int32_t)j.ctxs.size();
+    if (j.ranks > 0)
+        return raft_hip_run_presplit_local(ctxs, n_ctx, j.n_reads, j.rl, j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.col[4], j.col[5], ho, &j.s);
+    if (j.win)
+        return raft_hip_run_multi_windows(ctxs, n_ctx, j.n_reads, j.rl, j.n_rec, j.n_runs, j.rec_off.get(), j.win, j.sw.chunks, ho, &j.s);
+    if (j.n_runs > 0)
+        return raft_hip_run_multi_grouped(ctxs, n_ctx, j.n_reads, j.rl, j.n_rec, j.n_runs, j.rec_off.get(), j.col[1], j.col[2], j.sw.chunks, ho, &j.s);
+    return raft_hip_run_multi(ctxs, n_ctx, j.n_reads, j.rl, j.n_rec, j.col[0], j.col[1], j.col[2], j.sym ? nullptr : j.col[3], j.sym ? nullptr : j.col[4],
+                              j.sym ? nullptr : j.col[5], j.sw.chunks, ho, &j.s);
+}
+
+// The job, and the ladder behind it: an attempt that meets more windows at or above the limit than the exception list holds is
+// followed by the one cli_plan.hpp next_attempt names, three at the most.
+void run_engine(Job &j)
+{
+    const raft_cli::Capacities &c = j.cap;
+    int rc = RAFT_HIP_OK;
+    for (int64_t exc_cap = c.exc_cap0, attempt = 0; attempt < 3; ++attempt) {
+        if ((int64_t)j.exc_i.size() != exc_cap) {          // (a retry with more room: the first size was made and page-locked beside the tokenising)
+            if (!j.sw.no_pin) { (void)raft_hip_host_unregister(j.exc_i.data()); (void)raft_hip_host_unregister(j.exc_v.data()); }
+            j.exc_i.resize((size_t)exc_cap); j.exc_v.resize((size_t)exc_cap);
+            pin(j, j.exc_i.data(), j.exc_i.size() * 8); pin(j, j.exc_v.data(), j.exc_v.size() * 4);
         }
         raft_hip_host_outputs ho{};
-        ho.cov_offset = cov_off.data(); ho.cov8 = cov8.get(); ho.cov8_cap = n_win; ho.cov_width = cov_width;
-        ho.cov_anchor = cov_anchor.data(); ho.anchor_cap = (int64_t)cov_anchor.size();
-        ho.exc_index = exc_i.data(); ho.exc_value = exc_v.data(); ho.exc_cap = exc_cap;
-        ho.rep_offset = rep_off.data(); ho.rep_s = rep_s.get(); ho.rep_e = rep_e.get(); ho.rep_cap = rep_cap;
-        ho.frag_offset = frag_off.data(); ho.frag_begin = fb.get(); ho.frag_end = fe.get(); ho.frag_cap = frag_cap;
-        // upload, pass and download of consecutive read ranges overlap, on every device named (one piece for small inputs)
-        if (ranks > 0)
-            rc = raft_hip_run_presplit_local(ctxs.data(), (int32_t)ctxs.size(), n_reads, rl, n_rec, raft_host_paf_column(paf, 0), raft_host_paf_column(paf, 1),
-                                             raft_host_paf_column(paf, 2), raft_host_paf_column(paf, 3), raft_host_paf_column(paf, 4), raft_host_paf_column(paf, 5), &ho, &s);
-        else if (win)
-            rc = raft_hip_run_multi_windows(ctxs.data(), (int32_t)ctxs.size(), n_reads, rl, n_rec, n_runs, rec_off.get(), win,
-                                            chunks_env ? atoi(chunks_env) : 0, &ho, &s);
-        else if (n_runs > 0)
-            rc = raft_hip_run_multi_grouped(ctxs.data(), (int32_t)ctxs.size(), n_reads, rl, n_rec, n_runs, rec_off.get(),
-                                            raft_host_paf_column(paf, 1), raft_host_paf_column(paf, 2), chunks_env ? atoi(chunks_env) : 0, &ho, &s);
-        else
-            rc = raft_hip_run_multi(ctxs.data(), (int32_t)ctxs.size(), n_reads, rl, n_rec, raft_host_paf_column(paf, 0),
-                                    raft_host_paf_column(paf, 1), raft_host_paf_column(paf, 2), sym ? nullptr : raft_host_paf_column(paf, 3),
-                                    sym ? nullptr : raft_host_paf_column(paf, 4), sym ? nullptr : raft_host_paf_column(paf, 5),
-                                    chunks_env ? atoi(chunks_env) : 0, &ho, &s);
-        n_exc = ho.n_exc;
-        if (rc != RAFT_HIP_ERR_TOO_LARGE || attempt == 2 || n_exc <= exc_cap) break;
-        // more windows at or above the limit than the list holds (n_exc says how many): two bytes per window when a byte
-        // leaves more than one window in 16 on the list, else room for exactly those
-        if (cov_width == RAFT_HIP_COV_DELTA4 && n_exc > n_win / 8) cov_width = 2;      // (steps that mostly do not fit: not a coverage profile)
-        else if (cov_width == 1 && n_exc > n_win / 16) cov_width = 2;
-        else exc_cap = n_exc;
+        ho.cov_offset = j.cov_off.data(); ho.cov8 = j.cov8.get(); ho.cov8_cap = c.n_win; ho.cov_width = j.cov_width;
+        ho.cov_anchor = j.cov_anchor.data(); ho.anchor_cap = (int64_t)j.cov_anchor.size();
+        ho.exc_index = j.exc_i.data(); ho.exc_value = j.exc_v.data(); ho.exc_cap = exc_cap;
+        ho.rep_offset = j.rep_off.data(); ho.rep_s = j.rep_s.get(); ho.rep_e = j.rep_e.get(); ho.rep_cap = c.rep_cap;
+        ho.frag_offset = j.frag_off.data(); ho.frag_begin = j.fb.get(); ho.frag_end = j.fe.get(); ho.frag_cap = c.frag_cap;
+        rc = call_engine(j, &ho);
+        j.n_exc = ho.n_exc;
+        if (raft_cli::ladder_stops(rc, (int)attempt, j.n_exc, exc_cap)) break;
+        const raft_cli::Attempt next = raft_cli::next_attempt(j.cov_width, exc_cap, j.n_exc, c.n_win);
+        j.cov_width = next.cov_width;
+        exc_cap = next.exc_cap;
     }
-    if (rc != RAFT_HIP_OK) die(engine_error(rc, s.error_index));
-    stage("engine+fetch");
-    if (timing) fprintf(stderr, "TIMING devices_used %d input %s\n", s.n_devices_used, ranks > 0 ? "pre-split slices (one exchange step)" : win ? "windows" : (n_runs > 0 ? "grouped" : (sym ? "columns (offsets and window records derived by the engine)" : "columns")));
-    if (timing) fprintf(stderr, "TIMING coverage_encoding %s\n", cov_width == RAFT_HIP_COV_DELTA4 ? "delta4" : (cov_width == 2 ? "uint16" : "uint8"));
+    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, j.s.error_index));
+    stage(j, "engine+fetch");
+}
+
+void report(Job &j)
+{
+    const raft_hip_summary &s = j.s;
+    if (j.sw.timing) fprintf(stderr, "TIMING devices_used %d input %s\n", s.n_devices_used, raft_cli::input_label(j.ranks, j.win != nullptr, j.n_runs, j.sym));
+    if (j.sw.timing) fprintf(stderr, "TIMING coverage_encoding %s\n", raft_cli::encoding_label(j.cov_width));
     fprintf(stdout, "INFO, Symmetric overlaps %d \n", s.symmetric);            // chop.hpp:189-190
     fprintf(stdout, "INFO, length of alignments  %d()\n", (int)s.n_records);
     fprintf(stdout, "high_cov %d\n", s.high_cov);                              // repeat.hpp:91
+}
 
-    // the four output files are independent: the FASTA is written beside the coverage/repeat tables
-    int fasta_rc = RAFT_HOST_OK;
-    std::thread fasta_writer([&] { fasta_rc = raft_host_write_fasta(fasta_out.c_str(), reads, frag_off.data(), fb.get(), fe.get()); });
-    g_background[1] = &fasta_writer;
-    const int cov_rc = cov_width == RAFT_HIP_COV_DELTA4
-        ? raft_host_write_coverage_d4((p.prefix + ".coverage.txt").c_str(), n_reads, p.reso, cov_off.data(), cov8.get(), cov_anchor.data(), n_exc,
-                                      exc_i.data(), exc_v.data())
-        : raft_host_write_coverage_packed_w(cov_width, (p.prefix + ".coverage.txt").c_str(), n_reads, p.reso, cov_off.data(), cov8.get(), n_exc,
-                                            exc_i.data(), exc_v.data());
+void write_read_stats(Job &j)
+{
+    const Params &p = j.p;
+    std::vector<const char *> names((size_t)j.n_reads);
+    for (int32_t i = 0; i < j.n_reads; ++i) names[(size_t)i] = raft_host_reads_name(j.reads, i);
+    if (raft_host_write_read_stats((p.prefix + ".read_stats.tsv").c_str(), j.n_reads, names.data(), j.rl, p.reso, j.cen_intervals.data(), j.cen_contained.data(),
+                                   j.rs_sum.data(), j.rs_max.data(), j.rs_high.data(), j.rep_off.data(), j.frag_off.data()) != RAFT_HOST_OK)
+        die("ERROR, read_stats(), cannot write output files");
+}
+
+// the four output files are independent: the FASTA is written beside the coverage/repeat tables
+void write_outputs(Job &j)
+{
+    const Params &p = j.p;
+    const raft_hip_summary &s = j.s;
+    j.fasta_writer = std::thread([&j] { j.fasta_rc = raft_host_write_fasta(j.fasta_out.c_str(), j.reads, j.frag_off.data(), j.fb.get(), j.fe.get()); });
+    const int cov_rc = j.cov_width == RAFT_HIP_COV_DELTA4
+        ? raft_host_write_coverage_d4((p.prefix + ".coverage.txt").c_str(), j.n_reads, p.reso, j.cov_off.data(), j.cov8.get(), j.cov_anchor.data(), j.n_exc,
+                                      j.exc_i.data(), j.exc_v.data())
+        : raft_host_write_coverage_packed_w(j.cov_width, (p.prefix + ".coverage.txt").c_str(), j.n_reads, p.reso, j.cov_off.data(), j.cov8.get(), j.n_exc,
+                                            j.exc_i.data(), j.exc_v.data());
     if (cov_rc != RAFT_HOST_OK ||
-        raft_host_write_repeats((p.prefix + ".long_repeats.txt").c_str(), (p.prefix + ".long_repeats.bed").c_str(), reads,
-                                rep_off.data(), rep_s.get(), rep_e.get()) != RAFT_HOST_OK) {
+        raft_host_write_repeats((p.prefix + ".long_repeats.txt").c_str(), (p.prefix + ".long_repeats.bed").c_str(), j.reads,
+                                j.rep_off.data(), j.rep_s.get(), j.rep_e.get()) != RAFT_HOST_OK) {
         die("ERROR, repeat_annotate(), cannot write output files");
     }
-    if (p.read_stats) {
-        std::vector<const char *> names((size_t)n_reads);
-        for (int32_t i = 0; i < n_reads; ++i) names[(size_t)i] = raft_host_reads_name(reads, i);
-        if (raft_host_write_read_stats((p.prefix + ".read_stats.tsv").c_str(), n_reads, names.data(), rl, p.reso, cen_intervals.data(), cen_contained.data(),
-                                       rs_sum.data(), rs_max.data(), rs_high.data(), rep_off.data(), frag_off.data()) != RAFT_HOST_OK)
-            die("ERROR, read_stats(), cannot write output files");
-    }
-    stage("write_tables");
+    if (p.read_stats) write_read_stats(j);
+    stage(j, "write_tables");
     // repeat.hpp:173-178 (total_windows is an int in the reference; identical below 2^31 windows)
     const double cpw = (double)s.total_coverage / (double)s.total_windows;
     fprintf(stdout, "coverage per window is %f \n", cpw);
     fprintf(stdout, "coverage per window/average coverage is %f \n", cpw / p.est_cov);
     fprintf(stdout, "fraction_of_repeat_length %f \n", (double)s.total_repeat_length / (double)s.total_read_length);
 
-    fasta_writer.join();
-    if (fasta_rc != RAFT_HOST_OK) die("ERROR, break_reads(), cannot write " + fasta_out);
-    stage("write_fasta");
+    j.fasta_writer.join();
+    if (j.fasta_rc != RAFT_HOST_OK) die("ERROR, break_reads(), cannot write " + j.fasta_out);
+    stage(j, "write_fasta");
     fflush(stdout);
+}
 
-    const std::chrono::duration<double> wct = std::chrono::system_clock::now() - t_start;
+void print_totals(Job &j, int argc, char *argv[])
+{
+    const std::chrono::duration<double> wct = std::chrono::system_clock::now() - j.t_start;
     std::cout << "INFO, main(), program completed after " << wct.count() << " seconds\n";
     std::cout.flush();
-    fprintf(stdout, "INFO, %s(), CMD:", __func__);   // main.cpp:81-84
+    fprintf(stdout, "INFO, %s(), CMD:", "main");   // main.cpp:81-84
     for (int i = 0; i < argc; ++i) fprintf(stdout, " %s", argv[i]);
     fflush(stdout);
     std::cout << "\n";
-    if (p.read_stats) std::cout << "INFO, read_stats(), contained reads = " << n_contained << " of " << n_reads << "\n";
-    stage("stdout");
-    if (timing) {
+    if (j.p.read_stats) std::cout << "INFO, read_stats(), contained reads = " << j.n_contained << " of " << j.n_reads << "\n";
+    stage(j, "stdout");
+    if (j.sw.timing) {
         timespec ts{};
         clock_gettime(CLOCK_REALTIME, &ts);
-        fprintf(stderr, "TIMING %-16s %8.3f s\n", "main() total", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_main).count());
+        fprintf(stderr, "TIMING %-16s %8.3f s\n", "main() total", std::chrono::duration<double>(std::chrono::steady_clock::now() - j.t_main).count());
         fprintf(stderr, "TIMING %-16s %lld.%03ld\n", "leaving-at", (long long)ts.tv_sec, ts.tv_nsec / 1000000);
     }
+}
+
+} // namespace
+
+int main(int argc, char *argv[])
+{
+    Job job;
+    g_job = &job;
+    parse_options(job, argc, argv);
+    print_params(job);
+    check_inputs(job);
+    fill_engine_params(job);
+    read_switches(job);
+    start_clock(job);
+    start_devices(job);
+    start_paf_read(job);
+    load_reads(job);
+    start_output_prep(job);
+    parse_paf(job);
+    await_devices(job);
+    hand_over_symmetric_flag(job);
+    survey(job);
+    census(job);
+    prepare_input(job);
+    lock_inputs(job);
+    choose_encoding(job);
+    run_engine(job);
+    report(job);
+    write_outputs(job);
+    print_totals(job, argc, argv);
+    raft_host_text *const paf_text = job.paf_text;
+    raft_host_paf *const paf = job.paf;
+    raft_host_reads *const reads = job.reads;
+    const std::vector<raft_hip_ctx *> &ctxs = job.ctxs;
     // Everything is written and closed.  Unmapping a GB of reads, freeing the device buffers and tearing the HIP runtime
     // down cost 0.2-0.3 s of a run that takes a second: leave that to the kernel's process exit.
     const bool out_ok = fflush(stdout) == 0 && !ferror(stdout) && std::cout.good();

@@ -1,0 +1,317 @@
+// cli_plan_check.cpp -- raft_amd/host/cli_plan.hpp on its own: the device list, the output capacities, the record estimate, the
+// sampled run count, the coverage widths, the ladder after an overflowing exception list, the start-time field and the two
+// descriptions of the stage clock.  No HIP: a host compiler builds it (tests/test_cli_plan.py: under the address and
+// undefined-behaviour sanitizers).  Every expected value is a literal: what the statements of the former main() (raft_main.cpp at
+// 451f851, lines 139-181, 238-267, 425-437, 469-479) gave on the same inputs.
+#include "../raft_amd/host/cli_plan.hpp"
+
+#include <cstdio>
+#include <initializer_list>
+
+using namespace raft_cli;
+
+static int g_failed = 0;
+#define CHECK(cond, ...)                                                                   \
+    do {                                                                                   \
+        if (!(cond)) {                                                                     \
+            if (++g_failed <= 20) { fprintf(stderr, "%s:%d: %s -- ", __FILE__, __LINE__, #cond); fprintf(stderr, __VA_ARGS__); fputc('\n', stderr); } \
+        }                                                                                  \
+    } while (0)
+
+static const char *show(const char *s) { return s ? s : "(unset)"; }
+
+static void dev(const char *devices, const char *device, const char *ranks_text, int ranks, std::initializer_list<int> ids)
+{
+    const DeviceList l = device_list(devices, device, ranks_text);
+    CHECK(l.ranks == ranks, "RAFT_DEVICES=%s RAFT_DEVICE=%s RAFT_RANKS=%s: ranks %d, want %d", show(devices), show(device), show(ranks_text), l.ranks, ranks);
+    CHECK(l.devices == std::vector<int>(ids), "RAFT_DEVICES=%s RAFT_DEVICE=%s RAFT_RANKS=%s: %zu devices, first %d", show(devices), show(device), show(ranks_text),
+          l.devices.size(), l.devices.empty() ? -1 : l.devices[0]);
+}
+
+static void caps(std::vector<int32_t> len, int reso, int repeat_length, int interval_length, long long n_win, long long rep_cap, long long frag_cap,
+                 long long exc_cap0, long long n_anchor, long long cov8_bytes)
+{
+    const Capacities c = output_capacities((int32_t)len.size(), len.data(), reso, repeat_length, interval_length);
+    CHECK(c.n_win == n_win && c.rep_cap == rep_cap && c.frag_cap == frag_cap && c.exc_cap0 == exc_cap0 && c.n_anchor == n_anchor && c.cov8_bytes == cov8_bytes,
+          "%zu reads, reso %d, repeat_length %d, interval_length %d: %lld %lld %lld %lld %lld %lld", len.size(), reso, repeat_length, interval_length, (long long)c.n_win,
+          (long long)c.rep_cap, (long long)c.frag_cap, (long long)c.exc_cap0, (long long)c.n_anchor, (long long)c.cov8_bytes);
+}
+
+static void est(long long size, const char *name, long long want)
+{
+    CHECK(record_estimate(size, name) == want, "%lld bytes of %s: %lld, want %lld", size, name, (long long)record_estimate(size, name), want);
+}
+
+// An ascending query column of n_rec records with single low values in it: "sampledN" puts N of them on sampled positions,
+// "betweenN" one record behind a sampled position (which is a sampled position itself where every record is sampled).
+static std::vector<int32_t> make_q(const char *kind, int64_t n_rec)
+{
+    std::vector<int32_t> q((size_t)n_rec);
+    for (int64_t i = 0; i < n_rec; ++i) q[(size_t)i] = (int32_t)i;
+    const int64_t S = std::min<int64_t>(n_rec, 8192);
+    auto pos = [&](int64_t i) { return S > 1 ? i * (n_rec - 1) / (S - 1) : 0; };
+    int n = 0;
+    bool between = false;
+    if (sscanf(kind, "sampled%d", &n) == 1) between = false;
+    else if (sscanf(kind, "between%d", &n) == 1) between = true;
+    else if (strcmp(kind, "descending") == 0) { for (int64_t i = 0; i < n_rec; ++i) q[(size_t)i] = (int32_t)(n_rec - i); return q; }
+    for (int k = 1; k <= n; ++k) {               // n single low values, spread over the stream
+        const int64_t i = std::max<int64_t>(1, (S - 1) * k / (n + 1));
+        const int64_t at = pos(i) + (between ? 1 : 0);
+        if (at < n_rec) q[(size_t)at] = -1;
+    }
+    return q;
+}
+
+// descents: those of the whole column, a check of the generator (what the samples see of them is `want`)
+static void few(const char *kind, long long n_rec, int descents, bool want)
+{
+    const std::vector<int32_t> q = make_q(kind, n_rec);
+    int all = 0;
+    for (int64_t i = 1; i < n_rec; ++i) all += q[(size_t)i] < q[(size_t)i - 1];
+    CHECK(all == descents, "%s, %lld records: the column has %d descents, not %d", kind, n_rec, all, descents);
+    CHECK(few_sorted_runs(q.data(), n_rec) == want, "%s, %lld records: want %d", kind, n_rec, (int)want);
+}
+
+static void step(int cov_width, long long exc_cap, long long n_exc, long long n_win, int next_width, long long next_cap)
+{
+    const Attempt a = next_attempt(cov_width, exc_cap, n_exc, n_win);
+    CHECK(a.cov_width == next_width && a.exc_cap == next_cap, "width %d, room %lld, %lld exceptions, %lld windows: width %d, room %lld", cov_width, exc_cap, n_exc, n_win,
+          a.cov_width, (long long)a.exc_cap);
+}
+
+int main()
+{
+    // devices
+    dev("0,1", nullptr, nullptr, 0, {0, 1});
+    dev("0,1", "5", nullptr, 0, {0, 1});
+    dev("0,0,0", nullptr, nullptr, 0, {0, 0, 0});
+    dev("0,0,0", "5", nullptr, 0, {0, 0, 0});
+    dev("3", nullptr, nullptr, 0, {3});
+    dev("3", "5", nullptr, 0, {3});
+    dev("", nullptr, nullptr, 0, {0});
+    dev("", "5", nullptr, 0, {5});
+    dev("1,x", nullptr, nullptr, 0, {1});
+    dev("1,x", "5", nullptr, 0, {1});
+    dev("2,,3", nullptr, nullptr, 0, {2});
+    dev("2,,3", "5", nullptr, 0, {2});
+    dev("0,7,", nullptr, nullptr, 0, {0, 7});
+    dev("0,7,", "5", nullptr, 0, {0, 7});
+    dev(" 4", nullptr, nullptr, 0, {4});
+    dev(" 4", "5", nullptr, 0, {4});
+    dev(nullptr, nullptr, nullptr, 0, {0});
+    dev(nullptr, "5", nullptr, 0, {5});
+    dev("0,1", nullptr, "0", 1, {0});
+    dev(nullptr, "5", "0", 1, {5});
+    dev("0,1", nullptr, "3", 3, {0, 1, 0});
+    dev(nullptr, "5", "3", 3, {5, 5, 5});
+    dev("0,1", nullptr, "100", 64, {0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1});
+    dev(nullptr, "5", "100", 64, {5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5, 5});
+    dev("0,1", nullptr, "-2", 1, {0});
+    dev(nullptr, "5", "-2", 1, {5});
+    dev("2,,3", "6", "3", 3, {2, 2, 2});
+    dev("0,7,", nullptr, "5", 5, {0, 7, 0, 7, 0});
+    dev("", nullptr, "2", 2, {0, 0});
+    dev("0,1", nullptr, "x", 1, {0});
+    dev(nullptr, "x", nullptr, 0, {0});
+    // capacities
+    caps({}, 50, 10000, 10000, 0LL, 0LL, 0LL, 65536LL, 2LL, 2LL);
+    caps({0, 1, 49, 50, 51}, 50, 10000, 10000, 5LL, 0LL, 10LL, 65536LL, 2LL, 12LL);
+    caps({0, 1, 49, 50, 51}, 50, 100, 60, 5LL, 3LL, 12LL, 65536LL, 2LL, 12LL);
+    caps({0, 1, 2, 3}, 1, 10000, 10000, 6LL, 0LL, 8LL, 65536LL, 2LL, 14LL);
+    caps({0, 1, 2, 70000}, 1, 1, 1, 70003LL, 35003LL, 70011LL, 65536LL, 70LL, 140008LL);
+    caps({20000, 30000, 12345}, 50, 49, 10000, 1247LL, 625LL, 12LL, 65536LL, 3LL, 2496LL);
+    caps({20000, 30000, 12345}, 50, 1, 10000, 1247LL, 625LL, 12LL, 65536LL, 3LL, 2496LL);
+    caps({20000, 30000, 12345}, 7, 10000, 500, 8908LL, 6LL, 130LL, 65536LL, 10LL, 17818LL);
+    caps({1000000000, 1000000000, 1000000000}, 50, 10000, 10000, 60000000LL, 298507LL, 300006LL, 937500LL, 58595LL, 120000002LL);
+    caps({2147483647, 2147483647, 2147483647, 1}, 50, 10000, 10000, 128849020LL, 641039LL, 644253LL, 2013265LL, 125831LL, 257698042LL);
+    caps({2147483647, 2147483647}, 1, 10000, 10000, 4294967294LL, 429453LL, 429500LL, 67108863LL, 4194305LL, 8589934590LL);
+    // record estimate
+    est(0LL, "a.gz", 0LL);
+    est(0LL, ".gz", 0LL);
+    est(0LL, "x.paf.gz", 0LL);
+    est(0LL, "x.paf", 0LL);
+    est(0LL, "gz", 0LL);
+    est(59LL, "a.gz", 3LL);
+    est(59LL, ".gz", 0LL);
+    est(59LL, "x.paf.gz", 3LL);
+    est(59LL, "x.paf", 0LL);
+    est(59LL, "gz", 0LL);
+    est(60LL, "a.gz", 4LL);
+    est(60LL, ".gz", 1LL);
+    est(60LL, "x.paf.gz", 4LL);
+    est(60LL, "x.paf", 1LL);
+    est(60LL, "gz", 1LL);
+    est(2800000000LL, "a.gz", 186666666LL);
+    est(2800000000LL, ".gz", 46666666LL);
+    est(2800000000LL, "x.paf.gz", 186666666LL);
+    est(2800000000LL, "x.paf", 46666666LL);
+    est(2800000000LL, "gz", 46666666LL);
+    // few_sorted_runs
+    few("ascending", 1LL, 0, true);
+    few("descending", 1LL, 0, true);
+    few("sampled3", 1LL, 0, true);
+    few("sampled4", 1LL, 0, true);
+    few("between3", 1LL, 0, true);
+    few("between4", 1LL, 0, true);
+    few("between40", 1LL, 0, true);
+    few("ascending", 2LL, 0, true);
+    few("descending", 2LL, 1, true);
+    few("sampled3", 2LL, 1, true);
+    few("sampled4", 2LL, 1, true);
+    few("between3", 2LL, 0, true);
+    few("between4", 2LL, 0, true);
+    few("between40", 2LL, 0, true);
+    few("ascending", 8192LL, 0, true);
+    few("descending", 8192LL, 8191, false);
+    few("sampled3", 8192LL, 3, true);
+    few("sampled4", 8192LL, 4, false);
+    few("between3", 8192LL, 3, true);
+    few("between4", 8192LL, 4, false);
+    few("between40", 8192LL, 40, false);
+    few("ascending", 8193LL, 0, true);
+    few("descending", 8193LL, 8192, false);
+    few("sampled3", 8193LL, 3, true);
+    few("sampled4", 8193LL, 4, false);
+    few("between3", 8193LL, 3, true);
+    few("between4", 8193LL, 4, false);
+    few("between40", 8193LL, 40, false);
+    few("ascending", 100000LL, 0, true);
+    few("descending", 100000LL, 99999, false);
+    few("sampled3", 100000LL, 3, true);
+    few("sampled4", 100000LL, 4, false);
+    few("between3", 100000LL, 3, true);
+    few("between4", 100000LL, 4, true);
+    few("between40", 100000LL, 40, true);
+    // widths
+    CHECK(byte_width(false, 0) == 1, "byte_width");
+    CHECK(reserve_cov_width(false, false, 0) == 8, "reserve_cov_width");
+    CHECK(reserve_cov_width(true, false, 0) == 1, "reserve_cov_width");
+    CHECK(byte_width(false, 1) == 1, "byte_width");
+    CHECK(reserve_cov_width(false, false, 1) == 8, "reserve_cov_width");
+    CHECK(reserve_cov_width(true, false, 1) == 1, "reserve_cov_width");
+    CHECK(byte_width(false, 39) == 1, "byte_width");
+    CHECK(reserve_cov_width(false, false, 39) == 8, "reserve_cov_width");
+    CHECK(reserve_cov_width(true, false, 39) == 1, "reserve_cov_width");
+    CHECK(byte_width(false, 40) == 2, "byte_width");
+    CHECK(reserve_cov_width(false, false, 40) == 8, "reserve_cov_width");
+    CHECK(reserve_cov_width(true, false, 40) == 2, "reserve_cov_width");
+    CHECK(byte_width(false, 41) == 2, "byte_width");
+    CHECK(reserve_cov_width(false, false, 41) == 8, "reserve_cov_width");
+    CHECK(reserve_cov_width(true, false, 41) == 2, "reserve_cov_width");
+    CHECK(byte_width(true, 0) == 2, "byte_width");
+    CHECK(reserve_cov_width(false, true, 0) == 8, "reserve_cov_width");
+    CHECK(reserve_cov_width(true, true, 0) == 2, "reserve_cov_width");
+    CHECK(byte_width(true, 1) == 2, "byte_width");
+    CHECK(reserve_cov_width(false, true, 1) == 8, "reserve_cov_width");
+    CHECK(reserve_cov_width(true, true, 1) == 2, "reserve_cov_width");
+    CHECK(byte_width(true, 39) == 2, "byte_width");
+    CHECK(reserve_cov_width(false, true, 39) == 8, "reserve_cov_width");
+    CHECK(reserve_cov_width(true, true, 39) == 2, "reserve_cov_width");
+    CHECK(byte_width(true, 40) == 2, "byte_width");
+    CHECK(reserve_cov_width(false, true, 40) == 8, "reserve_cov_width");
+    CHECK(reserve_cov_width(true, true, 40) == 2, "reserve_cov_width");
+    CHECK(byte_width(true, 41) == 2, "byte_width");
+    CHECK(reserve_cov_width(false, true, 41) == 8, "reserve_cov_width");
+    CHECK(reserve_cov_width(true, true, 41) == 2, "reserve_cov_width");
+    CHECK(first_cov_width(0, false, false, 0, 39) == 1, "first_cov_width");
+    CHECK(first_cov_width(0, false, false, 0, 40) == 2, "first_cov_width");
+    CHECK(first_cov_width(0, false, false, 2, 39) == 1, "first_cov_width");
+    CHECK(first_cov_width(0, false, false, 2, 40) == 2, "first_cov_width");
+    CHECK(first_cov_width(0, false, true, 0, 39) == 1, "first_cov_width");
+    CHECK(first_cov_width(0, false, true, 0, 40) == 2, "first_cov_width");
+    CHECK(first_cov_width(0, false, true, 2, 39) == 1, "first_cov_width");
+    CHECK(first_cov_width(0, false, true, 2, 40) == 2, "first_cov_width");
+    CHECK(first_cov_width(0, true, false, 0, 39) == 8, "first_cov_width");
+    CHECK(first_cov_width(0, true, false, 0, 40) == 8, "first_cov_width");
+    CHECK(first_cov_width(0, true, false, 2, 39) == 1, "first_cov_width");
+    CHECK(first_cov_width(0, true, false, 2, 40) == 2, "first_cov_width");
+    CHECK(first_cov_width(0, true, true, 0, 39) == 1, "first_cov_width");
+    CHECK(first_cov_width(0, true, true, 0, 40) == 2, "first_cov_width");
+    CHECK(first_cov_width(0, true, true, 2, 39) == 1, "first_cov_width");
+    CHECK(first_cov_width(0, true, true, 2, 40) == 2, "first_cov_width");
+    CHECK(first_cov_width(1, false, false, 0, 39) == 8, "first_cov_width");
+    CHECK(first_cov_width(1, false, false, 0, 40) == 8, "first_cov_width");
+    CHECK(first_cov_width(1, false, false, 2, 39) == 1, "first_cov_width");
+    CHECK(first_cov_width(1, false, false, 2, 40) == 2, "first_cov_width");
+    CHECK(first_cov_width(1, false, true, 0, 39) == 1, "first_cov_width");
+    CHECK(first_cov_width(1, false, true, 0, 40) == 2, "first_cov_width");
+    CHECK(first_cov_width(1, false, true, 2, 39) == 1, "first_cov_width");
+    CHECK(first_cov_width(1, false, true, 2, 40) == 2, "first_cov_width");
+    CHECK(first_cov_width(1, true, false, 0, 39) == 8, "first_cov_width");
+    CHECK(first_cov_width(1, true, false, 0, 40) == 8, "first_cov_width");
+    CHECK(first_cov_width(1, true, false, 2, 39) == 1, "first_cov_width");
+    CHECK(first_cov_width(1, true, false, 2, 40) == 2, "first_cov_width");
+    CHECK(first_cov_width(1, true, true, 0, 39) == 1, "first_cov_width");
+    CHECK(first_cov_width(1, true, true, 0, 40) == 2, "first_cov_width");
+    CHECK(first_cov_width(1, true, true, 2, 39) == 1, "first_cov_width");
+    CHECK(first_cov_width(1, true, true, 2, 40) == 2, "first_cov_width");
+    // ladder
+    step(8, 65536LL, 125000LL, 1000000LL, 8, 125000LL);
+    step(8, 65536LL, 125001LL, 1000000LL, 2, 65536LL);
+    step(1, 65536LL, 62500LL, 1000000LL, 1, 62500LL);
+    step(1, 65536LL, 62501LL, 1000000LL, 2, 65536LL);
+    step(1, 65536LL, 125001LL, 1000000LL, 2, 65536LL);
+    step(2, 65536LL, 62501LL, 1000000LL, 2, 62501LL);
+    step(2, 65536LL, 999999LL, 1000000LL, 2, 999999LL);
+    step(8, 65536LL, 70000LL, 7LL, 2, 65536LL);
+    step(1, 65536LL, 70000LL, 15LL, 2, 65536LL);
+    step(1, 65536LL, 70000LL, 0LL, 2, 65536LL);
+    CHECK(ladder_stops(0, 0, 65535LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(0, 0, 65536LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(0, 0, 65537LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(0, 1, 65535LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(0, 1, 65536LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(0, 1, 65537LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(0, 2, 65535LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(0, 2, 65536LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(0, 2, 65537LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(8, 0, 65535LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(8, 0, 65536LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(8, 0, 65537LL, 65536LL) == false, "ladder_stops");
+    CHECK(ladder_stops(8, 1, 65535LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(8, 1, 65536LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(8, 1, 65537LL, 65536LL) == false, "ladder_stops");
+    CHECK(ladder_stops(8, 2, 65535LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(8, 2, 65536LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(8, 2, 65537LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(3, 0, 65535LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(3, 0, 65536LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(3, 0, 65537LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(3, 1, 65535LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(3, 1, 65536LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(3, 1, 65537LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(3, 2, 65535LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(3, 2, 65536LL, 65536LL) == true, "ladder_stops");
+    CHECK(ladder_stops(3, 2, 65537LL, 65536LL) == true, "ladder_stops");
+    // start time
+    CHECK(stat_start_time("4242 (raft) S 4 5 6 7 8 9 10 11 12 13 14 15 16 17 18 19 20 21 2200 23 24 25") == 2200ULL, "stat_start_time");
+    CHECK(stat_start_time("4242 (a b) S 4 5 6 7 8 9 10 11 12 13 14 15 16 17 18 19 20 21 2200 23 24 25") == 2200ULL, "stat_start_time");
+    CHECK(stat_start_time("4242 (x) y (z) S 4 5 6 7 8 9 10 11 12 13 14 15 16 17 18 19 20 21 2200 23 24 25") == 2200ULL, "stat_start_time");
+    CHECK(stat_start_time("4242 (raft) S 3 4 5") == 0ULL, "stat_start_time");
+    CHECK(stat_start_time("no parenthesis at all 1 2 3") == 0ULL, "stat_start_time");
+    CHECK(stat_start_time("") == 0ULL, "stat_start_time");
+    // labels
+    CHECK(strcmp(input_label(0, false, 0, false), "columns") == 0, "input_label");
+    CHECK(strcmp(input_label(0, false, 0, true), "columns (offsets and window records derived by the engine)") == 0, "input_label");
+    CHECK(strcmp(input_label(0, false, 2, false), "grouped") == 0, "input_label");
+    CHECK(strcmp(input_label(0, false, 2, true), "grouped") == 0, "input_label");
+    CHECK(strcmp(input_label(0, true, 0, false), "windows") == 0, "input_label");
+    CHECK(strcmp(input_label(0, true, 0, true), "windows") == 0, "input_label");
+    CHECK(strcmp(input_label(0, true, 2, false), "windows") == 0, "input_label");
+    CHECK(strcmp(input_label(0, true, 2, true), "windows") == 0, "input_label");
+    CHECK(strcmp(input_label(2, false, 0, false), "pre-split slices (one exchange step)") == 0, "input_label");
+    CHECK(strcmp(input_label(2, false, 0, true), "pre-split slices (one exchange step)") == 0, "input_label");
+    CHECK(strcmp(input_label(2, false, 2, false), "pre-split slices (one exchange step)") == 0, "input_label");
+    CHECK(strcmp(input_label(2, false, 2, true), "pre-split slices (one exchange step)") == 0, "input_label");
+    CHECK(strcmp(input_label(2, true, 0, false), "pre-split slices (one exchange step)") == 0, "input_label");
+    CHECK(strcmp(input_label(2, true, 0, true), "pre-split slices (one exchange step)") == 0, "input_label");
+    CHECK(strcmp(input_label(2, true, 2, false), "pre-split slices (one exchange step)") == 0, "input_label");
+    CHECK(strcmp(input_label(2, true, 2, true), "pre-split slices (one exchange step)") == 0, "input_label");
+    CHECK(strcmp(encoding_label(8), "delta4") == 0, "encoding_label");
+    CHECK(strcmp(encoding_label(2), "uint16") == 0, "encoding_label");
+    CHECK(strcmp(encoding_label(1), "uint8") == 0, "encoding_label");
+    if (g_failed) { fprintf(stderr, "cli_plan_check: %d checks failed\n", g_failed); return 1; }
+    printf("cli_plan_check: ok\n");
+    return 0;
+}

@@ -241,3 +241,55 @@ def test_cli_presplit_ranks(tmp_path, name, ranks):
         assert md5(open(tmp_path / f, "rb").read()) == digest, (name, f)
     line = [l for l in r.stderr.decode().splitlines() if l.startswith("TIMING devices_used")]
     assert line and line[0].split()[2] == str(ranks) and "pre-split" in line[0], r.stderr.decode()
+
+
+@pytest.mark.parametrize("name,lens,encoding", [("a_longer_list", [35000, 35000] + [70000] * 16, "uint8")])
+def test_cli_encoding_ladder(tmp_path, name, lens, encoding):
+    """The three-attempt ladder behind an overflowing exception list, through the CLI: -r 1 -e 30 with RAFT_NO_DELTA4=1, a
+    symmetric PAF of 256 records (0 -> 1) over the whole of both reads and their 256 mirrors, so every window of reads 0 and 1 sits
+    at 256 -- at or above a byte's limit -- and the list, which starts at max(65536, n_win / 64) = 65536 entries, is too short.
+    a_longer_list: 70,000 exceptions among 1.19 M windows, fewer than one in 16: the second attempt keeps the byte and brings a
+    list of exactly 70,000.  The files equal the oracle's arrays and, where it is built, the reference binary's files.
+    The rung that leaves the four-bit steps needs some 1e5 large steps in a set: tests/cli_plan_check.cpp covers it, not this.
+    The rung from one byte to two is not a case here because the CLI does not survive it: with reads 0 and 1 of 66,000 bases and
+    three of 100 (132,000 of 132,300 windows on the list, more than one in 16) the second attempt ends in `hipMemcpyAsync ...
+    invalid argument`, exit 1 -- the coverage array was page-locked for one byte per window, and the two-byte copy reaches beyond
+    the registered range (with RAFT_NO_PIN=1 the run gives `coverage_encoding uint16` and the reference's coverage file).  The decision
+    itself is in tests/cli_plan_check.cpp."""
+    import numpy as np
+    from raft_testlib import assert_same_result, have_ref_bin, oracle_run, result_from_ref_files, run_ref_binary
+    from raft_amd.params import RaftParams
+    rl = np.array(lens, np.int32)
+    qid = np.repeat(np.array([0, 1], np.int32), 256)
+    tid = 1 - qid
+    zero = np.zeros(qid.size, np.int32)
+    cols = [rl, qid, zero, rl[qid], tid, zero, rl[tid]]
+    names = [f"r{i}" for i in range(rl.size)]
+    write_fasta(tmp_path / "reads.fa", names, rl)
+    write_paf(tmp_path / "overlaps.paf", names, *cols)
+    args = ["-r", "1", "-e", "30", "-o", "out", "reads.fa", "overlaps.paf"]
+    r = subprocess.run([RAFT] + args, cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300,
+                       env=dict(os.environ, RAFT_NO_DELTA4="1", RAFT_TIMING="1"))
+    out, err = r.stdout.decode(), r.stderr.decode()
+    assert r.returncode == 0, out + err
+    assert f"TIMING coverage_encoding {encoding}\n" in err, err
+    want = oracle_run(RaftParams(reso=1, est_cov=30), *cols)
+    n_win = int(want["cov"].size)
+    n_exc = int((want["cov"] >= 255).sum())
+    assert max(65536, n_win // 64) == 65536 < n_exc and (n_exc > n_win // 16) == (encoding == "uint16")     # (the case is what the docstring says)
+    got = result_from_ref_files(str(tmp_path / "out"), names)
+    lines = out.split("\n")
+    got.update(symmetric=int("INFO, Symmetric overlaps 1 " in lines), high_cov=int([l for l in lines if l.startswith("high_cov ")][0].split()[1]),
+               total_windows=got["cov"].size, total_coverage=int(got["cov"].sum(dtype=np.int64)), total_read_length=int(rl.sum(dtype=np.int64)))
+    # what neither the files nor stdout carry as integers: the cut points (the fragments' bounds are made of them) and the summed
+    # repeat length, which stdout gives as a fraction
+    got.update(cut_offset=want["cut_offset"], cuts=want["cuts"], total_repeat_length=want["total_repeat_length"])
+    assert "fraction_of_repeat_length %f \n" % (want["total_repeat_length"] / want["total_read_length"]) in out
+    assert "coverage per window is %f \n" % (want["total_coverage"] / want["total_windows"]) in out
+    assert_same_result(got, want, name)
+    if have_ref_bin():
+        rc, ref_out = run_ref_binary(str(tmp_path), ["-r", "1", "-e", "30", "-o", "ref"], "reads.fa", "overlaps.paf")
+        assert rc == 0, ref_out[-400:]
+        for f in ("reads.fasta", "coverage.txt", "long_repeats.txt", "long_repeats.bed"):
+            assert md5(open(tmp_path / ("out." + f), "rb").read()) == md5(open(tmp_path / ("ref." + f), "rb").read()), (name, f)
+        assert strip_timing(out) == strip_timing(ref_out.decode())
