@@ -8,11 +8,13 @@ library is missing or no gfx950 device is present, construction fails.
 from __future__ import annotations
 
 import ctypes as C
+import operator
 import os
 from dataclasses import dataclass
 
 import numpy as np
 
+from . import _marshal as M
 from .params import RaftParams
 
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libraft_hip.so")
@@ -21,20 +23,6 @@ OK, ERR_PARAM, ERR_READ_ID, ERR_COORD, ERR_FRAGMENT, ERR_NOMEM, ERR_DEVICE, ERR_
 # Summary.flags (RAFT_HIP_SUM_*)
 SUM_BUCKET_WINDOWS, SUM_SPECULATED, SUM_DEEP_TILES, SUM_RERUN, SUM_KEPT_GEOMETRY = 1, 2, 4, 8, 16
 
-EXPORTS = (
-    "raft_hip_abi_version", "raft_hip_strerror", "raft_hip_last_error", "raft_hip_create", "raft_hip_destroy",
-    "raft_hip_set_params", "raft_hip_set_stream", "raft_hip_use_own_stream", "raft_hip_get_stream", "raft_hip_run_device", "raft_hip_run_host",
-    "raft_hip_finish", "raft_hip_outputs_device", "raft_hip_fetch", "raft_hip_last_timing", "raft_hip_set_tuning",
-    "raft_hip_selftest", "raft_hip_fetch_packed", "raft_hip_fetch_packed_w", "raft_hip_run_pipelined", "raft_hip_run_multi",
-    "raft_hip_set_output_width", "raft_hip_packed_device", "raft_hip_run_device_grouped", "raft_hip_run_host_grouped",
-    "raft_hip_run_multi_grouped", "raft_hip_host_register", "raft_hip_host_unregister", "raft_hip_comm_unique_id",
-    "raft_hip_comm_create", "raft_hip_comm_destroy", "raft_hip_exchange", "raft_hip_exchange_local", "raft_hip_warm_up", "raft_hip_reserve",
-    "raft_hip_run_device_windows", "raft_hip_run_host_windows", "raft_hip_run_multi_windows",
-    "raft_hip_fetch_delta4", "raft_hip_packed_anchor_device", "raft_hip_set_emit_cuts", "raft_hip_device_alloc", "raft_hip_device_free", "raft_hip_group_sides", "raft_hip_presplit_symmetric", "raft_hip_presplit_symmetric_local",
-    "raft_hip_trim", "raft_hip_pool_bytes", "raft_hip_run_presplit_local", "raft_hip_set_placement", "raft_hip_placement_trial",
-    "raft_hip_set_placement_trial", "raft_hip_cov_histogram", "raft_hip_estimate_coverage",
-    "raft_hip_read_stats", "raft_hip_census_device", "raft_hip_census_host",
-)
 COV_HIST_BINS = 4096              # RAFT_HIP_COV_HIST_BINS
 
 
@@ -84,6 +72,77 @@ class _CovEstimate(C.Structure):
 class _Outputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("cov_offset", "cov", "rep_offset", "rep_s", "rep_e", "cut_offset", "cuts",
                                           "frag_offset", "frag_read", "frag_begin", "frag_end")]
+
+
+_vp, _i32, _i64, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
+_P = C.POINTER
+_COLUMNS = [_i32, _vp, _i64] + [_vp] * 6                    # n_reads, read_len, n_rec, qid, qs, qe, tid, ts, te
+_GROUPED = [_i32, _vp, _i64, _i32, _vp]                     # n_reads, read_len, n_rec, n_runs, rec_offset
+_JOB = [_P(_HostOutputs), _P(_Summary)]
+_CENSUS = [_vp] + _COLUMNS + [_i32, _vp, _vp, _P(_i64), _P(_i64), _P(_f64)]
+
+# The C ABI: every entry point of include/raft_hip.h, in the header's order, as (restype, argtypes).  load_library declares
+# exactly this; tests/test_binding_tables.py compares it with the header, class by class.
+ABI = {
+    "raft_hip_abi_version": (C.c_int, []),
+    "raft_hip_strerror": (C.c_char_p, [C.c_int]),
+    "raft_hip_last_error": (C.c_char_p, [_vp]),
+    "raft_hip_create": (C.c_int, [C.c_int, _P(_Params), _P(_vp)]),
+    "raft_hip_destroy": (None, [_vp]),
+    "raft_hip_set_params": (C.c_int, [_vp, _P(_Params)]),
+    "raft_hip_set_stream": (C.c_int, [_vp, _vp]),
+    "raft_hip_use_own_stream": (C.c_int, [_vp]),
+    "raft_hip_get_stream": (_vp, [_vp]),
+    "raft_hip_run_device": (C.c_int, [_vp] + _COLUMNS),
+    "raft_hip_run_host": (C.c_int, [_vp] + _COLUMNS),
+    "raft_hip_run_device_grouped": (C.c_int, [_vp] + _GROUPED + [_vp, _vp, _vp, _i64]),
+    "raft_hip_run_host_grouped": (C.c_int, [_vp] + _GROUPED + [_vp, _vp, _i64]),
+    "raft_hip_run_device_windows": (C.c_int, [_vp] + _GROUPED + [_vp, _i64]),
+    "raft_hip_run_host_windows": (C.c_int, [_vp] + _GROUPED + [_vp, _i64]),
+    "raft_hip_finish": (C.c_int, [_vp, _P(_Summary)]),
+    "raft_hip_outputs_device": (C.c_int, [_vp, _P(_Outputs)]),
+    "raft_hip_fetch": (C.c_int, [_vp] + [_vp] * 11),
+    "raft_hip_fetch_packed": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _P(_i64)] + [_vp] * 7),
+    "raft_hip_fetch_packed_w": (C.c_int, [_vp, _i32, _vp, _vp, _i64, _vp, _vp, _P(_i64)] + [_vp] * 7),
+    "raft_hip_fetch_delta4": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _P(_i64)] + [_vp] * 7),
+    "raft_hip_set_output_width": (C.c_int, [_vp, _i32]),
+    "raft_hip_set_emit_cuts": (C.c_int, [_vp, _i32]),
+    "raft_hip_device_alloc": (C.c_int, [_vp, _i64, _P(_vp)]),
+    "raft_hip_device_free": (C.c_int, [_vp, _vp]),
+    "raft_hip_trim": (_i64, [C.c_int, _i64]),
+    "raft_hip_pool_bytes": (_i64, [C.c_int]),
+    "raft_hip_set_placement": (_i32, [_i32]),
+    "raft_hip_set_placement_trial": (C.c_int, [_vp, _i32]),
+    "raft_hip_placement_trial": (C.c_int, [_vp, _P(_f64), _P(_f64), _P(_i32)]),
+    "raft_hip_packed_device": (C.c_int, [_vp, _P(_i32), _P(_vp), _P(_vp), _P(_vp), _P(_i64)]),
+    "raft_hip_packed_anchor_device": (C.c_int, [_vp, _P(_vp), _P(_i64)]),
+    "raft_hip_run_pipelined": (C.c_int, [_vp] + _COLUMNS + [_i32] + _JOB),
+    "raft_hip_run_multi": (C.c_int, [_P(_vp), _i32] + _COLUMNS + [_i32] + _JOB),
+    "raft_hip_run_multi_grouped": (C.c_int, [_P(_vp), _i32] + _GROUPED + [_vp, _vp, _i32] + _JOB),
+    "raft_hip_run_multi_windows": (C.c_int, [_P(_vp), _i32] + _GROUPED + [_vp, _i32] + _JOB),
+    "raft_hip_comm_unique_id": (C.c_int, [_vp]),
+    "raft_hip_comm_create": (C.c_int, [C.c_int, _vp, _i32, _i32, _P(_vp)]),
+    "raft_hip_comm_destroy": (None, [_vp]),
+    "raft_hip_exchange": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _P(_Slice), _P(_Received)]),
+    "raft_hip_exchange_local": (C.c_int, [_P(_vp), _i32, _i32, _vp, _P(_Slice), _P(_Received)]),
+    "raft_hip_group_sides": (C.c_int, [_vp, _i32, _i64] + [_vp] * 6 + [_i32, _P(_Slice)]),
+    "raft_hip_presplit_symmetric": (C.c_int, [_vp, _vp, _i32, _i32, _P(_Records), _P(_i32)]),
+    "raft_hip_presplit_symmetric_local": (C.c_int, [_P(_vp), _i32, _P(_Records), _P(_i32)]),
+    "raft_hip_run_presplit_local": (C.c_int, [_P(_vp), _i32] + _COLUMNS + _JOB),
+    "raft_hip_host_register": (C.c_int, [_vp, C.c_uint64]),
+    "raft_hip_host_unregister": (C.c_int, [_vp]),
+    "raft_hip_warm_up": (C.c_int, [_vp]),
+    "raft_hip_reserve": (C.c_int, [_vp, _i32, _vp, _i64, _i32, _i32]),
+    "raft_hip_cov_histogram": (C.c_int, [_vp, _vp, _P(_f64)]),
+    "raft_hip_estimate_coverage": (C.c_int, [_vp, _i32, _P(_CovEstimate)]),
+    "raft_hip_read_stats": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _P(_f64)]),
+    "raft_hip_census_device": (C.c_int, _CENSUS),
+    "raft_hip_census_host": (C.c_int, _CENSUS),
+    "raft_hip_last_timing": (C.c_int, [_vp, _P(_f64), _P(_f64)]),
+    "raft_hip_set_tuning": (C.c_int, [_vp, _i32, _i32, _i32]),
+    "raft_hip_selftest": (C.c_int, [C.c_int]),
+}
+EXPORTS = tuple(ABI)
 
 
 @dataclass
@@ -145,72 +204,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     except ImportError:
         pass
     lib = C.CDLL(p)
-    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-    lib.raft_hip_abi_version.restype = C.c_int
-    lib.raft_hip_strerror.restype = C.c_char_p
-    lib.raft_hip_strerror.argtypes = [C.c_int]
-    lib.raft_hip_last_error.restype = C.c_char_p
-    lib.raft_hip_last_error.argtypes = [vp]
-    lib.raft_hip_create.argtypes = [C.c_int, C.POINTER(_Params), C.POINTER(vp)]
-    lib.raft_hip_destroy.argtypes = [vp]
-    lib.raft_hip_destroy.restype = None
-    lib.raft_hip_set_params.argtypes = [vp, C.POINTER(_Params)]
-    lib.raft_hip_set_stream.argtypes = [vp, vp]
-    lib.raft_hip_use_own_stream.argtypes = [vp]
-    lib.raft_hip_get_stream.argtypes = [vp]
-    lib.raft_hip_get_stream.restype = vp
-    lib.raft_hip_run_device.argtypes = [vp, i32, vp, i64, vp, vp, vp, vp, vp, vp]
-    lib.raft_hip_run_host.argtypes = [vp, i32, vp, i64, vp, vp, vp, vp, vp, vp]
-    lib.raft_hip_finish.argtypes = [vp, C.POINTER(_Summary)]
-    lib.raft_hip_outputs_device.argtypes = [vp, C.POINTER(_Outputs)]
-    lib.raft_hip_fetch.argtypes = [vp] + [vp] * 11
-    lib.raft_hip_fetch_packed.argtypes = [vp, vp, vp, i64, vp, vp, C.POINTER(i64)] + [vp] * 7
-    lib.raft_hip_fetch_packed_w.argtypes = [vp, i32, vp, vp, i64, vp, vp, C.POINTER(i64)] + [vp] * 7
-    lib.raft_hip_run_pipelined.argtypes = [vp, i32, vp, i64, vp, vp, vp, vp, vp, vp, i32, C.POINTER(_HostOutputs), C.POINTER(_Summary)]
-    lib.raft_hip_run_multi.argtypes = [C.POINTER(vp), i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, i32, C.POINTER(_HostOutputs), C.POINTER(_Summary)]
-    lib.raft_hip_run_device_grouped.argtypes = [vp, i32, vp, i64, i32, vp, vp, vp, vp, i64]
-    lib.raft_hip_run_presplit_local.argtypes = [C.POINTER(vp), i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, C.POINTER(_HostOutputs), C.POINTER(_Summary)]
-    lib.raft_hip_run_host_grouped.argtypes = [vp, i32, vp, i64, i32, vp, vp, vp, i64]
-    lib.raft_hip_run_multi_grouped.argtypes = [C.POINTER(vp), i32, i32, vp, i64, i32, vp, vp, vp, i32, C.POINTER(_HostOutputs), C.POINTER(_Summary)]
-    lib.raft_hip_fetch_delta4.argtypes = [vp, vp, vp, vp, i64, vp, vp, C.POINTER(i64)] + [vp] * 7
-    lib.raft_hip_packed_anchor_device.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
-    lib.raft_hip_run_device_windows.argtypes = [vp, i32, vp, i64, i32, vp, vp, i64]
-    lib.raft_hip_run_host_windows.argtypes = [vp, i32, vp, i64, i32, vp, vp, i64]
-    lib.raft_hip_run_multi_windows.argtypes = [C.POINTER(vp), i32, i32, vp, i64, i32, vp, vp, i32, C.POINTER(_HostOutputs), C.POINTER(_Summary)]
-    lib.raft_hip_comm_unique_id.argtypes = [vp]
-    lib.raft_hip_comm_create.argtypes = [C.c_int, vp, i32, i32, C.POINTER(vp)]
-    lib.raft_hip_comm_destroy.argtypes = [vp]
-    lib.raft_hip_comm_destroy.restype = None
-    lib.raft_hip_exchange.argtypes = [vp, vp, i32, i32, i32, vp, C.POINTER(_Slice), C.POINTER(_Received)]
-    lib.raft_hip_exchange_local.argtypes = [C.POINTER(vp), i32, i32, vp, C.POINTER(_Slice), C.POINTER(_Received)]
-    lib.raft_hip_warm_up.argtypes = [vp]
-    lib.raft_hip_reserve.argtypes = [vp, i32, vp, i64, i32, i32]
-    lib.raft_hip_host_register.argtypes = [vp, C.c_uint64]
-    lib.raft_hip_host_unregister.argtypes = [vp]
-    lib.raft_hip_last_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    lib.raft_hip_set_tuning.argtypes = [vp, i32, i32, i32]
-    lib.raft_hip_set_output_width.argtypes = [vp, i32]
-    lib.raft_hip_set_emit_cuts.argtypes = [vp, i32]
-    lib.raft_hip_device_alloc.argtypes = [vp, i64, C.POINTER(C.c_void_p)]
-    lib.raft_hip_device_free.argtypes = [vp, vp]
-    lib.raft_hip_trim.argtypes = [C.c_int, i64]
-    lib.raft_hip_trim.restype = i64
-    lib.raft_hip_pool_bytes.argtypes = [C.c_int]
-    lib.raft_hip_pool_bytes.restype = i64
-    lib.raft_hip_set_placement.argtypes = [i32]
-    lib.raft_hip_set_placement.restype = i32
-    lib.raft_hip_placement_trial.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]
-    lib.raft_hip_set_placement_trial.argtypes = [vp, i32]
-    lib.raft_hip_group_sides.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, i32, C.POINTER(_Slice)]
-    lib.raft_hip_presplit_symmetric.argtypes = [vp, vp, i32, i32, C.POINTER(_Records), C.POINTER(i32)]
-    lib.raft_hip_presplit_symmetric_local.argtypes = [C.POINTER(vp), i32, C.POINTER(_Records), C.POINTER(i32)]
-    lib.raft_hip_packed_device.argtypes = [vp, C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
-    lib.raft_hip_selftest.argtypes = [C.c_int]
-    lib.raft_hip_cov_histogram.argtypes = [vp, vp, C.POINTER(C.c_double)]
-    lib.raft_hip_estimate_coverage.argtypes = [vp, i32, C.POINTER(_CovEstimate)]
-    lib.raft_hip_read_stats.argtypes = [vp, i32, vp, vp, vp, C.POINTER(C.c_double)]
-    lib.raft_hip_census_device.argtypes = [vp, i32, vp, i64] + [vp] * 6 + [i32, vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_double)]
-    lib.raft_hip_census_host.argtypes = lib.raft_hip_census_device.argtypes
+    for name, (restype, argtypes) in ABI.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if path is None:
         _lib = lib
     return lib
@@ -227,6 +223,106 @@ class _DevArray:
     def __init__(self, ptr: int, n: int, typestr: str, owner):
         self.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (ptr or 0, False), "version": 2}
         self._owner = owner
+
+
+def _view(eng, ptr, n, typestr, dtype):
+    """Zero-copy torch view of n elements of the engine's device memory (an empty tensor for n = 0)."""
+    import torch
+    dev = f"cuda:{eng.device}"
+    if n == 0:
+        return torch.empty(0, dtype=dtype, device=dev)
+    return torch.as_tensor(_DevArray(ptr, n, typestr, eng), device=dev)
+
+
+# ---- the output layout ------------------------------------------------------------------------------------------------------
+# Every array a finished pass hands back, in the order the ABI lists them: key, dtype, the count that sizes it ("n1" = n_reads + 1,
+# "n_exc" = what the library reports, the others are Summary fields) and the forms that hold it -- F: raft_hip_fetch /
+# raft_hip_outputs_device, P: the packed fetches, H: the host-to-host entry points' raft_hip_host_outputs.  The coverage arrays
+# of the form's encoding come after cov_offset.
+_OUTPUTS = (
+    ("cov_offset", np.int64, "n1", "FPH"),
+    ("exc_index", np.int64, "n_exc", "PH"), ("exc_value", np.int32, "n_exc", "PH"),
+    ("rep_offset", np.int64, "n1", "FPH"), ("rep_s", np.int32, "n_repeats", "FPH"), ("rep_e", np.int32, "n_repeats", "FPH"),
+    ("cut_offset", np.int64, "n1", "F"), ("cuts", np.int32, "n_cuts", "F"),
+    ("frag_offset", np.int64, "n1", "FPH"), ("frag_read", np.int32, "n_fragments", "FP"),
+    ("frag_begin", np.int32, "n_fragments", "FPH"), ("frag_end", np.int32, "n_fragments", "FPH"),
+)
+# The coverage encodings by width (bytes per window; 8 = RAFT_HIP_COV_DELTA4): key, dtype, elements for n windows.
+_COVERAGE = {
+    4: (("cov", np.int32, lambda n: n),),
+    1: (("cov8", np.uint8, lambda n: n),),
+    2: (("cov8", np.uint16, lambda n: n),),
+    8: (("cov_nib", np.uint8, lambda n: (n + 1) // 2),              # two windows per byte
+        ("cov_anchor", np.int32, lambda n: (n + 1023) // 1024)),    # an anchor per 1024 windows
+}
+
+
+def _layout(form: str, width: int, n_windows: int, counts: dict) -> list:
+    """(key, dtype, elements) of every array of one form in one coverage width."""
+    rows = [(k, dt, counts[c]) for k, dt, c, forms in _OUTPUTS if form in forms]
+    rows[1:1] = [(k, dt, size(n_windows)) for k, dt, size in _COVERAGE[width]]
+    return rows
+
+
+def _counts(s, n_exc: int = 0) -> dict:
+    return {"n1": s.n_reads + 1, "n_exc": n_exc, "n_repeats": s.n_repeats, "n_cuts": s.n_cuts, "n_fragments": s.n_fragments}
+
+
+# outputs_device runs once per pass of a stream of batches: its rows (key, typestr, Summary field or "n1") are laid out here, once
+_DEVICE_VIEWS = tuple((k, np.dtype(dt).str, c) for k, dt, c in _layout("F", 4, "n_bins", {c: c for _, _, c, _ in _OUTPUTS}))
+_summary_values = operator.attrgetter(*(f for f, _ in _Summary._fields_))     # Summary(*_summary_values(s)): a _Summary as a Summary
+
+
+# ---- the input forms ----------------------------------------------------------------------------------------------------------
+def _need_int32_cuda(who: str, cols):
+    import torch
+    for t in cols:
+        if t is not None and (t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous()):
+            raise TypeError(f"{who} contiguous int32 CUDA tensors")
+
+
+def _host_columns(cols) -> list:
+    return [None if a is None else M.carray(a, np.int32) for a in cols]
+
+
+def _plain(cols) -> tuple:
+    """Plain columns -- read_len, qid, qs, qe and what there is of tid, ts, te (numpy arrays or tensors; None = absent) -- as
+    every entry point takes them: n_reads, read_len, n_rec, the record columns."""
+    return (M.count(cols[0]), M.ptr(cols[0]), M.count(cols[1]), *[M.ptr(c) for c in cols[1:]])
+
+
+def _need_equal_lengths(cols, n_rec: int):
+    for c in cols:
+        if c is not None and (c.size if isinstance(c, np.ndarray) else c.numel()) != n_rec:
+            raise ValueError("PAF columns differ in length")
+
+
+def _offsets_misfit(rec_offset, n_reads: int, int64=None) -> bool:
+    """Are these not the offsets [n_runs, n_reads + 1] of grouped input?  ``int64``: torch.int64 for a tensor, which must then be a
+    contiguous CUDA tensor of that dtype as well (a numpy array has been made contiguous int64 by then)."""
+    if int64 is not None and (rec_offset.dtype != int64 or not rec_offset.is_cuda or not rec_offset.is_contiguous()):
+        return True
+    shape = rec_offset.shape
+    return len(shape) != 2 or shape[1] != n_reads + 1
+
+
+_DEVICE_OFFSETS = "%s needs rec_offset as a contiguous int64 CUDA tensor [n_runs, n_reads + 1]"
+
+
+def _grouped_host(method: str, read_len, rec_offset, records, dtype) -> tuple:
+    """Grouped host input -- ``records``: the int32 columns (qs, qe), or (win,) as uint32 window records -- as the arrays to keep
+    alive (read_len, the records, rec_offset) and the arguments: n_reads, read_len, n_rec, n_runs, rec_offset, the records."""
+    rl = M.carray(read_len, np.int32)
+    rec = [M.carray(x, dtype) for x in records]
+    off = M.carray(rec_offset, np.int64)
+    if _offsets_misfit(off, rl.size) or any(x.size != rec[0].size for x in rec):
+        raise ValueError(f"{method}: rec_offset must be [n_runs, n_reads + 1]" + (", qs/qe of equal length" if len(rec) == 2 else ""))
+    return (rl, *rec, off), (rl.size, M.ptr(rl), rec[0].size, off.shape[0], M.ptr(off), *[M.ptr(x) for x in rec])
+
+
+def _contexts(engines) -> tuple:
+    """The contexts of a job that several engines share, as the ABI takes them: the array and its length."""
+    return (C.c_void_p * len(engines))(*[e._ctx for e in engines]), len(engines)
 
 
 class Engine:
@@ -281,8 +377,8 @@ class Engine:
     def reserve(self, read_len, n_rec_estimate: int, n_ctx: int = 1, cov_width: int = 1):
         """raft_hip_reserve: device buffers and page-locked staging of a coming host-to-host job, from the reads' lengths and an
         estimate of the record count (cov_width: 1, 2 or 8 = four-bit steps)."""
-        rl = np.ascontiguousarray(np.asarray(read_len), dtype=np.int32)
-        self._check(self._lib.raft_hip_reserve(self._ctx, rl.size, C.c_void_p(rl.ctypes.data if rl.size else 0), int(n_rec_estimate), int(n_ctx), int(cov_width)))
+        rl = M.carray(read_len, np.int32)
+        self._check(self._lib.raft_hip_reserve(self._ctx, rl.size, M.ptr(rl), int(n_rec_estimate), int(n_ctx), int(cov_width)))
 
     def placement_trial(self):
         """(first_ms, best_other_ms, kept) of the coverage array's placement trial -- kept: 0 the first placement, 1 a plain block, 2 another
@@ -337,19 +433,13 @@ class Engine:
         import torch
         self.use_torch_stream()
         cols = [qid, qs, qe] + ([] if symmetric else [tid, ts, te])
-        for t in cols:
-            if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
-                raise TypeError("group_sides needs contiguous int32 CUDA tensors")
-        ptr = [C.c_void_p(t.data_ptr() if t.numel() else 0) for t in cols] + ([C.c_void_p(0)] * 3 if symmetric else [])
+        _need_int32_cuda("group_sides needs", cols)
+        ptr = [M.ptr(t) for t in cols] + ([C.c_void_p(0)] * 3 if symmetric else [])
         out = _Slice()
         self._check(self._lib.raft_hip_group_sides(self._ctx, n_reads_total, int(qid.numel()), *ptr, 1 if symmetric else 0, C.byref(out)))
         n = int(out.n_rec)
         off = np.ctypeslib.as_array(C.cast(out.rec_offset, C.POINTER(C.c_int64)), shape=(1, n_reads_total + 1)).copy()
-        dev = f"cuda:{self.device}"
-
-        def view(p):
-            return torch.empty(0, dtype=torch.int32, device=dev) if n == 0 else torch.as_tensor(_DevArray(p, n, "<i4", self), device=dev)
-        return Slice(off, view(out.d_qs), view(out.d_qe))
+        return Slice(off, *[_view(self, p, n, "<i4", torch.int32) for p in (out.d_qs, out.d_qe)])
 
     def use_torch_stream(self):
         import torch
@@ -359,7 +449,6 @@ class Engine:
     def run_device(self, read_len, qid, qs, qe, tid=None, ts=None, te=None):
         """Inputs: int32 torch tensors on this engine's device (kept alive until the next pass); tid / ts / te may be None when
         the params assert symmetric_mode = 1."""
-        import torch
         cols = (read_len, qid, qs, qe, tid, ts, te)
         # (a caller that hands over the same tensors again -- a stream of batches through fixed buffers -- is checked once; a tensor
         # resized in place keeps its address, so the lengths are part of what must match)
@@ -368,15 +457,9 @@ class Engine:
                 all(t is None or (t.data_ptr(), t.numel()) == q for t, q in zip(cols, last[2])):
             args = last[1]
         else:
-            for t in cols:
-                if t is not None and (t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous()):
-                    raise TypeError("run_device needs contiguous int32 CUDA tensors")
-            n_rec = int(qid.numel())
-            for t in cols[2:]:
-                if t is not None and int(t.numel()) != n_rec:
-                    raise ValueError("PAF columns differ in length")
-            ptr = [C.c_void_p(t.data_ptr() if (t is not None and t.numel()) else 0) for t in cols]
-            args = (int(read_len.numel()), ptr[0], n_rec, *ptr[1:])
+            _need_int32_cuda("run_device needs", cols)
+            args = _plain(cols)
+            _need_equal_lengths(cols[2:], args[2])
             self._last_device_call = (cols, args, [None if t is None else (t.data_ptr(), t.numel()) for t in cols])
         self._keep = cols
         self.use_torch_stream()     # the tensors were produced on torch's current stream: order after it
@@ -388,19 +471,15 @@ class Engine:
         caller's sum of ceil(len / reso) (-1: unknown; >= 0: the pass runs without a host wait).  symmetric_mode must be 1."""
         import torch
         n_reads = int(read_len.numel())
-        if rec_offset.dtype != torch.int64 or not rec_offset.is_cuda or not rec_offset.is_contiguous() or rec_offset.dim() != 2 \
-                or rec_offset.shape[1] != n_reads + 1:
-            raise TypeError("run_device_grouped needs rec_offset as a contiguous int64 CUDA tensor [n_runs, n_reads + 1]")
+        if _offsets_misfit(rec_offset, n_reads, torch.int64):
+            raise TypeError(_DEVICE_OFFSETS % "run_device_grouped")
         cols = (read_len, qs, qe) + (() if qid is None else (qid,))
-        for t in cols:
-            if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
-                raise TypeError("run_device_grouped needs contiguous int32 CUDA tensors")
+        _need_int32_cuda("run_device_grouped needs", cols)
         n_rec = int(qs.numel())
-        if int(qe.numel()) != n_rec or (qid is not None and int(qid.numel()) != n_rec):
-            raise ValueError("PAF columns differ in length")
+        _need_equal_lengths(cols[2:], n_rec)
         self._keep = cols + (rec_offset,)
         self.use_torch_stream()
-        P = lambda t: C.c_void_p(t.data_ptr() if (t is not None and t.numel()) else 0)
+        P = M.ptr
         self._check(self._lib.raft_hip_run_device_grouped(self._ctx, n_reads, P(read_len), n_rec, int(rec_offset.shape[0]), P(rec_offset),
                                                           P(qid), P(qs), P(qe), int(n_bins)))
 
@@ -409,55 +488,39 @@ class Engine:
         (``hostio.pack_windows``); ``win`` an int32 or uint32-viewed CUDA tensor of 32-bit words.  symmetric_mode must be 1."""
         import torch
         n_reads = int(read_len.numel())
-        if rec_offset.dtype != torch.int64 or not rec_offset.is_cuda or not rec_offset.is_contiguous() or rec_offset.dim() != 2 \
-                or rec_offset.shape[1] != n_reads + 1:
-            raise TypeError("run_device_windows needs rec_offset as a contiguous int64 CUDA tensor [n_runs, n_reads + 1]")
+        if _offsets_misfit(rec_offset, n_reads, torch.int64):
+            raise TypeError(_DEVICE_OFFSETS % "run_device_windows")
         for t in (read_len, win):
             if t.element_size() != 4 or t.is_floating_point() or not t.is_cuda or not t.is_contiguous():
                 raise TypeError("run_device_windows needs contiguous 32-bit integer CUDA tensors")
         self._keep = (read_len, win, rec_offset)
         self.use_torch_stream()
-        P = lambda t: C.c_void_p(t.data_ptr() if (t is not None and t.numel()) else 0)
+        P = M.ptr
         self._check(self._lib.raft_hip_run_device_windows(self._ctx, n_reads, P(read_len), int(win.numel()), int(rec_offset.shape[0]), P(rec_offset),
                                                           P(win), int(n_bins)))
 
     def run_host_windows(self, read_len, rec_offset, win, n_bins: int = -1):
         """raft_hip_run_host_windows: numpy arrays; ``win`` uint32 window records."""
-        rl = np.ascontiguousarray(np.asarray(read_len), dtype=np.int32)
-        w = np.ascontiguousarray(np.asarray(win), dtype=np.uint32)
-        off = np.ascontiguousarray(np.asarray(rec_offset), dtype=np.int64)
-        if off.ndim != 2 or off.shape[1] != rl.size + 1:
-            raise ValueError("run_host_windows: rec_offset must be [n_runs, n_reads + 1]")
-        self._keep = (rl, w, off)
-        P = lambda x: C.c_void_p(x.ctypes.data if x.size else 0)
-        self._check(self._lib.raft_hip_run_host_windows(self._ctx, rl.size, P(rl), w.size, off.shape[0], P(off), P(w), int(n_bins)))
+        self._keep, args = _grouped_host("run_host_windows", read_len, rec_offset, (win,), np.uint32)
+        self._check(self._lib.raft_hip_run_host_windows(self._ctx, *args, int(n_bins)))
 
     def run_host_grouped(self, read_len, rec_offset, qs, qe, n_bins: int = -1):
         """raft_hip_run_host_grouped: numpy arrays; ``rec_offset`` int64 [n_runs, n_reads + 1]."""
-        rl, a, b = (np.ascontiguousarray(np.asarray(x), dtype=np.int32) for x in (read_len, qs, qe))
-        off = np.ascontiguousarray(np.asarray(rec_offset), dtype=np.int64)
-        if off.ndim != 2 or off.shape[1] != rl.size + 1 or a.size != b.size:
-            raise ValueError("run_host_grouped: rec_offset must be [n_runs, n_reads + 1], qs/qe of equal length")
-        self._keep = (rl, a, b, off)
-        P = lambda x: C.c_void_p(x.ctypes.data if x.size else 0)
-        self._check(self._lib.raft_hip_run_host_grouped(self._ctx, rl.size, P(rl), a.size, off.shape[0], P(off), P(a), P(b), int(n_bins)))
+        self._keep, args = _grouped_host("run_host_grouped", read_len, rec_offset, (qs, qe), np.int32)
+        self._check(self._lib.raft_hip_run_host_grouped(self._ctx, *args, int(n_bins)))
 
     def run_host(self, read_len, qid, qs, qe, tid=None, ts=None, te=None):
         """tid/ts/te may be None when the params assert symmetric_mode = 1 (they are then neither read nor uploaded)."""
-        cols = [None if a is None else np.ascontiguousarray(np.asarray(a), dtype=np.int32) for a in (read_len, qid, qs, qe, tid, ts, te)]
-        n_rec = cols[1].size
-        for a in cols[2:]:
-            if a is not None and a.size != n_rec:
-                raise ValueError("PAF columns differ in length")
+        cols = _host_columns((read_len, qid, qs, qe, tid, ts, te))
+        args = _plain(cols)
+        _need_equal_lengths(cols[2:], args[2])
         self._keep = cols
-        ptr = [C.c_void_p(a.ctypes.data if (a is not None and a.size) else 0) for a in cols]
-        self._check(self._lib.raft_hip_run_host(self._ctx, cols[0].size, ptr[0], n_rec, *ptr[1:]))
+        self._check(self._lib.raft_hip_run_host(self._ctx, *args))
 
     def finish(self) -> Summary:
         s = _Summary()
         rc = self._lib.raft_hip_finish(self._ctx, C.byref(s))
-        summ = Summary(s.n_reads, s.symmetric, s.high_cov, s.interval_path, s.n_segments, s.n_records, s.n_intervals, s.n_bins, s.n_repeats, s.n_cuts,
-                       s.n_fragments, s.total_coverage, s.total_windows, s.total_repeat_length, s.total_read_length, s.error_index, s.n_devices_used, s.flags)
+        summ = Summary(*_summary_values(s))
         self.summary = summ
         self._check(rc, summ.error_index)
         return summ
@@ -474,33 +537,9 @@ class Engine:
         pageable path's).  out: arrays of an earlier fetch to reuse when their sizes still fit (a caller that keeps
         one pinned set of buffers pays neither allocation nor page faults per pass)."""
         s = self.summary
-        n1 = s.n_reads + 1
-        spec = {
-            "cov_offset": (n1, np.int64), "cov": (s.n_bins if coverage else 0, np.int32),
-            "rep_offset": (n1, np.int64), "rep_s": (s.n_repeats, np.int32), "rep_e": (s.n_repeats, np.int32),
-            "cut_offset": (n1, np.int64), "cuts": (s.n_cuts, np.int32),
-            "frag_offset": (n1, np.int64), "frag_read": (s.n_fragments, np.int32),
-            "frag_begin": (s.n_fragments, np.int32), "frag_end": (s.n_fragments, np.int32),
-        }
-
-        def alloc(n, dt):
-            if pinned and n:
-                import torch
-                return torch.empty(int(n), dtype=torch.int64 if dt == np.int64 else torch.int32, pin_memory=True).numpy()
-            return np.empty(n, dt)
-
-        res = {}
-        for key, (n, dt) in spec.items():
-            have = out.get(key) if out else None
-            if have is not None and have.dtype == dt and have.size >= n and have.flags["C_CONTIGUOUS"]:
-                res[key] = have[:n]
-            else:
-                res[key] = alloc(n, dt)
-        out = res
-        order = ("cov_offset", "cov", "rep_offset", "rep_s", "rep_e", "cut_offset", "cuts", "frag_offset",
-                 "frag_read", "frag_begin", "frag_end")
-        ptr = [C.c_void_p(out[k].ctypes.data if out[k].size else 0) for k in order]
-        self._check(self._lib.raft_hip_fetch(self._ctx, *ptr))
+        have = out or {}
+        out = {k: M.fit(have.get(k), n, dt, pinned) for k, dt, n in _layout("F", 4, s.n_bins if coverage else 0, _counts(s))}
+        self._check(self._lib.raft_hip_fetch(self._ctx, *[M.ptr(a) for a in out.values()]))
         return out
 
     def host_output_buffers(self, read_len, pinned: bool = True, exc_cap: int = 1 << 20, width: int = 1) -> dict:
@@ -512,69 +551,38 @@ class Engine:
         minw = max((p.repeat_length + p.reso - 1) // p.reso, 1)
         caps = {"cov8": int(nb.sum()), "rep": (int(nb.sum()) + rl.size) // (minw + 1), "frag": int(rl.sum()) // p.interval_length + 2 * rl.size,
                 "exc": int(exc_cap)}
-        n1 = rl.size + 1
-
-        def alloc(n, dt):
-            n = max(int(n), 1)
-            if pinned:
-                import torch
-                if dt == np.uint16:      # (torch has no uint16 everywhere: page-locked bytes, viewed as uint16)
-                    return torch.empty(2 * n, dtype=torch.uint8, pin_memory=True).numpy().view(np.uint16)
-                tdt = {np.int64: torch.int64, np.int32: torch.int32, np.uint8: torch.uint8}[dt]
-                return torch.empty(n, dtype=tdt, pin_memory=True).numpy()
-            return np.empty(n, dt)
         if width == 8:       # delta4: two windows per byte + an anchor per 1024 windows ("cov_nib" / "cov_anchor" name the encoding)
             caps["exc"] = max(caps["exc"], caps["cov8"] // 128)      # (every tile's first window and the large steps: 0.2-0.3 % of a 32x set)
-            return {"cov_offset": alloc(n1, np.int64), "cov_nib": alloc((caps["cov8"] + 1) // 2, np.uint8), "cov_anchor": alloc((caps["cov8"] + 1023) // 1024, np.int32),
-                    "exc_index": alloc(caps["exc"], np.int64), "exc_value": alloc(caps["exc"], np.int32), "rep_offset": alloc(n1, np.int64),
-                    "rep_s": alloc(caps["rep"], np.int32), "rep_e": alloc(caps["rep"], np.int32), "frag_offset": alloc(n1, np.int64),
-                    "frag_begin": alloc(caps["frag"], np.int32), "frag_end": alloc(caps["frag"], np.int32)}
-        return {"cov_offset": alloc(n1, np.int64), "cov8": alloc(caps["cov8"], np.uint16 if width == 2 else np.uint8),
-                "exc_index": alloc(caps["exc"], np.int64),
-                "exc_value": alloc(caps["exc"], np.int32), "rep_offset": alloc(n1, np.int64), "rep_s": alloc(caps["rep"], np.int32),
-                "rep_e": alloc(caps["rep"], np.int32), "frag_offset": alloc(n1, np.int64), "frag_begin": alloc(caps["frag"], np.int32),
-                "frag_end": alloc(caps["frag"], np.int32)}
+        counts = {"n1": rl.size + 1, "n_exc": caps["exc"], "n_repeats": caps["rep"], "n_fragments": caps["frag"]}
+        rows = _layout("H", width if width in (2, 8) else 1, caps["cov8"], counts)
+        return {k: M.empty(max(int(n), 1), dt, pinned) for k, dt, n in rows}     # (at least one element: every pointer is a real one)
 
     def run_pipelined_grouped(self, read_len, rec_offset, qs, qe, n_chunks: int = 0, out: dict | None = None,
                               others: list | None = None):
         """raft_hip_run_multi_grouped: as ``run_pipelined`` with the caller's per-read record offsets (int64
         [n_runs, n_reads + 1]) in place of the query column."""
-        rl, a, b = (np.ascontiguousarray(np.asarray(x), dtype=np.int32) for x in (read_len, qs, qe))
-        off = np.ascontiguousarray(np.asarray(rec_offset), dtype=np.int64)
-        if off.ndim != 2 or off.shape[1] != rl.size + 1 or a.size != b.size:
-            raise ValueError("run_pipelined_grouped: rec_offset must be [n_runs, n_reads + 1], qs/qe of equal length")
-        if out is None:
-            out = self.host_output_buffers(rl, pinned=False)
-        ho = self._host_outputs(out)
-        P = lambda x: C.c_void_p(x.ctypes.data if x.size else 0)
-        s = _Summary()
-        ctxs = (C.c_void_p * (1 + len(others or [])))(self._ctx, *[e._ctx for e in (others or [])])
-        rc = self._lib.raft_hip_run_multi_grouped(ctxs, len(ctxs), rl.size, P(rl), a.size, off.shape[0], P(off), P(a), P(b), int(n_chunks),
-                                                  C.byref(ho), C.byref(s))
-        return self._pipelined_result(rc, s, ho, out)
+        keep, args = _grouped_host("run_pipelined_grouped", read_len, rec_offset, (qs, qe), np.int32)
+        return self._host_job(self._lib.raft_hip_run_multi_grouped, _contexts([self, *(others or [])]), keep[0], (*args, int(n_chunks)), out)
 
     def run_pipelined_windows(self, read_len, rec_offset, win, n_chunks: int = 0, out: dict | None = None, others: list | None = None):
         """raft_hip_run_multi_windows: as ``run_pipelined_grouped`` with window records (uint32, ``hostio.pack_windows``) in place
         of the two coordinate columns."""
-        rl = np.ascontiguousarray(np.asarray(read_len), dtype=np.int32)
-        w = np.ascontiguousarray(np.asarray(win), dtype=np.uint32)
-        off = np.ascontiguousarray(np.asarray(rec_offset), dtype=np.int64)
-        if off.ndim != 2 or off.shape[1] != rl.size + 1:
-            raise ValueError("run_pipelined_windows: rec_offset must be [n_runs, n_reads + 1]")
+        keep, args = _grouped_host("run_pipelined_windows", read_len, rec_offset, (win,), np.uint32)
+        return self._host_job(self._lib.raft_hip_run_multi_windows, _contexts([self, *(others or [])]), keep[0], (*args, int(n_chunks)), out)
+
+    def _host_job(self, entry, head, read_len, args, out):
+        """What the host-to-host methods share once their input is packed: buffers by default, the job, its trimmed results."""
         if out is None:
-            out = self.host_output_buffers(rl, pinned=False)
-        ho = self._host_outputs(out)
-        P = lambda x: C.c_void_p(x.ctypes.data if x.size else 0)
-        s = _Summary()
-        ctxs = (C.c_void_p * (1 + len(others or [])))(self._ctx, *[e._ctx for e in (others or [])])
-        rc = self._lib.raft_hip_run_multi_windows(ctxs, len(ctxs), rl.size, P(rl), w.size, off.shape[0], P(off), P(w), int(n_chunks),
-                                                  C.byref(ho), C.byref(s))
+            out = self.host_output_buffers(read_len, pinned=False)
+        ho, s = self._host_outputs(out), _Summary()
+        rc = entry(*head, *args, C.byref(ho), C.byref(s))
         return self._pipelined_result(rc, s, ho, out)
 
     def _host_outputs(self, out: dict) -> "_HostOutputs":
         ho = _HostOutputs()
-        for k in ("cov_offset", "exc_index", "exc_value", "rep_offset", "rep_s", "rep_e", "frag_offset", "frag_begin", "frag_end"):
-            setattr(ho, k, out[k].ctypes.data)
+        for k, _, _, forms in _OUTPUTS:
+            if "H" in forms:
+                setattr(ho, k, out[k].ctypes.data)
         ho.exc_cap, ho.rep_cap, ho.frag_cap = out["exc_index"].size, out["rep_s"].size, out["frag_begin"].size
         if "cov_nib" in out:                                               # delta4 (host_output_buffers(width=8))
             ho.cov8, ho.cov8_cap = out["cov_nib"].ctypes.data, 2 * out["cov_nib"].size
@@ -586,123 +594,56 @@ class Engine:
         return ho
 
     def _pipelined_result(self, rc, s, ho, out):
-        summ = Summary(**{f: int(getattr(s, f)) for f, _ in _Summary._fields_})
+        summ = Summary(*_summary_values(s))
         self.summary = summ
         self.last_n_exc = int(ho.n_exc)
         self._check(rc, summ.error_index)
-        n1 = summ.n_reads + 1
-        cov = ({"cov_nib": out["cov_nib"][:(summ.n_bins + 1) // 2], "cov_anchor": out["cov_anchor"][:(summ.n_bins + 1023) // 1024]} if "cov_nib" in out
-               else {"cov8": out["cov8"][:summ.n_bins]})
-        res = {"cov_offset": out["cov_offset"][:n1], **cov, "exc_index": out["exc_index"][:ho.n_exc],
-               "exc_value": out["exc_value"][:ho.n_exc], "rep_offset": out["rep_offset"][:n1], "rep_s": out["rep_s"][:summ.n_repeats],
-               "rep_e": out["rep_e"][:summ.n_repeats], "frag_offset": out["frag_offset"][:n1],
-               "frag_begin": out["frag_begin"][:summ.n_fragments], "frag_end": out["frag_end"][:summ.n_fragments]}
-        return res, summ
+        rows = _layout("H", 8 if "cov_nib" in out else 1, summ.n_bins, _counts(summ, ho.n_exc))
+        return {k: out[k][:n] for k, _, n in rows}, summ
 
     def run_pipelined(self, read_len, qid, qs, qe, tid=None, ts=None, te=None, n_chunks: int = 0, out: dict | None = None,
                       others: list | None = None):
         """raft_hip_run_pipelined: host columns in, host outputs out, with upload / pass / download of consecutive read
         ranges overlapped.  ``others``: more Engines (other GPUs of the node, or the same one) to share the job with
         (raft_hip_run_multi).  Returns (dict of arrays trimmed to their sizes -- views of ``out`` --, Summary)."""
-        cols = [None if a is None else np.ascontiguousarray(np.asarray(a), dtype=np.int32) for a in (read_len, qid, qs, qe, tid, ts, te)]
-        n_rec = cols[1].size
-        if out is None:
-            out = self.host_output_buffers(cols[0], pinned=False)
-        ho = self._host_outputs(out)
-        ptr = [C.c_void_p(a.ctypes.data if (a is not None and a.size) else 0) for a in cols]
-        s = _Summary()
+        cols = _host_columns((read_len, qid, qs, qe, tid, ts, te))
         if others:
-            ctxs = (C.c_void_p * (1 + len(others)))(self._ctx, *[e._ctx for e in others])
-            rc = self._lib.raft_hip_run_multi(ctxs, 1 + len(others), cols[0].size, ptr[0], n_rec, *ptr[1:], int(n_chunks),
-                                              C.byref(ho), C.byref(s))
+            entry, head = self._lib.raft_hip_run_multi, _contexts([self, *others])
         else:
-            rc = self._lib.raft_hip_run_pipelined(self._ctx, cols[0].size, ptr[0], n_rec, *ptr[1:], int(n_chunks), C.byref(ho), C.byref(s))
-        return self._pipelined_result(rc, s, ho, out)
+            entry, head = self._lib.raft_hip_run_pipelined, (self._ctx,)
+        return self._host_job(entry, head, cols[0], (*_plain(cols), int(n_chunks)), out)
 
     def run_presplit(self, read_len, qid, qs, qe, tid, ts, te, others: list, out: dict | None = None):
         """raft_hip_run_presplit_local: this Engine is rank 0, ``others`` ranks 1 .. -- the record stream is cut into as many
         contiguous slices, every slice's sides are grouped on its rank's device, ONE exchange routes them to the owners of their
         reads, every rank runs its grouped pass.  Same return as ``run_pipelined``."""
-        cols = [np.ascontiguousarray(np.asarray(a), dtype=np.int32) for a in (read_len, qid, qs, qe, tid, ts, te)]
-        if out is None:
-            out = self.host_output_buffers(cols[0], pinned=False)
-        ho = self._host_outputs(out)
-        ptr = [C.c_void_p(a.ctypes.data if a.size else 0) for a in cols]
-        s = _Summary()
-        ctxs = (C.c_void_p * (1 + len(others)))(self._ctx, *[e._ctx for e in others])
-        rc = self._lib.raft_hip_run_presplit_local(ctxs, 1 + len(others), cols[0].size, ptr[0], cols[1].size, *ptr[1:], C.byref(ho), C.byref(s))
-        return self._pipelined_result(rc, s, ho, out)
+        cols = _host_columns((read_len, qid, qs, qe, tid, ts, te))
+        return self._host_job(self._lib.raft_hip_run_presplit_local, _contexts([self, *others]), cols[0], _plain(cols), out)
 
     def fetch_packed(self, pinned: bool = False, out: dict | None = None, width: int = 1) -> dict:
         """Host copies with the coverage array in its transfer encoding (raft_hip_fetch_packed_w): ``cov8`` (uint8 per
         window, 255 = see exceptions; with ``width=2`` uint16, 65535), ``exc_index`` / ``exc_value`` (ascending), and the
         repeat / fragment tables.  ``out``: arrays of an earlier call to reuse (pinned buffers kept by the caller; the
         dtype of its ``cov8`` decides the width)."""
-        s = self.summary
-        n1 = s.n_reads + 1
         if out is not None and out.get("cov8") is not None:
             width = 2 if out["cov8"].dtype == np.uint16 else 1
-        cdt = np.uint16 if width == 2 else np.uint8
-        n_exc = C.c_int64(0)
-        none = [C.c_void_p(0)] * 7
-        rc = self._lib.raft_hip_fetch_packed_w(self._ctx, width, None, None, 0, None, None, C.byref(n_exc), *none)
-        self._check(rc)
-        spec = {"cov_offset": (n1, np.int64), "cov8": (s.n_bins, cdt), "exc_index": (n_exc.value, np.int64),
-                "exc_value": (n_exc.value, np.int32), "rep_offset": (n1, np.int64), "rep_s": (s.n_repeats, np.int32),
-                "rep_e": (s.n_repeats, np.int32), "frag_offset": (n1, np.int64), "frag_read": (s.n_fragments, np.int32),
-                "frag_begin": (s.n_fragments, np.int32), "frag_end": (s.n_fragments, np.int32)}
-
-        def alloc(n, dt):
-            if pinned and n:
-                import torch
-                if dt == np.uint16:
-                    return torch.empty(2 * int(n), dtype=torch.uint8, pin_memory=True).numpy().view(np.uint16)
-                tdt = {np.int64: torch.int64, np.int32: torch.int32, np.uint8: torch.uint8}[dt]
-                return torch.empty(int(n), dtype=tdt, pin_memory=True).numpy()
-            return np.empty(n, dt)
-
-        res = {}
-        for key, (n, dt) in spec.items():
-            have = out.get(key) if out else None
-            if have is not None and have.dtype == dt and have.size >= n and have.flags["C_CONTIGUOUS"]:
-                res[key] = have[:n]
-            else:
-                res[key] = alloc(n, dt)
-        ptr = {k: C.c_void_p(res[k].ctypes.data if res[k].size else 0) for k in res}
-        self._check(self._lib.raft_hip_fetch_packed_w(self._ctx, width, ptr["cov_offset"], ptr["cov8"], n_exc.value, ptr["exc_index"],
-                                                      ptr["exc_value"], C.byref(n_exc), ptr["rep_offset"], ptr["rep_s"], ptr["rep_e"],
-                                                      ptr["frag_offset"], ptr["frag_read"], ptr["frag_begin"], ptr["frag_end"]))
-        return res
+        return self._fetch_encoded(self._lib.raft_hip_fetch_packed_w, (self._ctx, width), 2 if width == 2 else 1, pinned, out)
 
     def fetch_delta4(self, pinned: bool = False, out: dict | None = None) -> dict:
         """Host copies with the coverage array in the four-bit step encoding (raft_hip_fetch_delta4): ``cov_nib`` (uint8,
         two windows per byte), ``cov_anchor`` (int32 per 1024 windows), ``exc_index`` / ``exc_value`` (ascending; ABSOLUTE values
         of the escaped windows), and the repeat / fragment tables.  ``hostio.unpack_coverage_d4`` restores the int32 array."""
-        s = self.summary
-        n1 = s.n_reads + 1
+        return self._fetch_encoded(self._lib.raft_hip_fetch_delta4, (self._ctx,), 8, pinned, out)
+
+    def _fetch_encoded(self, entry, head, width, pinned, out):
+        """The packed fetches: the size query (every pointer NULL, no room for exceptions), then the arrays."""
+        n_cov = len(_COVERAGE[width])
         n_exc = C.c_int64(0)
-        none = [C.c_void_p(0)] * 7
-        self._check(self._lib.raft_hip_fetch_delta4(self._ctx, None, None, None, 0, None, None, C.byref(n_exc), *none))
-        spec = {"cov_offset": (n1, np.int64), "cov_nib": ((s.n_bins + 1) // 2, np.uint8), "cov_anchor": ((s.n_bins + 1023) // 1024, np.int32),
-                "exc_index": (n_exc.value, np.int64), "exc_value": (n_exc.value, np.int32), "rep_offset": (n1, np.int64),
-                "rep_s": (s.n_repeats, np.int32), "rep_e": (s.n_repeats, np.int32), "frag_offset": (n1, np.int64),
-                "frag_read": (s.n_fragments, np.int32), "frag_begin": (s.n_fragments, np.int32), "frag_end": (s.n_fragments, np.int32)}
-
-        def alloc(n, dt):
-            if pinned and n:
-                import torch
-                tdt = {np.int64: torch.int64, np.int32: torch.int32, np.uint8: torch.uint8}[dt]
-                return torch.empty(int(n), dtype=tdt, pin_memory=True).numpy()
-            return np.empty(n, dt)
-
-        res = {}
-        for key, (n, dt) in spec.items():
-            have = out.get(key) if out else None
-            res[key] = have[:n] if (have is not None and have.dtype == dt and have.size >= n and have.flags["C_CONTIGUOUS"]) else alloc(n, dt)
-        ptr = {k: C.c_void_p(res[k].ctypes.data if res[k].size else 0) for k in res}
-        self._check(self._lib.raft_hip_fetch_delta4(self._ctx, ptr["cov_offset"], ptr["cov_nib"], ptr["cov_anchor"], n_exc.value, ptr["exc_index"],
-                                                    ptr["exc_value"], C.byref(n_exc), ptr["rep_offset"], ptr["rep_s"], ptr["rep_e"],
-                                                    ptr["frag_offset"], ptr["frag_read"], ptr["frag_begin"], ptr["frag_end"]))
+        self._check(entry(*head, *[None] * (1 + n_cov), 0, None, None, C.byref(n_exc), *[None] * 7))
+        have = out or {}
+        res = {k: M.fit(have.get(k), n, dt, pinned) for k, dt, n in _layout("P", width, self.summary.n_bins, _counts(self.summary, n_exc.value))}
+        ptr = [M.ptr(a) for a in res.values()]
+        self._check(entry(*head, *ptr[:1 + n_cov], n_exc.value, *ptr[1 + n_cov:3 + n_cov], C.byref(n_exc), *ptr[3 + n_cov:]))
         return res
 
     def outputs_device(self) -> dict:
@@ -714,18 +655,14 @@ class Engine:
         self._check(self._lib.raft_hip_outputs_device(self._ctx, C.byref(o)))
         s = self.summary
         n1 = s.n_reads + 1
-        spec = {"cov_offset": (n1, "<i8"), "cov": (s.n_bins, "<i4"), "rep_offset": (n1, "<i8"),
-                "rep_s": (s.n_repeats, "<i4"), "rep_e": (s.n_repeats, "<i4"), "cut_offset": (n1, "<i8"),
-                "cuts": (s.n_cuts, "<i4"), "frag_offset": (n1, "<i8"), "frag_read": (s.n_fragments, "<i4"),
-                "frag_begin": (s.n_fragments, "<i4"), "frag_end": (s.n_fragments, "<i4")}
         res = {}
-        for k, (n, ts) in spec.items():
+        for k, ts, c in _DEVICE_VIEWS:
+            n = n1 if c == "n1" else getattr(s, c)
             if n == 0:
                 res[k] = torch.empty(0, dtype=torch.int64 if ts == "<i8" else torch.int32, device=f"cuda:{self.device}")
             else:
                 res[k] = torch.as_tensor(_DevArray(getattr(o, k), n, ts, self), device=f"cuda:{self.device}")
         return res
-
 
     # -- the estimated coverage from the data -------------------------------------------
     last_histogram_seconds = 0.0      # device time of the last coverage_histogram() call's launches
@@ -764,7 +701,7 @@ class Engine:
         n = max(int(last.n_reads), 0) if last is not None else 0
         out = {"cov_sum": np.zeros(n, np.int64), "cov_max": np.zeros(n, np.int32), "high_windows": np.zeros(n, np.int32)}
         secs = C.c_double(0.0)
-        self._check(self._lib.raft_hip_read_stats(self._ctx, int(threshold), *(C.c_void_p(a.ctypes.data if a.size else 0) for a in out.values()),
+        self._check(self._lib.raft_hip_read_stats(self._ctx, int(threshold), *[M.ptr(a) for a in out.values()],
                                                   C.byref(secs)))
         self.last_read_stats_seconds = secs.value
         return out
@@ -779,28 +716,18 @@ class Engine:
             raise ValueError("census needs read_len, qid, qs, qe (and ts, te unless symmetric)")
         on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in cols if x is not None)
         if on_device:
-            import torch
-            for t in cols:
-                if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()):
-                    raise TypeError("census needs contiguous int32 CUDA tensors")
+            _need_int32_cuda("census needs", cols)
             self.use_torch_stream()
-            size = lambda t: int(t.numel())
-            P = lambda t: C.c_void_p(t.data_ptr() if (t is not None and t.numel()) else 0)
             fn = self._lib.raft_hip_census_device
         else:
-            cols = [None if x is None else np.ascontiguousarray(np.asarray(x.cpu() if hasattr(x, "is_cuda") else x), dtype=np.int32) for x in cols]
-            size = lambda a: int(a.size)
-            P = lambda a: C.c_void_p(a.ctypes.data if (a is not None and a.size) else 0)
+            cols = _host_columns([x.cpu() if hasattr(x, "is_cuda") else x for x in cols])
             fn = self._lib.raft_hip_census_host
-        n_reads, n_rec = size(cols[0]), size(cols[1])
-        for x in cols[2:]:
-            if x is not None and size(x) != n_rec:
-                raise ValueError("PAF columns differ in length")
-        ptr = [P(x) for x in cols] + ([C.c_void_p(0)] * 2 if symmetric else [])
+        args = _plain(cols) + ((C.c_void_p(0),) * 2 if symmetric else ())
+        n_reads = args[0]
+        _need_equal_lengths(cols[2:], args[2])
         intervals, contained = np.zeros(n_reads, np.int32), np.zeros(n_reads, np.uint8)
         n_cont, err, secs = C.c_int64(0), C.c_int64(-1), C.c_double(0.0)
-        rc = fn(self._ctx, n_reads, ptr[0], n_rec, *ptr[1:], 1 if symmetric else 0, C.c_void_p(intervals.ctypes.data if n_reads else 0),
-                C.c_void_p(contained.ctypes.data if n_reads else 0), C.byref(n_cont), C.byref(err), C.byref(secs))
+        rc = fn(self._ctx, *args, 1 if symmetric else 0, M.ptr(intervals), M.ptr(contained), C.byref(n_cont), C.byref(err), C.byref(secs))
         self._check(rc, err.value)
         self.last_census_seconds = secs.value
         return {"intervals": intervals, "contained": contained, "n_contained": int(n_cont.value)}
@@ -815,20 +742,15 @@ class Engine:
         self._check(self._lib.raft_hip_packed_device(self._ctx, C.byref(w), C.byref(codes), C.byref(ei), C.byref(ev), C.byref(n)))
         if w.value == 0:
             return None
-        dev = f"cuda:{self.device}"
-        def view(ptr, count, ts, dt):
-            if count == 0:
-                return torch.empty(0, dtype=dt, device=dev)
-            return torch.as_tensor(_DevArray(ptr.value, count, ts, self), device=dev)
-        if w.value == 8:                      # delta4: two windows per byte + block anchors
+        (key, _, size), *anchor = _COVERAGE[w.value]
+        wide = w.value == 2
+        res = {"width": w.value, key: _view(self, codes.value, size(self.summary.n_bins), "<i2" if wide else "|u1", torch.int16 if wide else torch.uint8)}
+        if anchor:                            # delta4: two windows per byte + block anchors
             an, na = C.c_void_p(), C.c_int64(0)
             self._check(self._lib.raft_hip_packed_anchor_device(self._ctx, C.byref(an), C.byref(na)))
-            return {"width": 8, "cov_nib": view(codes, (self.summary.n_bins + 1) // 2, "|u1", torch.uint8),
-                    "cov_anchor": view(an, na.value, "<i4", torch.int32),
-                    "exc_index": view(ei, n.value, "<i8", torch.int64), "exc_value": view(ev, n.value, "<i4", torch.int32)}
-        return {"width": w.value,
-                "cov8": view(codes, self.summary.n_bins, "|u1" if w.value == 1 else "<i2", torch.uint8 if w.value == 1 else torch.int16),
-                "exc_index": view(ei, n.value, "<i8", torch.int64), "exc_value": view(ev, n.value, "<i4", torch.int32)}
+            res[anchor[0][0]] = _view(self, an.value, na.value, "<i4", torch.int32)
+        res["exc_index"], res["exc_value"] = _view(self, ei.value, n.value, "<i8", torch.int64), _view(self, ev.value, n.value, "<i4", torch.int32)
+        return res
 
 
 class Slice:
@@ -840,35 +762,27 @@ class Slice:
         """``qe=None``: ``qs`` holds window records (one int32-viewed word per record, hostio.pack_windows) -- one column travels.
         ``device_offsets``: keep a copy of the offsets on the slice's device (raft_hip_slice::d_rec_offset), so that exchanging the
         same slice again uploads nothing."""
-        import torch
-        self.off = np.ascontiguousarray(np.asarray(rec_offset), dtype=np.int64)
+        self.off = M.carray(rec_offset, np.int64)
         if self.off.ndim != 2 or not (1 <= self.off.shape[0] <= 4):
             raise ValueError("Slice: rec_offset must be [n_runs (1..4), n_reads_total + 1]")
-        for t in (qs, qe):
-            if t is not None and (t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous()):
-                raise TypeError("Slice needs contiguous int32 CUDA tensors")
+        _need_int32_cuda("Slice needs", (qs, qe))
         self.qs, self.qe = qs, qe
-        self.d_off = torch.as_tensor(self.off).to(qs.device) if device_offsets else None
+        self.d_off = None
+        if device_offsets:
+            import torch
+            self.d_off = torch.as_tensor(self.off).to(qs.device)
 
     def c(self) -> "_Slice":
-        return _Slice(int(self.qs.numel()), int(self.off.shape[0]), self.off.ctypes.data, self.qs.data_ptr() if self.qs.numel() else 0,
-                      self.qe.data_ptr() if (self.qe is not None and self.qe.numel()) else 0,
-                      self.d_off.data_ptr() if self.d_off is not None else 0)
+        return _Slice(int(self.qs.numel()), int(self.off.shape[0]), self.off.ctypes.data, M.address(self.qs), M.address(self.qe), M.address(self.d_off))
 
 
 def _received_views(eng, r: "_Received") -> dict:
     """Zero-copy torch views of what a context received (valid until its next exchange)."""
     import torch
-    dev = f"cuda:{eng.device}"
-
-    def view(ptr, n, ts, dt):
-        if n == 0:
-            return torch.empty(0, dtype=dt, device=dev)
-        return torch.as_tensor(_DevArray(ptr, n, ts, eng), device=dev)
-    off = view(r.d_rec_offset, r.n_runs * (r.n_reads + 1), "<i8", torch.int64).reshape(r.n_runs, r.n_reads + 1)
+    off = _view(eng, r.d_rec_offset, r.n_runs * (r.n_reads + 1), "<i8", torch.int64).reshape(r.n_runs, r.n_reads + 1)
     return {"n_reads": int(r.n_reads), "n_rec": int(r.n_rec), "n_runs": int(r.n_runs), "rec_offset": off,
-            "qs": view(r.d_qs, r.n_rec, "<i4", torch.int32),      # (window records when the slices carried them: then "qe" is None)
-            "qe": view(r.d_qe, r.n_rec, "<i4", torch.int32) if (r.d_qe or r.n_rec == 0) else None}
+            "qs": _view(eng, r.d_qs, r.n_rec, "<i4", torch.int32),      # (window records when the slices carried them: then "qe" is None)
+            "qe": _view(eng, r.d_qe, r.n_rec, "<i4", torch.int32) if (r.d_qe or r.n_rec == 0) else None}
 
 
 def exchange_local(engines, bounds, slices) -> list:
@@ -876,10 +790,9 @@ def exchange_local(engines, bounds, slices) -> list:
     Slice per rank (on that rank's device).  Returns, per rank, the grouped input it received (torch views)."""
     import torch
     lib = load_library()
-    w = len(engines)
-    b = np.ascontiguousarray(np.asarray(bounds), dtype=np.int64)
+    b = M.carray(bounds, np.int64)
     torch.cuda.synchronize()
-    ctxs = (C.c_void_p * w)(*[e._ctx for e in engines])
+    ctxs, w = _contexts(engines)
     sl = (_Slice * w)(*[s.c() for s in slices])
     out = (_Received * w)()
     rc = lib.raft_hip_exchange_local(ctxs, w, int(slices[0].off.shape[1] - 1), C.c_void_p(b.ctypes.data), sl, out)
@@ -888,21 +801,16 @@ def exchange_local(engines, bounds, slices) -> list:
 
 
 def _records(cols) -> "_Records":
-    import torch
-    for t in cols:
-        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
-            raise TypeError("record columns must be contiguous int32 CUDA tensors")
-    n = int(cols[0].numel())
-    return _Records(n, *[t.data_ptr() if n else 0 for t in cols])
+    _need_int32_cuda("record columns must be", cols)
+    return _Records(int(cols[0].numel()), *[M.address(t) for t in cols])
 
 
 def presplit_symmetric_local(engines, slices_cols) -> bool:
     """raft_hip_presplit_symmetric_local: is the pre-split PAF symmetric?  ``slices_cols``: per rank its six device columns."""
     import torch
     lib = load_library()
-    w = len(engines)
     torch.cuda.synchronize()
-    ctxs = (C.c_void_p * w)(*[e._ctx for e in engines])
+    ctxs, w = _contexts(engines)
     recs = (_Records * w)(*[_records(c) for c in slices_cols])
     flag = C.c_int32(-1)
     engines[0]._check(lib.raft_hip_presplit_symmetric_local(ctxs, w, recs, C.byref(flag)))
@@ -931,7 +839,7 @@ class Comm:
 
     def exchange(self, eng, bounds, sl: Slice) -> dict:
         """raft_hip_exchange on the engine's stream; returns the grouped input this rank received (torch views)."""
-        b = np.ascontiguousarray(np.asarray(bounds), dtype=np.int64)
+        b = M.carray(bounds, np.int64)
         eng.use_torch_stream()
         cs, out = sl.c(), _Received()
         rc = self._lib.raft_hip_exchange(eng._ctx, self._comm, self.rank, self.world, int(sl.off.shape[1] - 1), C.c_void_p(b.ctypes.data),
@@ -956,12 +864,12 @@ class Comm:
 
 def estimate_coverage(hist) -> CoverageEstimate:
     """raft_hip_estimate_coverage on a histogram whose last bin is the clamp bin (host arithmetic: needs no device)."""
-    h = np.ascontiguousarray(np.asarray(hist), dtype=np.int64)
+    h = M.carray(hist, np.int64)
     if h.ndim != 1:
         raise ValueError("estimate_coverage needs a one-dimensional histogram")
     lib = load_library()
     e = _CovEstimate()
-    rc = lib.raft_hip_estimate_coverage(C.c_void_p(h.ctypes.data if h.size else 0), int(h.size), C.byref(e))
+    rc = lib.raft_hip_estimate_coverage(M.ptr(h), int(h.size), C.byref(e))
     if rc != OK:
         raise RaftError(rc, lib.raft_hip_strerror(rc).decode())
     return CoverageEstimate(int(e.est_cov), int(e.median), int(e.windows), int(e.windows_covered), int(e.windows_clamped), float(e.mean))

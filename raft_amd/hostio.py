@@ -6,17 +6,49 @@ import os
 
 import numpy as np
 
+from ._marshal import carray, ptr
+
 _LIB_PATH = os.environ.get("RAFT_HOST_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libraft_host.so")   # (override: sanitizer builds)
 OK, ERR_OPEN, ERR_DUP_NAME, ERR_UNKNOWN_NAME, ERR_IO, ERR_ARG = range(6)
 
-EXPORTS = ("raft_host_reads_load", "raft_host_reads_free", "raft_host_reads_count", "raft_host_reads_lengths",
-           "raft_host_reads_name", "raft_host_reads_bases", "raft_host_reads_real", "raft_host_paf_load", "raft_host_paf_free",
-           "raft_host_paf_count", "raft_host_paf_column", "raft_host_write_coverage", "raft_host_write_repeats",
-           "raft_host_write_fasta", "raft_host_set_threads", "raft_host_get_threads", "raft_host_split_naive",
-           "raft_host_paf_symmetric", "raft_host_unpack_coverage", "raft_host_write_coverage_packed",
-           "raft_host_unpack_coverage_w", "raft_host_write_coverage_packed_w", "raft_host_text_read", "raft_host_text_free",
-           "raft_host_paf_parse", "raft_host_group_offsets", "raft_host_pack_windows", "raft_host_unpack_coverage_d4",
-           "raft_host_write_coverage_d4", "raft_host_write_read_stats")
+_vp, _str, _i32, _i64 = C.c_void_p, C.c_char_p, C.c_int32, C.c_int64
+_P = C.POINTER
+
+# The C ABI: every entry point of include/raft_host.h, in the header's order, as (restype, argtypes).  load_library declares
+# exactly this; tests/test_binding_tables.py compares it with the header, class by class.
+ABI = {
+    "raft_host_set_threads": (C.c_int, [C.c_int]),
+    "raft_host_get_threads": (C.c_int, []),
+    "raft_host_reads_load": (C.c_int, [_str, _P(_vp)]),
+    "raft_host_reads_free": (None, [_vp]),
+    "raft_host_reads_count": (_i32, [_vp]),
+    "raft_host_reads_lengths": (_P(_i32), [_vp]),
+    "raft_host_reads_name": (_str, [_vp, _i32]),
+    "raft_host_reads_bases": (_P(C.c_char), [_vp, _i32]),
+    "raft_host_reads_real": (C.c_int, [_vp]),
+    "raft_host_paf_load": (C.c_int, [_str, _vp, _P(_vp), _str, C.c_int]),
+    "raft_host_text_read": (C.c_int, [_str, _P(_vp)]),
+    "raft_host_text_free": (None, [_vp]),
+    "raft_host_paf_parse": (C.c_int, [_vp, _vp, _P(_vp), _str, C.c_int]),
+    "raft_host_paf_free": (None, [_vp]),
+    "raft_host_paf_count": (_i64, [_vp]),
+    "raft_host_paf_column": (_P(_i32), [_vp, C.c_int]),
+    "raft_host_paf_symmetric": (C.c_int, [_vp]),
+    "raft_host_group_offsets": (C.c_int, [_i32, _i64, _vp, _i32, _P(_i32), _vp]),
+    "raft_host_unpack_coverage_d4": (C.c_int, [_i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "raft_host_write_coverage_d4": (C.c_int, [_str, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "raft_host_pack_windows": (C.c_int, [_i64, _vp, _vp, _i32, _vp, _P(_i64)]),
+    "raft_host_unpack_coverage": (C.c_int, [_i64, _vp, _i64, _vp, _vp, _vp]),
+    "raft_host_write_coverage_packed": (C.c_int, [_str, _i32, _i32, _vp, _vp, _i64, _vp, _vp]),
+    "raft_host_unpack_coverage_w": (C.c_int, [_i32, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "raft_host_write_coverage_packed_w": (C.c_int, [_i32, _str, _i32, _i32, _vp, _vp, _i64, _vp, _vp]),
+    "raft_host_write_coverage": (C.c_int, [_str, _i32, _i32, _vp, _vp]),
+    "raft_host_write_repeats": (C.c_int, [_str, _str, _vp, _vp, _vp, _vp]),
+    "raft_host_write_fasta": (C.c_int, [_str, _vp, _vp, _vp, _vp]),
+    "raft_host_write_read_stats": (C.c_int, [_str, _i32, _P(_str), _vp, _i32] + [_vp] * 7),
+    "raft_host_split_naive": (C.c_int, [_str, _str, _i32, _P(_i32)]),
+}
+EXPORTS = tuple(ABI)
 
 
 class HostError(RuntimeError):
@@ -35,38 +67,9 @@ def load_library():
         if not os.path.exists(_LIB_PATH):
             raise RuntimeError(f"{_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         lib = C.CDLL(_LIB_PATH)
-        vp = C.c_void_p
-        lib.raft_host_reads_load.argtypes = [C.c_char_p, C.POINTER(vp)]
-        lib.raft_host_reads_free.argtypes = [vp]; lib.raft_host_reads_free.restype = None
-        lib.raft_host_reads_count.argtypes = [vp]; lib.raft_host_reads_count.restype = C.c_int32
-        lib.raft_host_reads_lengths.argtypes = [vp]; lib.raft_host_reads_lengths.restype = C.POINTER(C.c_int32)
-        lib.raft_host_reads_name.argtypes = [vp, C.c_int32]; lib.raft_host_reads_name.restype = C.c_char_p
-        lib.raft_host_reads_bases.argtypes = [vp, C.c_int32]; lib.raft_host_reads_bases.restype = C.POINTER(C.c_char)
-        lib.raft_host_reads_real.argtypes = [vp]
-        lib.raft_host_paf_load.argtypes = [C.c_char_p, vp, C.POINTER(vp), C.c_char_p, C.c_int]
-        lib.raft_host_text_read.argtypes = [C.c_char_p, C.POINTER(vp)]
-        lib.raft_host_text_free.argtypes = [vp]
-        lib.raft_host_text_free.restype = None
-        lib.raft_host_paf_parse.argtypes = [vp, vp, C.POINTER(vp), C.c_char_p, C.c_int]
-        lib.raft_host_paf_free.argtypes = [vp]; lib.raft_host_paf_free.restype = None
-        lib.raft_host_paf_count.argtypes = [vp]; lib.raft_host_paf_count.restype = C.c_int64
-        lib.raft_host_paf_column.argtypes = [vp, C.c_int]; lib.raft_host_paf_column.restype = C.POINTER(C.c_int32)
-        lib.raft_host_write_coverage.argtypes = [C.c_char_p, C.c_int32, C.c_int32, vp, vp]
-        lib.raft_host_write_repeats.argtypes = [C.c_char_p, C.c_char_p, vp, vp, vp, vp]
-        lib.raft_host_write_fasta.argtypes = [C.c_char_p, vp, vp, vp, vp]
-        lib.raft_host_split_naive.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]
-        lib.raft_host_set_threads.argtypes = [C.c_int]
-        lib.raft_host_paf_symmetric.argtypes = [vp]
-        lib.raft_host_unpack_coverage.argtypes = [C.c_int64, vp, C.c_int64, vp, vp, vp]
-        lib.raft_host_write_coverage_packed.argtypes = [C.c_char_p, C.c_int32, C.c_int32, vp, vp, C.c_int64, vp, vp]
-        lib.raft_host_unpack_coverage_w.argtypes = [C.c_int32, C.c_int64, vp, C.c_int64, vp, vp, vp]
-        lib.raft_host_write_coverage_packed_w.argtypes = [C.c_int32, C.c_char_p, C.c_int32, C.c_int32, vp, vp, C.c_int64, vp, vp]
-        lib.raft_host_get_threads.argtypes = []
-        lib.raft_host_group_offsets.argtypes = [C.c_int32, C.c_int64, vp, C.c_int32, C.POINTER(C.c_int32), vp]
-        lib.raft_host_unpack_coverage_d4.argtypes = [C.c_int64, vp, vp, C.c_int64, vp, vp, vp]
-        lib.raft_host_write_coverage_d4.argtypes = [C.c_char_p, C.c_int32, C.c_int32, vp, vp, vp, C.c_int64, vp, vp]
-        lib.raft_host_pack_windows.argtypes = [C.c_int64, vp, vp, C.c_int32, vp, C.POINTER(C.c_int64)]
-        lib.raft_host_write_read_stats.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), vp, C.c_int32] + [vp] * 7
+        for name, (restype, argtypes) in ABI.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
     return _lib
 
@@ -82,14 +85,13 @@ def group_offsets(n_reads: int, qid, max_runs: int = 4, out=None):
     """raft_host_group_offsets: per-read record offsets of a query column that is at most ``max_runs`` runs sorted by read
     id -> int64 array [n_runs, n_reads + 1]; None when the column is not of that shape (more runs, ids out of range).
     ``out``: a caller-owned int64 array of at least max_runs * (n_reads + 1) entries (e.g. page-locked) to fill."""
-    q = np.ascontiguousarray(np.asarray(qid), dtype=np.int32)
+    q = carray(qid, np.int32)
     need = max_runs * (n_reads + 1)
     buf = out if out is not None else np.empty(need, np.int64)
     if buf.dtype != np.int64 or buf.size < need or not buf.flags["C_CONTIGUOUS"]:
         raise ValueError("group_offsets: out must be a contiguous int64 array of max_runs * (n_reads + 1) entries")
     n_runs = C.c_int32(0)
-    rc = load_library().raft_host_group_offsets(int(n_reads), int(q.size), C.c_void_p(q.ctypes.data if q.size else 0), int(max_runs),
-                                                C.byref(n_runs), C.c_void_p(buf.ctypes.data))
+    rc = load_library().raft_host_group_offsets(int(n_reads), int(q.size), ptr(q), int(max_runs), C.byref(n_runs), ptr(buf))
     if rc != OK:
         raise HostError(rc, "group_offsets")
     if n_runs.value == 0:
@@ -105,16 +107,14 @@ def pack_windows(qs, qe, reso: int, out=None):
     the engine's ``*_windows`` entries.  Returns the array, or None when some interval ends beyond window 65,535 (the caller
     keeps the coordinate columns).  A negative coordinate raises HostError(ERR_COORD) whose ``index`` names the record.
     ``out``: a caller-owned uint32 array of at least len(qs) entries (e.g. page-locked) to fill."""
-    a = np.ascontiguousarray(np.asarray(qs), dtype=np.int32)
-    b = np.ascontiguousarray(np.asarray(qe), dtype=np.int32)
+    a, b = carray(qs, np.int32), carray(qe, np.int32)
     if a.size != b.size:
         raise ValueError("pack_windows: qs / qe differ in length")
     buf = out if out is not None else np.empty(a.size, np.uint32)
     if buf.dtype != np.uint32 or buf.size < a.size or not buf.flags["C_CONTIGUOUS"]:
         raise ValueError("pack_windows: out must be a contiguous uint32 array of len(qs) entries")
     bad = C.c_int64(-1)
-    P = lambda x: C.c_void_p(x.ctypes.data if x.size else 0)
-    rc = load_library().raft_host_pack_windows(int(a.size), P(a), P(b), int(reso), P(buf), C.byref(bad))
+    rc = load_library().raft_host_pack_windows(int(a.size), ptr(a), ptr(b), int(reso), ptr(buf), C.byref(bad))
     if rc == ERR_RANGE:
         return None
     if rc != OK:
@@ -203,15 +203,22 @@ def _width_of(code) -> int:
     return 2 if np.asarray(code).dtype == np.uint16 else 1
 
 
+def _codes(code):
+    """The packed codes as they are handed over: (width, contiguous uint8 or uint16 array)."""
+    width = _width_of(code)
+    return width, carray(code, np.uint16 if width == 2 else np.uint8)
+
+
+def _exceptions(exc_index, exc_value):
+    return carray(exc_index, np.int64), carray(exc_value, np.int32)
+
+
 def unpack_coverage(code, exc_index, exc_value):
     """raft_host_unpack_coverage_w: the int32 coverage array from the packed form (uint8 or uint16 codes)."""
-    lib = load_library()
-    width = _width_of(code)
-    code = np.ascontiguousarray(code, np.uint16 if width == 2 else np.uint8)
-    xi, xv = np.ascontiguousarray(exc_index, np.int64), np.ascontiguousarray(exc_value, np.int32)
+    width, code = _codes(code)
+    xi, xv = _exceptions(exc_index, exc_value)
     out = np.empty(code.size, np.int32)
-    rc = lib.raft_host_unpack_coverage_w(width, code.size, C.c_void_p(code.ctypes.data), xi.size, C.c_void_p(xi.ctypes.data),
-                                         C.c_void_p(xv.ctypes.data), C.c_void_p(out.ctypes.data))
+    rc = load_library().raft_host_unpack_coverage_w(width, code.size, ptr(code), xi.size, ptr(xi), ptr(xv), ptr(out))
     if rc != OK:
         raise HostError(rc, "unpack_coverage")
     return out
@@ -219,37 +226,30 @@ def unpack_coverage(code, exc_index, exc_value):
 
 def unpack_coverage_d4(n_bins: int, cov_nib, cov_anchor, exc_index, exc_value):
     """raft_host_unpack_coverage_d4: the int32 coverage array from the four-bit step encoding."""
-    nib = np.ascontiguousarray(cov_nib, np.uint8)
-    an = np.ascontiguousarray(cov_anchor, np.int32)
-    xi, xv = np.ascontiguousarray(exc_index, np.int64), np.ascontiguousarray(exc_value, np.int32)
+    nib, an = carray(cov_nib, np.uint8), carray(cov_anchor, np.int32)
+    xi, xv = _exceptions(exc_index, exc_value)
     if nib.size < (n_bins + 1) // 2 or an.size < (n_bins + 1023) // 1024:
         raise ValueError("unpack_coverage_d4: cov_nib / cov_anchor too short")
     out = np.empty(n_bins, np.int32)
-    p = lambda x: C.c_void_p(x.ctypes.data if x.size else 0)
-    rc = load_library().raft_host_unpack_coverage_d4(int(n_bins), p(nib), p(an), xi.size, p(xi), p(xv), p(out))
+    rc = load_library().raft_host_unpack_coverage_d4(int(n_bins), ptr(nib), ptr(an), xi.size, ptr(xi), ptr(xv), ptr(out))
     if rc != OK:
         raise HostError(rc, "unpack_coverage_d4")
     return out
 
 
 def write_coverage_d4(path: str, n_reads: int, reso: int, cov_offset, cov_nib, cov_anchor, exc_index, exc_value):
-    co = np.ascontiguousarray(cov_offset, np.int64)
-    nib, an = np.ascontiguousarray(cov_nib, np.uint8), np.ascontiguousarray(cov_anchor, np.int32)
-    xi, xv = np.ascontiguousarray(exc_index, np.int64), np.ascontiguousarray(exc_value, np.int32)
-    p = lambda x: C.c_void_p(x.ctypes.data if x.size else 0)
-    rc = load_library().raft_host_write_coverage_d4(path.encode(), n_reads, reso, p(co), p(nib), p(an), xi.size, p(xi), p(xv))
+    co, nib, an = carray(cov_offset, np.int64), carray(cov_nib, np.uint8), carray(cov_anchor, np.int32)
+    xi, xv = _exceptions(exc_index, exc_value)
+    rc = load_library().raft_host_write_coverage_d4(path.encode(), n_reads, reso, ptr(co), ptr(nib), ptr(an), xi.size, ptr(xi), ptr(xv))
     if rc != OK:
         raise HostError(rc, path)
 
 
 def write_coverage_packed(path: str, n_reads: int, reso: int, cov_offset, code, exc_index, exc_value):
-    lib = load_library()
-    width = _width_of(code)
-    co = np.ascontiguousarray(cov_offset, np.int64)
-    code = np.ascontiguousarray(code, np.uint16 if width == 2 else np.uint8)
-    xi, xv = np.ascontiguousarray(exc_index, np.int64), np.ascontiguousarray(exc_value, np.int32)
-    p = lambda x: C.c_void_p(x.ctypes.data)
-    rc = lib.raft_host_write_coverage_packed_w(width, path.encode(), n_reads, reso, p(co), p(code), xi.size, p(xi), p(xv))
+    width, code = _codes(code)
+    co = carray(cov_offset, np.int64)
+    xi, xv = _exceptions(exc_index, exc_value)
+    rc = load_library().raft_host_write_coverage_packed_w(width, path.encode(), n_reads, reso, ptr(co), ptr(code), xi.size, ptr(xi), ptr(xv))
     if rc != OK:
         raise HostError(rc, path)
 
@@ -257,11 +257,11 @@ def write_coverage_packed(path: str, n_reads: int, reso: int, cov_offset, code, 
 def write_outputs(prefix: str, reads: Reads, reso: int, res: dict):
     """Writes PREFIX.coverage.txt / .long_repeats.txt / .long_repeats.bed / .reads.fasta from CSR arrays."""
     lib = load_library()
-    a = {k: np.ascontiguousarray(res[k]) for k in ("cov_offset", "cov", "rep_offset", "rep_s", "rep_e", "frag_offset", "frag_begin", "frag_end")}
-    p = lambda x: C.c_void_p(x.ctypes.data)
-    for rc in (lib.raft_host_write_coverage((prefix + ".coverage.txt").encode(), reads.n, reso, p(a["cov_offset"]), p(a["cov"])),
+    a = {k: carray(res[k]) for k in ("cov_offset", "cov", "rep_offset", "rep_s", "rep_e", "frag_offset", "frag_begin", "frag_end")}
+    p = {k: ptr(x) for k, x in a.items()}
+    for rc in (lib.raft_host_write_coverage((prefix + ".coverage.txt").encode(), reads.n, reso, p["cov_offset"], p["cov"]),
                lib.raft_host_write_repeats((prefix + ".long_repeats.txt").encode(), (prefix + ".long_repeats.bed").encode(), reads._h,
-                                           p(a["rep_offset"]), p(a["rep_s"]), p(a["rep_e"])),
-               lib.raft_host_write_fasta((prefix + ".reads.fasta").encode(), reads._h, p(a["frag_offset"]), p(a["frag_begin"]), p(a["frag_end"]))):
+                                           p["rep_offset"], p["rep_s"], p["rep_e"]),
+               lib.raft_host_write_fasta((prefix + ".reads.fasta").encode(), reads._h, p["frag_offset"], p["frag_begin"], p["frag_end"])):
         if rc != OK:
             raise HostError(rc, prefix)

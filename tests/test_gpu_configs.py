@@ -290,6 +290,35 @@ def test_pipelined_equals_oracle(kw, n_chunks, n_ctx):
         e2.close()
 
 
+def test_reserved_and_warmed_pipeline_equals_the_one_piece_pass():
+    """reserve + warm_up before a host-to-host job change nothing it computes: every array equals the one a second engine
+    fetches after run_host + finish (coverage through hostio.unpack_coverage); timing() reports that pass."""
+    from raft_amd import engine, hostio
+    from raft_amd.synth import make_overlaps
+    o = make_overlaps(300, seed=5)
+    cols = [c.numpy() for c in (o.read_len,) + o.columns()]
+    eng, ref = engine.Engine(RaftParams(est_cov=30), device=0), engine.Engine(RaftParams(est_cov=30), device=0)
+    try:
+        eng.reserve(cols[0], len(cols[1]))
+        eng.warm_up()
+        res, s = eng.run_pipelined(*cols)
+        ref.run_host(*cols)
+        s_ref = ref.finish()
+        want = ref.fetch()
+        pileup, whole = ref.timing()
+        assert np.array_equal(hostio.unpack_coverage(res["cov8"], res["exc_index"], res["exc_value"]), want["cov"])
+        for k in ("cov_offset", "rep_offset", "rep_s", "rep_e", "frag_offset", "frag_begin", "frag_end"):
+            assert res[k].dtype == want[k].dtype and np.array_equal(res[k], want[k]), k
+        assert (s.n_reads, s.n_bins, s.n_repeats, s.n_fragments, s.symmetric, s.total_coverage) == \
+            (s_ref.n_reads, s_ref.n_bins, s_ref.n_repeats, s_ref.n_fragments, s_ref.symmetric, s_ref.total_coverage)
+        assert s.n_reads == 300 and want["cov"].size == s.n_bins > 0
+        assert isinstance(pileup, float) and isinstance(whole, float) and np.isfinite([pileup, whole]).all()
+        assert 0 <= pileup <= whole
+    finally:
+        eng.close()
+        ref.close()
+
+
 def test_pipelined_shapes_and_fallbacks():
     from raft_amd import engine
     rng = np.random.default_rng(91)

@@ -612,3 +612,25 @@ def test_paf_tokeniser_fast_paths_against_the_rules(tmp_path, threads):
         reads.close()
     finally:
         hostio.set_threads(0)
+
+
+def test_writers_and_decoder_take_empty_arrays(tmp_path):
+    """Reads without windows, repeats or fragments.  The binding hands NULL for an array without elements; host_io.cpp reads
+    codes, exceptions, repeats and fragments only through offsets and counts, so every writer still emits its per-read lines."""
+    fa = tmp_path / "r.fa"
+    write_fasta(fa, ["a", "b"], [40, 60])
+    reads = hostio.Reads(str(fa))
+    zero, none, none64 = np.zeros(3, np.int64), np.empty(0, np.int32), np.empty(0, np.int64)
+    res = {"cov_offset": zero, "cov": none, "rep_offset": zero, "rep_s": none, "rep_e": none, "frag_offset": zero, "frag_begin": none,
+           "frag_end": none}
+    hostio.write_outputs(str(tmp_path / "e"), reads, 50, res)
+    assert (tmp_path / "e.coverage.txt").read_text() == "read 0 \nread 1 \n"
+    assert (tmp_path / "e.long_repeats.txt").read_text() == "read 0, \nread 1, \n"
+    assert (tmp_path / "e.reads.fasta").read_text() == ""
+    for code in (np.empty(0, np.uint8), np.empty(0, np.uint16)):
+        hostio.write_coverage_packed(str(tmp_path / "p.txt"), 2, 50, zero, code, none64, none)
+        assert (tmp_path / "p.txt").read_text() == "read 0 \nread 1 \n"
+        assert hostio.unpack_coverage(code, none64, none).size == 0
+    hostio.write_coverage_d4(str(tmp_path / "d.txt"), 2, 50, zero, np.empty(0, np.uint8), none, none64, none)
+    assert (tmp_path / "d.txt").read_text() == "read 0 \nread 1 \n"
+    assert hostio.unpack_coverage_d4(0, np.empty(0, np.uint8), none, none64, none).size == 0
