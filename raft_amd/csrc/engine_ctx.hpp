@@ -367,6 +367,12 @@ struct raft_hip_ctx {
     DevBuf cov8{bufs, DevBuf::kBig}, exc_idx{bufs}, exc_val{bufs}, exc_cnt{bufs};   // transfer encoding of cov[] (raft_hip_fetch_packed)
     DevBuf cov_hist{bufs};             // raft_hip_cov_histogram: RAFT_HIP_COV_HIST_BINS 64-bit counts, cleared at every call
     DevBuf rs_sum{bufs}, rs_max{bufs}, rs_high{bufs};   // raft_hip_read_stats: one value per read each, cleared at every call
+    // raft_hip_low_coverage (low_cov_lib.hip, libraft_hip_low.so; plain allocations: that library keeps no chunk pool): the two bitmaps (low windows, first windows of reads), run starts per tile and their prefix, the control
+    // words; per read low windows / low bases / class bits, the flag bytes, low_offset; per run start, end and read
+    DevBuf lc_bad{bufs}, lc_rs{bufs}, lc_tile_cnt{bufs}, lc_tile_base{bufs}, lc_ctl{bufs};
+    DevBuf lc_win{bufs}, lc_bases{bufs}, lc_flagw{bufs}, lc_flags{bufs}, lc_off{bufs};
+    DevBuf lc_s{bufs}, lc_e{bufs}, lc_read{bufs};
+    DevBuf lc_cov{bufs}, lc_abs{bufs};   // ... and, for a pass that holds no int32 array where one is needed, the decoded coverage and delta4's escape flags
     // raft_hip_census_*: counts and flag words per read, the flags as bytes, {first bad record, reads with a flag}; staging of the host form
     DevBuf cen_cnt{bufs}, cen_flags{bufs}, cen_out{bufs}, cen_ctl{bufs}, cen_len{bufs};
     DevBuf cen_col[6] = {DevBuf{bufs, DevBuf::kBig}, DevBuf{bufs, DevBuf::kBig}, DevBuf{bufs, DevBuf::kBig},

@@ -24,6 +24,7 @@ OK, ERR_PARAM, ERR_READ_ID, ERR_COORD, ERR_FRAGMENT, ERR_NOMEM, ERR_DEVICE, ERR_
 SUM_BUCKET_WINDOWS, SUM_SPECULATED, SUM_DEEP_TILES, SUM_RERUN, SUM_KEPT_GEOMETRY = 1, 2, 4, 8, 16
 
 COV_HIST_BINS = 4096              # RAFT_HIP_COV_HIST_BINS
+LOW_INTERIOR, LOW_HEAD, LOW_TAIL, LOW_UNCOVERED = 1, 2, 4, 8    # RAFT_HIP_LOW_*: bits of low_flags (Engine.low_coverage)
 
 
 class _Params(C.Structure):
@@ -67,6 +68,10 @@ class _Received(C.Structure):
 class _CovEstimate(C.Structure):
     _fields_ = [("est_cov", C.c_int32), ("median", C.c_int32), ("windows", C.c_int64), ("windows_covered", C.c_int64),
                 ("windows_clamped", C.c_int64), ("mean", C.c_double)]
+
+
+class _LowSummary(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_runs", "low_windows", "low_bases", "reads_with_runs", "reads_interior", "reads_uncovered")]
 
 
 class _Outputs(C.Structure):
@@ -144,6 +149,12 @@ ABI = {
 }
 EXPORTS = tuple(ABI)
 
+# ... and the entry points of include/raft_hip_low.h (libraft_hip_low.so, beside libraft_hip.so): load_low_library declares these
+LOW_ABI = {
+    "raft_hip_low_abi": (C.c_int, []),
+    "raft_hip_low_coverage": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _P(_LowSummary), _P(_f64)]),
+}
+
 
 @dataclass
 class Summary:
@@ -210,6 +221,28 @@ def load_library(path: str | None = None) -> C.CDLL:
     if path is None:
         _lib = lib
     return lib
+
+
+_low_lib = None
+
+
+def load_low_library() -> C.CDLL:
+    """Loads libraft_hip_low.so (behind libraft_hip.so, whose contexts it takes) and declares every entry point of
+    include/raft_hip_low.h; the two must have been built beside each other."""
+    global _low_lib
+    if _low_lib is None:
+        main = load_library()
+        p = os.path.join(os.path.dirname(_LIB_PATH), "libraft_hip_low.so")
+        if not os.path.exists(p):
+            raise RuntimeError(f"{p} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(p)
+        for name, (restype, argtypes) in LOW_ABI.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        if lib.raft_hip_low_abi() != main.raft_hip_abi_version():
+            raise RuntimeError(f"{p} was built beside ABI {lib.raft_hip_low_abi()}, libraft_hip.so is ABI {main.raft_hip_abi_version()}")
+        _low_lib = lib
+    return _low_lib
 
 
 def _cparams(p: RaftParams) -> _Params:
@@ -704,6 +737,32 @@ class Engine:
         self._check(self._lib.raft_hip_read_stats(self._ctx, int(threshold), *[M.ptr(a) for a in out.values()],
                                                   C.byref(secs)))
         self.last_read_stats_seconds = secs.value
+        return out
+
+    # -- where a read is not covered ---------------------------------------------------
+    last_low_coverage_seconds = 0.0   # device time of the launches of one raft_hip_low_coverage call: the last low_coverage()'s fetch
+
+    def low_coverage(self, low_cov: int = 0, uncovered_permille: int = 800) -> dict:
+        """raft_hip_low_coverage (libraft_hip_low.so): the runs of consecutive windows with coverage <= ``low_cov`` of every read of the finished pass, as
+        CSR in read order -- ``low_offset`` (int64 [n_reads + 1]), ``low_s`` / ``low_e`` (int32, bases) --, per read ``low_windows``
+        (int32) and ``low_flags`` (uint8: LOW_INTERIOR | LOW_HEAD | LOW_TAIL | LOW_UNCOVERED), and the totals ``n_runs``,
+        ``total_low_windows``, ``low_bases``, ``reads_with_runs``, ``reads_interior``, ``reads_uncovered``.  Computed on the device
+        from the form the pass wrote; cov[] is not downloaded.  Two calls of the library: the size query, then the fetch into arrays
+        of that size."""
+        last = getattr(self, "summary", None)
+        n = max(int(last.n_reads), 0) if last is not None else 0
+        sm, secs = _LowSummary(), C.c_double(0.0)
+        null = C.c_void_p(0)
+        args = (int(low_cov), int(uncovered_permille))
+        low = load_low_library()
+        self._check(low.raft_hip_low_coverage(self._ctx, *args, 0, null, null, null, null, null, C.byref(sm), C.byref(secs)))
+        out = {"low_offset": M.empty(n + 1, np.int64), "low_s": M.empty(int(sm.n_runs), np.int32), "low_e": M.empty(int(sm.n_runs), np.int32),
+               "low_windows": M.empty(n, np.int32), "low_flags": M.empty(n, np.uint8)}
+        self._check(low.raft_hip_low_coverage(self._ctx, *args, int(sm.n_runs), *[M.ptr(a) for a in out.values()], C.byref(sm),
+                                                    C.byref(secs)))
+        self.last_low_coverage_seconds = secs.value
+        out.update(n_runs=int(sm.n_runs), total_low_windows=int(sm.low_windows), low_bases=int(sm.low_bases),
+                   reads_with_runs=int(sm.reads_with_runs), reads_interior=int(sm.reads_interior), reads_uncovered=int(sm.reads_uncovered))
         return out
 
     def census(self, read_len, qid, qs, qe, tid, ts=None, te=None, symmetric: bool = False) -> dict:

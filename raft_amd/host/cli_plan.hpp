@@ -4,6 +4,7 @@
 // of raft_hip.h but its constants: a host compiler alone builds it (tests/cli_plan_check.cpp does, under the sanitizers).
 #pragma once
 #include "../../include/raft_hip.h"
+#include "../../include/raft_hip_low.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -133,6 +134,30 @@ inline Attempt next_attempt(int cov_width, int64_t exc_cap, int64_t n_exc, int64
     if (cov_width == RAFT_HIP_COV_DELTA4 && n_exc > n_win / 8) return {2, exc_cap};
     if (cov_width == 1 && n_exc > n_win / 16) return {2, exc_cap};
     return {cov_width, n_exc};
+}
+
+// --low-cov C: C is a whole number >= 0 written in digits alone (no sign, no blank, nothing behind it), at most INT32_MAX.
+inline bool parse_low_cov(const char *text, int32_t *low_cov)
+{
+    if (!text || !*text) return false;
+    int64_t v = 0;
+    for (const char *q = text; *q; ++q) {
+        if (*q < '0' || *q > '9') return false;
+        v = v * 10 + (*q - '0');
+        if (v > INT32_MAX) return false;
+    }
+    *low_cov = (int32_t)v;
+    return true;
+}
+
+// ... a read counts as uncovered when more than this many thousandths of its bases lie in low runs (yacrd's default for "not covered")
+constexpr int32_t kLowUncoveredPermille = 800;
+
+// The run arrays' first size: real data has a few runs per read (heads, tails, the odd gap); the call says what it needs when
+// that is not enough, and never more than RAFT_HIP_LOW_RUNS_MAX.
+inline int64_t low_run_capacity0(int64_t n_win, int32_t n_reads)
+{
+    return std::min<int64_t>(RAFT_HIP_LOW_RUNS_MAX(n_win, n_reads), 4 * (int64_t)n_reads + 1024);
 }
 
 // starttime of /proc/self/stat, in clock ticks since boot: field 22, counted behind the LAST ')' (state is field 3), so that a

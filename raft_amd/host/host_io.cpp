@@ -12,6 +12,7 @@
 //   * a PAF line is cut at '\n', loses one trailing '\r' (when longer than one byte), is split on TAB
 //     only and is skipped when it has fewer than 10 fields; numeric fields go through strtol.
 #include "../../include/raft_host.h"
+#include "../../include/raft_host_low.h"
 
 #include <emmintrin.h>
 #include <zlib.h>
@@ -1364,6 +1365,30 @@ int raft_host_write_read_stats(const char *path, int32_t n_reads, const char *co
         t.num(intervals[i]); t.ch('\t'); t.num((int)contained[i]); t.ch('\t');
         t.num((long long)cov_sum[i]); t.ch('\t'); t.num(cov_max[i]); t.ch('\t'); t.num(high_windows[i]); t.ch('\t');
         t.num((long long)(rep_offset[i + 1] - rep_offset[i])); t.ch('\t'); t.num((long long)(frag_offset[i + 1] - frag_offset[i])); t.ch('\n');
+    }
+    return t.close() ? RAFT_HOST_OK : RAFT_HOST_ERR_IO;
+}
+
+// The low-coverage runs of `raft --low-cov` as BED: one line per run, name, start, end, class (see raft_host.h)
+int raft_host_write_low_coverage(const char *path, int32_t n_reads, const char *const *names, const int64_t *low_offset, const int32_t *low_s,
+                                 const int32_t *low_e, const int32_t *read_len, int32_t reso)
+{
+    if (!path || n_reads < 0 || reso <= 0 || (n_reads > 0 && (!names || !low_offset || !read_len))) return RAFT_HOST_ERR_ARG;
+    if (n_reads > 0 && low_offset[n_reads] > low_offset[0] && (!low_s || !low_e)) return RAFT_HOST_ERR_ARG;
+    Out t(path);
+    if (!t.ok()) return RAFT_HOST_ERR_IO;
+    for (int32_t i = 0; i < n_reads; ++i) {
+        const size_t name_len = strlen(names[i]);
+        for (int64_t k = low_offset[i]; k < low_offset[i + 1]; ++k) {
+            // (a run that ends before the read's last window ends on a multiple of reso below the length: the clamp shows the tail)
+            const bool head = low_s[k] == 0, tail = low_e[k] == read_len[i];
+            t.str(names[i], name_len); t.ch('\t'); t.num(low_s[k]); t.ch('\t'); t.num(low_e[k]); t.ch('\t');
+            if (head && tail) t.str("whole", 5);
+            else if (head) t.str("head", 4);
+            else if (tail) t.str("tail", 4);
+            else t.str("interior", 8);
+            t.ch('\n');
+        }
     }
     return t.close() ? RAFT_HOST_OK : RAFT_HOST_ERR_IO;
 }

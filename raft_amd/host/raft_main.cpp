@@ -13,6 +13,8 @@
 // bring_up (the device contexts), paf_reader (the bytes of the overlaps file), out_prep (the arrays the results come back in)
 // and fasta_writer; where each is joined is part of what a phase does, and die() joins whatever still runs.
 #include "../../include/raft_hip.h"
+#include "../../include/raft_hip_low.h"
+#include "../../include/raft_host_low.h"
 #include "../../include/raft_host.h"
 #include "cli_plan.hpp"
 
@@ -42,6 +44,7 @@ struct Params {            // param.hpp:18-31
     std::string prefix = "raft";
     bool auto_cov = false;         // -e auto: est_cov is read from the data (a survey pass and its coverage histogram) before the job
     bool read_stats = false;       // --read-stats: PREFIX.read_stats.tsv, the per-read table (raft_hip_read_stats, raft_hip_census_host)
+    int32_t low_cov = -1;          // --low-cov C: PREFIX.low_coverage.bed, the runs of windows with coverage <= C (raft_hip_low_coverage); -1: not asked for
 };
 
 struct Switches {                  // the environment, as read_switches() found it
@@ -87,6 +90,10 @@ struct Job {
     std::vector<int32_t> rs_max, rs_high, cen_intervals;
     std::vector<uint8_t> cen_contained;
     int64_t n_contained = 0;
+    // --low-cov: the survey's low-coverage runs
+    std::vector<int64_t> low_off;
+    std::vector<int32_t> low_s, low_e;
+    raft_hip_low_summary low_sum{};
     // the form the job is handed over in, and what it brought back
     std::unique_ptr<int64_t[]> rec_off;
     int32_t n_runs = 0;
@@ -162,11 +169,13 @@ void parse_options(Job &j, int argc, char *argv[])
 {
     Params &p = j.p;
     int option;
-    // (the short options and their quirks are the reference's; the one long option is this program's own)
-    static const struct option long_options[] = {{"read-stats", no_argument, nullptr, 1000}, {nullptr, 0, nullptr, 0}};
+    // (the short options and their quirks are the reference's; the long options are this program's own)
+    static const struct option long_options[] = {{"read-stats", no_argument, nullptr, 1000}, {"low-cov", required_argument, nullptr, 1001},
+                                                 {nullptr, 0, nullptr, 0}};
     while ((option = getopt_long(argc, argv, "r:e:m:l:i:p:f:v:o:", long_options, nullptr)) != -1) {
         switch (option) {
         case 1000: p.read_stats = true; break;
+        case 1001: if (!raft_cli::parse_low_cov(optarg, &p.low_cov)) print_help(p); break;
         case 'r': p.reso = atoi(optarg); break;
         case 'e': p.auto_cov = strcmp(optarg, "auto") == 0; p.est_cov = p.auto_cov ? 0 : atoi(optarg); break;
         case 'm': p.cov_mul = std::stod(optarg); break;
@@ -419,6 +428,23 @@ int survey_read_stats(Job &j, int est_cov)
     return rc;
 }
 
+// --low-cov: the low-coverage runs of the pass that has just run.  The run arrays start at cli_plan.hpp's first size; a set with more
+// runs says so (RAFT_HIP_ERR_TOO_LARGE and the number) and is asked once more.
+int survey_low_coverage(Job &j, int64_t n_win)
+{
+    j.low_off.resize((size_t)j.n_reads + 1);
+    int64_t cap = raft_cli::low_run_capacity0(n_win, j.n_reads);
+    int rc = RAFT_HIP_OK;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        j.low_s.resize((size_t)cap); j.low_e.resize((size_t)cap);
+        rc = raft_hip_low_coverage(j.ctxs[0], j.p.low_cov, raft_cli::kLowUncoveredPermille, cap, j.low_off.data(), j.low_s.data(), j.low_e.data(), nullptr,
+                                   nullptr, &j.low_sum, nullptr);
+        if (rc != RAFT_HIP_ERR_TOO_LARGE) break;
+        cap = j.low_sum.n_runs;
+    }
+    return rc;
+}
+
 // -e auto: the survey.  cov[] does not depend on est_cov, so one one-piece pass on the first context under the placeholder holds
 // the number -e stands for: its coverage histogram is made on the device (32 KiB come back instead of cov[]) and the estimate
 // read from it (raft_hip.h).  The pass writes two-byte codes and no cut points -- nothing of it is fetched --, and its
@@ -428,11 +454,11 @@ int survey_read_stats(Job &j, int est_cov)
 //
 // --read-stats: the per-read table.  Its coverage summary (raft_hip_read_stats) is taken from the same survey pass, right behind
 // the histogram; without -e auto one such pass -- the survey's recipe -- runs here for it.  The job itself runs as it does
-// without the option.
+// without the option.  --low-cov: the same, for the low-coverage runs (raft_hip_low_coverage), behind the two.
 void survey(Job &j)
 {
     Params &p = j.p;
-    if (!p.auto_cov && !p.read_stats) return;
+    if (!p.auto_cov && !p.read_stats && p.low_cov < 0) return;
     raft_hip_ctx *ctx = j.ctxs[0];
     SurveySettings settings{ctx, j.sw.context_width};
     raft_hip_params sp = j.hp;
@@ -454,6 +480,7 @@ void survey(Job &j)
         if (rc == RAFT_HIP_OK) rc = raft_hip_estimate_coverage(hist.data(), RAFT_HIP_COV_HIST_BINS, &est);
     }
     if (rc == RAFT_HIP_OK && p.read_stats && est.est_cov > 0) rc = survey_read_stats(j, est.est_cov);
+    if (rc == RAFT_HIP_OK && p.low_cov >= 0) rc = survey_low_coverage(j, ss.n_bins);
     if (rc == RAFT_HIP_OK) rc = settings.restore_outputs();
     if (rc != RAFT_HIP_OK) die(engine_error(j, rc, -1));
     stage(j, "estimate");
@@ -598,6 +625,16 @@ void write_read_stats(Job &j)
         die("ERROR, read_stats(), cannot write output files");
 }
 
+void write_low_coverage(Job &j)
+{
+    const Params &p = j.p;
+    std::vector<const char *> names((size_t)j.n_reads);
+    for (int32_t i = 0; i < j.n_reads; ++i) names[(size_t)i] = raft_host_reads_name(j.reads, i);
+    if (raft_host_write_low_coverage((p.prefix + ".low_coverage.bed").c_str(), j.n_reads, names.data(), j.low_off.data(), j.low_s.data(), j.low_e.data(),
+                                     j.rl, p.reso) != RAFT_HOST_OK)
+        die("ERROR, low_coverage(), cannot write output files");
+}
+
 // the four output files are independent: the FASTA is written beside the coverage/repeat tables
 void write_outputs(Job &j)
 {
@@ -615,6 +652,7 @@ void write_outputs(Job &j)
         die("ERROR, repeat_annotate(), cannot write output files");
     }
     if (p.read_stats) write_read_stats(j);
+    if (p.low_cov >= 0) write_low_coverage(j);
     stage(j, "write_tables");
     // repeat.hpp:173-178 (total_windows is an int in the reference; identical below 2^31 windows)
     const double cpw = (double)s.total_coverage / (double)s.total_windows;
@@ -638,6 +676,9 @@ void print_totals(Job &j, int argc, char *argv[])
     fflush(stdout);
     std::cout << "\n";
     if (j.p.read_stats) std::cout << "INFO, read_stats(), contained reads = " << j.n_contained << " of " << j.n_reads << "\n";
+    if (j.p.low_cov >= 0)
+        std::cout << "INFO, low_coverage(), low_cov = " << j.p.low_cov << ", runs = " << j.low_sum.n_runs << ", reads with an interior run = "
+                  << j.low_sum.reads_interior << ", uncovered reads = " << j.low_sum.reads_uncovered << " of " << j.n_reads << "\n";
     stage(j, "stdout");
     if (j.sw.timing) {
         timespec ts{};

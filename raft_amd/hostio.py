@@ -49,6 +49,10 @@ ABI = {
     "raft_host_split_naive": (C.c_int, [_str, _str, _i32, _P(_i32)]),
 }
 EXPORTS = tuple(ABI)
+# ... and the function of include/raft_host_low.h, in the same library
+LOW_ABI = {
+    "raft_host_write_low_coverage": (C.c_int, [_str, _i32, _P(_str), _vp, _vp, _vp, _vp, _i32]),
+}
 
 
 class HostError(RuntimeError):
@@ -67,7 +71,7 @@ def load_library():
         if not os.path.exists(_LIB_PATH):
             raise RuntimeError(f"{_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         lib = C.CDLL(_LIB_PATH)
-        for name, (restype, argtypes) in ABI.items():
+        for name, (restype, argtypes) in list(ABI.items()) + list(LOW_ABI.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib

@@ -1,0 +1,23 @@
+"""The word arithmetic of the low-coverage runs (raft_amd/csrc/low_cov_bits.hpp) on the CPU: tests/low_cov_bits_check.cpp built by the
+host compiler under the address and undefined-behaviour sanitizers and run as a process of its own."""
+from __future__ import annotations
+
+import os
+import shutil
+import subprocess
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_low_cov_bits_check(tmp_path):
+    exe = str(tmp_path / "low_cov_bits_check")
+    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                            "-static-libasan", "-static-libubsan",                  # (the runtimes inside the program: nothing to load beside it)
+                            os.path.join(HERE, "low_cov_bits_check.cpp"), "-o", exe], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "low_cov_bits_check: ok" in run.stdout
