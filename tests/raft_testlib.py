@@ -1267,3 +1267,666 @@ def sides_pileup(reso, read_len, off, start, end):
     np.add.at(diff, cov_off[rid] + np.asarray(start, np.int64) // reso, 1)
     np.add.at(diff, cov_off[rid] + (np.asarray(end, np.int64) - 1) // reso + 1, -1)
     return np.cumsum(diff[:-1]).astype(np.int32)
+
+
+# ---- tail sets: the per-read tail of a pass (raft_amd/csrc/finalize.hpp) at its structural boundaries ---------------------------------
+# finalize_count_kernel -> tail_prefix_kernel -> finalize_fill_kernel<CUTS> / finalize_cuts_kernel order a read's repeats, mask its
+# cut-point markers, count and write its fragments and make the three offset arrays.  The sets below are built like the lattice sets
+# (self overlaps sorted by read, symmetric_mode = 1) with reso = 1, est_cov = 1, cov_mul = 1.0: a window is a base and every covered
+# base is high, so a record [s, e) IS a run of high windows at exact base positions and its flanked repeat is
+# (max(s - flank, 0), min(e + flank, len)) by construction.  Every set carries its closed form -- the repeats as a set per read, and
+# cuts, fragments and offsets from tail_model, a plain restatement of chop.hpp:209-321 in lists and loops that shares nothing with
+# the device's sweep arithmetic or the oracle's two-pointer loop.  tests/test_tail_cases.py pins the closed form to the oracle, the
+# constants below to the sources, and counts from the oracle's output (tail_census) that every class the sets aim at holds a read.
+TAIL_WAVE, TAIL_WG, TAIL_PREFIX_WG = 64, 256, 1024        # lanes of a wave, reads of a count / fill workgroup, entries of a prefix workgroup
+TAIL_REG_N, TAIL_TIE_N, TAIL_INSERTION_N, RUN_Q = 4, 16, 24, 16    # n <= 4 registers, n > 16 tie order, n <= 24 insertion sort, kRunQ
+TAIL_PREFIX_READS = TAIL_PREFIX_WG * TAIL_WG              # 262,144 reads: what one workgroup of tail_prefix_kernel scans
+TAIL_NS = (0, 1, 63, 64, 65, 255, 256, 257, TAIL_PREFIX_READS - 1, TAIL_PREFIX_READS, TAIL_PREFIX_READS + 1, TAIL_PREFIX_READS + 257)
+TAIL_DIVS, TAIL_FLANKS = (1, 2, 3, 7), (0, 2)
+TAIL_MARKERS_L = 10
+
+
+def tail_overlaps(div, L):
+    return (0, 1, L - 1, L, div * L)
+
+
+class TailFragmentError(ValueError):
+    """A fragment would begin before 0 or beyond the read's end (chop.hpp:280-321: the reference is not defined there)."""
+
+
+TAIL_VARIANTS = ("half-open s <= m < e", "half-open s < m <= e", "first marker maskable", "last marker maskable",
+                 "floor in the fragment count", "whole-read test nF <= div + 2", "overlap applied to fragment 1",
+                 "last fragment div intervals long, clipped", "repeats unflanked", "J = parts when len % L == 0")
+# Two changes that read like mistakes and are none: with nF = div + 1 kept markers the split gives ceil(div / div) = 1 fragment (0, len),
+# the whole read; and the last fragment's end index q + div is at least nF - 1, so clipping it to the list gives F[nF - 1].  Their wrong
+# neighbours are in TAIL_VARIANTS (the test two markers late; the last fragment's END POSITION begin marker + div*L clipped to len).
+TAIL_NO_MISTAKES = ("whole-read test nF <= div", "last fragment ending at F[q + div], index clipped")
+
+
+def tail_model(length, reps, L, div, overlap, variant=None, unflanked=None):
+    """One read: -> (kept markers F, fragments [(begin, end)]); raises TailFragmentError.  reps: the read's flanked, clamped repeats
+    (s, e), in any order.  Candidate markers are 0, L, 2L, ... and `length` itself when it is no multiple of L; the first, the last
+    and every marker m inside no repeat (closed: s <= m <= e) are kept; nF <= div + 1 kept markers leave the read whole, otherwise
+    fragment j of ceil((nF - 1) / div) begins at F[(j - 1) * div] (minus `overlap` from the second on) and ends at F[j * div], the
+    last one at F[nF - 1].
+    variant: one of TAIL_VARIANTS -- the same with ONE deliberate mistake, for tests/test_tail_cases.py to show that every one
+    of them is caught (unflanked: the runs themselves, for "repeats unflanked")."""
+    assert variant is None or variant in TAIL_VARIANTS + TAIL_NO_MISTAKES, variant
+    cand = list(range(0, length + 1, L))
+    if length % L:
+        cand.append(length)
+    if variant == "repeats unflanked":
+        reps = unflanked
+    last_i = len(cand) - 1
+    F = []
+    for i, m in enumerate(cand):
+        if variant == "half-open s <= m < e":
+            inside = any(s <= m < e for (s, e) in reps)
+        elif variant == "half-open s < m <= e":
+            inside = any(s < m <= e for (s, e) in reps)
+        else:
+            inside = any(s <= m <= e for (s, e) in reps)
+        first = i == 0 and variant != "first marker maskable"
+        last = i == last_i and variant != "last marker maskable" and not (variant == "J = parts when len % L == 0" and length % L == 0 and length > 0)
+        if first or last or not inside:
+            F.append(m)
+    nF = len(F)
+    if nF <= {"whole-read test nF <= div": div, "whole-read test nF <= div + 2": div + 2}.get(variant, div + 1):
+        return F, [(0, length)]
+    nf = (nF - 1) // div if variant == "floor in the fragment count" else -(-(nF - 1) // div)
+    frags = []
+    for j in range(1, nf + 1):
+        begin = F[(j - 1) * div] - (overlap if (j > 1 or variant == "overlap applied to fragment 1") else 0)
+        if begin < 0 or begin > length:
+            raise TailFragmentError(f"fragment {j} begins at {begin}, read length {length}")
+        end = F[j * div] if j < nf else F[nF - 1]
+        if variant == "last fragment ending at F[q + div], index clipped":
+            end = F[min(j * div, nF - 1)]
+        if j >= nf and variant == "last fragment div intervals long, clipped":
+            end = min(F[(j - 1) * div] + div * L, length)
+        frags.append((begin, end))
+    return F, frags
+
+
+def _merge_runs(runs):
+    """Records of one read as maximal runs of covered bases: sorted, touching or overlapping ones joined."""
+    out = []
+    for s, e in sorted(runs):
+        if out and s <= out[-1][1]:
+            out[-1][1] = max(out[-1][1], e)
+        else:
+            out.append([s, e])
+    return [(s, e) for s, e in out]
+
+
+def _rows(flat, start, count, idx):
+    """Concatenation of the rows flat[start[t] : start[t] + count[t]] for t in idx (numpy, no loop over idx)."""
+    cnt = count[idx]
+    total = int(cnt.sum())
+    if total == 0:
+        return np.empty(0, flat.dtype)
+    first = np.zeros(idx.size, np.int64)
+    np.cumsum(cnt[:-1], out=first[1:])
+    within = np.arange(total, dtype=np.int64) - np.repeat(first, cnt)
+    return flat[np.repeat(start[idx], cnt) + within]
+
+
+class TailCase:
+    """name, p (RaftParams), cols (seven columns), L / div / overlap / flank, and per read r: length(r), runs(r) (its records), kind(r);
+    expect: the closed form -- rep_offset, rep_s / rep_e (ordered by start, compared as a SET per read: the order under ties is the
+    oracle's), cut_offset, cuts, frag_offset, frag_read, frag_begin, frag_end, total_repeat_length, or error_read (the first read
+    whose fragments are not defined).  Reads are instances of templates: idx[r] names the template of read r."""
+
+    def __init__(self, name, p, templates, idx):
+        self.name, self.p, self.templates, self.idx = name, p, templates, np.asarray(idx, np.int64)
+        self.L, self.flank, self.overlap = p.interval_length, p.flanking_length, p.overlap_length
+        self.div = p.read_length // p.interval_length
+        nt = len(templates)
+        tlen = np.array([t[0] for t in templates], np.int64).reshape(nt)
+        assert p.reso == 1 and p.high_cov == 1 and all(0 <= s < e <= t[0] for t in templates for (s, e) in t[1]), name
+        cnt = {k: np.zeros(nt, np.int64) for k in ("rec", "rep", "cut", "frag")}
+        flat = {k: [] for k in ("rec_s", "rec_e", "rep_s", "rep_e", "cuts", "frag_begin", "frag_end")}
+        bp = np.zeros(nt, np.int64)
+        bad = np.zeros(nt, bool)
+        for t, (ln, runs, _) in enumerate(templates):
+            high = [(s, e) for (s, e) in _merge_runs(runs) if e - s >= p.repeat_length]
+            reps = [(max(s - self.flank, 0), min(e + self.flank, ln)) for (s, e) in high]
+            bp[t] = sum(e - s for (s, e) in high)
+            try:
+                F, frags = tail_model(ln, reps, self.L, self.div, self.overlap)
+            except TailFragmentError:
+                bad[t], F, frags = True, [], []
+            for k, rows in (("rec", sorted(runs)), ("rep", reps), ("frag", frags)):
+                cnt[k][t] = len(rows)
+                a, b = {"rec": ("rec_s", "rec_e"), "rep": ("rep_s", "rep_e"), "frag": ("frag_begin", "frag_end")}[k]
+                flat[a] += [x for x, _ in rows]
+                flat[b] += [y for _, y in rows]
+            cnt["cut"][t] = len(F)
+            flat["cuts"] += F
+        flat = {k: np.array(v, np.int32) for k, v in flat.items()}
+        start = {}
+        for k in cnt:
+            start[k] = np.zeros(nt, np.int64)
+            np.cumsum(cnt[k][:-1], out=start[k][1:])
+        self._t = {"cnt": cnt, "start": start, "flat": flat, "len": tlen}
+        idx = self.idx
+        n = idx.size
+        rl = tlen[idx].astype(np.int32) if n else np.empty(0, np.int32)
+        qid = np.repeat(np.arange(n, dtype=np.int64), cnt["rec"][idx] if n else 0).astype(np.int32)
+        qs, qe = (_rows(flat[k], start["rec"], cnt["rec"], idx) if n else np.empty(0, np.int32) for k in ("rec_s", "rec_e"))
+        self.cols = [rl, qid, qs, qe, qid.copy(), qs.copy(), qe.copy()]
+        ex = {}
+        for k, keys in (("rep", ("rep_s", "rep_e")), ("cut", ("cuts",)), ("frag", ("frag_begin", "frag_end"))):
+            off = np.zeros(n + 1, np.int64)
+            if n:
+                np.cumsum(cnt[k][idx], out=off[1:])
+            ex[k + "_offset"] = off
+            for key in keys:
+                ex[key] = _rows(flat[key], start[k], cnt[k], idx) if n else np.empty(0, np.int32)
+        ex["frag_read"] = np.repeat(np.arange(n, dtype=np.int64), cnt["frag"][idx] if n else 0).astype(np.int32)
+        ex["total_repeat_length"] = int(bp[idx].sum()) if n else 0
+        ex["total_read_length"] = int(rl.astype(np.int64).sum())
+        wrong = np.flatnonzero(bad[idx]) if n else np.empty(0, np.int64)
+        ex["error_read"] = int(wrong[0]) if wrong.size else -1
+        self.expect = ex
+
+    @property
+    def n_reads(self):
+        return int(self.idx.size)
+
+    @property
+    def triple(self):
+        return (self.div, self.overlap, self.flank)
+
+    def length(self, r):
+        return int(self.templates[int(self.idx[r])][0])
+
+    def runs(self, r):
+        return list(self.templates[int(self.idx[r])][1])
+
+    def kind(self, r):
+        return self.templates[int(self.idx[r])][2]
+
+    def reps(self, r):
+        """The closed form's flanked repeats of read r, ordered by start."""
+        c, s, f = self._t["cnt"]["rep"], self._t["start"]["rep"], self._t["flat"]
+        t = int(self.idx[r])
+        return list(zip(f["rep_s"][s[t]:s[t] + c[t]].tolist(), f["rep_e"][s[t]:s[t] + c[t]].tolist()))
+
+    def query_cols(self):
+        return tuple(self.cols[:4]) + (None, None, None)
+
+    def coordinate(self, r):
+        r = int(r)
+        reps = self.reps(r)
+        shown = str(reps) if len(reps) <= 6 else f"{len(reps)}: {reps[:3]} ... {reps[-2:]}"
+        return (f"set {self.name}, (div, overlap, flank) = {self.triple}, L = {self.L}: read {r} [{self.kind(r)}] len {self.length(r)}, "
+                f"repeats {shown}, lane {r % TAIL_WAVE}, wave {r // TAIL_WAVE}, workgroup {r // TAIL_WG}")
+
+    def oracle(self):
+        want = oracle_run(self.p, *self.cols)
+        want["symmetric"] = 1
+        return want
+
+
+def _tail_params(L, div, overlap, flank, repeat_length=3):
+    return RaftParams(reso=1, est_cov=1, cov_mul=1.0, repeat_length=repeat_length, interval_length=L, read_length=div * L,
+                      overlap_length=overlap, flanking_length=flank, symmetric_mode=1)
+
+
+def _tail_simple(name, p, reads):
+    return TailCase(name, p, reads, np.arange(len(reads)))
+
+
+TAIL_PARTS = (("repeats", "rep_offset", ("rep_s", "rep_e")), ("cuts", "cut_offset", ("cuts",)), ("fragments", "frag_offset", ("frag_begin", "frag_end")))
+
+
+def _sorted_pairs(off, s, e):
+    r = np.repeat(np.arange(off.size - 1), np.diff(off))
+    order = np.lexsort((e, s, r))
+    return s[order], e[order]
+
+
+def tail_first_difference(case, got, want, as_sets=False):
+    """None, or a sentence naming the first read whose repeats, cut points, fragments or offsets differ, as a tail coordinate.  Parts
+    that `got` does not hold (a host pipeline's outputs have no cut points) are left out.  as_sets: a read's repeats in any order."""
+    for what, ok, keys in TAIL_PARTS:
+        if ok not in got or any(k not in got for k in keys):
+            continue
+        go, wo = np.asarray(got[ok], np.int64), np.asarray(want[ok], np.int64)
+        if go.shape != wo.shape:
+            return f"{ok} has {go.size} entries, want {wo.size} ({case.name}, {case.triple})"
+        for r in np.flatnonzero(np.diff(go) != np.diff(wo))[:1]:
+            return f"number of {what} differs first in {case.coordinate(r)}: got {int(go[r + 1] - go[r])} want {int(wo[r + 1] - wo[r])}"
+        bad = np.flatnonzero(go != wo)
+        if bad.size:
+            return f"{ok} differs first at read {int(bad[0])}: got {int(go[bad[0]])} want {int(wo[bad[0]])}; {case.coordinate(min(int(bad[0]), max(case.n_reads - 1, 0))) if case.n_reads else case.name}"
+        cols_g, cols_w = [np.asarray(got[k]) for k in keys], [np.asarray(want[k]) for k in keys]
+        if as_sets and what == "repeats":
+            cols_g, cols_w = _sorted_pairs(go, *cols_g), _sorted_pairs(wo, *cols_w)
+        for k, g, w in zip(keys, cols_g, cols_w):
+            bad = np.flatnonzero(g != w)
+            if bad.size:
+                r = int(np.searchsorted(wo, bad[0], side="right") - 1)
+                return (f"{k} differs in {bad.size} of {g.size} entries, first in {case.coordinate(r)} at its entry {int(bad[0] - wo[r])}: "
+                        f"got {g[wo[r]:wo[r + 1]].tolist()[:40]} want {w[wo[r]:wo[r + 1]].tolist()[:40]}")
+    return None
+
+
+def assert_tail_result(case, got, want, what):
+    """assert_same_result whose message reads as a coordinate: set, parameter triple, `what` (kernel, pass, emit_cuts) and the first
+    differing read with its length, repeats, lane, wave and workgroup."""
+    msg = tail_first_difference(case, got, want)
+    assert msg is None, f"{what}: {msg}"
+    if "cov" in got and "cuts" in got:
+        assert_same_result(got, want, f"set {case.name}, {case.triple}, {what}")
+
+
+# -- the four sets
+
+def tail_markers(div, overlap, flank, L=TAIL_MARKERS_L, repeat_length=3):
+    """A few hundred reads under one (div, overlap, flank): every length 0 .. 3L + 1 and k*L + {-1, 0, 1} around the split threshold
+    and its multiples, without a repeat; one repeat whose flanked ends sit on kL - 1, kL, kL + 1 in all nine combinations, at read
+    lengths that put the kept markers on either side of div + 1 and of a multiple of div; a repeat strictly between two markers, on
+    the last interior marker, reaching the read's end, clamped to 0; two repeats whose flanked intervals overlap, share exactly one
+    marker, mask neighbouring markers and lie one marker apart.  (A second repeat wholly inside the first's flanks needs both clamped
+    at both ends -- a flank beyond the read: tail_counts.)"""
+    f, m = flank, repeat_length
+    reads = []
+
+    def add(ln, runs, kind):
+        runs = [(s, e) for (s, e) in runs]
+        if ln >= 0 and all(0 <= s and e - s >= 1 and e <= ln for (s, e) in runs) and all(a[1] < b[0] for a, b in zip(runs, runs[1:])):
+            reads.append((ln, runs, kind))
+            return True
+        return False
+
+    ks = sorted({div, div + 1, div + 2, 2 * div, 2 * div + 1, 5 * div})
+    for ln in list(range(0, 3 * L + 2)) + [k * L + d for k in ks for d in (-1, 0, 1)]:
+        add(ln, [], "length")
+    split_lens = sorted({(div + 1 + x) * L + t for x in range(0, 6) for t in (0, 1, L - 1)} | {(2 * div + 2) * L, (3 * div + 1) * L + 3})
+    for ln in split_lens:
+        for k in (1, 2):
+            for k2 in (k + 1, k + 2, k + 3):
+                for a in (-1, 0, 1):
+                    for b in (-1, 0, 1):
+                        s, e = k * L + a, k2 * L + b                     # the flanked ends; the run lies `flank` inside them
+                        if e - f - (s + f) >= m and e < ln:
+                            add(ln, [(s + f, e - f)], f"ends {a:+d},{b:+d}")
+    for ln in ((div + 2) * L, (div + 3) * L + 4, (2 * div + 3) * L + 1, (div + 1) * L, 2 * L + 5):
+        parts = ln // L
+        J = parts if ln % L else parts - 1
+        for k in (1, div, J - 1):
+            add(ln, [(k * L + 1 + f, (k + 1) * L - 1 - f)], "between markers")
+            add(ln, [(k * L + 1 + f, k * L + 1 + f + m)], "between markers")
+        add(ln, [(J * L - 1, J * L + 2)], "last interior marker")
+        add(ln, [(J * L - m, J * L)], "last interior marker")
+        add(ln, [(J * L, J * L + m)], "last interior marker")
+        add(ln, [(ln - m - 1, ln)], "reaches len")
+        add(ln, [(ln - m - 2, ln - 1)], "reaches len")
+        add(ln, [(ln - L - 2, ln)], "reaches len")
+        add(ln, [(0, m)], "clamped to 0")
+        add(ln, [(1, m + 1)], "clamped to 0")
+        add(ln, [(0, L + 1)], "clamped to 0")
+        add(ln, [(0, ln)], "whole read")
+        for k in (1, 2, div):
+            add(ln, [(k * L - 2, k * L + m - 2), (k * L + m - 1, k * L + 2 * m - 1)], "two, flanks overlap")
+            add(ln, [(k * L - 8 + f, k * L - f), (k * L + f, k * L + 8 - f)], "two, share a marker" if f else "two, one low base apart")
+            add(ln, [(k * L - 1, k * L + m - 1), ((k + 1) * L - 1, (k + 1) * L + m - 1)], "two, neighbouring markers")
+            add(ln, [(k * L - 1, k * L + m - 1), ((k + 2) * L - 1, (k + 2) * L + m - 1)], "two, one marker apart")
+            add(ln, [(k * L - m, k * L + 1), ((k + 2) * L - m, (k + 3) * L + 1)], "two, one marker apart")
+    return _tail_simple("tail_markers", _tail_params(L, div, overlap, flank, repeat_length), reads)
+
+
+TAIL_COUNT_NS = (0, 1, 2, 3, 4, 5, 6, 15, 16, 17, 18, 23, 24, 25, 26, 63, 64, 65, 130)
+TAIL_COUNTS_L, TAIL_COUNTS_FLANKS = 20, (8, 600, 10 ** 6)
+
+
+def _count_read(n, way, m=3, f=8, F=600):
+    """A read of n runs of m bases, one low base apart (a run every m + 1 bases: 64 runs end within 256 windows, more than kRunQ in
+    one half-row).  way: "plain" no two repeats clamp to 0 under flank f (the first run starts f + 2 bases in), "one" the first alone
+    does, "k2" / "k3" exactly two / three do, "kn": all of them clamp under flank F, and the read is long enough behind its last
+    run that their ends stay distinct.  Every repeat of a read has an end of its own unless the flank reaches beyond the read."""
+    step = m + 1
+    if way in ("plain", "one"):
+        s0 = f + 2 if way == "plain" else f - 1
+        runs = [(s0 + step * i, s0 + step * i + m) for i in range(n)]
+    elif way == "kn":
+        runs = [(step * i, step * i + m) for i in range(n)]
+    else:
+        k = min(int(way[1]), n)
+        assert k < int(way[1]) or step * (k - 1) <= f < step * (k + 1) + m      # the k-th run clamps, the next one does not
+        runs = [(step * i, step * i + m) for i in range(k)] + [(step * (k + 1) + m + step * i, step * (k + 1) + 2 * m + step * i) for i in range(n - k)]
+    end = runs[-1][1] if runs else 0
+    ln = end + (F + 10 if way == "kn" else 5 + n % 7)
+    return (ln, runs, f"n={n} {way}")
+
+
+def tail_counts(div, overlap, flank, L=TAIL_COUNTS_L, thin=False, repeat_length=3):
+    """Two workgroups and a bit of reads with n repeats for n in TAIL_COUNT_NS, laid out -- under flank 8 -- so that workgroup 0 holds a
+    wave whose 64 lanes ALL need the tie order (rep_std_sort), a wave where only lanes 0 and 63 do, a wave with one such lane among
+    reads of n <= 4 and a wave where a read of n > 24 sits next to one of n = 17, both tied: its four waves all hold a tied lane;
+    workgroup 1 holds one wave with a tied lane among every n without ties; the set ends in a wave of ten reads, the last one tied,
+    with dead lanes behind it.  Under flank 600 the "kn" reads clamp ALL their repeats to 0 with distinct ends (the ends of the
+    tied entries are then not monotone after the permutation), under flank 10^6 every repeat of the set is (0, len).
+    thin: every fourth read (the data fixture of the reference binary)."""
+    big, small, ways = (17, 18, 23, 24, 25, 26, 63, 64, 65, 130), (0, 1, 2, 3, 4, 5, 6, 15, 16), ("plain", "k2", "k3", "kn", "one")
+    m = repeat_length
+    spec = []
+    for lane in range(64):                                                  # wave 0: all tied
+        spec.append((big[lane % 10], ("k2", "k3", "kn")[lane % 3]))
+    for lane in range(64):                                                  # wave 1: lanes 0 and 63
+        spec.append((25, "k2") if lane == 0 else (17, "k3") if lane == 63 else (small[lane % 9], ways[lane % 5]))
+    for lane in range(64):                                                  # wave 2: one lane among n <= 4
+        spec.append((64, "k2") if lane == 17 else (lane % 5, ways[(lane // 5) % 5]))
+    for lane in range(64):                                                  # wave 3: n > 24 next to n = 17
+        spec.append((26, "k3") if lane == 5 else (17, "k2") if lane == 6 else (small[(lane + 3) % 9], ways[(lane // 9) % 5]))
+    for lane in range(64):                                                  # wave 4: every large n without ties, one tied lane
+        spec.append((130, "kn") if lane == 20 else (big[lane % 10], ("plain", "one")[(lane // 10) % 2]) if lane < 40 else (small[lane % 9], "plain"))
+    for w in range(3):                                                      # waves 5-7: no tie
+        for lane in range(64):
+            spec.append(((big + small)[(lane + 7 * w) % 19], ("plain", "one")[(lane + w) % 2]))
+    for lane in range(9):                                                   # wave 8, the last: dead lanes behind a tied read
+        spec.append((small[lane], ways[lane % 5]))
+    spec.append((63, "k2"))
+    if thin:
+        spec = spec[::4]
+    f = 8 if m == 3 else 2 * (m + 1) + 1                                     # (a larger repeat_length: runs of m bases, the designed flank scales)
+    reads = [_count_read(n, way, m=m, f=f) for (n, way) in spec]
+    return _tail_simple("tail_counts", _tail_params(L, div, overlap, flank, repeat_length), reads)
+
+
+TAIL_PIECES_L = 20
+TAIL_PIECES_TRIPLES = ((1, 0, 8), (3, TAIL_PIECES_L, 8), (2, 1, 0))
+
+
+def tail_pieces(div, overlap, flank, L=TAIL_PIECES_L):
+    """Reads of more than TILE_CAP windows (2, 3 and 4 pieces) among short reads: five of them in wave 0, the others in waves 1 and 4.
+    Records that end exactly on a piece edge with the next one beginning there (one run: its raw parts join); the same with ONE low
+    window on either side of the edge (two runs); two parts below repeat_length whose join reaches it, and one base short; a run
+    through a whole middle piece, exactly and with margins; a long read whose runs all fail; 4 joined from 6 raw records and 5 from
+    7 (the n <= 4 branch of the fill kernel looks at the re-counted list); more than 16 joined with two clamped to 0."""
+    C = TILE_CAP
+    long_reads = [
+        (2 * C + 300, [(C - 5, C), (C, C + 4)], "joins on the edge"),
+        (2 * C + 41, [(C - 6, C - 1), (C, C + 4), (2 * C - 5, 2 * C), (2 * C + 1, 2 * C + 5)], "one low window on the edge"),
+        (C + C // 2, [(C - 1, C + 2), (C + 40, C + 42)], "parts 1 + 2 reach repeat_length"),
+        (C + 700, [(C - 2, C + 1)], "parts 2 + 1 reach repeat_length"),
+        (C + 20, [(C - 1, C + 1), (300, 302)], "join one base short, all runs fail"),
+        (3 * C + 200, [(C - 10, 2 * C + 10)], "through a middle piece with margins"),
+        (3 * C + 1, [(C, 2 * C)], "a middle piece exactly"),
+        (3 * C + 517, [(C - 1, C + 1), (2 * C - 1, 2 * C + 1), (77, 79)], "all runs fail"),
+        (2 * C + 100, [(10, 14), (C - 3, C + 3), (2 * C - 2, 2 * C + 2), (2 * C + 50, 2 * C + 55)], "4 joined from 6 raw"),
+        (3 * C + 60, [(10, 14), (C - 3, C + 3), (2 * C - 2, 2 * C + 2), (3 * C - 1, 3 * C + 2), (3 * C + 50, 3 * C + 55)], "5 joined from 8 raw"),
+        (2 * C + 77, [(0, 3), (4, 7)] + [(40 + 9 * i, 44 + 9 * i) for i in range(12)] + [(C - 2, C + 2), (C + 30, C + 34), (2 * C - 4, 2 * C + 1), (2 * C + 20, 2 * C + 23)],
+         "18 joined, two clamped to 0"),
+        (3 * C + 999, [(C - 3, C), (C, C + 3), (2 * C - 1, 2 * C + 5), (3 * C, 3 * C + 3)], "four pieces"),
+        (2 * C + 2, [(0, 2 * C + 2)], "high from end to end"),
+        (C + 1, [(C - 3, C + 1)], "one window in the second piece"),
+    ]
+    places = {0: 0, 1: 9, 2: 30, 3: 31, 4: 63, 5: 64 + 2, 6: 64 + 40, 7: 64 + 63, 8: 256 + 0, 9: 256 + 1, 10: 256 + 17, 11: 256 + 33, 12: 256 + 62, 13: 256 + 63}
+    at = {v: k for k, v in places.items()}
+    reads = []
+    for r in range(256 + 64 + 13):
+        if r in at:
+            reads.append(long_reads[at[r]])
+            continue
+        ln = (7 * r) % 101
+        runs = []
+        if r % 3 == 1 and ln >= 12:
+            runs = [(ln // 2 - 2, ln // 2 + 2)]
+        if r % 3 == 2 and ln >= 30:
+            runs = [(2, 6), (ln - 9, ln - 4)]
+        reads.append((ln, runs, "short"))
+    return _tail_simple("tail_pieces", _tail_params(L, div, overlap, flank), reads)
+
+
+TAIL_OFFSETS_L = 20
+TAIL_SHAPES = ("no repeat, one fragment", "no repeat, three fragments", "one repeat", "five repeats")
+
+
+def tail_offsets(N, L=TAIL_OFFSETS_L):
+    """N reads of four shapes -- no repeat and one fragment, no repeat and three fragments, one repeat, five repeats -- chosen per read
+    by a hash of its index (not periodic in 64 or 256), under div = 1, overlap = 3, flank = 2.  Lengths stay below 100.  What is
+    compared are the FULL offset arrays and the totals: 262,144 reads are what one workgroup of tail_prefix_kernel scans."""
+    templates = ([(ln, [], TAIL_SHAPES[0]) for ln in (0, 1, 7, 19, 20)]
+                 + [(ln, [], TAIL_SHAPES[1]) for ln in (41, 55, 60)]
+                 + [(45, [(18, 23)], TAIL_SHAPES[2]), (30, [(5, 8)], TAIL_SHAPES[2]), (99, [(37, 64)], TAIL_SHAPES[2]), (61, [(0, 3)], TAIL_SHAPES[2])]
+                 + [(80, [(1, 4), (9, 12), (30, 33), (38, 42), (70, 73)], TAIL_SHAPES[3]),
+                    (97, [(17, 23), (27, 30), (31, 34), (58, 63), (94, 97)], TAIL_SHAPES[3])])
+    by_shape = [[t for t, x in enumerate(templates) if x[2] == s] for s in TAIL_SHAPES]
+    j = np.arange(N, dtype=np.uint64)
+    h = (j * np.uint64(0x9E3779B1) + np.uint64(0x7F4A7C15)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(15)
+    h = (h * np.uint64(0x85EBCA6B)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(13)
+    shape = (h & np.uint64(3)).astype(np.int64)
+    pick = ((h >> np.uint64(8)) % np.uint64(60)).astype(np.int64)
+    table = np.array([[by_shape[s][v % len(by_shape[s])] for v in range(60)] for s in range(4)], np.int64)
+    idx = table[shape, pick] if N else np.empty(0, np.int64)
+    return TailCase(f"tail_offsets/N {N}", _tail_params(L, 1, 3, 2), templates, idx)
+
+
+TAIL_ERROR_READS = (3, 70, 300, 700)
+
+
+def tail_error_set(short=(), L=10, div=2, n=800):
+    """Under overlap = div*L + 1 a read that splits and has lost no marker before its second fragment begins that fragment at -1.  Reads
+    TAIL_ERROR_READS (waves and workgroups apart) would split, all others stay whole; short: those of them made short enough to stay
+    whole as well."""
+    reads = []
+    for r in range(n):
+        if r in TAIL_ERROR_READS and r not in short:
+            reads.append(((div + 2) * L - 5, [], "splits"))
+        else:
+            reads.append(((r * 7) % (div * L + 1), [], "whole"))
+    return _tail_simple("tail_error", _tail_params(L, div, div * L + 1, 0), reads)
+
+
+def tail_census(case, want):
+    """Classes a set's reads fall in, counted from the ORACLE's output (repeats, cut points, fragments, coverage) and the reads' places
+    alone -- never from what the generator meant to build.  -> {class: count}"""
+    L, div = case.L, case.div
+    rl = np.asarray(case.cols[0], np.int64)
+    N = rl.size
+    ro, co, fo = (np.asarray(want[k], np.int64) for k in ("rep_offset", "cut_offset", "frag_offset"))
+    n, nF, nf = np.diff(ro), np.diff(co), np.diff(fo)
+    rs, re_ = np.asarray(want["rep_s"], np.int64), np.asarray(want["rep_e"], np.int64)
+    out = {}
+    second0 = np.zeros(N, bool)                        # the kernel's own test: the read's second repeat (ordered by start) begins at 0
+    has2 = n >= 2
+    second0[has2] = rs[ro[:-1][has2] + 1] == 0
+    tied = (n > TAIL_TIE_N) & second0
+    for v in (TAIL_REG_N, TAIL_REG_N + 1, TAIL_INSERTION_N, TAIL_INSERTION_N + 1):
+        out[("n", v)] = int(np.sum(n == v))
+    for v in (TAIL_TIE_N, TAIL_TIE_N + 1):
+        out[("n", v, "tied")] = int(np.sum((n == v) & second0))
+        out[("n", v, "untied")] = int(np.sum((n == v) & ~second0))
+    pad = (-N) % TAIL_WG
+    tw = np.concatenate([tied, np.zeros(pad, bool)]).reshape(-1, TAIL_WG // TAIL_WAVE, TAIL_WAVE) if N else np.zeros((0, 4, 64), bool)
+    per_wave = tw.sum(axis=2)
+    for v in (1, 2, 64):
+        out[("tied lanes in a wave", v)] = int(np.sum(per_wave == v))
+    waves_with = (per_wave > 0).sum(axis=1)
+    for v in (1, 4):
+        out[("waves of a workgroup with a tied lane", v)] = int(np.sum(waves_with == v))
+    if N and tied.any():
+        last = int(np.flatnonzero(tied)[-1])
+        out[("last wave", "dead lanes behind a tied read")] = int(last // TAIL_WAVE == (N - 1) // TAIL_WAVE and N % TAIL_WAVE != 0 and last == N - 1)
+        big, seventeen = tied & (n > TAIL_INSERTION_N), tied & (n == TAIL_TIE_N + 1)
+        out[("tied n > 24 next to tied n = 17", "same wave")] = int(np.sum(big[:-1] & seventeen[1:] & (np.arange(N - 1) % TAIL_WAVE != TAIL_WAVE - 1)))
+    r_of = np.repeat(np.arange(N), n)
+    nonmono = np.zeros(N, bool)
+    if rs.size > 1:
+        down = (re_[1:] < re_[:-1]) & (r_of[1:] == r_of[:-1])
+        nonmono[r_of[1:][down]] = True
+    out[("ends not monotone",)] = int(nonmono.sum())
+    for d in (-1, 0, 1):
+        out[("nF - (div + 1)", d)] = int(np.sum(nF - (div + 1) == d))
+    split = nf > 1
+    out[("(nF - 1) % div", "zero")] = int(np.sum(split & ((nF - 1) % div == 0)))
+    out[("(nF - 1) % div", "non-zero")] = int(np.sum(split & ((nF - 1) % div != 0)))
+    out[("len % L", "zero")] = int(np.sum((rl % L == 0) & (rl > 0)))
+    out[("len % L", "non-zero")] = int(np.sum(rl % L != 0))
+    out[("len", "< L")] = int(np.sum((rl < L) & (rl > 0)))
+    out[("len", "== L")] = int(np.sum(rl == L))
+    out[("len", "== 0")] = int(np.sum(rl == 0))
+    inner = (rs > 0) & (re_ < rl[r_of])                # flanked ends that are no clamp
+    for a in (L - 1, 0, 1):
+        for b in (L - 1, 0, 1):
+            out[("s % L, e % L", a, b)] = int(np.sum(inner & (rs % L == a) & (re_ % L == b)))
+    out[("first marker inside a repeat",)] = int(np.sum(rs == 0))
+    out[("last marker inside a repeat",)] = int(np.sum(re_ == rl[r_of]))
+    inside = lambda a, b: np.maximum(b // L - (a - 1) // L, 0)      # multiples of L in [a, b]
+    J = np.where(rl % L != 0, rl // L, rl // L - 1)                    # the last interior marker of a read is J * L
+    out[("repeat", "covers no marker")] = int(np.sum(inner & (inside(rs, re_) == 0)))
+    out[("repeat", "covers the last interior marker")] = int(np.sum(inner & (J[r_of] >= 1) & (rs <= J[r_of] * L) & (J[r_of] * L <= re_)))
+    pair = r_of[1:] == r_of[:-1] if rs.size > 1 else np.zeros(0, bool)
+    s1, e1, s2, e2 = rs[:-1], re_[:-1], rs[1:], re_[1:]
+    both = pair & (inside(s1, e1) > 0) & (inside(s2, e2) > 0) if rs.size > 1 else pair
+    out[("two repeats", "flanked intervals overlap")] = int(np.sum(pair & (s2 <= e1) & (s2 > s1) & (e2 > e1)))
+    out[("two repeats", "share exactly one marker")] = int(np.sum(pair & (s2 > s1) & (e2 > e1) & (inside(s2, e1) == 1)))
+    out[("two repeats", "no marker between")] = int(np.sum(both & (s2 > e1) & (inside(e1 + 1, s2 - 1) == 0)))
+    out[("two repeats", "one marker apart")] = int(np.sum(both & (s2 > e1) & (inside(e1 + 1, s2 - 1) == 1)))
+    out[("two repeats", "the second inside the first")] = int(np.sum(pair & (s2 >= s1) & (e2 < e1)))
+    # runs that qualify, from the coverage: ends of runs of high windows, per read
+    cov, cvo = np.asarray(want["cov"]), np.asarray(want["cov_offset"], np.int64)
+    W = np.diff(cvo)
+    high = cov >= want["high_cov"]
+    most, joins, apart, through = 0, 0, 0, 0
+    short_join = {"reaches": 0, "one short": 0}
+    m = case.p.repeat_length
+    for r in np.flatnonzero((n > RUN_Q) | (W > TILE_CAP)):
+        h = np.concatenate([[False], high[cvo[r]:cvo[r + 1]], [False]])
+        edge = np.flatnonzero(h[1:] != h[:-1])
+        b, e = edge[0::2], edge[1::2]                  # runs [b, e) of the read's windows
+        if W[r] <= TILE_CAP:
+            ends = e[(e - b) >= m]
+            if ends.size:                              # the most run ends within any 256 consecutive windows
+                most = max(most, int(np.max(np.searchsorted(ends, ends + HALF_ROW, side="left") - np.arange(ends.size))))
+            continue
+        for c in range(TILE_CAP, int(W[r]), TILE_CAP):
+            over = (b < c) & (e > c)
+            joins += int(np.sum(over))
+            apart += int(np.sum(e == c - 1) and np.sum(b == c)) + int(np.sum(e == c) and np.sum(b == c + 1))
+            for bb, ee in zip(b[over], e[over]):
+                if c - bb < m and ee - c < m:
+                    short_join["reaches" if ee - bb >= m else "one short"] += int(ee - bb >= m - 1)
+        through += int(np.sum((b <= TILE_CAP) & (e >= 2 * TILE_CAP)))
+    out[("run ends in 256 windows of a read", "max")] = most
+    out[("piece", "a run crosses an edge")] = joins
+    out[("piece", "one low window on an edge")] = apart
+    out[("piece", "short parts join and reach repeat_length")] = short_join["reaches"]
+    out[("piece", "short parts join one base short")] = short_join["one short"]
+    out[("piece", "a run through a middle piece")] = through
+    long_ = W > TILE_CAP
+    for k in (2, 3, 4):
+        out[("pieces", k)] = int(np.sum(-(-W // TILE_CAP) == k))
+    any_high = np.add.reduceat(high.astype(np.int64), cvo[:-1][W > 0]) if W.size and (W > 0).any() else np.zeros(0, np.int64)
+    hi = np.zeros(N, np.int64)
+    hi[W > 0] = any_high
+    out[("long read", "high windows, no repeat")] = int(np.sum(long_ & (hi > 0) & (n == 0)))
+    out[("long read", "n == 4")] = int(np.sum(long_ & (n == TAIL_REG_N)))
+    out[("long read", "n == 5")] = int(np.sum(long_ & (n == TAIL_REG_N + 1)))
+    out[("long read", "tied")] = int(np.sum(long_ & tied))
+    lw = np.bincount(np.flatnonzero(long_) // TAIL_WAVE, minlength=1)
+    out[("long reads in one wave", "max")] = int(lw.max()) if lw.size else 0
+    return out
+
+
+def tail_sort_hits_depth_limit(keys):
+    """Whether libstdc++'s introsort (bits/stl_algo.h, as restated in finalize.hpp rep_std_sort) of this key list reaches its
+    depth limit 2*floor(log2 n) with more than 16 elements left -- the heap-sort fallback.  A report for the census, not a condition:
+    a list that is sorted but for ties at 0 does not get there."""
+    a = list(keys)
+    n = len(a)
+    todo = [(0, n, 2 * (n.bit_length() - 1))] if n > 1 else []
+    while todo:
+        first, last, depth = todo.pop()
+        while last - first > 16:
+            if depth == 0:
+                return True
+            depth -= 1
+            mid, x, z = first + (last - first) // 2, first + 1, last - 1
+            if a[x] < a[mid]:
+                pick = mid if a[mid] < a[z] else z if a[x] < a[z] else x
+            else:
+                pick = x if a[x] < a[z] else z if a[mid] < a[z] else mid
+            a[first], a[pick] = a[pick], a[first]
+            lo, hi = first + 1, last
+            while True:
+                while a[lo] < a[first]:
+                    lo += 1
+                hi -= 1
+                while a[first] < a[hi]:
+                    hi -= 1
+                if not lo < hi:
+                    break
+                a[lo], a[hi] = a[hi], a[lo]
+                lo += 1
+            todo.append((lo, last, depth))
+            last = lo
+    return False
+
+
+# -- tests/golden/tail_ref.npz: tail_markers and a thinned tail_counts through the compiled reference binary (make_tail_ref.py).  The
+# command line sets repeat_length and interval_length together (-p), so the sets are regenerated with repeat_length = L and runs of
+# at least L bases; inputs are stored once per (set, div, flank) -- the overlap does not change them -- outputs per parameter triple.
+
+TAIL_REF_COUNTS_FLANKS = (43, 3000)
+
+
+def tail_ref_list():
+    """[(set name, div, overlap, flank)] in the fixture's order."""
+    out = [("tail_markers", div, ov, fl) for div in TAIL_DIVS for fl in TAIL_FLANKS for ov in tail_overlaps(div, TAIL_MARKERS_L)]
+    return out + [("tail_counts", div, ov, fl) for div in (1, 3) for fl in TAIL_REF_COUNTS_FLANKS for ov in (0, TAIL_COUNTS_L)]
+
+
+def tail_ref_build(name, div, overlap, flank):
+    if name == "tail_markers":
+        return tail_markers(div, overlap, flank, repeat_length=TAIL_MARKERS_L)
+    return tail_counts(div, overlap, flank, thin=True, repeat_length=TAIL_COUNTS_L)
+
+
+_tail_ref = None
+
+
+def tail_ref_count() -> int:
+    global _tail_ref
+    if _tail_ref is None:
+        with np.load(os.path.join(GOLDEN, "tail_ref.npz")) as z:
+            _tail_ref = {k: z[k] for k in z.files}
+    assert [tuple(x) for x in _tail_ref["triples"].tolist()] == [t[1:] for t in tail_ref_list()]
+    return int(_tail_ref["triples"].shape[0])
+
+
+def tail_ref_case(i: int):
+    """-> (set name, TailCase, expected dict as ref_fuzz_case gives it).  The case is rebuilt by its generator -- for the coordinates
+    of a failure message -- and must hold exactly the inputs the binary was given, which the fixture stores."""
+    tail_ref_count()
+    z = _tail_ref
+    name, div, overlap, flank = tail_ref_list()[i]
+    case = tail_ref_build(name, div, overlap, flank)
+    g = int(z["input_of"][i])
+    r0, r1 = (int(x) for x in z["off_reads"][g:g + 2])
+    c0, c1 = (int(x) for x in z["off_recs"][g:g + 2])
+    assert np.array_equal(case.cols[0], z["read_len"][r0:r1]) and all(np.array_equal(case.cols[k], z[nm][c0:c1]) for k, nm in ((1, "qid"), (2, "qs"), (3, "qe"))), \
+        f"tail_ref case {i}: the generator no longer makes the inputs of the fixture (regenerate it: tests/golden/make_tail_ref.py)"
+    assert [int(x) for x in z["params"][i]] == [case.p.reso, case.p.est_cov, case.p.repeat_length, case.p.interval_length, case.p.read_length,
+                                                 case.p.overlap_length, case.p.flanking_length]
+    b0, b1 = (int(x) for x in z["off_cov"][g:g + 2])
+    p0, p1 = (int(x) for x in z["off_rep"][i:i + 2])
+    f0, f1 = (int(x) for x in z["off_frag"][i:i + 2])
+    rep_offset = np.zeros(r1 - r0 + 1, np.int64)
+    np.cumsum(z["rep_cnt"][int(z["off_reads_out"][i]):int(z["off_reads_out"][i + 1])], out=rep_offset[1:])
+    exp = {"cov": z["cov"][b0:b1].astype(np.int32), "rep_offset": rep_offset, "rep_s": z["rep_s"][p0:p1], "rep_e": z["rep_e"][p0:p1],
+           "frag_read": z["frag_read"][f0:f1], "frag_begin": z["frag_begin"][f0:f1], "frag_end": z["frag_end"][f0:f1],
+           "symmetric": int(z["symmetric"][i]), "stats": str(z["stats"][i]),
+           "md5": dict(zip(("reads.fasta", "coverage.txt", "long_repeats.txt", "long_repeats.bed"), (str(x) for x in z["md5"][i])))}
+    return name, case, exp
+
+
+def tail_shapes(want):
+    """Per read, from the oracle's output: index into TAIL_SHAPES, -1 = none of them."""
+    n, nf = np.diff(want["rep_offset"]), np.diff(want["frag_offset"])
+    return np.where((n == 0) & (nf == 1), 0, np.where((n == 0) & (nf == 3), 1, np.where(n == 1, 2, np.where(n == 5, 3, -1))))

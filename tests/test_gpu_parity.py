@@ -169,6 +169,7 @@ def test_defined_errors_match_oracle(eng_mod):
         with pytest.raises(eng_mod.RaftError) as ge:
             run_engine(eng_mod, pp, [rl] + cols)
         assert ge.value.code == code
+        assert ge.value.index == 0, (code, ge.value.index)      # summary.error_index: the one record, and for FRAGMENT read 0 (230 bases: four markers)
     got, _ = run_engine(eng_mod, p, [rl] + one(0, 0, 250, 1, 0, 10))   # beyond len but inside the last window: defined
     assert_same_result(got, oracle_run(p, rl, *one(0, 0, 250, 1, 0, 10)), "e>len inside last window")
 
