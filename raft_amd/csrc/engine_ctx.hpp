@@ -373,6 +373,12 @@ struct raft_hip_ctx {
     DevBuf lc_win{bufs}, lc_bases{bufs}, lc_flagw{bufs}, lc_flags{bufs}, lc_off{bufs};
     DevBuf lc_s{bufs}, lc_e{bufs}, lc_read{bufs};
     DevBuf lc_cov{bufs}, lc_abs{bufs};   // ... and, for a pass that holds no int32 array where one is needed, the decoded coverage and delta4's escape flags
+    // raft_hip_repeat_overlaps_* (ovl_class_lib.hip, libraft_hip_ovl.so; plain allocations, as lc_*): the digest of every read's runs, per read the
+    // sides that touch / lie in a repeat (one word for both while they are counted: oc_tally) and the flag words, the flags as bytes, the control words, the class bytes before they go to the
+    // caller; staging of the host form (lengths, columns, the repeat arrays)
+    DevBuf oc_digest{bufs}, oc_tally{bufs}, oc_touch{bufs}, oc_repeat{bufs}, oc_flagw{bufs}, oc_flags{bufs}, oc_ctl{bufs}, oc_cls{bufs};
+    DevBuf oc_len{bufs}, oc_rep_off{bufs}, oc_rep_s{bufs}, oc_rep_e{bufs};
+    DevBuf oc_col[6] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
     // raft_hip_census_*: counts and flag words per read, the flags as bytes, {first bad record, reads with a flag}; staging of the host form
     DevBuf cen_cnt{bufs}, cen_flags{bufs}, cen_out{bufs}, cen_ctl{bufs}, cen_len{bufs};
     DevBuf cen_col[6] = {DevBuf{bufs, DevBuf::kBig}, DevBuf{bufs, DevBuf::kBig}, DevBuf{bufs, DevBuf::kBig},

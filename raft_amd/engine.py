@@ -25,6 +25,9 @@ SUM_BUCKET_WINDOWS, SUM_SPECULATED, SUM_DEEP_TILES, SUM_RERUN, SUM_KEPT_GEOMETRY
 
 COV_HIST_BINS = 4096              # RAFT_HIP_COV_HIST_BINS
 LOW_INTERIOR, LOW_HEAD, LOW_TAIL, LOW_UNCOVERED = 1, 2, 4, 8    # RAFT_HIP_LOW_*: bits of low_flags (Engine.low_coverage)
+# RAFT_HIP_OVL_*: bits of a record's class byte and of read_flags (Engine.repeat_overlaps)
+OVL_Q_REPEAT, OVL_T_REPEAT, OVL_Q_TOUCH, OVL_T_TOUCH, OVL_Q_CONTAINED, OVL_T_CONTAINED = 1, 2, 4, 8, 16, 32
+OVL_READ_CONTAINED, OVL_READ_ANCHORED = 1, 2
 
 
 class _Params(C.Structure):
@@ -72,6 +75,11 @@ class _CovEstimate(C.Structure):
 
 class _LowSummary(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_runs", "low_windows", "low_bases", "reads_with_runs", "reads_interior", "reads_uncovered")]
+
+
+class _OvlSummary(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_records", "q_touch", "t_touch", "q_repeat", "t_repeat", "both_repeat", "q_contained", "t_contained",
+                                         "reads_contained", "reads_repeat_contained")]
 
 
 class _Outputs(C.Structure):
@@ -153,6 +161,14 @@ EXPORTS = tuple(ABI)
 LOW_ABI = {
     "raft_hip_low_abi": (C.c_int, []),
     "raft_hip_low_coverage": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _P(_LowSummary), _P(_f64)]),
+}
+
+# ... and those of include/raft_hip_ovl.h (libraft_hip_ovl.so): load_ovl_library declares these
+_OVL_CALL = [_vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(_OvlSummary), _P(_i64), _P(_f64)]
+OVL_ABI = {
+    "raft_hip_ovl_abi": (C.c_int, []),
+    "raft_hip_repeat_overlaps_device": (C.c_int, _OVL_CALL),
+    "raft_hip_repeat_overlaps_host": (C.c_int, _OVL_CALL),
 }
 
 
@@ -243,6 +259,28 @@ def load_low_library() -> C.CDLL:
             raise RuntimeError(f"{p} was built beside ABI {lib.raft_hip_low_abi()}, libraft_hip.so is ABI {main.raft_hip_abi_version()}")
         _low_lib = lib
     return _low_lib
+
+
+_ovl_lib = None
+
+
+def load_ovl_library() -> C.CDLL:
+    """Loads libraft_hip_ovl.so (behind libraft_hip.so, whose contexts it takes) and declares every entry point of
+    include/raft_hip_ovl.h; the two must have been built beside each other."""
+    global _ovl_lib
+    if _ovl_lib is None:
+        main = load_library()
+        p = os.path.join(os.path.dirname(_LIB_PATH), "libraft_hip_ovl.so")
+        if not os.path.exists(p):
+            raise RuntimeError(f"{p} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(p)
+        for name, (restype, argtypes) in OVL_ABI.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        if lib.raft_hip_ovl_abi() != main.raft_hip_abi_version():
+            raise RuntimeError(f"{p} was built beside ABI {lib.raft_hip_ovl_abi()}, libraft_hip.so is ABI {main.raft_hip_abi_version()}")
+        _ovl_lib = lib
+    return _ovl_lib
 
 
 def _cparams(p: RaftParams) -> _Params:
@@ -763,6 +801,54 @@ class Engine:
         self.last_low_coverage_seconds = secs.value
         out.update(n_runs=int(sm.n_runs), total_low_windows=int(sm.low_windows), low_bases=int(sm.low_bases),
                    reads_with_runs=int(sm.reads_with_runs), reads_interior=int(sm.reads_interior), reads_uncovered=int(sm.reads_uncovered))
+        return out
+
+    # -- which overlaps lie inside repeats ----------------------------------------------
+    last_repeat_overlaps_seconds = 0.0   # device time of the launches of the last repeat_overlaps()
+
+    def repeat_overlaps(self, read_len, qid, qs, qe, tid, ts=None, te=None, *, min_anchor: int = 1000, symmetric: bool = False, repeats=None) -> dict:
+        """raft_hip_repeat_overlaps_device / _host (libraft_hip_ovl.so): every record classified against the repeat annotation --
+        ``cls`` (one byte per record: OVL_Q_REPEAT | OVL_T_REPEAT | OVL_Q_TOUCH | OVL_T_TOUCH | OVL_Q_CONTAINED | OVL_T_CONTAINED; a
+        side is REPEAT when it touches the union of its read's runs and fewer than ``min_anchor`` of its bases lie outside) --, per
+        read ``read_touch`` / ``read_repeat`` (int32: its sides with TOUCH / REPEAT, sides counted as the census counts them under
+        ``symmetric``) and ``read_flags`` (uint8: OVL_READ_CONTAINED | OVL_READ_ANCHORED; a read whose flags are OVL_READ_CONTAINED
+        alone is contained only inside repeats of its containers), and the summary's counts.  The columns are int32 torch tensors on
+        this engine's device (``cls`` is then a torch.uint8 tensor there; ``repeats`` must be tensors too) or numpy arrays (staged by
+        the library); ts / te may be None when ``symmetric``.  ``repeats``: None = the annotation of this context's finished pass,
+        else (rep_offset int64 [n_reads + 1], rep_s, rep_e int32)."""
+        if any(x is None for x in (read_len, qid, qs, qe, tid)) or (ts is None) != (te is None) or (not symmetric and ts is None):
+            raise ValueError("repeat_overlaps needs read_len, qid, qs, qe, tid (and ts, te unless symmetric)")
+        cols = [read_len, qid, qs, qe, tid] + ([] if ts is None else [ts, te])
+        rep = [None, None, None] if repeats is None else list(repeats)
+        if len(rep) != 3:
+            raise ValueError("repeats is (rep_offset, rep_s, rep_e)")
+        ovl = load_ovl_library()
+        on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in cols)
+        n_rec = M.count(qid)
+        if on_device:
+            import torch
+            _need_int32_cuda("repeat_overlaps needs", cols + rep[1:])
+            if rep[0] is not None and (rep[0].dtype != torch.int64 or not rep[0].is_cuda or not rep[0].is_contiguous()):
+                raise TypeError("repeat_overlaps needs rep_offset as a contiguous int64 CUDA tensor")
+            self.use_torch_stream()
+            fn = ovl.raft_hip_repeat_overlaps_device
+            cls = torch.zeros(n_rec, dtype=torch.uint8, device=qid.device)
+        else:
+            cols = _host_columns([x.cpu() if hasattr(x, "is_cuda") else x for x in cols])
+            rep = [None if a is None else M.carray(a.cpu() if hasattr(a, "is_cuda") else a, dt) for a, dt in zip(rep, (np.int64, np.int32, np.int32))]
+            fn = ovl.raft_hip_repeat_overlaps_host
+            cls = np.zeros(n_rec, np.uint8)
+        args = _plain(cols) + ((C.c_void_p(0),) * 2 if ts is None else ())
+        n_reads = args[0]
+        _need_equal_lengths(cols[2:], args[2])
+        n_rep = -1 if repeats is None else (M.count(rep[1]) if rep[1] is not None else 0)
+        out = {"cls": cls, "read_touch": np.zeros(n_reads, np.int32), "read_repeat": np.zeros(n_reads, np.int32), "read_flags": np.zeros(n_reads, np.uint8)}
+        sm, err, secs = _OvlSummary(), C.c_int64(-1), C.c_double(0.0)
+        rc = fn(self._ctx, *args, 1 if symmetric else 0, int(min_anchor), n_rep, *[M.ptr(a) for a in rep], *[M.ptr(a) for a in out.values()],
+                C.byref(sm), C.byref(err), C.byref(secs))
+        self._check(rc, err.value)
+        self.last_repeat_overlaps_seconds = secs.value
+        out.update({name: int(getattr(sm, name)) for name, _ in _OvlSummary._fields_})
         return out
 
     def census(self, read_len, qid, qs, qe, tid, ts=None, te=None, symmetric: bool = False) -> dict:

@@ -150,6 +150,15 @@ inline bool parse_low_cov(const char *text, int32_t *low_cov)
     return true;
 }
 
+// --repeat-overlaps A: A (min_anchor of raft_hip_repeat_overlaps_*) is a whole number >= 1 written in digits alone, at most INT32_MAX.
+inline bool parse_min_anchor(const char *text, int32_t *min_anchor)
+{
+    int32_t v = 0;
+    if (!parse_low_cov(text, &v) || v < 1) return false;
+    *min_anchor = v;
+    return true;
+}
+
 // ... a read counts as uncovered when more than this many thousandths of its bases lie in low runs (yacrd's default for "not covered")
 constexpr int32_t kLowUncoveredPermille = 800;
 

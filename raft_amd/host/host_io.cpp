@@ -13,6 +13,7 @@
 //     only and is skipped when it has fewer than 10 fields; numeric fields go through strtol.
 #include "../../include/raft_host.h"
 #include "../../include/raft_host_low.h"
+#include "../../include/raft_host_ovl.h"
 
 #include <emmintrin.h>
 #include <zlib.h>
@@ -1391,6 +1392,43 @@ int raft_host_write_low_coverage(const char *path, int32_t n_reads, const char *
         }
     }
     return t.close() ? RAFT_HOST_OK : RAFT_HOST_ERR_IO;
+}
+
+// The two tables of `raft --repeat-overlaps` (see raft_host_ovl.h): per read, and per record with a side inside a repeat.  Blocks of
+// lines are formatted side by side and written in order (write_ordered).
+int raft_host_write_repeat_overlaps(const char *reads_path, const char *records_path, int32_t n_reads, const char *const *names,
+                                    const int32_t *read_len, const int32_t *read_touch, const int32_t *read_repeat, const uint8_t *read_flags,
+                                    int64_t n_rec, const int32_t *qid, const int32_t *qs, const int32_t *qe, const int32_t *tid, const int32_t *ts,
+                                    const int32_t *te, const uint8_t *cls)
+{
+    if (n_reads < 0 || n_rec < 0 || (n_reads > 0 && !names)) return RAFT_HOST_ERR_ARG;
+    if (reads_path && n_reads > 0 && (!read_len || !read_touch || !read_repeat || !read_flags)) return RAFT_HOST_ERR_ARG;
+    if (records_path && n_rec > 0 && (!qid || !qs || !qe || !tid || !cls || (ts == nullptr) != (te == nullptr))) return RAFT_HOST_ERR_ARG;
+    if (records_path)
+        for (int64_t i = 0; i < n_rec; ++i)
+            if ((cls[i] & 3) && ((uint32_t)qid[i] >= (uint32_t)n_reads || (uint32_t)tid[i] >= (uint32_t)n_reads)) return RAFT_HOST_ERR_ARG;
+    int rc = RAFT_HOST_OK;
+    if (reads_path)
+        rc = write_ordered(reads_path, n_reads, 1 << 12, [](long long) { return 1ll; }, [&](long long r, std::string &o) {
+            o.append(names[r]); o.push_back('\t');
+            put_num(o, read_len[r]); o.push_back('\t'); put_num(o, read_touch[r]); o.push_back('\t'); put_num(o, read_repeat[r]); o.push_back('\t');
+            o.append(!(read_flags[r] & 1) ? "no" : (read_flags[r] & 2) ? "anchored" : "repeat");
+            o.push_back('\n');
+        });
+    if (rc == RAFT_HOST_OK && records_path)
+        rc = write_ordered(records_path, n_rec, 1 << 14, [](long long) { return 1ll; }, [&](long long i, std::string &o) {
+            const unsigned c = cls[i];
+            if (!(c & 3u)) return;
+            o.append(names[qid[i]]); o.push_back('\t'); put_num(o, qs[i]); o.push_back('\t'); put_num(o, qe[i]); o.push_back('\t');
+            o.append(names[tid[i]]); o.push_back('\t');
+            if (ts) { put_num(o, ts[i]); o.push_back('\t'); put_num(o, te[i]); o.push_back('\t'); }
+            else o.append("-\t-\t");
+            o.append((c & 3u) == 3u ? "both" : (c & 1u) ? "query" : "target");
+            o.push_back('\t');
+            o.append((c & 16u) ? "query" : (c & 32u) ? "target" : "-");
+            o.push_back('\n');
+        });
+    return rc;
 }
 
 // split_naive.cpp:10-44: every read is cut into consecutive pieces of split_len bases, no overlaps, written as

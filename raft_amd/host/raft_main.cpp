@@ -15,6 +15,8 @@
 #include "../../include/raft_hip.h"
 #include "../../include/raft_hip_low.h"
 #include "../../include/raft_host_low.h"
+#include "../../include/raft_hip_ovl.h"
+#include "../../include/raft_host_ovl.h"
 #include "../../include/raft_host.h"
 #include "cli_plan.hpp"
 
@@ -45,6 +47,7 @@ struct Params {            // param.hpp:18-31
     bool auto_cov = false;         // -e auto: est_cov is read from the data (a survey pass and its coverage histogram) before the job
     bool read_stats = false;       // --read-stats: PREFIX.read_stats.tsv, the per-read table (raft_hip_read_stats, raft_hip_census_host)
     int32_t low_cov = -1;          // --low-cov C: PREFIX.low_coverage.bed, the runs of windows with coverage <= C (raft_hip_low_coverage); -1: not asked for
+    int32_t min_anchor = 0;        // --repeat-overlaps A: PREFIX.repeat_overlaps.tsv and .records.tsv (raft_hip_repeat_overlaps_host); 0: not asked for
 };
 
 struct Switches {                  // the environment, as read_switches() found it
@@ -94,6 +97,10 @@ struct Job {
     std::vector<int64_t> low_off;
     std::vector<int32_t> low_s, low_e;
     raft_hip_low_summary low_sum{};
+    // --repeat-overlaps: the records' class bytes, the reads' tallies and flags; the query column as tokenised where prepare_input writes over it
+    std::vector<uint8_t> ovl_cls, ovl_flags;
+    std::vector<int32_t> ovl_touch, ovl_repeat, ovl_qid;
+    raft_hip_ovl_summary ovl_sum{};
     // the form the job is handed over in, and what it brought back
     std::unique_ptr<int64_t[]> rec_off;
     int32_t n_runs = 0;
@@ -171,11 +178,13 @@ void parse_options(Job &j, int argc, char *argv[])
     int option;
     // (the short options and their quirks are the reference's; the long options are this program's own)
     static const struct option long_options[] = {{"read-stats", no_argument, nullptr, 1000}, {"low-cov", required_argument, nullptr, 1001},
+                                                 {"repeat-overlaps", required_argument, nullptr, 1002},
                                                  {nullptr, 0, nullptr, 0}};
     while ((option = getopt_long(argc, argv, "r:e:m:l:i:p:f:v:o:", long_options, nullptr)) != -1) {
         switch (option) {
         case 1000: p.read_stats = true; break;
         case 1001: if (!raft_cli::parse_low_cov(optarg, &p.low_cov)) print_help(p); break;
+        case 1002: if (!raft_cli::parse_min_anchor(optarg, &p.min_anchor)) print_help(p); break;
         case 'r': p.reso = atoi(optarg); break;
         case 'e': p.auto_cov = strcmp(optarg, "auto") == 0; p.est_cov = p.auto_cov ? 0 : atoi(optarg); break;
         case 'm': p.cov_mul = std::stod(optarg); break;
@@ -520,6 +529,7 @@ void census(Job &j)
 void prepare_input(Job &j)
 {
     const bool prepare = j.sw.cli_prepare && j.ranks == 0;
+    if (prepare && j.p.min_anchor > 0) j.ovl_qid.assign(j.col[0], j.col[0] + j.n_rec);   // (--repeat-overlaps reads the query ids after the job)
     if (prepare && j.sym && j.n_rec > 0 && !j.sw.no_grouped) {
         j.rec_off.reset(new int64_t[(size_t)4 * ((size_t)j.n_reads + 1)]);
         if (raft_host_group_offsets(j.n_reads, j.n_rec, j.col[0], 4, &j.n_runs, j.rec_off.get()) != RAFT_HOST_OK) j.n_runs = 0;
@@ -605,6 +615,34 @@ void run_engine(Job &j)
     stage(j, "engine+fetch");
 }
 
+// --repeat-overlaps: the tokenised columns against the job's own repeat annotation -- the host arrays long_repeats.txt is written
+// from, so it is the same call whichever way the job ran (one device or several, ranks, -e auto).  Both sides are classified; the
+// reads' tallies follow the job's symmetric flag, as the census does.
+void repeat_overlaps(Job &j)
+{
+    if (j.p.min_anchor <= 0) return;
+    j.ovl_cls.resize((size_t)j.n_rec); j.ovl_flags.resize((size_t)j.n_reads);
+    j.ovl_touch.resize((size_t)j.n_reads); j.ovl_repeat.resize((size_t)j.n_reads);
+    if (!j.ovl_qid.empty()) j.col[0] = j.ovl_qid.data();
+    int64_t bad_index = -1;
+    const int rc = raft_hip_repeat_overlaps_host(j.ctxs[0], j.n_reads, j.rl, j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.col[4], j.col[5], j.sym ? 1 : 0,
+                                                 j.p.min_anchor, j.rep_off[(size_t)j.n_reads], j.rep_off.data(), j.rep_s.get(), j.rep_e.get(),
+                                                 j.ovl_cls.data(), j.ovl_touch.data(), j.ovl_repeat.data(), j.ovl_flags.data(), &j.ovl_sum, &bad_index, nullptr);
+    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
+    stage(j, "repeat_overlaps");
+}
+
+void write_repeat_overlaps(Job &j)
+{
+    const Params &p = j.p;
+    std::vector<const char *> names((size_t)j.n_reads);
+    for (int32_t i = 0; i < j.n_reads; ++i) names[(size_t)i] = raft_host_reads_name(j.reads, i);
+    if (raft_host_write_repeat_overlaps((p.prefix + ".repeat_overlaps.tsv").c_str(), (p.prefix + ".repeat_overlaps.records.tsv").c_str(), j.n_reads,
+                                        names.data(), j.rl, j.ovl_touch.data(), j.ovl_repeat.data(), j.ovl_flags.data(), j.n_rec, j.col[0], j.col[1],
+                                        j.col[2], j.col[3], j.col[4], j.col[5], j.ovl_cls.data()) != RAFT_HOST_OK)
+        die("ERROR, repeat_overlaps(), cannot write output files");
+}
+
 void report(Job &j)
 {
     const raft_hip_summary &s = j.s;
@@ -653,6 +691,7 @@ void write_outputs(Job &j)
     }
     if (p.read_stats) write_read_stats(j);
     if (p.low_cov >= 0) write_low_coverage(j);
+    if (p.min_anchor > 0) write_repeat_overlaps(j);
     stage(j, "write_tables");
     // repeat.hpp:173-178 (total_windows is an int in the reference; identical below 2^31 windows)
     const double cpw = (double)s.total_coverage / (double)s.total_windows;
@@ -679,6 +718,10 @@ void print_totals(Job &j, int argc, char *argv[])
     if (j.p.low_cov >= 0)
         std::cout << "INFO, low_coverage(), low_cov = " << j.p.low_cov << ", runs = " << j.low_sum.n_runs << ", reads with an interior run = "
                   << j.low_sum.reads_interior << ", uncovered reads = " << j.low_sum.reads_uncovered << " of " << j.n_reads << "\n";
+    if (j.p.min_anchor > 0)
+        std::cout << "INFO, repeat_overlaps(), min_anchor = " << j.p.min_anchor << ", records = " << j.ovl_sum.n_records << ", query side in a repeat = "
+                  << j.ovl_sum.q_repeat << ", target side = " << j.ovl_sum.t_repeat << ", both = " << j.ovl_sum.both_repeat << ", contained reads = "
+                  << j.ovl_sum.reads_contained << ", contained only inside repeats = " << j.ovl_sum.reads_repeat_contained << "\n";
     stage(j, "stdout");
     if (j.sw.timing) {
         timespec ts{};
@@ -713,6 +756,7 @@ int main(int argc, char *argv[])
     lock_inputs(job);
     choose_encoding(job);
     run_engine(job);
+    repeat_overlaps(job);
     report(job);
     write_outputs(job);
     print_totals(job, argc, argv);
