@@ -98,6 +98,17 @@ inline bool few_sorted_runs(const int32_t *qid, int64_t n_rec)
 // is not known yet: two.
 inline int byte_width(bool auto_cov, int est_cov) { return auto_cov || est_cov >= 40 ? 2 : 1; }
 
+// The bytes of the coverage array an attempt in `cov_width` writes: one or two per window, or a four-bit step per window.  The
+// array is allocated for the widest of them (Capacities::cov8_bytes); it is page-locked for the first attempt's byte encoding
+// beside the tokenising, and an attempt that needs more than is page-locked registers the array anew (a copy that leaves a
+// registered range is an invalid argument to the runtime; the same copy into memory that is not registered at all is not).
+inline int64_t cov_bytes_needed(int cov_width, int64_t n_win)
+{
+    return cov_width == RAFT_HIP_COV_DELTA4 ? (n_win + 1) / 2 : (n_win + 1) * (int64_t)cov_width;
+}
+
+inline bool cov_range_too_short(int cov_width, int64_t n_win, int64_t bytes_locked) { return cov_bytes_needed(cov_width, n_win) > bytes_locked; }
+
 // What the device buffers are reserved for before the overlaps are tokenised: what a hifiasm-shaped PAF will use.
 inline int reserve_cov_width(bool no_delta4, bool auto_cov, int est_cov) { return no_delta4 ? byte_width(auto_cov, est_cov) : RAFT_HIP_COV_DELTA4; }
 

@@ -84,6 +84,7 @@ struct Job {
     raft_cli::Capacities cap;
     std::vector<int64_t> cov_off, rep_off, frag_off;
     std::unique_ptr<uint8_t[]> cov8;
+    int64_t cov8_locked = 0;                  // the bytes of cov8 that are page-locked (cli_plan.hpp cov_bytes_needed)
     std::unique_ptr<int32_t[]> rep_s, rep_e, fb, fe;
     std::vector<int64_t> exc_i;
     std::vector<int32_t> exc_v;
@@ -109,6 +110,7 @@ struct Job {
     int cov_width = 1;
     raft_hip_summary s{};
     int64_t n_exc = 0;
+    int n_attempts = 0;                       // engine calls of the ladder (run_engine)
     int fasta_rc = RAFT_HOST_OK;
     std::thread bring_up, paf_reader, out_prep, fasta_writer;
 };
@@ -331,7 +333,8 @@ void load_reads(Job &j)
 // Coverage returns in its transfer encoding (a byte per window + the windows at or above 255): a quarter of the
 // int32 array's bytes over PCIe, and the formatter reads it as it is.  They are allocated and page-locked beside
 // the tokenising of the overlaps (pinning untouched pages costs their first touch: 0.1 s for the 2 GB of a human set);
-// page-locking and reserving wait for the contexts and are left out when one of them did not come up.
+// page-locking and reserving wait for the contexts and are left out when one of them did not come up.  The coverage array is
+// page-locked for the byte width of the first attempt; an attempt of the ladder that needs more registers it anew (run_engine).
 void prepare_outputs(Job &j)
 {
     const Params &p = j.p;
@@ -346,7 +349,8 @@ void prepare_outputs(Job &j)
     for (size_t d = 0; d < j.devices.size(); ++d) if (j.create_rc[d] != RAFT_HIP_OK) return;
     pin(j, j.exc_i.data(), j.exc_i.size() * 8); pin(j, j.exc_v.data(), j.exc_v.size() * 4);
     pin(j, j.cov_anchor.data(), j.cov_anchor.size() * 4);
-    pin(j, j.cov8.get(), ((size_t)c.n_win + 1) * raft_cli::byte_width(p.auto_cov, p.est_cov));
+    j.cov8_locked = raft_cli::cov_bytes_needed(raft_cli::byte_width(p.auto_cov, p.est_cov), c.n_win);
+    pin(j, j.cov8.get(), (size_t)j.cov8_locked);
     pin(j, j.fb.get(), ((size_t)c.frag_cap + 1) * 4); pin(j, j.fe.get(), ((size_t)c.frag_cap + 1) * 4);
     pin(j, j.rep_s.get(), ((size_t)c.rep_cap + 1) * 4); pin(j, j.rep_e.get(), ((size_t)c.rep_cap + 1) * 4);
     pin(j, j.cov_off.data(), j.cov_off.size() * 8); pin(j, j.frag_off.data(), j.frag_off.size() * 8); pin(j, j.rep_off.data(), j.rep_off.size() * 8);
@@ -598,6 +602,11 @@ void run_engine(Job &j)
             j.exc_i.resize((size_t)exc_cap); j.exc_v.resize((size_t)exc_cap);
             pin(j, j.exc_i.data(), j.exc_i.size() * 8); pin(j, j.exc_v.data(), j.exc_v.size() * 4);
         }
+        if (raft_cli::cov_range_too_short(j.cov_width, c.n_win, j.cov8_locked)) {   // (a retry in a wider encoding than the array was page-locked for)
+            if (!j.sw.no_pin) (void)raft_hip_host_unregister(j.cov8.get());
+            j.cov8_locked = raft_cli::cov_bytes_needed(j.cov_width, c.n_win);
+            pin(j, j.cov8.get(), (size_t)j.cov8_locked);
+        }
         raft_hip_host_outputs ho{};
         ho.cov_offset = j.cov_off.data(); ho.cov8 = j.cov8.get(); ho.cov8_cap = c.n_win; ho.cov_width = j.cov_width;
         ho.cov_anchor = j.cov_anchor.data(); ho.anchor_cap = (int64_t)j.cov_anchor.size();
@@ -606,6 +615,7 @@ void run_engine(Job &j)
         ho.frag_offset = j.frag_off.data(); ho.frag_begin = j.fb.get(); ho.frag_end = j.fe.get(); ho.frag_cap = c.frag_cap;
         rc = call_engine(j, &ho);
         j.n_exc = ho.n_exc;
+        j.n_attempts = (int)attempt + 1;
         if (raft_cli::ladder_stops(rc, (int)attempt, j.n_exc, exc_cap)) break;
         const raft_cli::Attempt next = raft_cli::next_attempt(j.cov_width, exc_cap, j.n_exc, c.n_win);
         j.cov_width = next.cov_width;
@@ -646,7 +656,7 @@ void write_repeat_overlaps(Job &j)
 void report(Job &j)
 {
     const raft_hip_summary &s = j.s;
-    if (j.sw.timing) fprintf(stderr, "TIMING devices_used %d input %s\n", s.n_devices_used, raft_cli::input_label(j.ranks, j.win != nullptr, j.n_runs, j.sym));
+    if (j.sw.timing) fprintf(stderr, "TIMING devices_used %d input %s attempts %d\n", s.n_devices_used, raft_cli::input_label(j.ranks, j.win != nullptr, j.n_runs, j.sym), j.n_attempts);
     if (j.sw.timing) fprintf(stderr, "TIMING coverage_encoding %s\n", raft_cli::encoding_label(j.cov_width));
     fprintf(stdout, "INFO, Symmetric overlaps %d \n", s.symmetric);            // chop.hpp:189-190
     fprintf(stdout, "INFO, length of alignments  %d()\n", (int)s.n_records);

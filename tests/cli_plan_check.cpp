@@ -284,6 +284,27 @@ int main()
     CHECK(ladder_stops(3, 2, 65535LL, 65536LL) == true, "ladder_stops");
     CHECK(ladder_stops(3, 2, 65536LL, 65536LL) == true, "ladder_stops");
     CHECK(ladder_stops(3, 2, 65537LL, 65536LL) == true, "ladder_stops");
+    // the bytes of the coverage array an attempt writes, and whether the page-locked range holds them: -e below 40 locks
+    // (n_win + 1) bytes beside the tokenising, which holds a first attempt in bytes or four-bit steps and no attempt in two bytes
+    CHECK(cov_bytes_needed(1, 132300LL) == 132301LL, "cov_bytes_needed");
+    CHECK(cov_bytes_needed(2, 132300LL) == 264602LL, "cov_bytes_needed");
+    CHECK(cov_bytes_needed(8, 132300LL) == 66150LL, "cov_bytes_needed");
+    CHECK(cov_bytes_needed(8, 132301LL) == 66151LL, "cov_bytes_needed");
+    CHECK(cov_bytes_needed(1, 0LL) == 1LL && cov_bytes_needed(2, 0LL) == 2LL && cov_bytes_needed(8, 0LL) == 0LL, "cov_bytes_needed");
+    CHECK(cov_bytes_needed(2, 3000000000LL) == 6000000002LL, "cov_bytes_needed beyond 32 bits");
+    for (long long n_win : {0LL, 1LL, 132300LL, 3000000000LL}) {
+        const Capacities c0 = output_capacities(0, nullptr, 50, 2000, 1000);
+        CHECK(c0.cov8_bytes == 2, "an empty job's coverage array");
+        for (int w : {1, 2, 8}) CHECK(cov_bytes_needed(w, n_win) <= (n_win + 1) * 2, "the array as allocated holds width %d of %lld windows", w, n_win);
+        const long long one = cov_bytes_needed(byte_width(false, 39), n_win), two = cov_bytes_needed(byte_width(false, 40), n_win);
+        CHECK(cov_range_too_short(1, n_win, one) == false, "a byte per window in the range locked for it");
+        CHECK(cov_range_too_short(8, n_win, one) == false, "four-bit steps in the range locked for a byte");
+        CHECK(cov_range_too_short(2, n_win, one) == true, "two bytes per window leave the range locked for one");
+        CHECK(cov_range_too_short(2, n_win, two) == false && cov_range_too_short(1, n_win, two) == false && cov_range_too_short(8, n_win, two) == false,
+              "nothing leaves the range locked for two");
+        CHECK(cov_range_too_short(2, n_win, two - 1) == true && cov_range_too_short(1, n_win, one - 1) == true, "one byte short");
+        CHECK(cov_range_too_short(1, n_win, 0) == true && cov_range_too_short(2, n_win, 0) == true, "nothing locked yet");
+    }
     // start time
     CHECK(stat_start_time("4242 (raft) S 4 5 6 7 8 9 10 11 12 13 14 15 16 17 18 19 20 21 2200 23 24 25") == 2200ULL, "stat_start_time");
     CHECK(stat_start_time("4242 (a b) S 4 5 6 7 8 9 10 11 12 13 14 15 16 17 18 19 20 21 2200 23 24 25") == 2200ULL, "stat_start_time");

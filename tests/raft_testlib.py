@@ -1930,3 +1930,192 @@ def tail_shapes(want):
     """Per read, from the oracle's output: index into TAIL_SHAPES, -1 = none of them."""
     n, nf = np.diff(want["rep_offset"]), np.diff(want["frag_offset"])
     return np.where((n == 0) & (nf == 1), 0, np.where((n == 0) & (nf == 3), 1, np.where(n == 1, 2, np.where(n == 5, 3, -1))))
+
+
+# ---- exception-list capacity sets: how MANY windows an encoding lists, on either side of every first size -----------------------------
+# The lattice sets put single values on either side of the encodings' limits; these put a chosen NUMBER K of windows on an
+# encoding's exception list -- one below, at and one above the size the list has when a route first fills it -- so that the
+# comparisons between a count and a capacity (pack.hpp `slot < exc_cap`, engine.hip `n_exc > exc_cap` / `n_exc <= cap`) are each
+# tested where `<` and `<=` differ.  The first sizes, by route (raft_amd/csrc/engine.hip ensure_buffers, pack_coverage; pinned to
+# the source text by tests/test_exc_capacity_cases.py):
+#     a pass that writes the encoding itself        max(4096, B / 64)      B: the windows of the set
+#     an int32 pass encoded afterwards              max(4096, B / 512) for one or two bytes per window, max(4096, B / 64) for four-bit steps
+# Sets are self overlaps sorted by read id on a context with symmetric_mode = 1 (as the lattice sets), reso 50:
+#     widths 1 / 2   "hot" reads with 255 / 65,535 (+ 0..2) records over their whole length -- "short": reads of 64 windows and one
+#                    shorter read for the rest; "long": ONE read of K windows, which the wave kernel cuts into pieces -- between
+#                    "cold" reads of up to 4000 windows with two records each, which fill the set up to B windows.  65,535 records
+#                    on a read make its tiles ones of 2^15 intervals or more: pileup_deep_kernel's, in the same pass.
+#     width 8        (four-bit steps made from an int32 array) K one-window reads, alternately 8 deep and uncovered: every step is
+#                    +-8; then the cold reads.
+# Closed form of the list: flatnonzero(cov >= limit), or flatnonzero(|cov[w] - cov[w-1]| > 7) with cov[-1] = 0, over the closed form
+# of the coverage (the reads' record counts).  A pass that writes four-bit steps ITSELF also lists every tile's first window: no
+# closed form of the data, and no case here -- tests/test_gpu_exc_capacity.py sweeps the read count across the first size instead.
+EXC_CAP_FLOOR = 4096
+EXC_LIMIT = {1: 255, 2: 65535}
+EXC_ROUTES = ("pass", "reencode")
+EXC_RESO = 50
+EXC_COLD_W, EXC_COLD_DEPTH, EXC_HOT_W = 4000, 2, 64
+EXC_B_ARM = 4100                           # cap0 of the sets whose first size follows B: B = 64 * 4100, 512 * 4100
+
+
+def exc_divisor(route, width):
+    """B / divisor is the arm of the first size that follows the set's size; None: no such route (a pass that writes four-bit steps
+    lists more than the data's large steps)."""
+    if route == "pass":
+        return 64 if width in (1, 2) else None
+    return 64 if width == 8 else 512
+
+
+def exc_cap0(route, width, B):
+    return max(EXC_CAP_FLOOR, B // exc_divisor(route, width))
+
+
+def exc_closed_list(cov, width):
+    cov = np.asarray(cov, np.int64)
+    if width == 8:
+        return np.flatnonzero(np.abs(np.diff(np.concatenate([[0], cov]))) > 7)
+    return np.flatnonzero(cov >= EXC_LIMIT[width])
+
+
+def exc_classes(width, K, B):
+    """{(width, route, arm, K - cap0)} of the routes on whose first size a set of B windows with K listed ones sits (|K - cap0| <= 1)."""
+    out = set()
+    for route in EXC_ROUTES:
+        div = exc_divisor(route, width)
+        if div is not None and abs(K - exc_cap0(route, width, B)) <= 1:
+            out.add((width, route, "4096" if B // div < EXC_CAP_FLOOR else f"B/{div}", K - exc_cap0(route, width, B)))
+    return out
+
+
+class ExcCase:
+    """name, p (symmetric_mode = 1), cols (seven columns), width (1, 2; 8: four-bit steps made from int32), geometry, B (windows), K
+    (target count), cov / cov_offset (closed form), expect (closed form of the list: ascending window indices)."""
+
+    def __init__(self, name, p, cols, width, geometry, K, cov_offset, cov):
+        self.name, self.p, self.cols, self.width, self.geometry, self.K = name, p, cols, width, geometry, K
+        self.cov_offset, self.cov = cov_offset, cov
+        self.B = int(cov.size)
+        self.expect = exc_closed_list(cov, width)
+
+    @property
+    def n_reads(self):
+        return int(self.cols[0].size)
+
+    def query_cols(self):
+        return tuple(self.cols[:4]) + (None, None, None)
+
+    def cap0(self, route):
+        return exc_cap0(route, self.width, self.B)
+
+    def classes(self):
+        return exc_classes(self.width, self.K, self.B)
+
+    def oracle(self):
+        want = oracle_run(self.p, *self.cols)
+        want["symmetric"] = 1
+        return want
+
+
+def _exc_build(name, width, geometry, K, W, depth, extra):
+    """Per read: W windows, `depth` records over the whole read, `extra` records over its windows [1, W - 1)."""
+    W, depth, extra = (np.asarray(x, np.int64) for x in (W, depth, extra))
+    assert np.all(W >= 1) and np.all((extra == 0) | (W >= 3))
+    n = W.size
+    rl = (W * EXC_RESO).astype(np.int32)
+    off = np.zeros(n + 1, np.int64)
+    np.cumsum(W, out=off[1:])
+    cnt = depth + extra
+    first = np.zeros(n + 1, np.int64)
+    np.cumsum(cnt, out=first[1:])
+    qid = np.repeat(np.arange(n, dtype=np.int64), cnt)
+    part = np.arange(int(first[-1]), dtype=np.int64) - first[qid] >= depth[qid]
+    qs = np.where(part, EXC_RESO, 0).astype(np.int32)
+    qe = np.where(part, rl[qid].astype(np.int64) - EXC_RESO, rl[qid]).astype(np.int32)
+    qid = qid.astype(np.int32)
+    cov = np.repeat(depth, W)
+    inner = np.ones(int(off[-1]), bool)
+    inner[off[:-1]] = False
+    inner[off[1:] - 1] = False
+    cov = (cov + np.where(inner, np.repeat(extra, W), 0)).astype(np.int32)
+    p = RaftParams(reso=EXC_RESO, est_cov=30, cov_mul=1.0, repeat_length=4 * EXC_RESO, interval_length=20 * EXC_RESO, read_length=40 * EXC_RESO,
+                   overlap_length=0, flanking_length=100, symmetric_mode=1)
+    case = ExcCase(name, p, [rl, qid, qs, qe, qid.copy(), qs.copy(), qe.copy()], width, geometry, K, off, cov)
+    assert case.expect.size == K, (name, case.expect.size, K)
+    return case
+
+
+def _exc_cold(n_windows):
+    """Cold reads that hold exactly n_windows windows."""
+    return [EXC_COLD_W] * (n_windows // EXC_COLD_W) + ([n_windows % EXC_COLD_W] if n_windows % EXC_COLD_W else [])
+
+
+def exc_capacity_case(width, geometry, K, B):
+    """One set: K windows on the list of `width`, B windows in all (B - K of them cold, half before the hot reads and half behind)."""
+    name = f"w{width}/{geometry}/K={K}/B={B}"
+    if width == 8:
+        assert geometry == "steps"
+        hotW, hot_depth, hot_extra = [1] * K, [8 * (1 - i % 2) for i in range(K)], [0] * K
+        before, behind = [], _exc_cold(B - K)
+    else:
+        L = EXC_LIMIT[width]
+        if geometry == "short":
+            hotW = [EXC_HOT_W] * (K // EXC_HOT_W) + ([K % EXC_HOT_W] if K % EXC_HOT_W else [])
+        else:
+            assert geometry == "long"
+            hotW = [K] if K else []
+        hot_depth = [L + i % 3 for i in range(len(hotW))]
+        hot_extra = [2 if w >= 3 else 0 for w in hotW]
+        cold = B - K
+        before, behind = _exc_cold(cold // 2), _exc_cold(cold - cold // 2)
+    W = before + hotW + behind
+    depth = [EXC_COLD_DEPTH] * len(before) + hot_depth + [EXC_COLD_DEPTH] * len(behind)
+    extra = [0] * len(before) + hot_extra + [0] * len(behind)
+    return _exc_build(name, width, geometry, K, W, depth, extra)
+
+
+def exc_capacity_list(which="boundary"):
+    """(width, geometry, K, B) of every set.  "boundary": K = cap0 - 1, cap0, cap0 + 1 where the 4096 arm decides the first size
+    (both routes at once) and where the B arm does (B = 64 * 4100: a pass, and four-bit steps afterwards; B = 512 * 4100: one or two
+    bytes afterwards).  "small": K = 0, 1, 2 (the fetch contract).  The two-byte sets cost the oracle K * 65,535 increments: one
+    geometry each, and the short reads -- 4.2e6 records -- once."""
+    out = []
+    if which == "small":
+        for width in (1, 2, 8):
+            out += [(width, "steps" if width == 8 else "short", K, K + 2 * EXC_COLD_W + 100) for K in (0, 1, 2)]
+        return out
+    for d in (-1, 0, 1):
+        K, KB = EXC_CAP_FLOOR + d, EXC_B_ARM + d
+        for g in ("short", "long"):
+            out += [(1, g, K, K + 4 * EXC_COLD_W), (1, g, KB, 64 * EXC_B_ARM), (1, g, KB, 512 * EXC_B_ARM)]
+        out += [(2, "long", K, K + 4 * EXC_COLD_W), (2, "long", KB, 64 * EXC_B_ARM), (2, "long", KB, 512 * EXC_B_ARM)]
+        out += [(8, "steps", K, K + 4 * EXC_COLD_W), (8, "steps", KB, 64 * EXC_B_ARM)]
+    out.append((2, "short", EXC_CAP_FLOOR + 1, EXC_CAP_FLOOR + 1 + 4 * EXC_COLD_W))
+    return out
+
+
+def exc_case_id(spec):
+    return "w%d-%s-K%d-B%d" % spec
+
+
+def exc_capacity_cases(which="boundary"):
+    """Generator over the built cases (a two-byte set holds up to 4.2e6 records: one at a time)."""
+    for spec in exc_capacity_list(which):
+        yield exc_capacity_case(*spec)
+
+
+def exc_steps_set(n_alt, B):
+    """The width-8 geometry for a pass that writes the steps itself: n_alt one-window reads, alternately 8 deep and uncovered, then cold
+    reads up to B windows.  The list then holds the n_alt large steps AND every tile's first window."""
+    return exc_capacity_case(8, "steps", n_alt, B)
+
+
+def delta4_reference(cov):
+    """The four-bit step encoding of an int32 array with nothing forced: (cov_nib, cov_anchor, exc_index, exc_value)."""
+    cov = np.asarray(cov, np.int64)
+    n = cov.size
+    step = np.diff(np.concatenate([[0], cov]))
+    code = np.where(np.abs(step) <= 7, step + 8, 0).astype(np.uint8)
+    code = np.concatenate([code, np.zeros(n % 2, np.uint8)])
+    xi = np.flatnonzero(np.abs(step) > 7).astype(np.int64)
+    anchor = np.concatenate([[0], cov[D4_BLOCK - 1::D4_BLOCK]])[: (n + D4_BLOCK - 1) // D4_BLOCK].astype(np.int32)
+    return (code[0::2] | (code[1::2] << 4)).astype(np.uint8), anchor, xi, cov[xi].astype(np.int32)

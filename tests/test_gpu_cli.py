@@ -250,12 +250,8 @@ def test_cli_encoding_ladder(tmp_path, name, lens, encoding):
     at 256 -- at or above a byte's limit -- and the list, which starts at max(65536, n_win / 64) = 65536 entries, is too short.
     a_longer_list: 70,000 exceptions among 1.19 M windows, fewer than one in 16: the second attempt keeps the byte and brings a
     list of exactly 70,000.  The files equal the oracle's arrays and, where it is built, the reference binary's files.
-    The rung that leaves the four-bit steps needs some 1e5 large steps in a set: tests/cli_plan_check.cpp covers it, not this.
-    The rung from one byte to two is not a case here because the CLI does not survive it: with reads 0 and 1 of 66,000 bases and
-    three of 100 (132,000 of 132,300 windows on the list, more than one in 16) the second attempt ends in `hipMemcpyAsync ...
-    invalid argument`, exit 1 -- the coverage array was page-locked for one byte per window, and the two-byte copy reaches beyond
-    the registered range (with RAFT_NO_PIN=1 the run gives `coverage_encoding uint16` and the reference's coverage file).  The decision
-    itself is in tests/cli_plan_check.cpp."""
+    The other rungs -- one byte to two, four-bit steps to two bytes or to a longer list, and a list exactly at its first size -- are
+    the cases of tests/test_gpu_cli_ladder.py; the decisions themselves are in tests/cli_plan_check.cpp."""
     import numpy as np
     from raft_testlib import assert_same_result, have_ref_bin, oracle_run, result_from_ref_files, run_ref_binary
     from raft_amd.params import RaftParams
