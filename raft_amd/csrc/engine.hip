@@ -690,6 +690,7 @@ static int fill_pileup_args(raft_hip_ctx *c, PassPlan &P, PileupArgs &pa)
     pa.n_tiles = P.n_tiles; pa.n_reads = P.n_reads;
     pa.reso = c->prm.reso; pa.high_cov = c->high_cov; pa.repeat_length = c->prm.repeat_length; pa.flank = c->prm.flanking_length;
     pa.cov = ow == 4 ? c->cov.as<int32_t>() : nullptr;
+    pa.tile_batch = cov_line_bit(pa.cov);    // (the rest of the word: launch_pileup)
     pa.covp = ow == 4 ? nullptr : c->cov8.p; pa.n_exc = &ctrl->n_exc; pa.exc_cap = c->exc_cap;
     pa.cov_anchor = ow == kCovDelta4 ? c->cov_anchor.as<int32_t>() : nullptr; pa.d4_shift = c->d4_shift;
     if (ow == kCovDelta4) {
@@ -825,7 +826,7 @@ static int launch_pileup(raft_hip_ctx *c, PassPlan &P, PileupArgs &pa)
     hc_mark(P, "ev_pile0");
     const bool win = P.lean || P.bwin;
     int n_waves = (int)std::max<long long>(1, std::min<long long>(wave_grid_waves(win), P.n_tiles));
-    pa.tile_batch = 1;
+    pa.tile_batch = (pa.tile_batch & kCovLineBit) | 1;
     int n_ctr = 8;
 #ifdef RAFT_WAVE_DIAG   // (make DEFS=-DRAFT_WAVE_DIAG: run-time switches for tools/mode_probe.py -- workers, parts of the kernel, counters)
     if (const char *e = getenv("RAFT_WAVE_WAVES")) n_waves = std::max(1, std::min(n_waves, atoi(e)));

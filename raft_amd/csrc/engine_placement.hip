@@ -51,6 +51,7 @@ int placement_trial(raft_hip_ctx *c, hipStream_t st, const PileupArgs &pa, int o
     auto one_run = [&](int32_t *cov_p, hipEvent_t e0, hipEvent_t e1) -> int {
         PileupArgs x = pa;
         x.cov = cov_p;
+        x.tile_batch = (pa.tile_batch & ~kCovLineBit) | cov_line_bit(cov_p);
         HIP_TRY(c, hipMemsetAsync(c->rep_cnt.p, 0, (size_t)std::max(N, 1LL) * 4, st));
         HIP_TRY(c, hipMemsetAsync(c->wave_ctr.p, 0, (size_t)kWaveCounters * kCtrStride * 4, st));
         HIP_TRY(c, hipMemsetAsync(&ctrl->n_deep, 0, 4, st));

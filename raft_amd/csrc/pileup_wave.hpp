@@ -95,7 +95,11 @@ __device__ __forceinline__ int wave_shl1(int v, int last)      // lane l takes l
 // Three processes each, `profiles/r05_store_policy_ab.txt`: ultralong columns 2.65 -> 2.58 ms every time, headline 2.04-2.07 where plain
 // stores gave 2.05-2.22, the pass 1.5 % shorter.  Write-through (`sc1`: the line is dropped from the L2 at once) fetched 8 % less
 // and took 12 % longer; the packed encodings (a quarter / an eighth of the bytes) gain nothing from `nt` and stay plain.
+#ifdef RAFT_W_PLAIN_STORES          // (A/B: the int32 stores without the bit)
+template <int OW> struct CovAux { static constexpr int v = 0; };
+#else
 template <int OW> struct CovAux { static constexpr int v = OW == 4 ? 2 : 0; };
+#endif
 // (the record slots' loads stay plain: marked non-temporal like the coverage stores, the column form ran 2-8 % slower in one process --
 // 2.175 / 2.197 against 2.136 / 2.031 ms, three contexts each, tools/lib_ab.py -- and the window-record form the same, 1.571 / 1.567)
 constexpr int kRecAux = 0;
@@ -121,6 +125,19 @@ __device__ __forceinline__ void wave_tile_loop(WaveSmem<SLOTS> &sm, const TileCu
     if (uni(*(volatile int32_t *)a.err_flags) & (kErrExtra | kErrStop)) { leave_empty(); return; }
     const int n_seg_tiles = (int)a.n_tiles;      // segments (quantum tiles) tile_desc_kernel cut: boundaries cuts[0 .. n_seg_tiles]
     constexpr int CAP = SLOTS - 4;               // windows of a tile: 3 alignment slots + CAP + 1 sentinel
+    // Where a tile's array begins in cov[].  The int32 rows are 1 KiB stores (64 lanes x 16 bytes): begun on a 16-byte boundary a store
+    // covers seven whole 128-byte lines and two partial ones, and the partial line at a row's end is completed only by the next row's
+    // first store, a row of arithmetic later.  With the array begun on a line (32 windows) every full row's store is eight whole lines
+    // -- for the tiles that still fit: (g_lo & 31) + nwin <= SLOTS - 1.  The cut below leaves a tile of several reads one read
+    // shorter where it has to; a single read or a piece of up to CAP windows that does not fit keeps the 4-window origin.  The
+    // packed forms keep it always (delta4's lists depend on where tiles begin; the byte forms are not bound by their stores), and so
+    // does an array that is not itself on a line (kCovLineBit, raft_types.hpp).  -DRAFT_W_ALIGN4: the 4-window origin everywhere, for A/B.
+#ifdef RAFT_W_ALIGN4
+    constexpr int ALIGN = 4;
+#else
+    constexpr int ALIGN = OW == 4 ? 32 : 4;
+#endif
+    const bool on_lines = ALIGN > 4 && (a.tile_batch & kCovLineBit) != 0;
     const unsigned win_m1 = a.div_shift < 0 ? ~0u : 0u;
     const int win_sh = a.div_shift < 0 ? 0 : a.div_shift;
     constexpr unsigned kLimit = OW == 1 ? 255u : 65535u;
@@ -285,7 +302,11 @@ __device__ __forceinline__ void wave_tile_loop(WaveSmem<SLOTS> &sm, const TileCu
         // "belongs to this range": the ballot is a prefix of the lanes, lane 0 -- the tile's first read -- always in it)
         const int cv0 = uni(rd.cv);
         const int rel = rd.cv - cv0;
-        const unsigned long long okm = __ballot(ts.r + lane <= R_end && (unsigned)rel <= (unsigned)CAP && lane < rd.n);
+        // (a line-aligned array has up to 31 slots in front of the tile's first window: the reads behind the first fit behind those, the
+        // first read alone -- entry 1 is its end -- is asked for CAP as ever: it is taken whole, never in pieces, on the origin that holds it)
+        int fit = CAP;
+        if (ALIGN > 4 && on_lines) fit = min(CAP, SLOTS - 1 - (int)(ts.g & (long long)(ALIGN - 1)));
+        const unsigned long long okm = __ballot(ts.r + lane <= R_end && (unsigned)rel <= (unsigned)(lane <= 1 ? CAP : fit) && lane < rd.n);
         int nr = (int)__popcll(okm) - 1;
         int piece = 0, n_pieces = 1, nb_read = 0;
         cur.r_a = ts.r;
@@ -394,7 +415,8 @@ __device__ __forceinline__ void wave_tile_loop(WaveSmem<SLOTS> &sm, const TileCu
         (void)tile_id;
 
         const int r_a = cur.r_a;
-        const long long a0 = cur.g_lo & ~3LL;
+        long long a0 = cur.g_lo & ~3LL;
+        if (ALIGN > 4 && on_lines && (int)(cur.g_lo & (long long)(ALIGN - 1)) + cur.nwin <= SLOTS - 1) a0 = cur.g_lo & ~(long long)(ALIGN - 1);
         const int off0 = (int)(cur.g_lo - a0);
         const int t_end = off0 + cur.nwin;
         const int rows_all = (t_end + 1 + 511) >> 9;

@@ -93,7 +93,7 @@ struct PileupArgs {
     int32_t *err_flags;           // device word, OR of kErr*
     long long *err_index;         // first offending interval index (min)
     int32_t *tile_counter;        // the ranges are handed out through these counters (pileup_wave.hpp next_range; zeroed before the pass)
-    int32_t tile_batch;           // bits 24..28: counters in use - 1; bits 20..23: diagnostic switches (-DRAFT_WAVE_DIAG builds)
+    int32_t tile_batch;           // bits 24..28: counters in use - 1; bits 20..23: diagnostic switches (-DRAFT_WAVE_DIAG builds); bit 29: kCovLineBit
     int32_t piece_w;              // delta4: tile ids below this have slots of their own for the windows they list
     int32_t *slow_counter;        // delta4: the counter those tile ids are drawn from
     // tiles too deep for the wave kernel's 16-bit difference array (pileup_deep.hpp): listed by it, piled up by pileup_deep_kernel
@@ -121,6 +121,10 @@ __host__ __device__ __forceinline__ long long sample_pos(long long j, long long 
     const long long p = j << sh;
     return p < n - 1 ? p : n - 1;
 }
+
+// PileupArgs::tile_batch: cov[] begins on a 128-byte line, so the wave kernel may begin its int32 tile arrays on lines (pileup_wave.hpp ALIGN)
+constexpr int32_t kCovLineBit = 1 << 29;
+inline int32_t cov_line_bit(const void *cov) { return cov && reinterpret_cast<unsigned long long>(cov) % 128u == 0u ? kCovLineBit : 0; }
 
 constexpr int kRunQ = 16; // parked runs per wave and window before falling back to immediate emission
 constexpr int kNone = -1;
