@@ -413,6 +413,12 @@ int  raft_hip_run_multi_windows(raft_hip_ctx *const *ctxs, int32_t n_ctx, int32_
  * raft_host_pack_windows -- every rank of an exchange in the same form); what arrives then has d_qe = NULL and goes to
  * raft_hip_run_device_windows(ctx, got.n_reads, ..., got.n_runs, got.d_rec_offset, (const uint32_t *)got.d_qs, n_bins): half the
  * bytes over xGMI.
+ * The form of an exchange is ONE: raft_hip_exchange_local takes it from the first slice that has records (a slice without records
+ * may hold any pointers, NULL included; no records anywhere: the coordinate form) and returns RAFT_HIP_ERR_PARAM when another
+ * slice with records is in the other form.  raft_hip_exchange cannot look at its peers' pointers: every rank posts sends and
+ * receives by its OWN d_qe, so a rank whose slice is empty must still say which form the exchange has -- in a coordinate-form
+ * exchange it passes a non-NULL d_qe (any device address: nothing is read through it), in a window-form exchange NULL.  A slice
+ * from raft_hip_group_sides does: its two columns are never NULL.
  * The slices' device columns must be complete when the call is made (raft_hip_exchange: on the context's stream, or
  * their producers synchronised; raft_hip_exchange_local: synchronised), and stay untouched until the exchange is done. */
 #define RAFT_HIP_MAX_RUNS 16
@@ -451,16 +457,17 @@ int  raft_hip_exchange_local(raft_hip_ctx *const *ctxs, int32_t world, int32_t n
  * contiguous piece per destination -- and the receiver runs raft_hip_run_device_grouped on what arrives (the sides are
  * already expanded: a grouped pass piles up what it is given).  symmetric != 0: query sides only.
  * The arrays belong to the context and live until its next raft_hip_group_sides or pass of the general bucketing path;
- * the record columns are device arrays, complete when the call is made.  Errors: RAFT_HIP_ERR_READ_ID (an id outside
+ * the record columns are device arrays, complete when the call is made.  out->d_qs / d_qe are never NULL, not even for a slice
+ * without intervals (they say "coordinate form" to the exchange).  Errors: RAFT_HIP_ERR_READ_ID (an id outside
  * [0, n_reads_total): error_index via raft_hip_last_error text), RAFT_HIP_ERR_TOO_LARGE (2^31 intervals or more). */
 int  raft_hip_group_sides(raft_hip_ctx *ctx, int32_t n_reads_total, int64_t n_rec, const int32_t *d_qid, const int32_t *d_qs,
                           const int32_t *d_qe, const int32_t *d_tid, const int32_t *d_ts, const int32_t *d_te, int32_t symmetric,
                           raft_hip_slice *out);
 
 /* ... and the flag such a job needs first: is the pre-split PAF symmetric (chop.hpp:171-184: some record i > 0 is record 0
- * with query and target swapped)?  Record 0 is rank 0's first record; every rank looks for its mirror in its own slice (one
- * kernel over the six columns) and the verdict is the OR over the ranks -- two all-gathers of a few words (RCCL), or host
- * copies between the contexts of one process.  Every rank returns the same *symmetric.  A stream without records is not
+ * with query and target swapped)?  Record 0 is the first record of the first rank whose slice has any (rank 0's, unless the
+ * stream has fewer records than ranks); every rank looks for its mirror in its own slice (one kernel over the six columns) and
+ * the verdict is the OR over the ranks -- two all-gathers of a few words (RCCL), or host copies between the contexts of one process.  Every rank returns the same *symmetric.  A stream without records is not
  * symmetric.  (Replaces raft_amd/dist.py global_symmetric_flag: torch broadcast + all-reduce.) */
 typedef struct raft_hip_records {
     int64_t n_rec;                                       /* records of this rank's slice */
@@ -477,7 +484,8 @@ int  raft_hip_presplit_symmetric_local(raft_hip_ctx *const *ctxs, int32_t world,
  * not); the call uploads the slices, finds the symmetric flag (raft_hip_presplit_symmetric_local), expands and groups every
  * slice's sides (raft_hip_group_sides), routes them to the owners of their reads (raft_hip_exchange_local: contiguous read
  * ranges of equal window counts), runs every rank's grouped pass and writes the ranks' outputs into `out` in read order -- the
- * same arrays, bounds and errors as raft_hip_run_multi; out->cov_width 1 or 2.  ctxs[0]'s parameters apply to all.
+ * same arrays, bounds and errors as raft_hip_run_multi (RAFT_HIP_ERR_READ_ID with summary->error_index = the stream's first record
+ * that names a read outside [0, n_reads)); out->cov_width 1 or 2.  ctxs[0]'s parameters apply to all.
  * One process per GPU: the same steps with raft_hip_presplit_symmetric / raft_hip_exchange over RCCL. */
 int  raft_hip_run_presplit_local(raft_hip_ctx *const *ctxs, int32_t world, int32_t n_reads, const int32_t *read_len, int64_t n_rec,
                                  const int32_t *qid, const int32_t *qs, const int32_t *qe,

@@ -962,6 +962,10 @@ int run_grouped(raft_hip_ctx *c, int32_t n_reads, const int32_t *d_len, int64_t 
                 const uint32_t *d_win)
 {
     if (!c || !d_rec_offset) return RAFT_HIP_ERR_PARAM;
+    if (n_rec > 0 && !d_win && (!d_qs || !d_qe)) {          // (what an exchange of window records hands back goes to raft_hip_run_device_windows)
+        c->last_error = "grouped input: records without both coordinate columns";
+        return RAFT_HIP_ERR_PARAM;
+    }
     if (c->force_bucket && d_qid && c->prm.symmetric_mode == 1)          // (tests, A/B: the counting-sort path needs no offsets)
         return raft_hip_run_device(c, n_reads, d_len, n_rec, d_qid, d_qs, d_qe, nullptr, nullptr, nullptr);
     raft_hip_ctx::PassArgs in{};

@@ -321,6 +321,7 @@ struct raft_hip_ctx {
     DevBuf b_cnt{bufs}, b_off{bufs}, b_rid{bufs, DevBuf::kBig}, b_s{bufs, DevBuf::kBig}, b_e{bufs, DevBuf::kBig};
     DevBuf gs_rid{bufs, DevBuf::kBig}, gs_s{bufs, DevBuf::kBig}, gs_e{bufs, DevBuf::kBig}, gs_off{bufs}, gs_err{bufs};  // raft_hip_group_sides: the slice it hands back (+ its error word)
     std::vector<long long> gs_off_host;
+    long long gs_err_index = -1;      // raft_hip_group_sides: the record (index into the slice) its last RAFT_HIP_ERR_READ_ID named
     // general streams, large inputs: (read id, start | end << 32) per side, before and after the radix sort; long runs of reads without intervals
     DevBuf rs_k0{bufs, DevBuf::kBig}, rs_k1{bufs, DevBuf::kBig}, rs_v0{bufs, DevBuf::kBig}, rs_v1{bufs, DevBuf::kBig}, gaps{bufs};
     DevBuf in_len{bufs};              // staging for raft_hip_run_host: the read lengths (the columns: in_col below)

@@ -93,10 +93,12 @@ int raft_hip_group_sides(raft_hip_ctx *c, int32_t n_reads_total, int64_t n_rec, 
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     c->gs_off_host.assign((size_t)N1, 0);
+    c->gs_err_index = -1;
     long long n_valid = 0;
+    // (at least one entry: a slice without intervals still hands back two columns, which is what says "coordinate form" to an exchange)
+    HIP_TRY(c, c->gs_s.ensure((size_t)std::max(n_ent, 1LL) * 4)); HIP_TRY(c, c->gs_e.ensure((size_t)std::max(n_ent, 1LL) * 4));
     if (n_ent > 0) {
         HIP_TRY(c, c->gs_rid.ensure((size_t)n_ent * 4));
-        HIP_TRY(c, c->gs_s.ensure((size_t)n_ent * 4)); HIP_TRY(c, c->gs_e.ensure((size_t)n_ent * 4));
         HIP_TRY(c, c->gs_off.ensure((size_t)N1 * 8));
         HIP_TRY(c, c->gs_err.ensure(16));
         HIP_TRY(c, hipMemsetAsync(c->gs_err.p, 0, 8, st));
@@ -114,6 +116,7 @@ int raft_hip_group_sides(raft_hip_ctx *c, int32_t n_reads_total, int64_t n_rec, 
         HIP_TRY(c, hipMemcpyAsync(err, c->gs_err.p, 16, hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));
         if ((int32_t)err[0] & kErrReadId) {
+            c->gs_err_index = err[1];
             c->last_error = "raft_hip_group_sides: record " + std::to_string(err[1]) + " names a read outside [0, n_reads_total)";
             return RAFT_HIP_ERR_READ_ID;
         }
@@ -165,10 +168,12 @@ int raft_hip_presplit_symmetric_local(raft_hip_ctx *const *ctxs, int32_t world, 
     if (!ctxs || world < 1 || !slices || !symmetric) return RAFT_HIP_ERR_PARAM;
     for (int p = 0; p < world; ++p) if (!ctxs[p] || !records_ok(slices[p])) return RAFT_HIP_ERR_PARAM;
     *symmetric = 0;
-    if (slices[0].n_rec == 0) return RAFT_HIP_OK;          // (record 0 is rank 0's first record: without it nothing can mirror it)
+    int first = -1;                                          // record 0 is the first record of the first slice that has any
+    for (int p = 0; p < world && first < 0; ++p) if (slices[p].n_rec > 0) first = p;
+    if (first < 0) return RAFT_HIP_OK;                       // (a stream without records: nothing can mirror anything)
     FirstRecord f{};
-    { const int rc = read_first_record(ctxs[0], slices[0], &f); if (rc != RAFT_HIP_OK) return rc; }
-    for (int p = 0; p < world; ++p) { const int rc = queue_mirror_search(ctxs[p], slices[p], f, p == 0); if (rc != RAFT_HIP_OK) return rc; }
+    { const int rc = read_first_record(ctxs[first], slices[first], &f); if (rc != RAFT_HIP_OK) return rc; }
+    for (int p = 0; p < world; ++p) { const int rc = queue_mirror_search(ctxs[p], slices[p], f, p == first); if (rc != RAFT_HIP_OK) return rc; }
     for (int p = 0; p < world; ++p) {
         raft_hip_ctx *c = ctxs[p];
         int32_t found = 0;
@@ -195,7 +200,7 @@ int raft_hip_presplit_symmetric(raft_hip_ctx *c, void *comm_v, int32_t rank, int
     std::vector<long long> rows(kRow * (size_t)world, 0);
     long long *my = rows.data() + kRow * (size_t)rank;
     my[7] = ok_mine ? 1 : 0;
-    if (ok_mine && mine->n_rec > 0 && rank == 0) {
+    if (ok_mine && mine->n_rec > 0) {                       // (record 0 is the first record of the first rank that has any: every such rank offers its own)
         FirstRecord f{};
         const int rc = read_first_record(c, *mine, &f);
         if (rc != RAFT_HIP_OK) my[7] = 0;
@@ -215,14 +220,16 @@ int raft_hip_presplit_symmetric(raft_hip_ctx *c, void *comm_v, int32_t rank, int
     bool all_ok = true;
     for (int p = 0; p < world; ++p) all_ok = all_ok && rows[kRow * (size_t)p + 7] == 1;
     FirstRecord f{};
-    const bool have_first = all_ok && rows[6] == 1;
-    for (int k = 0; k < 6; ++k) f.v[k] = (int32_t)rows[(size_t)k];
+    int first = -1;
+    for (int p = 0; p < world && first < 0; ++p) if (rows[kRow * (size_t)p + 6] == 1) first = p;
+    const bool have_first = all_ok && first >= 0;
+    if (have_first) for (int k = 0; k < 6; ++k) f.v[k] = (int32_t)rows[kRow * (size_t)first + (size_t)k];
     // second round: one word per rank
     std::vector<long long> flags((size_t)world, 0);
     if (have_first) {
         // (whatever fails here is announced in the second round, not returned: the other ranks are on their way into that collective)
         int32_t found = 0;
-        const bool ok = queue_mirror_search(c, *mine, f, rank == 0) == RAFT_HIP_OK &&
+        const bool ok = queue_mirror_search(c, *mine, f, rank == first) == RAFT_HIP_OK &&
                         hipMemcpyAsync(&found, c->gs_err.p, 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
         if (!ok) (void)hipGetLastError();
         flags[(size_t)rank] = ok ? (found ? 1 : 0) : -1;
@@ -276,8 +283,16 @@ int raft_hip_exchange_local(raft_hip_ctx *const *ctxs, int32_t world, int32_t n_
         if (bounds[p] < 0 || bounds[p] > bounds[p + 1] || bounds[p + 1] > n_reads_total) return RAFT_HIP_ERR_PARAM;
     }
     if (bounds[0] != 0 || bounds[world] != n_reads_total) return RAFT_HIP_ERR_PARAM;
-    const bool one_col = slices[0].d_qe == nullptr;       // window records: one column travels
-    for (int p = 1; p < world; ++p) if ((slices[p].d_qe == nullptr) != one_col && slices[p].n_rec > 0 && slices[0].n_rec > 0) return RAFT_HIP_ERR_PARAM;
+    // window records: one column travels.  The form is the first non-empty slice's (an empty slice's pointers say nothing; no
+    // records at all: coordinates), and every other non-empty slice must have it.
+    int form_of = -1;
+    for (int p = 0; p < world && form_of < 0; ++p) if (slices[p].n_rec > 0) form_of = p;
+    const bool one_col = form_of >= 0 && slices[form_of].d_qe == nullptr;
+    for (int p = 0; p < world; ++p)
+        if (slices[p].n_rec > 0 && (slices[p].d_qe == nullptr) != one_col) {
+            ctxs[0]->last_error = "raft_hip_exchange_local: rank " + std::to_string(p) + "'s slice is not in the form of rank " + std::to_string(form_of) + "'s (coordinates / window records)";
+            return RAFT_HIP_ERR_PARAM;
+        }
     for (int g = 0; g < world; ++g) {
         raft_hip_ctx *c = ctxs[g];
         const long long b0 = bounds[g], b1 = bounds[g + 1], n1 = b1 - b0 + 1;
@@ -553,7 +568,15 @@ int raft_hip_run_presplit_local(raft_hip_ctx *const *ctxs, int32_t world, int32_
         return raft_hip_group_sides(ctxs[r], n_reads, q.n_rec, q.d_qid, q.d_qs, q.d_qe, q.d_tid, q.d_ts, q.d_te, sym, &slices[(size_t)r]);
     });
     if (rc != RAFT_HIP_OK) {
-        if (summary) { memset(summary, 0, sizeof *summary); summary->error_index = -1; }
+        if (summary) {
+            memset(summary, 0, sizeof *summary); summary->error_index = -1;
+            // (the first rank that failed holds the stream's first offending record: the slices are consecutive)
+            for (int r = 0; r < world; ++r)
+                if (rcs[(size_t)r] != RAFT_HIP_OK) {
+                    if (rcs[(size_t)r] == RAFT_HIP_ERR_READ_ID && ctxs[r]->gs_err_index >= 0) summary->error_index = n_rec * r / world + ctxs[r]->gs_err_index;
+                    break;
+                }
+        }
         return rc;
     }
     // 4. ONE exchange step

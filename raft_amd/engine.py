@@ -510,7 +510,9 @@ class Engine:
         self._check(self._lib.raft_hip_group_sides(self._ctx, n_reads_total, int(qid.numel()), *ptr, 1 if symmetric else 0, C.byref(out)))
         n = int(out.n_rec)
         off = np.ctypeslib.as_array(C.cast(out.rec_offset, C.POINTER(C.c_int64)), shape=(1, n_reads_total + 1)).copy()
-        return Slice(off, *[_view(self, p, n, "<i4", torch.int32) for p in (out.d_qs, out.d_qe)])
+        sl = Slice(off, *[_view(self, p, n, "<i4", torch.int32) for p in (out.d_qs, out.d_qe)])
+        sl.ptrs = (int(out.d_qs or 0), int(out.d_qe or 0))   # (the context's columns as they are: not NULL, not even without intervals)
+        return sl
 
     def use_torch_stream(self):
         import torch
@@ -912,13 +914,15 @@ class Slice:
             raise ValueError("Slice: rec_offset must be [n_runs (1..4), n_reads_total + 1]")
         _need_int32_cuda("Slice needs", (qs, qe))
         self.qs, self.qe = qs, qe
+        self.ptrs = None                                      # group_sides: where the context's columns lie (an empty tensor has no address)
         self.d_off = None
         if device_offsets:
             import torch
             self.d_off = torch.as_tensor(self.off).to(qs.device)
 
     def c(self) -> "_Slice":
-        return _Slice(int(self.qs.numel()), int(self.off.shape[0]), self.off.ctypes.data, M.address(self.qs), M.address(self.qe), M.address(self.d_off))
+        d_qs, d_qe = self.ptrs or (M.address(self.qs), M.address(self.qe))
+        return _Slice(int(self.qs.numel()), int(self.off.shape[0]), self.off.ctypes.data, d_qs, d_qe, M.address(self.d_off))
 
 
 def _received_views(eng, r: "_Received") -> dict:

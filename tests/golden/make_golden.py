@@ -78,6 +78,14 @@ def micro_cases():
     cases["g4"] = (fa, paf, ["-e", "1", "-m", "1.3", "-r", "50", "-p", "100", "-l", "200", "-f", "10"])
     # G5: the -v fallthrough renames the outputs (main.cpp:51-55): prefix becomes "20"
     cases["g5_vprefix"] = (cases["g2"][0], cases["g2"][1], ["-e", "2", "-r", "50", "-p", "100", "-l", "200", "-f", "30", "-v", "20"])
+    # G6 / G7: fewer records than ranks (tests/test_gpu_presplit_edges.py runs them with RAFT_RANKS=3 and 8): two reads, one overlap
+    # and its mirror -- symmetric, one interval per read -- and the same PAF with the mirror dropped -- not symmetric, the target side
+    # is piled up too
+    fa = f">r0\n{seq_of(1234)}\n>r1\n{seq_of(900, 1)}\n"
+    paf = paf_line("r0", 1234, 300, 900, "+", "r1", 900, 0, 600) + paf_line("r1", 900, 0, 600, "+", "r0", 1234, 300, 900)
+    args = ["-e", "1", "-m", "1.0", "-r", "50", "-p", "100", "-l", "200", "-f", "30", "-v", "20", "-o", "raft"]
+    cases["g6_mirrored_pair"] = (fa, paf, args)
+    cases["g7_half_pair"] = (fa, paf.split("\n")[0] + "\n", args)
     return cases
 
 

@@ -198,7 +198,10 @@ def test_non_symmetric_presplit_group_sides_then_exchange_equals_oracle(world, s
     assert e.value.code == engine.ERR_READ_ID
     empty = [torch.empty(0, dtype=torch.int32, device="cuda:0")] * 6
     sl0 = engs[0].group_sides(o.n_reads, *empty, symmetric=False)
-    assert sl0.qs.numel() == 0 and not sl0.off.any()
+    # nothing in, nothing out -- in the coordinate form all the same: an empty slice's two columns are real addresses (what says
+    # "coordinates" to an exchange; tests/test_gpu_presplit_edges.py has the fresh context)
+    assert sl0.qs.numel() == 0 and sl0.qe.numel() == 0 and sl0.off.shape == (1, o.n_reads + 1) and not sl0.off.any()
+    assert sl0.ptrs[0] and sl0.ptrs[1] and sl0.c().d_qs and sl0.c().d_qe and sl0.c().n_rec == 0
     for e_ in engs:
         e_.close()
 

@@ -78,7 +78,7 @@ def _params_from_args(args):
     return p
 
 
-@pytest.mark.parametrize("name", ["g1", "g2", "g4", "g5_vprefix"])
+@pytest.mark.parametrize("name", ["g1", "g2", "g4", "g5_vprefix", "g6_mirrored_pair", "g7_half_pair"])
 def test_oracle_micro_vectors(name):
     d = os.path.join(GOLDEN, "micro", name)
     meta = MAN["micro"][name]
