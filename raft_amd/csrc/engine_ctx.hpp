@@ -380,6 +380,13 @@ struct raft_hip_ctx {
     DevBuf oc_digest{bufs}, oc_tally{bufs}, oc_touch{bufs}, oc_repeat{bufs}, oc_flagw{bufs}, oc_flags{bufs}, oc_ctl{bufs}, oc_cls{bufs};
     DevBuf oc_len{bufs}, oc_rep_off{bufs}, oc_rep_s{bufs}, oc_rep_e{bufs};
     DevBuf oc_col[6] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
+    // raft_hip_frag_overlaps_* (frag_ovl_lib.hip, libraft_hip_frag.so; plain allocations, as oc_*): the digest of every read's rows and of its runs,
+    // the reads' whole-spanned flag words and contained rows, the difference slots (n_frag + 1), per row touch / span / contained / repeat bases,
+    // the scan's partial sums, the control words; staging of the host form (lengths, columns, the table, the repeat arrays)
+    DevBuf fo_digest{bufs}, fo_rep_digest{bufs}, fo_whole{bufs}, fo_read{bufs}, fo_slot{bufs}, fo_scan{bufs}, fo_ctl{bufs};
+    DevBuf fo_out[4] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
+    DevBuf fo_len{bufs}, fo_tab_off{bufs}, fo_tab_b{bufs}, fo_tab_e{bufs}, fo_rep_off{bufs}, fo_rep_s{bufs}, fo_rep_e{bufs};
+    DevBuf fo_col[6] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
     // raft_hip_census_*: counts and flag words per read, the flags as bytes, {first bad record, reads with a flag}; staging of the host form
     DevBuf cen_cnt{bufs}, cen_flags{bufs}, cen_out{bufs}, cen_ctl{bufs}, cen_len{bufs};
     DevBuf cen_col[6] = {DevBuf{bufs, DevBuf::kBig}, DevBuf{bufs, DevBuf::kBig}, DevBuf{bufs, DevBuf::kBig},

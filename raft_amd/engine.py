@@ -82,6 +82,15 @@ class _OvlSummary(C.Structure):
                                          "reads_contained", "reads_repeat_contained")]
 
 
+class _FragTable(C.Structure):      # raft_hip_frag_table and raft_hip_frag_repeats: a count and the three arrays of a CSR table
+    _fields_ = [("n", C.c_int64), ("offset", C.c_void_p), ("first", C.c_void_p), ("second", C.c_void_p)]
+
+
+class _FragSummary(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_records", "n_fragments", "frags_untouched", "frags_spanned", "frags_contained", "frags_contained_repeat",
+                                         "reads_whole_spanned", "reads_any_contained", "reads_all_contained")]
+
+
 class _Outputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("cov_offset", "cov", "rep_offset", "rep_s", "rep_e", "cut_offset", "cuts",
                                           "frag_offset", "frag_read", "frag_begin", "frag_end")]
@@ -169,6 +178,14 @@ OVL_ABI = {
     "raft_hip_ovl_abi": (C.c_int, []),
     "raft_hip_repeat_overlaps_device": (C.c_int, _OVL_CALL),
     "raft_hip_repeat_overlaps_host": (C.c_int, _OVL_CALL),
+}
+
+# ... and those of include/raft_hip_frag.h (libraft_hip_frag.so): load_frag_library declares these
+_FRAG_CALL = [_vp, _i32, _vp, _P(_Records), _i32, _P(_FragTable), _P(_FragTable), _vp, _vp, _vp, _vp, _vp, _P(_FragSummary), _P(_i64), _P(_f64)]
+FRAG_ABI = {
+    "raft_hip_frag_abi": (C.c_int, []),
+    "raft_hip_frag_overlaps_device": (C.c_int, _FRAG_CALL),
+    "raft_hip_frag_overlaps_host": (C.c_int, _FRAG_CALL),
 }
 
 
@@ -281,6 +298,28 @@ def load_ovl_library() -> C.CDLL:
             raise RuntimeError(f"{p} was built beside ABI {lib.raft_hip_ovl_abi()}, libraft_hip.so is ABI {main.raft_hip_abi_version()}")
         _ovl_lib = lib
     return _ovl_lib
+
+
+_frag_lib = None
+
+
+def load_frag_library() -> C.CDLL:
+    """Loads libraft_hip_frag.so (behind libraft_hip.so, whose contexts it takes) and declares every entry point of
+    include/raft_hip_frag.h; the two must have been built beside each other."""
+    global _frag_lib
+    if _frag_lib is None:
+        main = load_library()
+        p = os.path.join(os.path.dirname(_LIB_PATH), "libraft_hip_frag.so")
+        if not os.path.exists(p):
+            raise RuntimeError(f"{p} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(p)
+        for name, (restype, argtypes) in FRAG_ABI.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        if lib.raft_hip_frag_abi() != main.raft_hip_abi_version():
+            raise RuntimeError(f"{p} was built beside ABI {lib.raft_hip_frag_abi()}, libraft_hip.so is ABI {main.raft_hip_abi_version()}")
+        _frag_lib = lib
+    return _frag_lib
 
 
 def _cparams(p: RaftParams) -> _Params:
@@ -851,6 +890,69 @@ class Engine:
         self._check(rc, err.value)
         self.last_repeat_overlaps_seconds = secs.value
         out.update({name: int(getattr(sm, name)) for name, _ in _OvlSummary._fields_})
+        return out
+
+    # -- which fragments stay contained ------------------------------------------------------
+    last_fragment_overlaps_seconds = 0.0   # device time of the launches of the last fragment_overlaps()
+
+    def fragment_overlaps(self, read_len, qid, qs, qe, tid, ts, te, symmetric: bool = False, fragments=None, repeats=None) -> dict:
+        """raft_hip_frag_overlaps_device / _host (libraft_hip_frag.so): the record stream joined with a fragment table -- per fragment
+        ``frag_touch``, ``frag_span``, ``frag_contained`` (int32: the overlap sides that touch the row, span it end to end, and span it
+        with the partner's side inside one fragment of the partner) and ``frag_repeat`` (its bases inside the read's repeats), per read
+        ``read_contained`` (int32 numpy: its rows with frag_contained > 0), and the summary's counts.  Sides are counted as the census
+        counts them under ``symmetric``; all six columns are needed either way.  The columns are int32 torch tensors on this engine's
+        device (the per-fragment arrays are then tensors there; ``fragments`` and ``repeats`` must be tensors too) or numpy arrays
+        (staged by the library).  ``fragments``: None = the rows of this context's finished pass, else (frag_offset int64
+        [n_reads + 1], frag_begin, frag_end int32).  ``repeats``: None = the annotation of this context's finished pass, () = none
+        (frag_repeat is 0), else (rep_offset int64 [n_reads + 1], rep_s, rep_e int32)."""
+        cols = [read_len, qid, qs, qe, tid, ts, te]
+        if any(x is None for x in cols):
+            raise ValueError("fragment_overlaps needs read_len, qid, qs, qe, tid, ts, te")
+        tab = [None, None, None] if fragments is None else list(fragments)
+        rep = [None, None, None] if repeats is None or len(repeats) == 0 else list(repeats)
+        if len(tab) != 3 or len(rep) != 3:
+            raise ValueError("fragments is (frag_offset, frag_begin, frag_end), repeats is (rep_offset, rep_s, rep_e)")
+        frag = load_frag_library()
+        on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in cols)
+        if on_device:
+            import torch
+            _need_int32_cuda("fragment_overlaps needs", cols + tab[1:] + rep[1:])
+            for o in (tab[0], rep[0]):
+                if o is not None and (o.dtype != torch.int64 or not o.is_cuda or not o.is_contiguous()):
+                    raise TypeError("fragment_overlaps needs frag_offset and rep_offset as contiguous int64 CUDA tensors")
+            self.use_torch_stream()
+            fn = frag.raft_hip_frag_overlaps_device
+        else:
+            host = lambda a: a.cpu() if hasattr(a, "is_cuda") else a
+            cols = _host_columns([host(x) for x in cols])
+            tab, rep = ([None if a is None else M.carray(host(a), dt) for a, dt in zip(t, (np.int64, np.int32, np.int32))] for t in (tab, rep))
+            fn = frag.raft_hip_frag_overlaps_host
+        n_reads, n_rec = M.count(cols[0]), M.count(cols[1])
+        _need_equal_lengths(cols[2:], n_rec)
+        for t, what in ((tab, "fragments"), (rep, "repeats")):       # (the library is told no lengths: what it will read must be there)
+            if any(a is not None for a in t) and (any(a is None for a in t) or M.count(t[0]) != n_reads + 1 or M.count(t[1]) != M.count(t[2])):
+                raise ValueError(f"{what} is (offsets [n_reads + 1], two arrays of one length)")
+        if fragments is None:
+            n_frag = -1
+            last = getattr(self, "summary", None)
+            rows = int(last.n_fragments) if last is not None else 0      # (what the outputs need; the library checks the state)
+        else:
+            n_frag = rows = M.count(tab[1]) if tab[1] is not None else 0
+        n_rep = -1 if repeats is None else (M.count(rep[1]) if rep[1] is not None else 0)
+        names = ("frag_touch", "frag_span", "frag_contained", "frag_repeat")
+        if on_device:
+            out = {k: torch.zeros(rows, dtype=torch.int32, device=qid.device) for k in names}
+        else:
+            out = {k: np.zeros(rows, np.int32) for k in names}
+        out["read_contained"] = np.zeros(n_reads, np.int32)
+        records = _Records(n_rec, *[M.address(c) for c in cols[1:]])
+        table, annotation = _FragTable(n_frag, *[M.address(a) for a in tab]), _FragTable(n_rep, *[M.address(a) for a in rep])
+        sm, err, secs = _FragSummary(), C.c_int64(-1), C.c_double(0.0)
+        rc = fn(self._ctx, n_reads, M.ptr(cols[0]), C.byref(records), 1 if symmetric else 0, C.byref(table), C.byref(annotation),
+                *[M.ptr(a) for a in out.values()], C.byref(sm), C.byref(err), C.byref(secs))
+        self._check(rc, err.value)
+        self.last_fragment_overlaps_seconds = secs.value
+        out.update({name: int(getattr(sm, name)) for name, _ in _FragSummary._fields_})
         return out
 
     def census(self, read_len, qid, qs, qe, tid, ts=None, te=None, symmetric: bool = False) -> dict:

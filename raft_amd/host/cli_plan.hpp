@@ -170,6 +170,21 @@ inline bool parse_min_anchor(const char *text, int32_t *min_anchor)
     return true;
 }
 
+// The query column is written over by the window records prepare_input makes; the options that read the ids after the job keep a copy.
+inline bool keeps_query_ids(bool prepare, int32_t min_anchor, bool fragment_overlaps)
+{
+    return prepare && (min_anchor > 0 || fragment_overlaps);
+}
+
+// --fragment-overlaps: the option's stdout line, the last one, from raft_hip_frag_summary's counts
+inline std::string fragment_overlaps_line(int64_t fragments, int64_t spanned, int64_t contained, int64_t contained_repeat, int64_t reads_whole,
+                                          int64_t reads_all, int32_t n_reads)
+{
+    return "INFO, fragment_overlaps(), fragments = " + std::to_string(fragments) + ", spanned = " + std::to_string(spanned) + ", contained = " +
+           std::to_string(contained) + ", contained with repeat = " + std::to_string(contained_repeat) + ", reads spanned whole = " +
+           std::to_string(reads_whole) + ", reads with every fragment contained = " + std::to_string(reads_all) + " of " + std::to_string(n_reads);
+}
+
 // ... a read counts as uncovered when more than this many thousandths of its bases lie in low runs (yacrd's default for "not covered")
 constexpr int32_t kLowUncoveredPermille = 800;
 

@@ -14,6 +14,7 @@
 #include "../../include/raft_host.h"
 #include "../../include/raft_host_low.h"
 #include "../../include/raft_host_ovl.h"
+#include "../../include/raft_host_frag.h"
 
 #include <emmintrin.h>
 #include <zlib.h>
@@ -1429,6 +1430,28 @@ int raft_host_write_repeat_overlaps(const char *reads_path, const char *records_
             o.push_back('\n');
         });
     return rc;
+}
+
+// The table of `raft --fragment-overlaps` (see raft_host_frag.h): one line per fragment row.  Blocks of reads (weighed by their rows) are
+// formatted side by side and written in order (write_ordered).
+int raft_host_write_fragments(const char *path, int32_t n_reads, const char *const *names, const int64_t *frag_offset, const int32_t *frag_begin,
+                              const int32_t *frag_end, const int32_t *frag_touch, const int32_t *frag_span, const int32_t *frag_contained,
+                              const int32_t *frag_repeat)
+{
+    if (!path || n_reads < 0 || !frag_offset || frag_offset[0] != 0 || (n_reads > 0 && !names)) return RAFT_HOST_ERR_ARG;
+    for (int32_t r = 0; r < n_reads; ++r)
+        if (frag_offset[r + 1] < frag_offset[r]) return RAFT_HOST_ERR_ARG;
+    if (frag_offset[n_reads] > 0 && (!frag_begin || !frag_end || !frag_touch || !frag_span || !frag_contained || !frag_repeat)) return RAFT_HOST_ERR_ARG;
+    return write_ordered(path, n_reads, 1 << 12, [&](long long r) { return (long long)(frag_offset[r + 1] - frag_offset[r]) + 1; },
+                         [&](long long r, std::string &o) {
+                             for (int64_t k = frag_offset[r]; k < frag_offset[r + 1]; ++k) {
+                                 put_num(o, k + 1); o.push_back('\t'); o.append(names[r]);
+                                 for (const int32_t *col : {frag_begin, frag_end, frag_touch, frag_span, frag_contained, frag_repeat}) {
+                                     o.push_back('\t'); put_num(o, col[k]);
+                                 }
+                                 o.push_back('\n');
+                             }
+                         });
 }
 
 // split_naive.cpp:10-44: every read is cut into consecutive pieces of split_len bases, no overlaps, written as

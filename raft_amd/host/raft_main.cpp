@@ -17,6 +17,8 @@
 #include "../../include/raft_host_low.h"
 #include "../../include/raft_hip_ovl.h"
 #include "../../include/raft_host_ovl.h"
+#include "../../include/raft_hip_frag.h"
+#include "../../include/raft_host_frag.h"
 #include "../../include/raft_host.h"
 #include "cli_plan.hpp"
 
@@ -47,6 +49,7 @@ struct Params {            // param.hpp:18-31
     bool auto_cov = false;         // -e auto: est_cov is read from the data (a survey pass and its coverage histogram) before the job
     bool read_stats = false;       // --read-stats: PREFIX.read_stats.tsv, the per-read table (raft_hip_read_stats, raft_hip_census_host)
     int32_t low_cov = -1;          // --low-cov C: PREFIX.low_coverage.bed, the runs of windows with coverage <= C (raft_hip_low_coverage); -1: not asked for
+    bool fragment_overlaps = false;   // --fragment-overlaps: PREFIX.fragments.tsv, the fragments against the overlaps (raft_hip_frag_overlaps_host)
     int32_t min_anchor = 0;        // --repeat-overlaps A: PREFIX.repeat_overlaps.tsv and .records.tsv (raft_hip_repeat_overlaps_host); 0: not asked for
 };
 
@@ -102,6 +105,9 @@ struct Job {
     std::vector<uint8_t> ovl_cls, ovl_flags;
     std::vector<int32_t> ovl_touch, ovl_repeat, ovl_qid;
     raft_hip_ovl_summary ovl_sum{};
+    // --fragment-overlaps: per fragment the sides that touch, span and contain it, its bases inside repeats
+    std::vector<int32_t> frag_touch, frag_span, frag_contained, frag_repeat;
+    raft_hip_frag_summary frag_sum{};
     // the form the job is handed over in, and what it brought back
     std::unique_ptr<int64_t[]> rec_off;
     int32_t n_runs = 0;
@@ -180,13 +186,14 @@ void parse_options(Job &j, int argc, char *argv[])
     int option;
     // (the short options and their quirks are the reference's; the long options are this program's own)
     static const struct option long_options[] = {{"read-stats", no_argument, nullptr, 1000}, {"low-cov", required_argument, nullptr, 1001},
-                                                 {"repeat-overlaps", required_argument, nullptr, 1002},
+                                                 {"repeat-overlaps", required_argument, nullptr, 1002}, {"fragment-overlaps", no_argument, nullptr, 1003},
                                                  {nullptr, 0, nullptr, 0}};
     while ((option = getopt_long(argc, argv, "r:e:m:l:i:p:f:v:o:", long_options, nullptr)) != -1) {
         switch (option) {
         case 1000: p.read_stats = true; break;
         case 1001: if (!raft_cli::parse_low_cov(optarg, &p.low_cov)) print_help(p); break;
         case 1002: if (!raft_cli::parse_min_anchor(optarg, &p.min_anchor)) print_help(p); break;
+        case 1003: p.fragment_overlaps = true; break;
         case 'r': p.reso = atoi(optarg); break;
         case 'e': p.auto_cov = strcmp(optarg, "auto") == 0; p.est_cov = p.auto_cov ? 0 : atoi(optarg); break;
         case 'm': p.cov_mul = std::stod(optarg); break;
@@ -533,7 +540,7 @@ void census(Job &j)
 void prepare_input(Job &j)
 {
     const bool prepare = j.sw.cli_prepare && j.ranks == 0;
-    if (prepare && j.p.min_anchor > 0) j.ovl_qid.assign(j.col[0], j.col[0] + j.n_rec);   // (--repeat-overlaps reads the query ids after the job)
+    if (raft_cli::keeps_query_ids(prepare, j.p.min_anchor, j.p.fragment_overlaps)) j.ovl_qid.assign(j.col[0], j.col[0] + j.n_rec);   // (--repeat-overlaps and --fragment-overlaps read the query ids after the job)
     if (prepare && j.sym && j.n_rec > 0 && !j.sw.no_grouped) {
         j.rec_off.reset(new int64_t[(size_t)4 * ((size_t)j.n_reads + 1)]);
         if (raft_host_group_offsets(j.n_reads, j.n_rec, j.col[0], 4, &j.n_runs, j.rec_off.get()) != RAFT_HOST_OK) j.n_runs = 0;
@@ -642,6 +649,34 @@ void repeat_overlaps(Job &j)
     stage(j, "repeat_overlaps");
 }
 
+// --fragment-overlaps: the tokenised columns against the job's own fragment rows and repeat annotation -- the host arrays reads.fasta and
+// long_repeats.txt are written from, so it is the same call whichever way the job ran (one device or several, ranks, -e auto): the
+// whole-job arrays go to the first context.  Sides are counted under the job's symmetric flag, as the census counts them.
+void fragment_overlaps(Job &j)
+{
+    if (!j.p.fragment_overlaps) return;
+    const int64_t n_frag = j.frag_off[(size_t)j.n_reads];
+    for (std::vector<int32_t> *v : {&j.frag_touch, &j.frag_span, &j.frag_contained, &j.frag_repeat}) v->resize((size_t)n_frag);
+    if (!j.ovl_qid.empty()) j.col[0] = j.ovl_qid.data();
+    const raft_hip_records rec{j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.col[4], j.col[5]};
+    const raft_hip_frag_table table{n_frag, j.frag_off.data(), j.fb.get(), j.fe.get()};
+    const raft_hip_frag_repeats repeats{j.rep_off[(size_t)j.n_reads], j.rep_off.data(), j.rep_s.get(), j.rep_e.get()};
+    int64_t bad_index = -1;
+    const int rc = raft_hip_frag_overlaps_host(j.ctxs[0], j.n_reads, j.rl, &rec, j.sym ? 1 : 0, &table, &repeats, j.frag_touch.data(), j.frag_span.data(),
+                                               j.frag_contained.data(), j.frag_repeat.data(), nullptr, &j.frag_sum, &bad_index, nullptr);
+    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
+    stage(j, "fragment_overlaps");
+}
+
+void write_fragment_overlaps(Job &j)
+{
+    std::vector<const char *> names((size_t)j.n_reads);
+    for (int32_t i = 0; i < j.n_reads; ++i) names[(size_t)i] = raft_host_reads_name(j.reads, i);
+    if (raft_host_write_fragments((j.p.prefix + ".fragments.tsv").c_str(), j.n_reads, names.data(), j.frag_off.data(), j.fb.get(), j.fe.get(),
+                                  j.frag_touch.data(), j.frag_span.data(), j.frag_contained.data(), j.frag_repeat.data()) != RAFT_HOST_OK)
+        die("ERROR, fragment_overlaps(), cannot write output files");
+}
+
 void write_repeat_overlaps(Job &j)
 {
     const Params &p = j.p;
@@ -702,6 +737,7 @@ void write_outputs(Job &j)
     if (p.read_stats) write_read_stats(j);
     if (p.low_cov >= 0) write_low_coverage(j);
     if (p.min_anchor > 0) write_repeat_overlaps(j);
+    if (p.fragment_overlaps) write_fragment_overlaps(j);
     stage(j, "write_tables");
     // repeat.hpp:173-178 (total_windows is an int in the reference; identical below 2^31 windows)
     const double cpw = (double)s.total_coverage / (double)s.total_windows;
@@ -732,6 +768,10 @@ void print_totals(Job &j, int argc, char *argv[])
         std::cout << "INFO, repeat_overlaps(), min_anchor = " << j.p.min_anchor << ", records = " << j.ovl_sum.n_records << ", query side in a repeat = "
                   << j.ovl_sum.q_repeat << ", target side = " << j.ovl_sum.t_repeat << ", both = " << j.ovl_sum.both_repeat << ", contained reads = "
                   << j.ovl_sum.reads_contained << ", contained only inside repeats = " << j.ovl_sum.reads_repeat_contained << "\n";
+    if (j.p.fragment_overlaps)
+        std::cout << raft_cli::fragment_overlaps_line(j.frag_sum.n_fragments, j.frag_sum.frags_spanned, j.frag_sum.frags_contained,
+                                                      j.frag_sum.frags_contained_repeat, j.frag_sum.reads_whole_spanned, j.frag_sum.reads_all_contained,
+                                                      j.n_reads) << "\n";
     stage(j, "stdout");
     if (j.sw.timing) {
         timespec ts{};
@@ -767,6 +807,7 @@ int main(int argc, char *argv[])
     choose_encoding(job);
     run_engine(job);
     repeat_overlaps(job);
+    fragment_overlaps(job);
     report(job);
     write_outputs(job);
     print_totals(job, argc, argv);

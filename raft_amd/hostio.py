@@ -57,6 +57,10 @@ LOW_ABI = {
 OVL_ABI = {
     "raft_host_write_repeat_overlaps": (C.c_int, [_str, _str, _i32, _P(_str), _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+# ... and of include/raft_host_frag.h
+FRAG_ABI = {
+    "raft_host_write_fragments": (C.c_int, [_str, _i32, _P(_str), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
 
 
 class HostError(RuntimeError):
@@ -75,7 +79,7 @@ def load_library():
         if not os.path.exists(_LIB_PATH):
             raise RuntimeError(f"{_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         lib = C.CDLL(_LIB_PATH)
-        for name, (restype, argtypes) in list(ABI.items()) + list(LOW_ABI.items()) + list(OVL_ABI.items()):
+        for name, (restype, argtypes) in list(ABI.items()) + list(LOW_ABI.items()) + list(OVL_ABI.items()) + list(FRAG_ABI.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
