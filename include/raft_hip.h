@@ -365,7 +365,9 @@ int  raft_hip_run_pipelined(raft_hip_ctx *ctx, int32_t n_reads, const int32_t *r
  * embarrassingly across the 8 GPUs of one node"; SURVEY.md §8(e) host-routed mode, no collective): the host cuts the
  * reads into consecutive ranges of equal record counts, context d gets the d-th group of ranges and runs the chunked
  * pipeline on it with its own upload / download streams, all devices at once; outputs land in the caller's arrays in read
- * order exactly as from one device.  ctxs[0]'s parameters and tuning apply to all.  Contexts are made with
+ * order exactly as from one device.  ctxs[0]'s parameters and tuning apply to all for the duration of the call: when it
+ * returns -- with or without an error, from the chunked pipeline as from the host-routed path -- every other context has
+ * the parameters it had before (its tuning stays that of ctxs[0]), and holds no pass if it took part.  Contexts are made with
  * raft_hip_create(device_ids[d], ...) -- one call per device instead of SURVEY §8(b)'s create(device_ids[], n_dev): a
  * context IS one device + its streams and buffers, and two contexts may share a device (how the single-GPU tests drive
  * this path).  rep_cap / frag_cap must reach the bounds stated above (each device writes at its bound and the gaps are

@@ -561,6 +561,7 @@ struct PipelinePlan {
     std::vector<DeviceJob> jobs;
     std::vector<std::unique_ptr<DeriveRing>> rings;
     std::vector<ChunkResult> res;
+    std::vector<std::unique_ptr<SetupGuard>> lent;   // the other contexts under the first one's parameters: their own come back with the call
     // Exceptions (windows at or above the encoding's limit) have no useful bound per device -- one device may hold all the
     // repeat-rich reads -- so every chunk takes its room from ONE cursor over the caller's list; chunks of different
     // devices interleave there and are put into read order when all are done.  A chunk that no longer fits still counts:
@@ -697,7 +698,7 @@ int place_jobs(PipelinePlan &P)
     return RAFT_HIP_OK;
 }
 
-// parameters of the first context for all, the lanes; then the caller's capacities against what the placement needs
+// parameters of the first context for all (until the call returns), the lanes; then the caller's capacities against what the placement needs
 int prepare_contexts(PipelinePlan &P)
 {
     raft_hip_ctx *c = P.c;
@@ -705,8 +706,8 @@ int prepare_contexts(PipelinePlan &P)
     for (int d = 0; d < P.n_job; ++d) {
         raft_hip_ctx *jc = P.jobs[(size_t)d].c;
         if (d > 0) {
-            const int rc0 = raft_hip_set_params(jc, &c->prm);
-            if (rc0 != RAFT_HIP_OK) return rc0;
+            // (as the routed path does; a pass of its own that the context holds is dropped by drain_and_collect, once lanes have run)
+            P.lent.push_back(std::make_unique<SetupGuard>(jc, &c->prm, jc->out_width, true));
             jc->tile_q = c->tile_q;
         }
         const int rc = prepare_lanes(jc);
