@@ -387,6 +387,16 @@ struct raft_hip_ctx {
     DevBuf fo_out[4] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
     DevBuf fo_len{bufs}, fo_tab_off{bufs}, fo_tab_b{bufs}, fo_tab_e{bufs}, fo_rep_off{bufs}, fo_rep_s{bufs}, fo_rep_e{bufs};
     DevBuf fo_col[6] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
+    // raft_hip_repeat_stats_* (repeat_stats_lib.hip, libraft_hip_rst.so; plain allocations, as fo_*; rst_ and not rs_: raft_hip_read_stats and the
+    // radix sort hold those names): the digest of every read's runs, the read of every run, the counter slots, the control words; per run touch /
+    // span / inside, windows / min / max / high windows, the coverage sum, the flag bytes; the coverage decoded to int32 and delta4's escape flags
+    // for a pass that holds no int32 array; staging of the host form (lengths, columns, the repeat arrays)
+    DevBuf rst_digest{bufs}, rst_run_read{bufs}, rst_slot{bufs}, rst_ctl{bufs}, rst_sum{bufs}, rst_flags{bufs};
+    DevBuf rst_cnt[3] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
+    DevBuf rst_win[4] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
+    DevBuf rst_cov{bufs}, rst_abs{bufs};
+    DevBuf rst_len{bufs}, rst_rep_off{bufs}, rst_rep_s{bufs}, rst_rep_e{bufs};
+    DevBuf rst_col[6] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
     // raft_hip_census_*: counts and flag words per read, the flags as bytes, {first bad record, reads with a flag}; staging of the host form
     DevBuf cen_cnt{bufs}, cen_flags{bufs}, cen_out{bufs}, cen_ctl{bufs}, cen_len{bufs};
     DevBuf cen_col[6] = {DevBuf{bufs, DevBuf::kBig}, DevBuf{bufs, DevBuf::kBig}, DevBuf{bufs, DevBuf::kBig},

@@ -91,6 +91,11 @@ class _FragSummary(C.Structure):
                                          "reads_whole_spanned", "reads_any_contained", "reads_all_contained")]
 
 
+class _RstSummary(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_runs", "runs_empty", "runs_interior", "runs_touched", "runs_spanned", "interior_spanned",
+                                         "sides_touch", "sides_span", "sides_inside", "windows", "cov_sum")]
+
+
 class _Outputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("cov_offset", "cov", "rep_offset", "rep_s", "rep_e", "cut_offset", "cuts",
                                           "frag_offset", "frag_read", "frag_begin", "frag_end")]
@@ -187,6 +192,15 @@ FRAG_ABI = {
     "raft_hip_frag_overlaps_device": (C.c_int, _FRAG_CALL),
     "raft_hip_frag_overlaps_host": (C.c_int, _FRAG_CALL),
 }
+
+# ... and those of include/raft_hip_rst.h (libraft_hip_rst.so): load_rst_library declares these
+_RST_CALL = [_vp, _i32, _vp, _P(_Records), _i32, _i64, _vp, _vp, _vp, _i32] + [_vp] * 9 + [_P(_RstSummary), _P(_i64), _P(_f64)]
+RST_ABI = {
+    "raft_hip_rst_abi": (C.c_int, []),
+    "raft_hip_repeat_stats_device": (C.c_int, _RST_CALL),
+    "raft_hip_repeat_stats_host": (C.c_int, _RST_CALL),
+}
+RST_EMPTY, RST_AT_START, RST_AT_END = 1, 2, 4
 
 
 @dataclass
@@ -320,6 +334,28 @@ def load_frag_library() -> C.CDLL:
             raise RuntimeError(f"{p} was built beside ABI {lib.raft_hip_frag_abi()}, libraft_hip.so is ABI {main.raft_hip_abi_version()}")
         _frag_lib = lib
     return _frag_lib
+
+
+_rst_lib = None
+
+
+def load_rst_library() -> C.CDLL:
+    """Loads libraft_hip_rst.so (behind libraft_hip.so, whose contexts it takes) and declares every entry point of
+    include/raft_hip_rst.h; the two must have been built beside each other."""
+    global _rst_lib
+    if _rst_lib is None:
+        main = load_library()
+        p = os.path.join(os.path.dirname(_LIB_PATH), "libraft_hip_rst.so")
+        if not os.path.exists(p):
+            raise RuntimeError(f"{p} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(p)
+        for name, (restype, argtypes) in RST_ABI.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        if lib.raft_hip_rst_abi() != main.raft_hip_abi_version():
+            raise RuntimeError(f"{p} was built beside ABI {lib.raft_hip_rst_abi()}, libraft_hip.so is ABI {main.raft_hip_abi_version()}")
+        _rst_lib = lib
+    return _rst_lib
 
 
 def _cparams(p: RaftParams) -> _Params:
@@ -953,6 +989,75 @@ class Engine:
         self._check(rc, err.value)
         self.last_fragment_overlaps_seconds = secs.value
         out.update({name: int(getattr(sm, name)) for name, _ in _FragSummary._fields_})
+        return out
+
+    # -- one row per repeat run ----------------------------------------------------------------
+    last_repeat_stats_seconds = 0.0   # device time of the launches of the last repeat_stats()
+    RUN_COUNTS = ("run_touch", "run_span", "run_inside")
+    RUN_COVERAGE = ("run_windows", "run_cov_min", "run_cov_max", "run_high", "run_cov_sum")
+
+    def repeat_stats(self, read_len, qid=None, qs=None, qe=None, tid=None, ts=None, te=None, *, symmetric: bool = False, repeats=None,
+                     threshold=None) -> dict:
+        """raft_hip_repeat_stats_device / _host (libraft_hip_rst.so): one row per repeat run -- ``run_touch``, ``run_span``,
+        ``run_inside`` (int32: the overlap sides that reach into the run, cover it end to end, lie wholly inside it; sides counted as
+        the census counts them under ``symmetric``), ``run_windows``, ``run_cov_min``, ``run_cov_max``, ``run_high`` (int32) and
+        ``run_cov_sum`` (int64) over the run's windows of the finished pass's coverage (``run_high``: windows with coverage >=
+        ``threshold``), ``run_flags`` (uint8: RST_EMPTY | RST_AT_START | RST_AT_END; 0 = interior), and the summary's counts.  All
+        arrays are numpy.  ``threshold``: None = the context's high_cov = int(est_cov * cov_mul), 0 = no coverage part (the five
+        coverage arrays are then None).  The columns are int32 torch tensors on this engine's device (``repeats`` must be tensors
+        too) or numpy arrays (staged by the library); qid .. te all None = no records; ts / te may be None when ``symmetric``.
+        ``repeats``: None = the annotation of this context's finished pass, else (rep_offset int64 [n_reads + 1], rep_s, rep_e int32)."""
+        if read_len is None:
+            raise ValueError("repeat_stats needs read_len")
+        rec = [qid, qs, qe, tid, ts, te]
+        have = qid is not None
+        if have and (any(x is None for x in rec[:4]) or (ts is None) != (te is None) or (not symmetric and ts is None)):
+            raise ValueError("repeat_stats needs qid, qs, qe, tid (and ts, te unless symmetric), or no record column at all")
+        if not have and any(x is not None for x in rec):
+            raise ValueError("repeat_stats needs qid, qs, qe, tid (and ts, te unless symmetric), or no record column at all")
+        if threshold is None:
+            threshold = int(self.params.est_cov * self.params.cov_mul)
+        rep = [None, None, None] if repeats is None else list(repeats)
+        if len(rep) != 3:
+            raise ValueError("repeats is (rep_offset, rep_s, rep_e)")
+        rst = load_rst_library()
+        cols = [read_len] + [x for x in rec if x is not None]
+        on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in cols)
+        if on_device:
+            import torch
+            _need_int32_cuda("repeat_stats needs", cols + rep[1:])
+            if rep[0] is not None and (rep[0].dtype != torch.int64 or not rep[0].is_cuda or not rep[0].is_contiguous()):
+                raise TypeError("repeat_stats needs rep_offset as a contiguous int64 CUDA tensor")
+            self.use_torch_stream()
+            fn = rst.raft_hip_repeat_stats_device
+        else:
+            host = lambda a: a.cpu() if hasattr(a, "is_cuda") else a
+            cols = _host_columns([host(x) for x in cols])
+            rep = [None if a is None else M.carray(host(a), dt) for a, dt in zip(rep, (np.int64, np.int32, np.int32))]
+            fn = rst.raft_hip_repeat_stats_host
+        n_reads = M.count(cols[0])
+        n_rec = M.count(cols[1]) if have else 0
+        _need_equal_lengths(cols[1:], n_rec)
+        if any(a is not None for a in rep) and (rep[0] is None or (rep[1] is None) != (rep[2] is None) or M.count(rep[0]) != n_reads + 1
+                                                or (rep[1] is not None and M.count(rep[1]) != M.count(rep[2]))):
+            raise ValueError("repeats is (offsets [n_reads + 1], two arrays of one length)")   # (the library is told no lengths)
+        if repeats is None:
+            n_rep = -1
+            last = getattr(self, "summary", None)
+            rows = int(last.n_repeats) if last is not None else 0        # (what the outputs need; the library checks the state)
+        else:
+            n_rep = rows = M.count(rep[1]) if rep[1] is not None else 0
+        out = {k: np.zeros(rows, np.int32) for k in self.RUN_COUNTS}
+        out.update({k: (np.zeros(rows, np.int64 if k == "run_cov_sum" else np.int32) if threshold != 0 else None) for k in self.RUN_COVERAGE})
+        out["run_flags"] = np.zeros(rows, np.uint8)
+        fields = cols[1:] + [None] * (7 - len(cols))
+        records = _Records(n_rec, *[M.address(c) for c in fields])
+        sm, err, secs = _RstSummary(), C.c_int64(-1), C.c_double(0.0)
+        rc = fn(self._ctx, n_reads, M.ptr(cols[0]), C.byref(records) if have else None, 1 if symmetric else 0, n_rep, *[M.ptr(a) for a in rep],
+                int(threshold), *[M.ptr(a) for a in out.values()], C.byref(sm), C.byref(err), C.byref(secs))
+        self._check(rc, err.value)
+        self.last_repeat_stats_seconds = secs.value
+        out.update({name: int(getattr(sm, name)) for name, _ in _RstSummary._fields_})
         return out
 
     def census(self, read_len, qid, qs, qe, tid, ts=None, te=None, symmetric: bool = False) -> dict:

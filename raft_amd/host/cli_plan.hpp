@@ -185,6 +185,31 @@ inline std::string fragment_overlaps_line(int64_t fragments, int64_t spanned, in
            std::to_string(reads_whole) + ", reads with every fragment contained = " + std::to_string(reads_all) + " of " + std::to_string(n_reads);
 }
 
+// --repeat-stats: the table needs coverage and annotation under the job's final parameters in one finished one-piece pass -- the survey's
+// recipe.  The options that make the survey run:
+inline bool survey_needed(bool auto_cov, bool read_stats, int32_t low_cov, bool repeat_stats)
+{
+    return auto_cov || read_stats || low_cov >= 0 || repeat_stats;
+}
+
+// ... with -e N the survey pass is that pass already; with -e auto it ran under a placeholder, and one more runs under the estimate
+inline bool repeat_stats_second_pass(bool auto_cov, bool repeat_stats) { return auto_cov && repeat_stats; }
+
+// ... the threshold of its high windows: the job's high_cov (repeat.hpp:89-90), at least 1
+inline int32_t repeat_stats_threshold(int est_cov, double cov_mul)
+{
+    const int32_t high_cov = (int32_t)(est_cov * cov_mul);
+    return high_cov > 1 ? high_cov : 1;
+}
+
+// ... its stdout line, behind the line of --fragment-overlaps, from raft_hip_rst_summary's counts
+inline std::string repeat_stats_line(int64_t runs, int64_t interior, int64_t spanned, int64_t interior_spanned, int64_t touched, int64_t sides_inside)
+{
+    return "INFO, repeat_stats(), repeats = " + std::to_string(runs) + ", interior = " + std::to_string(interior) + ", spanned = " +
+           std::to_string(spanned) + ", interior spanned = " + std::to_string(interior_spanned) + ", untouched = " + std::to_string(runs - touched) +
+           ", sides inside a repeat = " + std::to_string(sides_inside);
+}
+
 // ... a read counts as uncovered when more than this many thousandths of its bases lie in low runs (yacrd's default for "not covered")
 constexpr int32_t kLowUncoveredPermille = 800;
 

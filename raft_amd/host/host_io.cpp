@@ -15,6 +15,7 @@
 #include "../../include/raft_host_low.h"
 #include "../../include/raft_host_ovl.h"
 #include "../../include/raft_host_frag.h"
+#include "../../include/raft_host_rst.h"
 
 #include <emmintrin.h>
 #include <zlib.h>
@@ -1447,6 +1448,34 @@ int raft_host_write_fragments(const char *path, int32_t n_reads, const char *con
                              for (int64_t k = frag_offset[r]; k < frag_offset[r + 1]; ++k) {
                                  put_num(o, k + 1); o.push_back('\t'); o.append(names[r]);
                                  for (const int32_t *col : {frag_begin, frag_end, frag_touch, frag_span, frag_contained, frag_repeat}) {
+                                     o.push_back('\t'); put_num(o, col[k]);
+                                 }
+                                 o.push_back('\n');
+                             }
+                         });
+}
+
+// The table of `raft --repeat-stats` (see raft_host_rst.h): one line per repeat run.  Blocks of reads (weighed by their runs) are formatted
+// side by side and written in order (write_ordered).
+int raft_host_write_repeat_stats(const char *path, int32_t n_reads, const char *const *names, const int64_t *rep_offset, const int32_t *rep_s,
+                                 const int32_t *rep_e, const uint8_t *run_flags, const int32_t *run_windows, const int64_t *run_cov_sum,
+                                 const int32_t *run_cov_min, const int32_t *run_cov_max, const int32_t *run_high, const int32_t *run_touch,
+                                 const int32_t *run_span, const int32_t *run_inside)
+{
+    if (!path || n_reads < 0 || !rep_offset || rep_offset[0] != 0 || (n_reads > 0 && !names)) return RAFT_HOST_ERR_ARG;
+    for (int32_t r = 0; r < n_reads; ++r)
+        if (rep_offset[r + 1] < rep_offset[r]) return RAFT_HOST_ERR_ARG;
+    if (rep_offset[n_reads] > 0 && (!rep_s || !rep_e || !run_flags || !run_windows || !run_cov_sum || !run_cov_min || !run_cov_max || !run_high ||
+                                    !run_touch || !run_span || !run_inside))
+        return RAFT_HOST_ERR_ARG;
+    return write_ordered(path, n_reads, 1 << 12, [&](long long r) { return (long long)(rep_offset[r + 1] - rep_offset[r]) + 1; },
+                         [&](long long r, std::string &o) {
+                             for (int64_t k = rep_offset[r]; k < rep_offset[r + 1]; ++k) {
+                                 const unsigned f = run_flags[k];
+                                 o.append(names[r]); o.push_back('\t'); put_num(o, rep_s[k]); o.push_back('\t'); put_num(o, rep_e[k]); o.push_back('\t');
+                                 o.append((f & 1u) ? "empty" : (f & 6u) == 6u ? "whole" : (f & 2u) ? "head" : (f & 4u) ? "tail" : "interior");
+                                 o.push_back('\t'); put_num(o, run_windows[k]); o.push_back('\t'); put_num(o, run_cov_sum[k]);
+                                 for (const int32_t *col : {run_cov_min, run_cov_max, run_high, run_touch, run_span, run_inside}) {
                                      o.push_back('\t'); put_num(o, col[k]);
                                  }
                                  o.push_back('\n');

@@ -19,6 +19,8 @@
 #include "../../include/raft_host_ovl.h"
 #include "../../include/raft_hip_frag.h"
 #include "../../include/raft_host_frag.h"
+#include "../../include/raft_hip_rst.h"
+#include "../../include/raft_host_rst.h"
 #include "../../include/raft_host.h"
 #include "cli_plan.hpp"
 
@@ -50,6 +52,7 @@ struct Params {            // param.hpp:18-31
     bool read_stats = false;       // --read-stats: PREFIX.read_stats.tsv, the per-read table (raft_hip_read_stats, raft_hip_census_host)
     int32_t low_cov = -1;          // --low-cov C: PREFIX.low_coverage.bed, the runs of windows with coverage <= C (raft_hip_low_coverage); -1: not asked for
     bool fragment_overlaps = false;   // --fragment-overlaps: PREFIX.fragments.tsv, the fragments against the overlaps (raft_hip_frag_overlaps_host)
+    bool repeat_stats = false;     // --repeat-stats: PREFIX.long_repeats.stats.tsv, one line per repeat run (raft_hip_repeat_stats_host)
     int32_t min_anchor = 0;        // --repeat-overlaps A: PREFIX.repeat_overlaps.tsv and .records.tsv (raft_hip_repeat_overlaps_host); 0: not asked for
 };
 
@@ -108,6 +111,12 @@ struct Job {
     // --fragment-overlaps: per fragment the sides that touch, span and contain it, its bases inside repeats
     std::vector<int32_t> frag_touch, frag_span, frag_contained, frag_repeat;
     raft_hip_frag_summary frag_sum{};
+    // --repeat-stats: per repeat run of the stats pass the sides that touch, span and lie inside it, its coverage, its flags
+    std::vector<int32_t> rst_touch, rst_span, rst_inside, rst_windows, rst_min, rst_max, rst_high;
+    std::vector<int64_t> rst_cov_sum;
+    std::vector<uint8_t> rst_flags;
+    raft_hip_rst_summary rst_sum{};
+    bool rst_done = false;
     // the form the job is handed over in, and what it brought back
     std::unique_ptr<int64_t[]> rec_off;
     int32_t n_runs = 0;
@@ -187,6 +196,7 @@ void parse_options(Job &j, int argc, char *argv[])
     // (the short options and their quirks are the reference's; the long options are this program's own)
     static const struct option long_options[] = {{"read-stats", no_argument, nullptr, 1000}, {"low-cov", required_argument, nullptr, 1001},
                                                  {"repeat-overlaps", required_argument, nullptr, 1002}, {"fragment-overlaps", no_argument, nullptr, 1003},
+                                                 {"repeat-stats", no_argument, nullptr, 1004},
                                                  {nullptr, 0, nullptr, 0}};
     while ((option = getopt_long(argc, argv, "r:e:m:l:i:p:f:v:o:", long_options, nullptr)) != -1) {
         switch (option) {
@@ -194,6 +204,7 @@ void parse_options(Job &j, int argc, char *argv[])
         case 1001: if (!raft_cli::parse_low_cov(optarg, &p.low_cov)) print_help(p); break;
         case 1002: if (!raft_cli::parse_min_anchor(optarg, &p.min_anchor)) print_help(p); break;
         case 1003: p.fragment_overlaps = true; break;
+        case 1004: p.repeat_stats = true; break;
         case 'r': p.reso = atoi(optarg); break;
         case 'e': p.auto_cov = strcmp(optarg, "auto") == 0; p.est_cov = p.auto_cov ? 0 : atoi(optarg); break;
         case 'm': p.cov_mul = std::stod(optarg); break;
@@ -465,6 +476,20 @@ int survey_low_coverage(Job &j, int64_t n_win)
     return rc;
 }
 
+// --repeat-stats: one row per repeat run of the pass that has just run -- its own annotation, its coverage, the tokenised columns
+// under the job's symmetric flag as census() hands them over --, before prepare_input() writes window records over the query column.
+int survey_repeat_stats(Job &j, int est_cov, int64_t n_repeats, int64_t *bad_index)
+{
+    for (std::vector<int32_t> *v : {&j.rst_touch, &j.rst_span, &j.rst_inside, &j.rst_windows, &j.rst_min, &j.rst_max, &j.rst_high}) v->resize((size_t)n_repeats);
+    j.rst_cov_sum.resize((size_t)n_repeats); j.rst_flags.resize((size_t)n_repeats);
+    const raft_hip_records rec{j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.sym ? nullptr : j.col[4], j.sym ? nullptr : j.col[5]};
+    j.rst_done = true;
+    return raft_hip_repeat_stats_host(j.ctxs[0], j.n_reads, j.rl, &rec, j.sym ? 1 : 0, -1, nullptr, nullptr, nullptr,
+                                      raft_cli::repeat_stats_threshold(est_cov, j.p.cov_mul), j.rst_touch.data(), j.rst_span.data(), j.rst_inside.data(),
+                                      j.rst_windows.data(), j.rst_min.data(), j.rst_max.data(), j.rst_high.data(), j.rst_cov_sum.data(), j.rst_flags.data(),
+                                      &j.rst_sum, bad_index, nullptr);
+}
+
 // -e auto: the survey.  cov[] does not depend on est_cov, so one one-piece pass on the first context under the placeholder holds
 // the number -e stands for: its coverage histogram is made on the device (32 KiB come back instead of cov[]) and the estimate
 // read from it (raft_hip.h).  The pass writes two-byte codes and no cut points -- nothing of it is fetched --, and its
@@ -475,10 +500,13 @@ int survey_low_coverage(Job &j, int64_t n_win)
 // --read-stats: the per-read table.  Its coverage summary (raft_hip_read_stats) is taken from the same survey pass, right behind
 // the histogram; without -e auto one such pass -- the survey's recipe -- runs here for it.  The job itself runs as it does
 // without the option.  --low-cov: the same, for the low-coverage runs (raft_hip_low_coverage), behind the two.
+// --repeat-stats: the table of the repeat runs (raft_hip_repeat_stats_host) needs coverage AND annotation under the job's final est_cov:
+// with -e N the survey pass is that pass; with -e auto one more pass of the same recipe runs under the estimate (one more upload of
+// the columns), and the table is taken right behind it.
 void survey(Job &j)
 {
     Params &p = j.p;
-    if (!p.auto_cov && !p.read_stats && p.low_cov < 0) return;
+    if (!raft_cli::survey_needed(p.auto_cov, p.read_stats, p.low_cov, p.repeat_stats)) return;
     raft_hip_ctx *ctx = j.ctxs[0];
     SurveySettings settings{ctx, j.sw.context_width};
     raft_hip_params sp = j.hp;
@@ -501,6 +529,20 @@ void survey(Job &j)
     }
     if (rc == RAFT_HIP_OK && p.read_stats && est.est_cov > 0) rc = survey_read_stats(j, est.est_cov);
     if (rc == RAFT_HIP_OK && p.low_cov >= 0) rc = survey_low_coverage(j, ss.n_bins);
+    if (rc == RAFT_HIP_OK && p.repeat_stats && est.est_cov > 0) {
+        if (raft_cli::repeat_stats_second_pass(p.auto_cov, p.repeat_stats)) {
+            sp.est_cov = est.est_cov;
+            rc = raft_hip_set_params(ctx, &sp);
+            if (rc == RAFT_HIP_OK)
+                rc = raft_hip_run_host(ctx, j.n_reads, j.rl, j.n_rec, j.col[0], j.col[1], j.col[2], targets ? j.col[3] : nullptr, targets ? j.col[4] : nullptr,
+                                       targets ? j.col[5] : nullptr);
+            if (rc == RAFT_HIP_OK) rc = raft_hip_finish(ctx, &ss);
+            if (rc != RAFT_HIP_OK) die(engine_error(j, rc, ss.error_index));
+        }
+        int64_t bad_index = -1;
+        rc = survey_repeat_stats(j, est.est_cov, ss.n_repeats, &bad_index);
+        if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
+    }
     if (rc == RAFT_HIP_OK) rc = settings.restore_outputs();
     if (rc != RAFT_HIP_OK) die(engine_error(j, rc, -1));
     stage(j, "estimate");
@@ -677,6 +719,21 @@ void write_fragment_overlaps(Job &j)
         die("ERROR, fragment_overlaps(), cannot write output files");
 }
 
+// --repeat-stats: the file is written from the job's own runs, beside long_repeats.txt; the rows come from the stats pass, which must
+// have found the same number of runs
+void write_repeat_stats(Job &j)
+{
+    const int64_t n_rep = j.rep_off[(size_t)j.n_reads];
+    if (!j.rst_done || (int64_t)j.rst_flags.size() != n_rep)
+        die("ERROR, repeat_stats(), the stats pass found " + std::to_string(j.rst_flags.size()) + " repeats, the job " + std::to_string(n_rep));
+    std::vector<const char *> names((size_t)j.n_reads);
+    for (int32_t i = 0; i < j.n_reads; ++i) names[(size_t)i] = raft_host_reads_name(j.reads, i);
+    if (raft_host_write_repeat_stats((j.p.prefix + ".long_repeats.stats.tsv").c_str(), j.n_reads, names.data(), j.rep_off.data(), j.rep_s.get(), j.rep_e.get(),
+                                     j.rst_flags.data(), j.rst_windows.data(), j.rst_cov_sum.data(), j.rst_min.data(), j.rst_max.data(), j.rst_high.data(),
+                                     j.rst_touch.data(), j.rst_span.data(), j.rst_inside.data()) != RAFT_HOST_OK)
+        die("ERROR, repeat_stats(), cannot write output files");
+}
+
 void write_repeat_overlaps(Job &j)
 {
     const Params &p = j.p;
@@ -738,6 +795,7 @@ void write_outputs(Job &j)
     if (p.low_cov >= 0) write_low_coverage(j);
     if (p.min_anchor > 0) write_repeat_overlaps(j);
     if (p.fragment_overlaps) write_fragment_overlaps(j);
+    if (p.repeat_stats) write_repeat_stats(j);
     stage(j, "write_tables");
     // repeat.hpp:173-178 (total_windows is an int in the reference; identical below 2^31 windows)
     const double cpw = (double)s.total_coverage / (double)s.total_windows;
@@ -772,6 +830,9 @@ void print_totals(Job &j, int argc, char *argv[])
         std::cout << raft_cli::fragment_overlaps_line(j.frag_sum.n_fragments, j.frag_sum.frags_spanned, j.frag_sum.frags_contained,
                                                       j.frag_sum.frags_contained_repeat, j.frag_sum.reads_whole_spanned, j.frag_sum.reads_all_contained,
                                                       j.n_reads) << "\n";
+    if (j.p.repeat_stats)
+        std::cout << raft_cli::repeat_stats_line(j.rst_sum.n_runs, j.rst_sum.runs_interior, j.rst_sum.runs_spanned, j.rst_sum.interior_spanned,
+                                                 j.rst_sum.runs_touched, j.rst_sum.sides_inside) << "\n";
     stage(j, "stdout");
     if (j.sw.timing) {
         timespec ts{};

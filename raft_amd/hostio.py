@@ -61,6 +61,10 @@ OVL_ABI = {
 FRAG_ABI = {
     "raft_host_write_fragments": (C.c_int, [_str, _i32, _P(_str), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+# ... and of include/raft_host_rst.h
+RST_ABI = {
+    "raft_host_write_repeat_stats": (C.c_int, [_str, _i32, _P(_str)] + [_vp] * 12),
+}
 
 
 class HostError(RuntimeError):
@@ -79,7 +83,7 @@ def load_library():
         if not os.path.exists(_LIB_PATH):
             raise RuntimeError(f"{_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         lib = C.CDLL(_LIB_PATH)
-        for name, (restype, argtypes) in list(ABI.items()) + list(LOW_ABI.items()) + list(OVL_ABI.items()) + list(FRAG_ABI.items()):
+        for name, (restype, argtypes) in list(ABI.items()) + list(LOW_ABI.items()) + list(OVL_ABI.items()) + list(FRAG_ABI.items()) + list(RST_ABI.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
