@@ -1,13 +1,12 @@
 // engine.hip -- context, launch sequence and C ABI (include/raft_hip.h) of the
 // MI355X engine.  One context = one device + one stream + grow-only device
 // buffers; one pass = the kernels listed in DESIGN.md §Kernels, in order.
-#include "engine_ctx.hpp"
+#include "cov_decode.hpp"
 
 #include "bucket.hpp"
 #include "sort_pairs.hpp"
 #include "device_scan.hpp"
 #include "finalize.hpp"
-#include "pack.hpp"
 #include "cov_hist.hpp"
 #include "read_stats.hpp"
 #include "census.hpp"
@@ -102,12 +101,6 @@ __global__ void selftest_kernel(const int *in, int *out_dpp, int *out_shfl, unsi
     if ((threadIdx.x & 63) == 0) ballots[threadIdx.x >> 6] = b;
 }
 
-
-// blocks of `per_block` items for n of them, one at least and `cap` at most
-inline unsigned grid_for(long long n, long long per_block, long long cap)
-{
-    return (unsigned)std::max<long long>(1, std::min<long long>((n + per_block - 1) / per_block, cap));
-}
 
 } // namespace
 
@@ -281,12 +274,6 @@ struct PassPlan {
     int symmetric, n_desc;
     long long desc[kMaxSeg];
 };
-
-#define PHASE(expr)                                              \
-    do {                                                         \
-        const int rc_ = (expr);                                  \
-        if (rc_ != RAFT_HIP_OK) return rc_;                      \
-    } while (0)
 
 // (RAFT_HOST_CLOCK=1: where the host is, us after entering, when it has issued what -- a speculative pass over an eighth of the
 // bench set is issued in 26 us, 2-3 us a launch: profiles/r06_host_clock.txt)
@@ -1122,45 +1109,18 @@ static int materialise_cuts(raft_hip_ctx *c)
     return RAFT_HIP_OK;
 }
 
-// cov[] as int32 after a pass that wrote its encoding directly: decoded on the device, once, for the caller that asks
+// cov[] as int32 after a pass that wrote its encoding directly: decoded on the device, once, for the caller that asks.  (Without
+// the int32 array the pass wrote one or two bytes a window or four-bit steps: decode_cov's answer for any other width cannot come.)
 static int materialise_cov(raft_hip_ctx *c)
 {
     if (c->cov_valid) return RAFT_HIP_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    const long long B = c->sum.n_bins;
-    HIP_TRY(c, c->cov.ensure((size_t)std::max(B, 1LL) * 4));
-    if (B > 0) {
-        const bool d4 = c->pass_width == kCovDelta4;
-        if (d4) {
-            if (c->d4_shift != 0) return RAFT_HIP_ERR_STATE;      // (a pipeline lane's chunk: its blocks do not begin at its first window)
-            HIP_TRY(c, c->abs_bits.ensure(((size_t)B / 32 + 2) * 4));
-            hipLaunchKernelGGL(delta4_expand_kernel, dim3(grid_for(B / 32, 256, 256 * 16)), dim3(256), 0, c->stream,
-                               c->cov8.as<uint8_t>(), B, c->cov.as<int32_t>(), c->abs_bits.as<unsigned>());
-        } else if (c->pass_width == 1)
-            hipLaunchKernelGGL(unpack_cov_kernel<uint8_t>, dim3(grid_for(B / 4, 256, 256 * 16)), dim3(256), 0, c->stream, c->cov8.as<uint8_t>(), B, c->cov.as<int32_t>());
-        else
-            hipLaunchKernelGGL(unpack_cov_kernel<uint16_t>, dim3(grid_for(B / 4, 256, 256 * 16)), dim3(256), 0, c->stream, c->cov8.as<uint16_t>(), B, c->cov.as<int32_t>());
-        if (c->n_exc > 0)      // the listed windows, over what the codes gave (delta4: before the walk that adds the steps up)
-            hipLaunchKernelGGL(scatter_exceptions_kernel, dim3((unsigned)std::min<long long>((c->n_exc + 255) / 256, 4096)), dim3(256), 0, c->stream,
-                               c->exc_idx.as<long long>(), c->exc_val.as<int32_t>(), c->n_exc, c->cov.as<int32_t>());
-        if (d4)
-            hipLaunchKernelGGL(delta4_walk_kernel, dim3(grid_for(B / kD4Block, 256, 256 * 16)), dim3(256), 0, c->stream,
-                               B, c->cov_anchor.as<int32_t>(), c->abs_bits.as<unsigned>(), c->cov.as<int32_t>());
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
+    PHASE(decode_cov(c, c->cov, c->abs_bits, "materialise_cov"));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->cov_valid = true;
     return RAFT_HIP_OK;
 }
 
-// Rows of the copy tables of raft_hip_fetch and fetch_packed_impl: a destination the caller left NULL, or nothing to copy, is skipped.
-struct CopyRow { void *dst; const void *src; size_t bytes; };
-static int queue_copies(raft_hip_ctx *c, std::initializer_list<CopyRow> rows)
-{
-    for (const CopyRow &j : rows)
-        if (j.dst && j.bytes) HIP_TRY(c, hipMemcpyAsync(j.dst, j.src, j.bytes, hipMemcpyDeviceToHost, c->stream));
-    return RAFT_HIP_OK;
-}
 static int queue_repeat_rows(raft_hip_ctx *c, int64_t *rep_offset, int32_t *rep_s, int32_t *rep_e)
 {
     return queue_copies(c, {{rep_offset, c->rep_off.p, ((size_t)c->sum.n_reads + 1) * 8}, {rep_s, c->rep_s.p, (size_t)c->sum.n_repeats * 4},
@@ -1177,7 +1137,7 @@ int pack_coverage(raft_hip_ctx *c, int width)
 {
     if (c->packed_width == width) return RAFT_HIP_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    { const int rc = materialise_cov(c); if (rc != RAFT_HIP_OK) return rc; }   // (a pass that wrote the other width)
+    PHASE(materialise_cov(c));                             // (a pass that wrote the other width)
     const long long B = c->sum.n_bins;
     const bool d4 = width == kCovDelta4;
     HIP_TRY(c, c->cov8.ensure(d4 ? (size_t)std::max(B, 1LL) / 2 + 16 : (size_t)std::max(B, 1LL) * (size_t)width + 16));
@@ -1508,7 +1468,7 @@ int raft_hip_outputs_device(raft_hip_ctx *c, raft_hip_outputs *o)
     if (!c || !o) return RAFT_HIP_ERR_PARAM;
     if (!c->finished || c->pending_err) return RAFT_HIP_ERR_STATE;
     { const int rc = materialise_cuts(c); if (rc != RAFT_HIP_OK) return rc; }
-    { const int rc = materialise_cov(c); if (rc != RAFT_HIP_OK) return rc; }
+    PHASE(materialise_cov(c));
     ++c->geom_id;                                  // (cov_offset goes out writable: the next pass scans the geometry again)
     o->cov_offset = c->cov_off.as<int64_t>(); o->cov = c->cov.as<int32_t>();
     o->rep_offset = c->rep_off.as<int64_t>(); o->rep_s = c->rep_s.as<int32_t>(); o->rep_e = c->rep_e.as<int32_t>();
@@ -1526,7 +1486,7 @@ int raft_hip_fetch(raft_hip_ctx *c, int64_t *cov_offset, int32_t *cov, int64_t *
     if (!c->finished || c->pending_err) return RAFT_HIP_ERR_STATE;
     HIP_TRY(c, hipSetDevice(c->device));
     if (cuts) { const int rc = materialise_cuts(c); if (rc != RAFT_HIP_OK) return rc; }
-    if (cov) { const int rc = materialise_cov(c); if (rc != RAFT_HIP_OK) return rc; }
+    if (cov) PHASE(materialise_cov(c));
     PHASE(queue_copies(c, {{cov_offset, c->cov_off.p, ((size_t)c->sum.n_reads + 1) * 8}, {cov, c->cov.p, (size_t)c->sum.n_bins * 4}}));
     PHASE(queue_repeat_rows(c, rep_offset, rep_s, rep_e));
     PHASE(queue_copies(c, {{cut_offset, c->cut_off.p, ((size_t)c->sum.n_reads + 1) * 8}, {cuts, c->cuts.p, (size_t)c->sum.n_cuts * 4}}));
@@ -1571,14 +1531,14 @@ int raft_hip_cov_histogram(raft_hip_ctx *c, int64_t *hist, double *kernel_second
     HIP_TRY(c, hipSetDevice(c->device));
     const long long B = c->sum.n_bins;
     // codes as the pass wrote them (a caller that had them re-encoded in another width since holds the int32 array as well: that one then)
-    const bool codes = (c->pass_width == 1 || c->pass_width == 2) && c->packed_width == c->pass_width;
-    if (!codes) { const int rc = materialise_cov(c); if (rc != RAFT_HIP_OK) return rc; }
+    const bool codes = pass_holds_codes(c);
+    if (!codes) PHASE(materialise_cov(c));
     else if (c->n_exc > c->exc_cap) { c->last_error = "raft_hip_cov_histogram: the pass's exception list is incomplete"; return RAFT_HIP_ERR_DEVICE; }
     HIP_TRY(c, c->cov_hist.ensure((size_t)kCovHistBins * 8));
-    if (kernel_seconds && !c->ev_hist0) { HIP_TRY(c, hipEventCreate(&c->ev_hist0)); HIP_TRY(c, hipEventCreate(&c->ev_hist1)); }
+    QueryTimer timer(c, kernel_seconds);
     unsigned long long *d_hist = c->cov_hist.as<unsigned long long>();
     HIP_TRY(c, hipMemsetAsync(d_hist, 0, (size_t)kCovHistBins * 8, c->stream));
-    if (kernel_seconds) HIP_TRY(c, hipEventRecord(c->ev_hist0, c->stream));
+    PHASE(timer.start());
     if (B > 0) {
         if (!codes) {
             hipLaunchKernelGGL(cov_hist_kernel<int32_t>, dim3(cov_hist_grid(B / kCovHistLaneWindows<int32_t>, B)), dim3(kCovHistThreads), 0, c->stream,
@@ -1596,14 +1556,10 @@ int raft_hip_cov_histogram(raft_hip_ctx *c, int64_t *hist, double *kernel_second
         }
         HIP_TRY(c, hipGetLastError());
     }
-    if (kernel_seconds) HIP_TRY(c, hipEventRecord(c->ev_hist1, c->stream));
+    PHASE(timer.stop());
     HIP_TRY(c, hipMemcpyAsync(hist, d_hist, (size_t)kCovHistBins * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));           // (the one wait of the call: it returns host values)
-    if (kernel_seconds) {
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_hist0, c->ev_hist1));
-        *kernel_seconds = ms * 1e-3;
-    }
+    PHASE(timer.seconds(kernel_seconds));
     return RAFT_HIP_OK;
 }
 
@@ -1616,19 +1572,19 @@ int raft_hip_read_stats(raft_hip_ctx *c, int32_t threshold, int64_t *cov_sum, in
     HIP_TRY(c, hipSetDevice(c->device));
     const long long B = c->sum.n_bins;
     const int32_t n_reads = c->sum.n_reads;
-    const bool codes = (c->pass_width == 1 || c->pass_width == 2) && c->packed_width == c->pass_width;
-    if (!codes) { const int rc = materialise_cov(c); if (rc != RAFT_HIP_OK) return rc; }
+    const bool codes = pass_holds_codes(c);
+    if (!codes) PHASE(materialise_cov(c));
     else if (c->n_exc > c->exc_cap) { c->last_error = "raft_hip_read_stats: the pass's exception list is incomplete"; return RAFT_HIP_ERR_DEVICE; }
     const size_t n = (size_t)std::max(n_reads, 1);
     HIP_TRY(c, c->rs_sum.ensure(n * 8));
     HIP_TRY(c, c->rs_max.ensure(n * 4));
     HIP_TRY(c, c->rs_high.ensure(n * 4));
-    if (kernel_seconds && !c->ev_hist0) { HIP_TRY(c, hipEventCreate(&c->ev_hist0)); HIP_TRY(c, hipEventCreate(&c->ev_hist1)); }
+    QueryTimer timer(c, kernel_seconds);
     ReadStatsOut out{c->rs_sum.as<unsigned long long>(), c->rs_max.as<int32_t>(), c->rs_high.as<int32_t>()};
     HIP_TRY(c, hipMemsetAsync(out.sum, 0, n * 8, c->stream));
     HIP_TRY(c, hipMemsetAsync(out.max, 0, n * 4, c->stream));
     HIP_TRY(c, hipMemsetAsync(out.high, 0, n * 4, c->stream));
-    if (kernel_seconds) HIP_TRY(c, hipEventRecord(c->ev_hist0, c->stream));
+    PHASE(timer.start());
     if (B > 0 && n_reads > 0) {
         const long long *off = c->cov_off.as<long long>();
         const unsigned thr = (unsigned)threshold;
@@ -1649,20 +1605,16 @@ int raft_hip_read_stats(raft_hip_ctx *c, int32_t threshold, int64_t *cov_sum, in
         }
         HIP_TRY(c, hipGetLastError());
     }
-    if (kernel_seconds) HIP_TRY(c, hipEventRecord(c->ev_hist1, c->stream));
+    PHASE(timer.stop());
     PHASE(queue_copies(c, {{cov_sum, out.sum, (size_t)n_reads * 8}, {cov_max, out.max, (size_t)n_reads * 4}, {high_windows, out.high, (size_t)n_reads * 4}}));
     HIP_TRY(c, hipStreamSynchronize(c->stream));           // (the one wait of the call)
-    if (kernel_seconds) {
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_hist0, c->ev_hist1));
-        *kernel_seconds = ms * 1e-3;
-    }
+    PHASE(timer.seconds(kernel_seconds));
     return RAFT_HIP_OK;
 }
 
 // What the record stream says about each read (census.hpp): intervals per read under the final flag `symmetric`, contained flags.
 // Independent of any pass: the call reads its arguments and writes buffers of its own.
-static int census_run(raft_hip_ctx *c, int32_t n_reads, const int32_t *d_len, int64_t n_rec, const int32_t *const d_col[6], int32_t symmetric,
+static int census_run(raft_hip_ctx *c, int32_t n_reads, const int32_t *d_len, const RecordCols &rec, int32_t symmetric,
                       int32_t *intervals, uint8_t *contained, int64_t *n_contained, int64_t *error_index, double *kernel_seconds)
 {
     const size_t n = (size_t)std::max(n_reads, 1);
@@ -1670,81 +1622,69 @@ static int census_run(raft_hip_ctx *c, int32_t n_reads, const int32_t *d_len, in
     HIP_TRY(c, c->cen_flags.ensure(n * 4));
     HIP_TRY(c, c->cen_out.ensure(n));
     HIP_TRY(c, c->cen_ctl.ensure(16));
-    if (kernel_seconds && !c->ev_hist0) { HIP_TRY(c, hipEventCreate(&c->ev_hist0)); HIP_TRY(c, hipEventCreate(&c->ev_hist1)); }
+    QueryTimer timer(c, kernel_seconds);
     unsigned long long *ctl = c->cen_ctl.as<unsigned long long>();        // [0] first bad record, [1] reads with a flag
     HIP_TRY(c, hipMemsetAsync(c->cen_cnt.p, 0, n * 4, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->cen_flags.p, 0, n * 4, c->stream));
-    HIP_TRY(c, hipMemsetAsync(ctl, 0xFF, 8, c->stream));
-    HIP_TRY(c, hipMemsetAsync(ctl + 1, 0, 8, c->stream));
-    if (kernel_seconds) HIP_TRY(c, hipEventRecord(c->ev_hist0, c->stream));
+    PHASE(clear_ctl(c, ctl, 2));
+    PHASE(timer.start());
+    const int64_t n_rec = rec.n_rec;
     if (n_rec > 0) {
-        CensusArgs A{d_len, d_col[0], d_col[1], d_col[2], d_col[3], symmetric ? nullptr : d_col[4], symmetric ? nullptr : d_col[5], (long long)n_rec, n_reads,
+        CensusArgs A{d_len, rec.col[0], rec.col[1], rec.col[2], rec.col[3], rec.col[4], rec.col[5], (long long)n_rec, n_reads,
                      symmetric ? 1 : 0, c->cen_cnt.as<unsigned>(), c->cen_flags.as<unsigned>(), ctl};
-        uintptr_t bits = 0;
-        for (int k = 0; k < (symmetric ? 4 : 6); ++k) bits |= reinterpret_cast<uintptr_t>(d_col[k]);
-        if (bits & 15) hipLaunchKernelGGL(census_kernel<false>, dim3(census_grid(n_rec)), dim3(kCensusThreads), 0, c->stream, A);
-        else hipLaunchKernelGGL(census_kernel<true>, dim3(census_grid(n_rec)), dim3(kCensusThreads), 0, c->stream, A);
+        if (aligned16(rec)) hipLaunchKernelGGL(census_kernel<true>, dim3(census_grid(n_rec)), dim3(kCensusThreads), 0, c->stream, A);
+        else hipLaunchKernelGGL(census_kernel<false>, dim3(census_grid(n_rec)), dim3(kCensusThreads), 0, c->stream, A);
     }
     if (n_reads > 0)
         hipLaunchKernelGGL(census_pack_kernel, dim3((unsigned)std::min<long long>(((long long)n_reads + 255) / 256, 1024)), dim3(256), 0, c->stream,
                            c->cen_flags.as<unsigned>(), n_reads, c->cen_out.as<uint8_t>(), ctl + 1);
     HIP_TRY(c, hipGetLastError());
-    if (kernel_seconds) HIP_TRY(c, hipEventRecord(c->ev_hist1, c->stream));
+    PHASE(timer.stop());
     unsigned long long h_ctl[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(h_ctl, ctl, 16, hipMemcpyDeviceToHost, c->stream));
+    PHASE(read_ctl(c, ctl, h_ctl, 2));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (kernel_seconds) {
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_hist0, c->ev_hist1));
-        *kernel_seconds = ms * 1e-3;
-    }
-    if (h_ctl[0] != ~0ull) {
-        if (error_index) *error_index = (int64_t)h_ctl[0];
-        c->last_error = "census: a record names a read id outside [0, n_reads)";
-        return RAFT_HIP_ERR_READ_ID;
-    }
-    if (error_index) *error_index = -1;
+    PHASE(timer.seconds(kernel_seconds));
+    PHASE(first_bad_record(c, h_ctl[0], error_index, "census: a record names a read id outside [0, n_reads)"));
     if (n_contained) *n_contained = (int64_t)h_ctl[1];
     PHASE(queue_copies(c, {{intervals, c->cen_cnt.p, (size_t)n_reads * 4}, {contained, c->cen_out.p, (size_t)n_reads}}));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return RAFT_HIP_OK;
 }
 
-static bool census_args_ok(const raft_hip_ctx *c, int32_t n_reads, const int32_t *len, int64_t n_rec, const int32_t *qid, const int32_t *qs,
-                           const int32_t *qe, const int32_t *tid, const int32_t *ts, const int32_t *te, int32_t symmetric)
+// the record columns as the census reads them: under `symmetric` ts / te are not looked at, whatever the caller passed
+static RecordCols census_cols(int64_t n_rec, const int32_t *qid, const int32_t *qs, const int32_t *qe, const int32_t *tid, const int32_t *ts,
+                              const int32_t *te, int32_t symmetric)
 {
-    if (!c || n_reads < 0 || n_rec < 0 || (n_reads > 0 && !len)) return false;
-    if (n_rec > 0 && (!qid || !qs || !qe || !tid)) return false;
-    if (n_rec > 0 && !symmetric && (!ts || !te)) return false;
-    return true;
+    return RecordCols{n_rec, {qid, qs, qe, tid, symmetric ? nullptr : ts, symmetric ? nullptr : te}};
+}
+
+static bool census_args_ok(const raft_hip_ctx *c, int32_t n_reads, const int32_t *len, const RecordCols &rec, int32_t symmetric)
+{
+    if (!c || n_reads < 0 || rec.n_rec < 0 || (n_reads > 0 && !len)) return false;
+    return record_cols_ok(rec, symmetric != 0, TargetCols::unread_if_symmetric);
 }
 
 int raft_hip_census_device(raft_hip_ctx *c, int32_t n_reads, const int32_t *d_read_len, int64_t n_rec, const int32_t *d_qid, const int32_t *d_qs,
                            const int32_t *d_qe, const int32_t *d_tid, const int32_t *d_ts, const int32_t *d_te, int32_t symmetric,
                            int32_t *intervals, uint8_t *contained, int64_t *n_contained, int64_t *error_index, double *kernel_seconds)
 {
-    if (!census_args_ok(c, n_reads, d_read_len, n_rec, d_qid, d_qs, d_qe, d_tid, d_ts, d_te, symmetric)) return RAFT_HIP_ERR_PARAM;
+    const RecordCols rec = census_cols(n_rec, d_qid, d_qs, d_qe, d_tid, d_ts, d_te, symmetric);
+    if (!census_args_ok(c, n_reads, d_read_len, rec, symmetric)) return RAFT_HIP_ERR_PARAM;
     HIP_TRY(c, hipSetDevice(c->device));
-    const int32_t *col[6] = {d_qid, d_qs, d_qe, d_tid, d_ts, d_te};
-    return census_run(c, n_reads, d_read_len, n_rec, col, symmetric, intervals, contained, n_contained, error_index, kernel_seconds);
+    return census_run(c, n_reads, d_read_len, rec, symmetric, intervals, contained, n_contained, error_index, kernel_seconds);
 }
 
+// The same from host arrays, staged through the census's own buffers (cen_len, cen_col).
 int raft_hip_census_host(raft_hip_ctx *c, int32_t n_reads, const int32_t *read_len, int64_t n_rec, const int32_t *qid, const int32_t *qs,
                          const int32_t *qe, const int32_t *tid, const int32_t *ts, const int32_t *te, int32_t symmetric,
                          int32_t *intervals, uint8_t *contained, int64_t *n_contained, int64_t *error_index, double *kernel_seconds)
 {
-    if (!census_args_ok(c, n_reads, read_len, n_rec, qid, qs, qe, tid, ts, te, symmetric)) return RAFT_HIP_ERR_PARAM;
+    RecordCols rec = census_cols(n_rec, qid, qs, qe, tid, ts, te, symmetric);
+    if (!census_args_ok(c, n_reads, read_len, rec, symmetric)) return RAFT_HIP_ERR_PARAM;
     HIP_TRY(c, hipSetDevice(c->device));
-    const int32_t *h[6] = {qid, qs, qe, tid, ts, te};
-    const int32_t *col[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    HIP_TRY(c, c->cen_len.ensure((size_t)std::max(n_reads, 1) * 4));
-    if (n_reads > 0) HIP_TRY(c, hipMemcpyAsync(c->cen_len.p, read_len, (size_t)n_reads * 4, hipMemcpyHostToDevice, c->stream));
-    for (int k = 0; k < (symmetric ? 4 : 6); ++k) {
-        HIP_TRY(c, c->cen_col[k].ensure((size_t)std::max<int64_t>(n_rec, 1) * 4));
-        if (n_rec > 0) HIP_TRY(c, hipMemcpyAsync(c->cen_col[k].p, h[k], (size_t)n_rec * 4, hipMemcpyHostToDevice, c->stream));
-        col[k] = c->cen_col[k].as<int32_t>();
-    }
-    return census_run(c, n_reads, c->cen_len.as<int32_t>(), n_rec, col, symmetric, intervals, contained, n_contained, error_index, kernel_seconds);
+    PHASE(stage_host(c, c->cen_len, read_len, (size_t)n_reads, &read_len));
+    PHASE(stage_columns(c, c->cen_col, rec));
+    return census_run(c, n_reads, read_len, rec, symmetric, intervals, contained, n_contained, error_index, kernel_seconds);
 }
 
 // The estimate read from a histogram: the mode of the covered, unclamped bins smoothed over three neighbours (see raft_hip.h).

@@ -12,6 +12,9 @@
 //   pipeline_plan.hpp     its arithmetic, free of HIP: WindowDiv, the sorted runs, the chunk plan, the jobs' places, derive_slice
 //   engine_exchange.hip   pre-split PAF: symmetric flag across ranks, grouped sides, the exchange (RCCL / peer copies), the pre-split job
 //   engine_placement.hip  where buffers lie: pool, trim, policy, the placement trial, the callers' input buffers, page-locking
+//   query_host.hpp        the host side the queries about a finished pass share (engine.hip's and the four *_lib.hip libraries'):
+//                         phases, copy tables, staging of a host form, the event pair, the control words
+//   query_args.hpp        their decisions about arguments, free of HIP; cov_decode.hpp: the coverage decoded to int32, one launch sequence
 #pragma once
 #include "../../include/raft_hip.h"
 #include "raft_types.hpp"
@@ -368,36 +371,38 @@ struct raft_hip_ctx {
     DevBuf cov8{bufs, DevBuf::kBig}, exc_idx{bufs}, exc_val{bufs}, exc_cnt{bufs};   // transfer encoding of cov[] (raft_hip_fetch_packed)
     DevBuf cov_hist{bufs};             // raft_hip_cov_histogram: RAFT_HIP_COV_HIST_BINS 64-bit counts, cleared at every call
     DevBuf rs_sum{bufs}, rs_max{bufs}, rs_high{bufs};   // raft_hip_read_stats: one value per read each, cleared at every call
-    // raft_hip_low_coverage (low_cov_lib.hip, libraft_hip_low.so; plain allocations: that library keeps no chunk pool): the two bitmaps (low windows, first windows of reads), run starts per tile and their prefix, the control
-    // words; per read low windows / low bases / class bits, the flag bytes, low_offset; per run start, end and read
+    // The queries beside the engine (libraft_hip_low.so, _ovl.so, _frag.so, _rst.so; all plain allocations: those libraries keep no chunk
+    // pool) share what none of them keeps between calls.  q_len, q_col, q_csr_a, q_csr_b: the staging of a host form -- lengths, the six
+    // columns, the three arrays of a table the caller gave (repeat_overlaps, repeat_stats: the repeats in q_csr_a; fragment_overlaps:
+    // the fragment table in q_csr_a, the repeats in q_csr_b).  q_cov, q_abs: for a pass that holds no int32 array where a query needs
+    // one, the decoded coverage and delta4's escape flags (cov_decode.hpp).  One set is sound because every query call ends in a wait
+    // for the stream before it returns, and a context is used by one caller at a time: no call finds another's input still in use.
+    // The working and output buffers below are each query's own.
+    DevBuf q_len{bufs}, q_cov{bufs}, q_abs{bufs};
+    DevBuf q_col[6] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
+    DevBuf q_csr_a[3] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}}, q_csr_b[3] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
+    // raft_hip_low_coverage (low_cov_lib.hip): the two bitmaps (low windows, first windows of reads), run starts per tile and their
+    // prefix, the control words; per read low windows / low bases / class bits, the flag bytes, low_offset; per run start, end and read
     DevBuf lc_bad{bufs}, lc_rs{bufs}, lc_tile_cnt{bufs}, lc_tile_base{bufs}, lc_ctl{bufs};
     DevBuf lc_win{bufs}, lc_bases{bufs}, lc_flagw{bufs}, lc_flags{bufs}, lc_off{bufs};
     DevBuf lc_s{bufs}, lc_e{bufs}, lc_read{bufs};
-    DevBuf lc_cov{bufs}, lc_abs{bufs};   // ... and, for a pass that holds no int32 array where one is needed, the decoded coverage and delta4's escape flags
-    // raft_hip_repeat_overlaps_* (ovl_class_lib.hip, libraft_hip_ovl.so; plain allocations, as lc_*): the digest of every read's runs, per read the
-    // sides that touch / lie in a repeat (one word for both while they are counted: oc_tally) and the flag words, the flags as bytes, the control words, the class bytes before they go to the
-    // caller; staging of the host form (lengths, columns, the repeat arrays)
+    // raft_hip_repeat_overlaps_* (ovl_class_lib.hip): the digest of every read's runs, per read the sides that touch / lie in a repeat
+    // (one word for both while they are counted: oc_tally) and the flag words, the flags as bytes, the control words, the class bytes
+    // before they go to the caller
     DevBuf oc_digest{bufs}, oc_tally{bufs}, oc_touch{bufs}, oc_repeat{bufs}, oc_flagw{bufs}, oc_flags{bufs}, oc_ctl{bufs}, oc_cls{bufs};
-    DevBuf oc_len{bufs}, oc_rep_off{bufs}, oc_rep_s{bufs}, oc_rep_e{bufs};
-    DevBuf oc_col[6] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
-    // raft_hip_frag_overlaps_* (frag_ovl_lib.hip, libraft_hip_frag.so; plain allocations, as oc_*): the digest of every read's rows and of its runs,
-    // the reads' whole-spanned flag words and contained rows, the difference slots (n_frag + 1), per row touch / span / contained / repeat bases,
-    // the scan's partial sums, the control words; staging of the host form (lengths, columns, the table, the repeat arrays)
+    // raft_hip_frag_overlaps_* (frag_ovl_lib.hip): the digest of every read's rows and of its runs, the reads' whole-spanned flag words
+    // and contained rows, the difference slots (n_frag + 1), per row touch / span / contained / repeat bases, the scan's partial sums,
+    // the control words
     DevBuf fo_digest{bufs}, fo_rep_digest{bufs}, fo_whole{bufs}, fo_read{bufs}, fo_slot{bufs}, fo_scan{bufs}, fo_ctl{bufs};
     DevBuf fo_out[4] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
-    DevBuf fo_len{bufs}, fo_tab_off{bufs}, fo_tab_b{bufs}, fo_tab_e{bufs}, fo_rep_off{bufs}, fo_rep_s{bufs}, fo_rep_e{bufs};
-    DevBuf fo_col[6] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
-    // raft_hip_repeat_stats_* (repeat_stats_lib.hip, libraft_hip_rst.so; plain allocations, as fo_*; rst_ and not rs_: raft_hip_read_stats and the
-    // radix sort hold those names): the digest of every read's runs, the read of every run, the counter slots, the control words; per run touch /
-    // span / inside, windows / min / max / high windows, the coverage sum, the flag bytes; the coverage decoded to int32 and delta4's escape flags
-    // for a pass that holds no int32 array; staging of the host form (lengths, columns, the repeat arrays)
+    // raft_hip_repeat_stats_* (repeat_stats_lib.hip; rst_ and not rs_: raft_hip_read_stats and the radix sort hold those names): the
+    // digest of every read's runs, the read of every run, the counter slots, the control words; per run touch / span / inside,
+    // windows / min / max / high windows, the coverage sum, the flag bytes
     DevBuf rst_digest{bufs}, rst_run_read{bufs}, rst_slot{bufs}, rst_ctl{bufs}, rst_sum{bufs}, rst_flags{bufs};
     DevBuf rst_cnt[3] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
     DevBuf rst_win[4] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
-    DevBuf rst_cov{bufs}, rst_abs{bufs};
-    DevBuf rst_len{bufs}, rst_rep_off{bufs}, rst_rep_s{bufs}, rst_rep_e{bufs};
-    DevBuf rst_col[6] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
-    // raft_hip_census_*: counts and flag words per read, the flags as bytes, {first bad record, reads with a flag}; staging of the host form
+    // raft_hip_census_*: counts and flag words per read, the flags as bytes, {first bad record, reads with a flag}; staging of the host form --
+    // the census's own and not q_*: it lives in the engine library, whose chunk pool backs the columns (kBig), which the side libraries' must not be
     DevBuf cen_cnt{bufs}, cen_flags{bufs}, cen_out{bufs}, cen_ctl{bufs}, cen_len{bufs};
     DevBuf cen_col[6] = {DevBuf{bufs, DevBuf::kBig}, DevBuf{bufs, DevBuf::kBig}, DevBuf{bufs, DevBuf::kBig},
                          DevBuf{bufs, DevBuf::kBig}, DevBuf{bufs, DevBuf::kBig}, DevBuf{bufs, DevBuf::kBig}};

@@ -1,70 +1,14 @@
 // low_cov_lib.hip -- libraft_hip_low.so: raft_hip_low_coverage (include/raft_hip_low.h), the low-coverage runs of a finished pass.
 //
 // A library of its own beside libraft_hip.so: the set of entry points of include/raft_hip.h is closed (ABI 11), and this query needs
-// nothing of the engine but the context it is handed -- the buffers a finished pass left (engine_ctx.hpp), the stream, and buffers of
-// its own registered with the context like every other (lc_*).  Both libraries are built from this tree against the same
-// engine_ctx.hpp, and raft_hip_low_abi() says which ABI version of the engine this one was built beside.
-#include "engine_ctx.hpp"
+// nothing of the engine but the context it is handed -- the buffers a finished pass left (engine_ctx.hpp), the stream, and buffers
+// registered with the context like every other (lc_*, and the queries' shared decoded coverage q_cov).  Both libraries are built from
+// this tree against the same engine_ctx.hpp, and raft_hip_low_abi() says which ABI version of the engine this one was built beside.
+#include "cov_decode.hpp"
 #include "../../include/raft_hip_low.h"
-#include "pack.hpp"
 #include "low_cov.hpp"
 
 #include <algorithm>
-
-namespace {
-
-#define PHASE(expr)                                              \
-    do {                                                         \
-        const int rc_ = (expr);                                  \
-        if (rc_ != RAFT_HIP_OK) return rc_;                      \
-    } while (0)
-
-inline unsigned grid_for(long long n, long long per_block, long long cap)
-{
-    return (unsigned)std::max<long long>(1, std::min<long long>((n + per_block - 1) / per_block, cap));
-}
-
-// a destination the caller left NULL, or nothing to copy, is skipped
-int queue_copy(raft_hip_ctx *c, void *dst, const void *src, size_t bytes)
-{
-    if (dst && bytes) HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-    return RAFT_HIP_OK;
-}
-
-// The int32 array of the last pass: the context's own when it holds one (a pass that wrote int32, or one somebody fetched), else
-// decoded from the codes or four-bit steps into a buffer of this query's (lc_cov) with the kernels of pack.hpp in the order
-// engine.hip's materialise_cov runs them.  Nothing of the engine's is allocated, written or marked here.
-int int32_cov(raft_hip_ctx *c, const int32_t **out)
-{
-    if (c->cov_valid) { *out = c->cov.as<int32_t>(); return RAFT_HIP_OK; }
-    const long long B = c->sum.n_bins;
-    HIP_TRY(c, c->lc_cov.ensure((size_t)std::max(B, 1LL) * 4));
-    int32_t *cov = c->lc_cov.as<int32_t>();
-    *out = cov;
-    if (B > 0) {
-        const bool d4 = c->pass_width == kCovDelta4;
-        if (d4) {
-            if (c->d4_shift != 0) return RAFT_HIP_ERR_STATE;      // (a pipeline lane's chunk: its blocks do not begin at its first window)
-            HIP_TRY(c, c->lc_abs.ensure(((size_t)B / 32 + 2) * 4));
-            hipLaunchKernelGGL(delta4_expand_kernel, dim3(grid_for(B / 32, 256, 256 * 16)), dim3(256), 0, c->stream,
-                               c->cov8.as<uint8_t>(), B, cov, c->lc_abs.as<unsigned>());
-        } else if (c->pass_width == 1)
-            hipLaunchKernelGGL(unpack_cov_kernel<uint8_t>, dim3(grid_for(B / 4, 256, 256 * 16)), dim3(256), 0, c->stream, c->cov8.as<uint8_t>(), B, cov);
-        else if (c->pass_width == 2)
-            hipLaunchKernelGGL(unpack_cov_kernel<uint16_t>, dim3(grid_for(B / 4, 256, 256 * 16)), dim3(256), 0, c->stream, c->cov8.as<uint16_t>(), B, cov);
-        else { c->last_error = "raft_hip_low_coverage: the pass holds neither int32 nor an encoding"; return RAFT_HIP_ERR_STATE; }
-        if (c->n_exc > 0)      // the listed windows, over what the codes gave (delta4: before the walk that adds the steps up)
-            hipLaunchKernelGGL(scatter_exceptions_kernel, dim3((unsigned)std::min<long long>((c->n_exc + 255) / 256, 4096)), dim3(256), 0, c->stream,
-                               c->exc_idx.as<long long>(), c->exc_val.as<int32_t>(), c->n_exc, cov);
-        if (d4)
-            hipLaunchKernelGGL(delta4_walk_kernel, dim3(grid_for(B / kD4Block, 256, 256 * 16)), dim3(256), 0, c->stream,
-                               B, c->cov_anchor.as<int32_t>(), c->lc_abs.as<unsigned>(), cov);
-        HIP_TRY(c, hipGetLastError());
-    }
-    return RAFT_HIP_OK;
-}
-
-} // namespace
 
 extern "C" {
 
@@ -81,12 +25,12 @@ int raft_hip_low_coverage(raft_hip_ctx *c, int32_t low_cov, int32_t uncovered_pe
     HIP_TRY(c, hipSetDevice(c->device));
     const long long B = c->sum.n_bins;
     const int32_t n_reads = c->sum.n_reads;
-    const bool pass_codes = (c->pass_width == 1 || c->pass_width == 2) && c->packed_width == c->pass_width;
+    const bool pass_codes = pass_holds_codes(c);
     if (pass_codes && c->n_exc > c->exc_cap) { c->last_error = "raft_hip_low_coverage: the pass's exception list is incomplete"; return RAFT_HIP_ERR_DEVICE; }
     // codes in place while low_cov lies below the code's limit: a code at the limit is then not low, whatever its window holds
     const bool codes = pass_codes && (long long)low_cov < (c->pass_width == 1 ? 255ll : 65535ll);
     const int32_t *cov32 = nullptr;
-    if (!codes) { const int rc = int32_cov(c, &cov32); if (rc != RAFT_HIP_OK) return rc; }
+    if (!codes) PHASE(query_cov(c, "raft_hip_low_coverage", &cov32));
     const long long n_words = (B + kLowWordWindows - 1) / kLowWordWindows;
     const long long n_tiles = (n_words + kLowTileWords - 1) / kLowTileWords;
     const size_t n = (size_t)std::max(n_reads, 1);
@@ -98,7 +42,7 @@ int raft_hip_low_coverage(raft_hip_ctx *c, int32_t low_cov, int32_t uncovered_pe
     HIP_TRY(c, c->lc_win.ensure(n * 4)); HIP_TRY(c, c->lc_bases.ensure(n * 4)); HIP_TRY(c, c->lc_flagw.ensure(n * 4));
     HIP_TRY(c, c->lc_flags.ensure(n)); HIP_TRY(c, c->lc_off.ensure((n + 1) * 8));
     HIP_TRY(c, c->len_seen.ensure(n * 4));                 // (a context whose passes never saw a read has none)
-    if (kernel_seconds && !c->ev_hist0) { HIP_TRY(c, hipEventCreate(&c->ev_hist0)); HIP_TRY(c, hipEventCreate(&c->ev_hist1)); }
+    QueryTimer timer(c, kernel_seconds);
     unsigned long long *bad = c->lc_bad.as<unsigned long long>(), *rs = c->lc_rs.as<unsigned long long>(), *ctl = c->lc_ctl.as<unsigned long long>();
     const long long *off = c->cov_off.as<long long>();
     LowReads acc{c->lc_win.as<unsigned>(), c->lc_bases.as<unsigned>(), c->lc_flagw.as<unsigned>()};
@@ -107,8 +51,8 @@ int raft_hip_low_coverage(raft_hip_ctx *c, int32_t low_cov, int32_t uncovered_pe
     HIP_TRY(c, hipMemsetAsync(acc.windows, 0, n * 4, c->stream));
     HIP_TRY(c, hipMemsetAsync(acc.bases, 0, n * 4, c->stream));
     HIP_TRY(c, hipMemsetAsync(acc.flag_words, 0, n * 4, c->stream));
-    double seconds = 0.0;
-    if (kernel_seconds) HIP_TRY(c, hipEventRecord(c->ev_hist0, c->stream));
+    double head_seconds = 0.0, tail_seconds = 0.0;      // (two spans: the host sizes the run arrays in between)
+    PHASE(timer.start());
     if (B > 0 && n_reads > 0) {
         const unsigned thr = (unsigned)low_cov;
         auto mark_grid = [&](int lane_windows) { return dim3((unsigned)((n_words * kLowWordWindows / lane_windows + kLowMarkGroups - 1) / kLowMarkGroups)); };
@@ -128,21 +72,17 @@ int raft_hip_low_coverage(raft_hip_ctx *c, int32_t low_cov, int32_t uncovered_pe
                            c->lc_tile_base.as<long long>(), ctl);
         HIP_TRY(c, hipGetLastError());
     }
-    if (kernel_seconds) HIP_TRY(c, hipEventRecord(c->ev_hist1, c->stream));
+    PHASE(timer.stop());
     unsigned long long h_ctl[kLowCtlWords] = {};
-    HIP_TRY(c, hipMemcpyAsync(h_ctl, ctl, 8, hipMemcpyDeviceToHost, c->stream));
+    PHASE(read_ctl(c, ctl, h_ctl, 1));
     HIP_TRY(c, hipStreamSynchronize(c->stream));           // (the run total: it sizes the run arrays)
-    if (kernel_seconds) {
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_hist0, c->ev_hist1));
-        seconds = ms * 1e-3;
-    }
+    PHASE(timer.seconds(&head_seconds));
     const long long n_runs = (long long)h_ctl[0];
     if (n_runs < 0 || n_runs > (B + n_reads) / 2) { c->last_error = "raft_hip_low_coverage: more runs than windows and reads allow"; return RAFT_HIP_ERR_DEVICE; }
     const size_t nr = (size_t)std::max(n_runs, 1LL);
     HIP_TRY(c, c->lc_s.ensure(nr * 4)); HIP_TRY(c, c->lc_e.ensure(nr * 4)); HIP_TRY(c, c->lc_read.ensure(nr * 4));
     LowRuns runs{c->lc_s.as<int32_t>(), c->lc_e.as<int32_t>(), c->lc_read.as<int32_t>()};
-    if (kernel_seconds) HIP_TRY(c, hipEventRecord(c->ev_hist0, c->stream));
+    PHASE(timer.start());
     if (n_runs > 0) {
         hipLaunchKernelGGL(low_fill_kernel, dim3((unsigned)n_tiles), dim3(kLowThreads), 0, c->stream, bad, rs, n_words, c->lc_tile_base.as<long long>(), off,
                            c->len_seen.as<int32_t>(), n_reads, c->prm.reso, n_runs, runs, ctl);
@@ -153,19 +93,15 @@ int raft_hip_low_coverage(raft_hip_ctx *c, int32_t low_cov, int32_t uncovered_pe
                        runs.read, n_runs, c->len_seen.as<int32_t>(), n_reads, uncovered_permille, acc, c->lc_off.as<long long>(),
                        c->lc_flags.as<uint8_t>(), ctl);
     HIP_TRY(c, hipGetLastError());
-    if (kernel_seconds) HIP_TRY(c, hipEventRecord(c->ev_hist1, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(h_ctl, ctl, sizeof h_ctl, hipMemcpyDeviceToHost, c->stream));
+    PHASE(timer.stop());
+    PHASE(read_ctl(c, ctl, h_ctl, kLowCtlWords));
     const bool fits = n_runs <= run_cap;
-    PHASE(queue_copy(c, low_offset, c->lc_off.p, ((size_t)n_reads + 1) * 8));
-    PHASE(queue_copy(c, low_windows, acc.windows, (size_t)n_reads * 4));
-    PHASE(queue_copy(c, low_flags, c->lc_flags.p, (size_t)n_reads));
-    if (fits) { PHASE(queue_copy(c, low_s, runs.s, (size_t)n_runs * 4)); PHASE(queue_copy(c, low_e, runs.e, (size_t)n_runs * 4)); }
+    PHASE(queue_copies(c, {{low_offset, c->lc_off.p, ((size_t)n_reads + 1) * 8}, {low_windows, acc.windows, (size_t)n_reads * 4},
+                           {low_flags, c->lc_flags.p, (size_t)n_reads}}));
+    if (fits) PHASE(queue_copies(c, {{low_s, runs.s, (size_t)n_runs * 4}, {low_e, runs.e, (size_t)n_runs * 4}}));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (kernel_seconds) {
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_hist0, c->ev_hist1));
-        *kernel_seconds = seconds + ms * 1e-3;
-    }
+    PHASE(timer.seconds(&tail_seconds));
+    if (kernel_seconds) *kernel_seconds = head_seconds + tail_seconds;
     if (h_ctl[6]) { c->last_error = "raft_hip_low_coverage: a run's rank fell outside the run total"; return RAFT_HIP_ERR_DEVICE; }
     if (sum) {
         sum->n_runs = n_runs; sum->low_windows = (int64_t)h_ctl[1]; sum->low_bases = (int64_t)h_ctl[2];

@@ -270,92 +270,50 @@ def load_library(path: str | None = None) -> C.CDLL:
     return lib
 
 
-_low_lib = None
+# The libraries beside libraft_hip.so: tag -> (file, its ABI table, the function that says which engine ABI it was built beside)
+_SIDE = {"low": ("libraft_hip_low.so", LOW_ABI, "raft_hip_low_abi"), "ovl": ("libraft_hip_ovl.so", OVL_ABI, "raft_hip_ovl_abi"),
+         "frag": ("libraft_hip_frag.so", FRAG_ABI, "raft_hip_frag_abi"), "rst": ("libraft_hip_rst.so", RST_ABI, "raft_hip_rst_abi")}
+_side_libs: dict = {}
+
+
+def _load_side_library(tag: str) -> C.CDLL:
+    """Loads one library of ``_SIDE`` (behind libraft_hip.so, whose contexts it takes) and declares every entry point of its header;
+    the two must have been built beside each other."""
+    if tag not in _side_libs:
+        file, abi, abi_fn = _SIDE[tag]
+        main = load_library()
+        p = os.path.join(os.path.dirname(_LIB_PATH), file)
+        if not os.path.exists(p):
+            raise RuntimeError(f"{p} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        lib = C.CDLL(p)
+        for name, (restype, argtypes) in abi.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        built_beside = getattr(lib, abi_fn)()
+        if built_beside != main.raft_hip_abi_version():
+            raise RuntimeError(f"{p} was built beside ABI {built_beside}, libraft_hip.so is ABI {main.raft_hip_abi_version()}")
+        _side_libs[tag] = lib
+    return _side_libs[tag]
 
 
 def load_low_library() -> C.CDLL:
-    """Loads libraft_hip_low.so (behind libraft_hip.so, whose contexts it takes) and declares every entry point of
-    include/raft_hip_low.h; the two must have been built beside each other."""
-    global _low_lib
-    if _low_lib is None:
-        main = load_library()
-        p = os.path.join(os.path.dirname(_LIB_PATH), "libraft_hip_low.so")
-        if not os.path.exists(p):
-            raise RuntimeError(f"{p} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(p)
-        for name, (restype, argtypes) in LOW_ABI.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        if lib.raft_hip_low_abi() != main.raft_hip_abi_version():
-            raise RuntimeError(f"{p} was built beside ABI {lib.raft_hip_low_abi()}, libraft_hip.so is ABI {main.raft_hip_abi_version()}")
-        _low_lib = lib
-    return _low_lib
-
-
-_ovl_lib = None
+    """libraft_hip_low.so with every entry point of include/raft_hip_low.h declared."""
+    return _load_side_library("low")
 
 
 def load_ovl_library() -> C.CDLL:
-    """Loads libraft_hip_ovl.so (behind libraft_hip.so, whose contexts it takes) and declares every entry point of
-    include/raft_hip_ovl.h; the two must have been built beside each other."""
-    global _ovl_lib
-    if _ovl_lib is None:
-        main = load_library()
-        p = os.path.join(os.path.dirname(_LIB_PATH), "libraft_hip_ovl.so")
-        if not os.path.exists(p):
-            raise RuntimeError(f"{p} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(p)
-        for name, (restype, argtypes) in OVL_ABI.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        if lib.raft_hip_ovl_abi() != main.raft_hip_abi_version():
-            raise RuntimeError(f"{p} was built beside ABI {lib.raft_hip_ovl_abi()}, libraft_hip.so is ABI {main.raft_hip_abi_version()}")
-        _ovl_lib = lib
-    return _ovl_lib
-
-
-_frag_lib = None
+    """libraft_hip_ovl.so with every entry point of include/raft_hip_ovl.h declared."""
+    return _load_side_library("ovl")
 
 
 def load_frag_library() -> C.CDLL:
-    """Loads libraft_hip_frag.so (behind libraft_hip.so, whose contexts it takes) and declares every entry point of
-    include/raft_hip_frag.h; the two must have been built beside each other."""
-    global _frag_lib
-    if _frag_lib is None:
-        main = load_library()
-        p = os.path.join(os.path.dirname(_LIB_PATH), "libraft_hip_frag.so")
-        if not os.path.exists(p):
-            raise RuntimeError(f"{p} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(p)
-        for name, (restype, argtypes) in FRAG_ABI.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        if lib.raft_hip_frag_abi() != main.raft_hip_abi_version():
-            raise RuntimeError(f"{p} was built beside ABI {lib.raft_hip_frag_abi()}, libraft_hip.so is ABI {main.raft_hip_abi_version()}")
-        _frag_lib = lib
-    return _frag_lib
-
-
-_rst_lib = None
+    """libraft_hip_frag.so with every entry point of include/raft_hip_frag.h declared."""
+    return _load_side_library("frag")
 
 
 def load_rst_library() -> C.CDLL:
-    """Loads libraft_hip_rst.so (behind libraft_hip.so, whose contexts it takes) and declares every entry point of
-    include/raft_hip_rst.h; the two must have been built beside each other."""
-    global _rst_lib
-    if _rst_lib is None:
-        main = load_library()
-        p = os.path.join(os.path.dirname(_LIB_PATH), "libraft_hip_rst.so")
-        if not os.path.exists(p):
-            raise RuntimeError(f"{p} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        lib = C.CDLL(p)
-        for name, (restype, argtypes) in RST_ABI.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        if lib.raft_hip_rst_abi() != main.raft_hip_abi_version():
-            raise RuntimeError(f"{p} was built beside ABI {lib.raft_hip_rst_abi()}, libraft_hip.so is ABI {main.raft_hip_abi_version()}")
-        _rst_lib = lib
-    return _rst_lib
+    """libraft_hip_rst.so with every entry point of include/raft_hip_rst.h declared."""
+    return _load_side_library("rst")
 
 
 def _cparams(p: RaftParams) -> _Params:
@@ -464,6 +422,19 @@ def _grouped_host(method: str, read_len, rec_offset, records, dtype) -> tuple:
     if _offsets_misfit(off, rl.size) or any(x.size != rec[0].size for x in rec):
         raise ValueError(f"{method}: rec_offset must be [n_runs, n_reads + 1]" + (", qs/qe of equal length" if len(rec) == 2 else ""))
     return (rl, *rec, off), (rl.size, M.ptr(rl), rec[0].size, off.shape[0], M.ptr(off), *[M.ptr(x) for x in rec])
+
+
+_CSR_DTYPES = (np.int64, np.int32, np.int32)      # a CSR table by read: offsets [n_reads + 1], two row arrays
+
+
+def _csr_count(given: bool, table) -> int:
+    """The count a library takes with the three arrays of a table: -1 = the context's own pass, else its rows (0 without row arrays)."""
+    return -1 if not given else (M.count(table[1]) if table[1] is not None else 0)
+
+
+def _summary_dict(sm) -> dict:
+    """A summary structure of 64-bit counts as the dict entries a query's result ends with."""
+    return {name: int(getattr(sm, name)) for name, _ in sm._fields_}
 
 
 def _contexts(engines) -> tuple:
@@ -880,6 +851,35 @@ class Engine:
                    reads_with_runs=int(sm.reads_with_runs), reads_interior=int(sm.reads_interior), reads_uncovered=int(sm.reads_uncovered))
         return out
 
+    # -- the queries about a record stream ------------------------------------------------
+    def _record_query(self, who: str, cols, tables: dict, offsets_error: str = "") -> tuple:
+        """The input of a query about a record stream, ready for its library.  ``cols``: read_len and the record columns that there
+        are; ``tables``: by name the three arrays of a CSR table the caller gave, or three None.  All columns on the device: the
+        device form, every array then a contiguous CUDA tensor of its dtype, on the engine's torch stream; else the host form, every
+        array a contiguous numpy array.  Columns are of one length, a table is (offsets [n_reads + 1], two arrays of one length) --
+        the library is told no lengths: what it will read must be there.  -> on_device, cols, tables' arrays, n_reads, n_rec"""
+        tabs = list(tables.values())
+        on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in cols if x is not None)
+        if on_device:
+            import torch
+            _need_int32_cuda(f"{who} needs", list(cols) + [a for t in tabs for a in t[1:]])
+            for t in tabs:
+                if t[0] is not None and (t[0].dtype != torch.int64 or not t[0].is_cuda or not t[0].is_contiguous()):
+                    raise TypeError(offsets_error)
+            self.use_torch_stream()
+        else:
+            host = lambda a: a.cpu() if hasattr(a, "is_cuda") else a
+            cols = _host_columns([None if x is None else host(x) for x in cols])
+            tabs = [[None if a is None else M.carray(host(a), dt) for a, dt in zip(t, _CSR_DTYPES)] for t in tabs]
+        n_reads = M.count(cols[0])
+        n_rec = M.count(cols[1]) if len(cols) > 1 else 0
+        _need_equal_lengths(cols[2:], n_rec)
+        for what, t in zip(tables, tabs):
+            if any(a is not None for a in t) and (t[0] is None or (t[1] is None) != (t[2] is None) or M.count(t[0]) != n_reads + 1
+                                                  or (t[1] is not None and M.count(t[1]) != M.count(t[2]))):
+                raise ValueError(f"{what} is (offsets [n_reads + 1], two arrays of one length)")
+        return (on_device, cols, *tabs, n_reads, n_rec)
+
     # -- which overlaps lie inside repeats ----------------------------------------------
     last_repeat_overlaps_seconds = 0.0   # device time of the launches of the last repeat_overlaps()
 
@@ -900,32 +900,23 @@ class Engine:
         if len(rep) != 3:
             raise ValueError("repeats is (rep_offset, rep_s, rep_e)")
         ovl = load_ovl_library()
-        on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in cols)
-        n_rec = M.count(qid)
+        on_device, cols, rep, n_reads, n_rec = self._record_query("repeat_overlaps", cols, {"repeats": rep},
+                                                                  "repeat_overlaps needs rep_offset as a contiguous int64 CUDA tensor")
         if on_device:
             import torch
-            _need_int32_cuda("repeat_overlaps needs", cols + rep[1:])
-            if rep[0] is not None and (rep[0].dtype != torch.int64 or not rep[0].is_cuda or not rep[0].is_contiguous()):
-                raise TypeError("repeat_overlaps needs rep_offset as a contiguous int64 CUDA tensor")
-            self.use_torch_stream()
             fn = ovl.raft_hip_repeat_overlaps_device
             cls = torch.zeros(n_rec, dtype=torch.uint8, device=qid.device)
         else:
-            cols = _host_columns([x.cpu() if hasattr(x, "is_cuda") else x for x in cols])
-            rep = [None if a is None else M.carray(a.cpu() if hasattr(a, "is_cuda") else a, dt) for a, dt in zip(rep, (np.int64, np.int32, np.int32))]
             fn = ovl.raft_hip_repeat_overlaps_host
             cls = np.zeros(n_rec, np.uint8)
         args = _plain(cols) + ((C.c_void_p(0),) * 2 if ts is None else ())
-        n_reads = args[0]
-        _need_equal_lengths(cols[2:], args[2])
-        n_rep = -1 if repeats is None else (M.count(rep[1]) if rep[1] is not None else 0)
         out = {"cls": cls, "read_touch": np.zeros(n_reads, np.int32), "read_repeat": np.zeros(n_reads, np.int32), "read_flags": np.zeros(n_reads, np.uint8)}
         sm, err, secs = _OvlSummary(), C.c_int64(-1), C.c_double(0.0)
-        rc = fn(self._ctx, *args, 1 if symmetric else 0, int(min_anchor), n_rep, *[M.ptr(a) for a in rep], *[M.ptr(a) for a in out.values()],
-                C.byref(sm), C.byref(err), C.byref(secs))
+        rc = fn(self._ctx, *args, 1 if symmetric else 0, int(min_anchor), _csr_count(repeats is not None, rep), *[M.ptr(a) for a in rep],
+                *[M.ptr(a) for a in out.values()], C.byref(sm), C.byref(err), C.byref(secs))
         self._check(rc, err.value)
         self.last_repeat_overlaps_seconds = secs.value
-        out.update({name: int(getattr(sm, name)) for name, _ in _OvlSummary._fields_})
+        out.update(_summary_dict(sm))
         return out
 
     # -- which fragments stay contained ------------------------------------------------------
@@ -949,34 +940,18 @@ class Engine:
         if len(tab) != 3 or len(rep) != 3:
             raise ValueError("fragments is (frag_offset, frag_begin, frag_end), repeats is (rep_offset, rep_s, rep_e)")
         frag = load_frag_library()
-        on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in cols)
-        if on_device:
-            import torch
-            _need_int32_cuda("fragment_overlaps needs", cols + tab[1:] + rep[1:])
-            for o in (tab[0], rep[0]):
-                if o is not None and (o.dtype != torch.int64 or not o.is_cuda or not o.is_contiguous()):
-                    raise TypeError("fragment_overlaps needs frag_offset and rep_offset as contiguous int64 CUDA tensors")
-            self.use_torch_stream()
-            fn = frag.raft_hip_frag_overlaps_device
-        else:
-            host = lambda a: a.cpu() if hasattr(a, "is_cuda") else a
-            cols = _host_columns([host(x) for x in cols])
-            tab, rep = ([None if a is None else M.carray(host(a), dt) for a, dt in zip(t, (np.int64, np.int32, np.int32))] for t in (tab, rep))
-            fn = frag.raft_hip_frag_overlaps_host
-        n_reads, n_rec = M.count(cols[0]), M.count(cols[1])
-        _need_equal_lengths(cols[2:], n_rec)
-        for t, what in ((tab, "fragments"), (rep, "repeats")):       # (the library is told no lengths: what it will read must be there)
-            if any(a is not None for a in t) and (any(a is None for a in t) or M.count(t[0]) != n_reads + 1 or M.count(t[1]) != M.count(t[2])):
-                raise ValueError(f"{what} is (offsets [n_reads + 1], two arrays of one length)")
+        on_device, cols, tab, rep, n_reads, n_rec = self._record_query(
+            "fragment_overlaps", cols, {"fragments": tab, "repeats": rep},
+            "fragment_overlaps needs frag_offset and rep_offset as contiguous int64 CUDA tensors")
+        fn = frag.raft_hip_frag_overlaps_device if on_device else frag.raft_hip_frag_overlaps_host
+        n_frag = rows = _csr_count(fragments is not None, tab)
         if fragments is None:
-            n_frag = -1
             last = getattr(self, "summary", None)
             rows = int(last.n_fragments) if last is not None else 0      # (what the outputs need; the library checks the state)
-        else:
-            n_frag = rows = M.count(tab[1]) if tab[1] is not None else 0
-        n_rep = -1 if repeats is None else (M.count(rep[1]) if rep[1] is not None else 0)
+        n_rep = _csr_count(repeats is not None, rep)
         names = ("frag_touch", "frag_span", "frag_contained", "frag_repeat")
         if on_device:
+            import torch
             out = {k: torch.zeros(rows, dtype=torch.int32, device=qid.device) for k in names}
         else:
             out = {k: np.zeros(rows, np.int32) for k in names}
@@ -988,7 +963,7 @@ class Engine:
                 *[M.ptr(a) for a in out.values()], C.byref(sm), C.byref(err), C.byref(secs))
         self._check(rc, err.value)
         self.last_fragment_overlaps_seconds = secs.value
-        out.update({name: int(getattr(sm, name)) for name, _ in _FragSummary._fields_})
+        out.update(_summary_dict(sm))
         return out
 
     # -- one row per repeat run ----------------------------------------------------------------
@@ -1021,32 +996,13 @@ class Engine:
         if len(rep) != 3:
             raise ValueError("repeats is (rep_offset, rep_s, rep_e)")
         rst = load_rst_library()
-        cols = [read_len] + [x for x in rec if x is not None]
-        on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in cols)
-        if on_device:
-            import torch
-            _need_int32_cuda("repeat_stats needs", cols + rep[1:])
-            if rep[0] is not None and (rep[0].dtype != torch.int64 or not rep[0].is_cuda or not rep[0].is_contiguous()):
-                raise TypeError("repeat_stats needs rep_offset as a contiguous int64 CUDA tensor")
-            self.use_torch_stream()
-            fn = rst.raft_hip_repeat_stats_device
-        else:
-            host = lambda a: a.cpu() if hasattr(a, "is_cuda") else a
-            cols = _host_columns([host(x) for x in cols])
-            rep = [None if a is None else M.carray(host(a), dt) for a, dt in zip(rep, (np.int64, np.int32, np.int32))]
-            fn = rst.raft_hip_repeat_stats_host
-        n_reads = M.count(cols[0])
-        n_rec = M.count(cols[1]) if have else 0
-        _need_equal_lengths(cols[1:], n_rec)
-        if any(a is not None for a in rep) and (rep[0] is None or (rep[1] is None) != (rep[2] is None) or M.count(rep[0]) != n_reads + 1
-                                                or (rep[1] is not None and M.count(rep[1]) != M.count(rep[2]))):
-            raise ValueError("repeats is (offsets [n_reads + 1], two arrays of one length)")   # (the library is told no lengths)
+        on_device, cols, rep, n_reads, n_rec = self._record_query("repeat_stats", [read_len] + [x for x in rec if x is not None], {"repeats": rep},
+                                                                  "repeat_stats needs rep_offset as a contiguous int64 CUDA tensor")
+        fn = rst.raft_hip_repeat_stats_device if on_device else rst.raft_hip_repeat_stats_host
+        n_rep = rows = _csr_count(repeats is not None, rep)
         if repeats is None:
-            n_rep = -1
             last = getattr(self, "summary", None)
             rows = int(last.n_repeats) if last is not None else 0        # (what the outputs need; the library checks the state)
-        else:
-            n_rep = rows = M.count(rep[1]) if rep[1] is not None else 0
         out = {k: np.zeros(rows, np.int32) for k in self.RUN_COUNTS}
         out.update({k: (np.zeros(rows, np.int64 if k == "run_cov_sum" else np.int32) if threshold != 0 else None) for k in self.RUN_COVERAGE})
         out["run_flags"] = np.zeros(rows, np.uint8)
@@ -1057,7 +1013,7 @@ class Engine:
                 int(threshold), *[M.ptr(a) for a in out.values()], C.byref(sm), C.byref(err), C.byref(secs))
         self._check(rc, err.value)
         self.last_repeat_stats_seconds = secs.value
-        out.update({name: int(getattr(sm, name)) for name, _ in _RstSummary._fields_})
+        out.update(_summary_dict(sm))
         return out
 
     def census(self, read_len, qid, qs, qe, tid, ts=None, te=None, symmetric: bool = False) -> dict:
@@ -1068,17 +1024,9 @@ class Engine:
         cols = [read_len, qid, qs, qe, tid] + ([] if symmetric else [ts, te])
         if any(x is None for x in cols[:4]) or (not symmetric and (ts is None or te is None)):
             raise ValueError("census needs read_len, qid, qs, qe (and ts, te unless symmetric)")
-        on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in cols if x is not None)
-        if on_device:
-            _need_int32_cuda("census needs", cols)
-            self.use_torch_stream()
-            fn = self._lib.raft_hip_census_device
-        else:
-            cols = _host_columns([x.cpu() if hasattr(x, "is_cuda") else x for x in cols])
-            fn = self._lib.raft_hip_census_host
+        on_device, cols, n_reads, _ = self._record_query("census", cols, {})
+        fn = self._lib.raft_hip_census_device if on_device else self._lib.raft_hip_census_host
         args = _plain(cols) + ((C.c_void_p(0),) * 2 if symmetric else ())
-        n_reads = args[0]
-        _need_equal_lengths(cols[2:], args[2])
         intervals, contained = np.zeros(n_reads, np.int32), np.zeros(n_reads, np.uint8)
         n_cont, err, secs = C.c_int64(0), C.c_int64(-1), C.c_double(0.0)
         rc = fn(self._ctx, *args, 1 if symmetric else 0, M.ptr(intervals), M.ptr(contained), C.byref(n_cont), C.byref(err), C.byref(secs))
