@@ -347,7 +347,10 @@ typedef struct raft_hip_host_outputs {
  * call falls back for any other input (and for any chunk that reports a data error, so that errors are reported
  * exactly as by raft_hip_run_host).  tid/ts/te may be NULL when symmetric_mode = 1.  RAFT_HIP_ERR_TOO_LARGE: a
  * capacity in `out` was too small (size them by the bounds above).  Device-resident outputs of the context are NOT valid
- * after this call (raft_hip_fetch / raft_hip_outputs_device return RAFT_HIP_ERR_STATE).
+ * after this call (raft_hip_fetch / raft_hip_outputs_device return RAFT_HIP_ERR_STATE) -- of a job that ran in chunks.  A job
+ * served in one piece (the fall-back above) leaves its pass on the context as raft_hip_run_host + raft_hip_finish would, in the
+ * transfer encoding: raft_hip_fetch and the queries about a finished pass (raft_hip_cov_histogram and the calls valid where it is)
+ * answer for it.  A caller that has not cut the job itself cannot rely on either; the queries are meant for passes of its own.
  * Derived input (ABI 7).  With symmetric_mode = 1, a stream of one or two sorted runs and reads below 65,535 windows, the
  * engine's host side derives -- chunk by chunk, on threads of its own, beside the uploads of the chunks before -- what
  * raft_hip_run_multi_windows would have to be handed: where every read's records begin (from qid) and the records as

@@ -57,7 +57,9 @@ int raft_hip_frag_abi(void);
  *     of the context; a pass in flight on the stream is waited for.  With n_frag == 0 frag_begin / frag_end may be NULL.  All three
  *     NULL with n_frag == -1: the context's own finished pass -- valid exactly where raft_hip_read_stats is (otherwise
  *     RAFT_HIP_ERR_STATE); n_reads must be that pass's (otherwise RAFT_HIP_ERR_PARAM); nothing of the pass is written and no geometry
- *     is handed out (a later speculated pass still reports RAFT_HIP_SUM_KEPT_GEOMETRY).
+ *     is handed out (a later speculated pass still reports RAFT_HIP_SUM_KEPT_GEOMETRY).  The own table is whole behind a pass run
+ *     with raft_hip_set_emit_cuts(ctx, 0) too: only the cut points (cuts[]) wait for the first fetch that asks for them, every pass
+ *     writes its frag_* rows and rep_* runs itself, and this call neither needs nor materialises the cut points.
  *   raft_hip_frag_repeats: as in raft_hip_repeat_overlaps_*: explicit arrays (rep_offset int64 [n_reads + 1], rep_s / rep_e int32
  *     [n_rep]; checked as there, a violation is RAFT_HIP_ERR_PARAM), or all NULL with n_rep == -1 for the context's own finished pass
  *     (the same state rule), or all NULL with n_rep == 0 for none: frag_repeat is then all zeros.

@@ -1526,8 +1526,8 @@ int raft_hip_fetch_packed(raft_hip_ctx *c, int64_t *cov_offset, uint8_t *cov8, i
 int raft_hip_cov_histogram(raft_hip_ctx *c, int64_t *hist, double *kernel_seconds)
 {
     static_assert(kCovHistBins == RAFT_HIP_COV_HIST_BINS, "cov_hist.hpp and raft_hip.h disagree");
-    if (!c || !hist) return RAFT_HIP_ERR_PARAM;
-    if (!c->finished || c->pending_err) return RAFT_HIP_ERR_STATE;
+    if (!c || !hist) return refuse(c, RAFT_HIP_ERR_PARAM, "raft_hip_cov_histogram", kBadArgs);
+    if (!c->finished || c->pending_err) return refuse(c, RAFT_HIP_ERR_STATE, "raft_hip_cov_histogram", kNoPass);
     HIP_TRY(c, hipSetDevice(c->device));
     const long long B = c->sum.n_bins;
     // codes as the pass wrote them (a caller that had them re-encoded in another width since holds the int32 array as well: that one then)
@@ -1567,8 +1567,8 @@ int raft_hip_cov_histogram(raft_hip_ctx *c, int64_t *hist, double *kernel_second
 // the pass holds, as the histogram above.  Nothing of the pass is written, no geometry goes out.
 int raft_hip_read_stats(raft_hip_ctx *c, int32_t threshold, int64_t *cov_sum, int32_t *cov_max, int32_t *high_windows, double *kernel_seconds)
 {
-    if (!c || threshold < 1) return RAFT_HIP_ERR_PARAM;
-    if (!c->finished || c->pending_err) return RAFT_HIP_ERR_STATE;
+    if (!c || threshold < 1) return refuse(c, RAFT_HIP_ERR_PARAM, "raft_hip_read_stats", "threshold < 1");
+    if (!c->finished || c->pending_err) return refuse(c, RAFT_HIP_ERR_STATE, "raft_hip_read_stats", kNoPass);
     HIP_TRY(c, hipSetDevice(c->device));
     const long long B = c->sum.n_bins;
     const int32_t n_reads = c->sum.n_reads;
@@ -1669,7 +1669,7 @@ int raft_hip_census_device(raft_hip_ctx *c, int32_t n_reads, const int32_t *d_re
                            int32_t *intervals, uint8_t *contained, int64_t *n_contained, int64_t *error_index, double *kernel_seconds)
 {
     const RecordCols rec = census_cols(n_rec, d_qid, d_qs, d_qe, d_tid, d_ts, d_te, symmetric);
-    if (!census_args_ok(c, n_reads, d_read_len, rec, symmetric)) return RAFT_HIP_ERR_PARAM;
+    if (!census_args_ok(c, n_reads, d_read_len, rec, symmetric)) return refuse(c, RAFT_HIP_ERR_PARAM, "census", kBadArgs);
     HIP_TRY(c, hipSetDevice(c->device));
     return census_run(c, n_reads, d_read_len, rec, symmetric, intervals, contained, n_contained, error_index, kernel_seconds);
 }
@@ -1680,7 +1680,7 @@ int raft_hip_census_host(raft_hip_ctx *c, int32_t n_reads, const int32_t *read_l
                          int32_t *intervals, uint8_t *contained, int64_t *n_contained, int64_t *error_index, double *kernel_seconds)
 {
     RecordCols rec = census_cols(n_rec, qid, qs, qe, tid, ts, te, symmetric);
-    if (!census_args_ok(c, n_reads, read_len, rec, symmetric)) return RAFT_HIP_ERR_PARAM;
+    if (!census_args_ok(c, n_reads, read_len, rec, symmetric)) return refuse(c, RAFT_HIP_ERR_PARAM, "census", kBadArgs);
     HIP_TRY(c, hipSetDevice(c->device));
     PHASE(stage_host(c, c->cen_len, read_len, (size_t)n_reads, &read_len));
     PHASE(stage_columns(c, c->cen_col, rec));

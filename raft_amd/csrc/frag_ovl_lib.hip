@@ -26,16 +26,17 @@ struct FragCall {
 // what both forms check before anything is staged: counts, columns, the table and the annotation, the state an own-pass call needs
 int check_call(raft_hip_ctx *c, const FragCall &a)
 {
-    if (!c || a.n_reads < 0 || a.rec.n_rec < 0 || (a.n_reads > 0 && !a.len)) return RAFT_HIP_ERR_PARAM;
-    if (!record_cols_ok(a.rec, a.symmetric != 0, TargetCols::always)) return RAFT_HIP_ERR_PARAM;
+    const char *who = "fragment_overlaps";
+    if (!c || a.n_reads < 0 || a.rec.n_rec < 0 || (a.n_reads > 0 && !a.len)) return refuse(c, RAFT_HIP_ERR_PARAM, who, kBadArgs);
+    if (!record_cols_ok(a.rec, a.symmetric != 0, TargetCols::always)) return refuse(c, RAFT_HIP_ERR_PARAM, who, kBadArgs);
     const CsrKind table = csr_arg_kind(a.table), rep = csr_arg_kind(a.rep);
-    if (table == CsrKind::bad || table == CsrKind::none || rep == CsrKind::bad) return RAFT_HIP_ERR_PARAM;    // (the annotation may be left out)
+    if (table == CsrKind::bad || table == CsrKind::none || rep == CsrKind::bad) return refuse(c, RAFT_HIP_ERR_PARAM, who, kBadArgs);    // (the annotation may be left out)
     const bool own_table = table == CsrKind::own, own_rep = rep == CsrKind::own;
-    if (a.rec.n_rec >= (int64_t(1) << 30) || a.table.count >= (int64_t(1) << 31) - 1) return RAFT_HIP_ERR_TOO_LARGE;
+    if (a.rec.n_rec >= (int64_t(1) << 30) || a.table.count >= (int64_t(1) << 31) - 1) return refuse(c, RAFT_HIP_ERR_TOO_LARGE, who, "too many records or rows");
     if (own_table || own_rep) {                               // the context's own finished pass
-        if (!c->finished || c->pending_err) return RAFT_HIP_ERR_STATE;
-        if (a.n_reads != c->sum.n_reads) return RAFT_HIP_ERR_PARAM;
-        if (own_table && c->sum.n_fragments >= (int64_t(1) << 31) - 1) return RAFT_HIP_ERR_TOO_LARGE;
+        if (!c->finished || c->pending_err) return refuse(c, RAFT_HIP_ERR_STATE, who, kNoPass);
+        if (a.n_reads != c->sum.n_reads) return refuse(c, RAFT_HIP_ERR_PARAM, who, kOtherReads);
+        if (own_table && c->sum.n_fragments >= (int64_t(1) << 31) - 1) return refuse(c, RAFT_HIP_ERR_TOO_LARGE, who, "too many records or rows");
     }
     return RAFT_HIP_OK;
 }

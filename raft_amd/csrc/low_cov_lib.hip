@@ -20,8 +20,8 @@ int raft_hip_low_abi(void) { return RAFT_HIP_ABI_VERSION; }
 int raft_hip_low_coverage(raft_hip_ctx *c, int32_t low_cov, int32_t uncovered_permille, int64_t run_cap, int64_t *low_offset, int32_t *low_s,
                           int32_t *low_e, int32_t *low_windows, uint8_t *low_flags, raft_hip_low_summary *sum, double *kernel_seconds)
 {
-    if (!c || low_cov < 0 || uncovered_permille < 0 || uncovered_permille > 1000) return RAFT_HIP_ERR_PARAM;
-    if (!c->finished || c->pending_err) return RAFT_HIP_ERR_STATE;
+    if (!c || low_cov < 0 || uncovered_permille < 0 || uncovered_permille > 1000) return refuse(c, RAFT_HIP_ERR_PARAM, "raft_hip_low_coverage", kBadArgs);
+    if (!c->finished || c->pending_err) return refuse(c, RAFT_HIP_ERR_STATE, "raft_hip_low_coverage", kNoPass);
     HIP_TRY(c, hipSetDevice(c->device));
     const long long B = c->sum.n_bins;
     const int32_t n_reads = c->sum.n_reads;

@@ -24,15 +24,17 @@ struct OvlCall {
 // what both forms check before anything is staged: counts, columns, the three repeat arrays, the state an own-pass call needs
 int check_call(raft_hip_ctx *c, const OvlCall &a)
 {
-    if (!c || a.n_reads < 0 || a.rec.n_rec < 0 || a.min_anchor < 1 || (a.n_reads > 0 && !a.len)) return RAFT_HIP_ERR_PARAM;
-    if (!record_cols_ok(a.rec, a.symmetric != 0, TargetCols::unless_symmetric)) return RAFT_HIP_ERR_PARAM;
+    const char *who = "repeat_overlaps";
+    if (c && a.min_anchor < 1) return refuse(c, RAFT_HIP_ERR_PARAM, who, "min_anchor < 1");
+    if (!c || a.n_reads < 0 || a.rec.n_rec < 0 || (a.n_reads > 0 && !a.len)) return refuse(c, RAFT_HIP_ERR_PARAM, who, kBadArgs);
+    if (!record_cols_ok(a.rec, a.symmetric != 0, TargetCols::unless_symmetric)) return refuse(c, RAFT_HIP_ERR_PARAM, who, kBadArgs);
     const CsrKind rep = csr_arg_kind(a.rep);
     if (rep == CsrKind::own) {                                // the context's own finished pass
-        if (!c->finished || c->pending_err) return RAFT_HIP_ERR_STATE;
-        if (a.n_reads != c->sum.n_reads) return RAFT_HIP_ERR_PARAM;
+        if (!c->finished || c->pending_err) return refuse(c, RAFT_HIP_ERR_STATE, who, kNoPass);
+        if (a.n_reads != c->sum.n_reads) return refuse(c, RAFT_HIP_ERR_PARAM, who, kOtherReads);
         return RAFT_HIP_OK;
     }
-    return rep == CsrKind::given ? RAFT_HIP_OK : RAFT_HIP_ERR_PARAM;
+    return rep == CsrKind::given ? RAFT_HIP_OK : refuse(c, RAFT_HIP_ERR_PARAM, who, kBadArgs);
 }
 
 int ovl_run(raft_hip_ctx *c, const OvlCall &a)

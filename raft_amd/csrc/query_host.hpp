@@ -9,6 +9,7 @@
 #include "query_args.hpp"
 
 #include <initializer_list>
+#include <string>
 
 namespace raft {
 
@@ -19,6 +20,16 @@ namespace raft {
         const int rc_ = (expr);                                  \
         if (rc_ != RAFT_HIP_OK) return rc_;                      \
     } while (0)
+
+// A query refused on the host before any launch: the code, and the context's message naming the call and the reason (raft_hip_last_error).
+inline int refuse(raft_hip_ctx *c, int code, const char *who, const char *why)
+{
+    if (c) c->last_error = std::string(who) + ": " + why;
+    return code;
+}
+constexpr const char *kNoPass = "the context holds no finished pass (none ran, the last one reported an error, or a host-to-host job ran in chunks)";
+constexpr const char *kOtherReads = "n_reads is not that of the context's finished pass";
+constexpr const char *kBadArgs = "an argument out of range or a missing array";
 
 // blocks of `per_block` items for n of them, one at least and `cap` at most
 inline unsigned grid_for(long long n, long long per_block, long long cap)

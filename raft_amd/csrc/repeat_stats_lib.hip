@@ -28,17 +28,18 @@ struct RstCall {
 // what both forms check before anything is staged: counts, columns, the three repeat arrays, the state the call needs
 int check_call(raft_hip_ctx *c, const RstCall &a)
 {
-    if (!c || a.n_reads < 0 || a.rec.n_rec < 0 || a.threshold < 0 || (a.n_reads > 0 && !a.len)) return RAFT_HIP_ERR_PARAM;
-    if (!record_cols_ok(a.rec, a.symmetric != 0, TargetCols::unless_symmetric)) return RAFT_HIP_ERR_PARAM;
-    if (a.threshold == 0 && (a.win[0] || a.win[1] || a.win[2] || a.win[3] || a.cov_sum)) return RAFT_HIP_ERR_PARAM;
+    const char *who = "repeat_stats";
+    if (!c || a.n_reads < 0 || a.rec.n_rec < 0 || a.threshold < 0 || (a.n_reads > 0 && !a.len)) return refuse(c, RAFT_HIP_ERR_PARAM, who, kBadArgs);
+    if (!record_cols_ok(a.rec, a.symmetric != 0, TargetCols::unless_symmetric)) return refuse(c, RAFT_HIP_ERR_PARAM, who, kBadArgs);
+    if (a.threshold == 0 && (a.win[0] || a.win[1] || a.win[2] || a.win[3] || a.cov_sum)) return refuse(c, RAFT_HIP_ERR_PARAM, who, "threshold 0 takes no coverage output");
     const CsrKind rep = csr_arg_kind(a.rep);
     const bool own = rep == CsrKind::own;
-    if (!own && rep != CsrKind::given) return RAFT_HIP_ERR_PARAM;
-    if (a.rec.n_rec >= (int64_t(1) << 30) || a.rep.count >= (int64_t(1) << 31) - 1) return RAFT_HIP_ERR_TOO_LARGE;
+    if (!own && rep != CsrKind::given) return refuse(c, RAFT_HIP_ERR_PARAM, who, kBadArgs);
+    if (a.rec.n_rec >= (int64_t(1) << 30) || a.rep.count >= (int64_t(1) << 31) - 1) return refuse(c, RAFT_HIP_ERR_TOO_LARGE, who, "too many records or runs");
     if (own || a.threshold >= 1) {                            // the context's own finished pass: its annotation, its coverage
-        if (!c->finished || c->pending_err) return RAFT_HIP_ERR_STATE;
-        if (a.n_reads != c->sum.n_reads) return RAFT_HIP_ERR_PARAM;
-        if (own && c->sum.n_repeats >= (int64_t(1) << 31) - 1) return RAFT_HIP_ERR_TOO_LARGE;
+        if (!c->finished || c->pending_err) return refuse(c, RAFT_HIP_ERR_STATE, who, kNoPass);
+        if (a.n_reads != c->sum.n_reads) return refuse(c, RAFT_HIP_ERR_PARAM, who, kOtherReads);
+        if (own && c->sum.n_repeats >= (int64_t(1) << 31) - 1) return refuse(c, RAFT_HIP_ERR_TOO_LARGE, who, "too many records or runs");
     }
     return RAFT_HIP_OK;
 }

@@ -812,8 +812,9 @@ class Engine:
 
     def read_stats(self, threshold: int | None = None) -> dict:
         """raft_hip_read_stats: per read of the finished pass ``cov_sum`` (int64), ``cov_max`` and ``high_windows`` (int32; windows
-        with coverage >= ``threshold``, by default the context's high_cov = int(est_cov * cov_mul)).  Reduced on the device from the
-        form the pass wrote; cov[] is not downloaded."""
+        with coverage >= ``threshold``, by default the context's high_cov = int(est_cov * cov_mul) under the parameters in force at
+        this call -- after a ``set_params`` those, not the finished pass's).  Reduced on the device from the form the pass wrote;
+        cov[] is not downloaded."""
         if threshold is None:
             threshold = int(self.params.est_cov * self.params.cov_mul)
         last = getattr(self, "summary", None)
@@ -978,9 +979,10 @@ class Engine:
         the census counts them under ``symmetric``), ``run_windows``, ``run_cov_min``, ``run_cov_max``, ``run_high`` (int32) and
         ``run_cov_sum`` (int64) over the run's windows of the finished pass's coverage (``run_high``: windows with coverage >=
         ``threshold``), ``run_flags`` (uint8: RST_EMPTY | RST_AT_START | RST_AT_END; 0 = interior), and the summary's counts.  All
-        arrays are numpy.  ``threshold``: None = the context's high_cov = int(est_cov * cov_mul), 0 = no coverage part (the five
-        coverage arrays are then None).  The columns are int32 torch tensors on this engine's device (``repeats`` must be tensors
-        too) or numpy arrays (staged by the library); qid .. te all None = no records; ts / te may be None when ``symmetric``.
+        arrays are numpy.  ``threshold``: None = the context's high_cov = int(est_cov * cov_mul) under the parameters in force at
+        this call (after a ``set_params`` those, not the finished pass's), 0 = no coverage part (the five coverage arrays are then
+        None).  The columns are int32 torch tensors on this engine's device (``repeats`` must be tensors too) or numpy arrays (staged
+        by the library); qid .. te all None = no records; ts / te may be None when ``symmetric``.
         ``repeats``: None = the annotation of this context's finished pass, else (rep_offset int64 [n_reads + 1], rep_s, rep_e int32)."""
         if read_len is None:
             raise ValueError("repeat_stats needs read_len")

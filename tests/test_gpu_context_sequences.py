@@ -82,13 +82,15 @@ def _read_back(eng, s, route, width, want, what, rng):
             assert int(_scalars(s)[k]) == int(want[k]), f"{what}: {k}"
 
 
-def run_sequence(seed, n_steps=N_STEPS):
-    """Runs generate(seed, n_steps) on one Engine; returns the summary flags of its passes.  Raises with the op list on a mismatch."""
+def run_sequence(seed, n_steps=N_STEPS, ops=None, query=None):
+    """Runs generate(seed, n_steps) on one Engine; returns the summary flags of its passes.  Raises with the op list on a mismatch.
+    ``ops``: that list with ``{"op": "query", ...}`` entries between its ops (tests/query_sequence_model.py), every one handed to
+    ``query(engine, state, flags so far, step, op)`` -- the engine is the second one where the op says ``on="eng2"``."""
     import random
 
     import torch
     from raft_amd import engine, hostio
-    ops = generate(seed, n_steps)
+    ops = generate(seed, n_steps) if ops is None else ops
     rng = random.Random(seed * 7919 + 1)
     dev = "cuda:0"
     st = {"variant": 0, "mode": None, "width": 4, "tensors": None, "content": None, "finished": False}
@@ -110,6 +112,9 @@ def run_sequence(seed, n_steps=N_STEPS):
             what = f"seed {seed}, step {i} ({e['op']})"
             op = e["op"]
             try:
+                if op == "query":
+                    query(eng2 if e.get("on") == "eng2" else eng, st, flags, i, e)
+                    continue
                 if op in ("same", "copy", "alias", "new", "targets"):
                     if op == "same" and st["tensors"] is None:
                         op = "new"; e = dict(e, set=st["content"] or "runs_a")
