@@ -95,7 +95,8 @@ typedef struct raft_hip_summary {
                                    and the pileup kernel read those (4 bytes per interval) instead of coordinate columns;
                                    bit 1 -- the pass was built, without its host wait, on what the context's previous pass over a stream
                                    of the same shape had found (sizes, sorted runs), and the device confirmed it (raft_hip_run_device);
-                                   bits 2, 3, 4 -- see RAFT_HIP_SUM_DEEP_TILES, RAFT_HIP_SUM_RERUN, RAFT_HIP_SUM_KEPT_GEOMETRY.
+                                   bits 2, 3, 4, 5 -- see RAFT_HIP_SUM_DEEP_TILES, RAFT_HIP_SUM_RERUN, RAFT_HIP_SUM_KEPT_GEOMETRY,
+                                   RAFT_HIP_SUM_GRADED_RANGES.
                                    After a re-run the bits describe the pass that produced the results (plus RERUN) */
 } raft_hip_summary;
 #define RAFT_HIP_SUM_BUCKET_WINDOWS 1
@@ -104,6 +105,8 @@ typedef struct raft_hip_summary {
 #define RAFT_HIP_SUM_RERUN 8        /* raft_hip_finish ran the pass more than once (a refuted guess or assumption, a list that had to grow) */
 #define RAFT_HIP_SUM_KEPT_GEOMETRY 16   /* a speculated pass that reused the per-read geometry (window / repeat-slot offsets, tile starts)
                                            of the pass it was built on and only compared the read lengths with that pass's */
+#define RAFT_HIP_SUM_GRADED_RANGES 32   /* the pass that produced the results cut the ranges of its pileup kernel's hand-out by a graded
+                                           quantum (large sets; a host-to-host job: one of its chunks did) */
 
 /* Device-resident outputs of the last run (valid until the next run/destroy).
  * Layout is CSR per read, FASTA-index order (= reference output order):

@@ -200,8 +200,8 @@ static int wait_stamped(raft_hip_ctx *c, const volatile long long *lines, int n_
 // ---- run_pass, phase by phase.  Each phase reads and writes one plain PassPlan and returns an engine error code.
 
 // The environment switches of a pass.  They are read at EVERY pass (tests flip them inside one process), and this is the one place
-// that lists them.  Read elsewhere: RAFT_NO_SPIN by both host waits (wait_stamped); once per process RAFT_HOST_CLOCK (hc_mark),
-// RAFT_GRADED_QUANTUM (choose_quantum) and RAFT_PLACEMENT_TRIALS (engine_ctx.hpp); RAFT_COV_WIDTH at raft_hip_create.
+// that lists them.  Read elsewhere: RAFT_NO_SPIN by both host waits (wait_stamped); once per process RAFT_HOST_CLOCK (hc_mark)
+// and RAFT_PLACEMENT_TRIALS (engine_ctx.hpp); RAFT_COV_WIDTH at raft_hip_create.
 struct PassSwitches {
     bool no_window_kernel;    // RAFT_NO_WINDOW_KERNEL: window records are unpacked to coordinate columns however few the runs
     bool always_inspect;      // RAFT_ALWAYS_INSPECT: no pass verifies in its kernels (A/B measurements; bench.py times both forms)
@@ -214,6 +214,8 @@ struct PassSwitches {
     bool no_bucket_windows;   // RAFT_NO_BUCKET_WINDOWS: the general bucketing sorts coordinate pairs
     int extra_cap;            // RAFT_EXTRA_CAP (tests: tiles without slots of their own); -1: not set
     int deep_min;             // RAFT_DEEP_MIN (tests: ordinary tiles through pileup_deep_kernel); 0: not set
+    bool graded_off;          // RAFT_GRADED_QUANTUM=0: every set gets a uniform quantum, as until round 6
+    long long graded_min;     // RAFT_GRADED_MIN (tests: small sets under the graded quantum): graded from this many tiles' worth of windows on; -1: not set
 };
 static PassSwitches read_switches()
 {
@@ -225,6 +227,9 @@ static PassSwitches read_switches()
     const char *ec = getenv("RAFT_EXTRA_CAP"), *dm = getenv("RAFT_DEEP_MIN");
     s.extra_cap = ec ? std::max(0, atoi(ec)) : -1;
     s.deep_min = dm ? std::max(1, atoi(dm)) : 0;
+    const char *gq = getenv("RAFT_GRADED_QUANTUM"), *gm = getenv("RAFT_GRADED_MIN");
+    s.graded_off = gq && atoi(gq) == 0;
+    s.graded_min = gm ? std::max(0LL, atoll(gm)) : -1;
     return s;
 }
 
@@ -274,6 +279,26 @@ struct PassPlan {
     int symmetric, n_desc;
     long long desc[kMaxSeg];
 };
+
+// The quantum a pass over B windows runs on (choose_quantum; reset_and_decide asks for the remembered shape's B, before the pass has
+// its own): by the context's tuning, the environment's switches and B alone.
+static Quantum quantum_for(const raft_hip_ctx *c, const PassSwitches &sw, long long B)
+{
+    const long long q3 = 3LL * (kTileCap / 128) * 128, q1 = (kTileCap / 128) * 128;
+    const int Q = c->tile_q ? std::max(256, c->tile_q) : (int)std::max(2 * q1, std::min(q3, (B / (2LL * wave_grid_waves(true))) / 128 * 128));
+    // A set with many tiles per worker gets a GRADED quantum (quantum.hpp Quantum): most of each eighth of the set in ranges of
+    // eight tiles' worth, its last tenth in ranges of two -- half the boundaries tile_desc_kernel has to look up, and the kernel's end
+    // waits for a short draw.  (RAFT_GRADED_QUANTUM=0: uniform, as until round 6.  RAFT_GRADED_MIN=<n>: graded from n tiles' worth
+    // of windows on -- 0: always -- so that tests reach this path with small sets.)
+    const long long graded_min = sw.graded_min >= 0 ? sw.graded_min : 64LL * wave_grid_waves(true);
+    const bool graded = !c->tile_q && !sw.graded_off && B / kTileCap >= graded_min && (B + 7) / 8 + 128 < (1LL << 31);
+    return graded ? graded_quantum(B, 8 * (int)q1, 2 * (int)q1, 0.9) : uniform_quantum(Q);
+}
+// (the kind, and for a graded one everything graded_quantum returned)
+static bool same_quantum(const Quantum &a, const Quantum &b)
+{
+    return a.q == b.q && a.share == b.share && a.per_share == b.per_share && a.n_long == b.n_long && a.q_long == b.q_long && a.q_short == b.q_short;
+}
 
 // (RAFT_HOST_CLOCK=1: where the host is, us after entering, when it has issued what -- a speculative pass over an eighth of the
 // bench set is issued in 26 us, 2-3 us a launch: profiles/r06_host_clock.txt)
@@ -374,7 +399,7 @@ static void reset_and_decide(raft_hip_ctx *c, const raft_hip_ctx::PassArgs &in, 
     const bool shape_fits = c->shape.valid && c->shape.n_reads == P.n_reads && c->shape.n_rec == P.n_rec && c->shape.len == (const void *)P.d_len &&
                             c->shape.qid == (const void *)P.d_qid && c->shape.reso == c->prm.reso && c->shape.minbins == c->minbins &&
                             c->shape.interval_length == c->prm.interval_length && c->shape.symmetric_mode == c->prm.symmetric_mode &&
-                            c->shape.tile_q == c->tile_q;
+                            c->shape.tile_q == c->tile_q && same_quantum(c->shape.qz, quantum_for(c, P.sw, c->shape.B));
     P.speculate = P.spec && shape_fits && P.N > 0 && !c->is_lane && !P.sw.no_speculate;
     P.known = P.N > 0 && (P.speculate || (P.no_wait && !P.sw.no_fused_head));
     c->speculated = P.speculate;
@@ -516,14 +541,8 @@ static int find_sizes(raft_hip_ctx *c, const raft_hip_ctx::PassArgs &in, PassPla
 static void choose_quantum(raft_hip_ctx *c, PassPlan &P)
 {
     const long long B = P.B;
-    const long long q3 = 3LL * (kTileCap / 128) * 128, q1 = (kTileCap / 128) * 128;
-    const int Q = c->tile_q ? std::max(256, c->tile_q) : (int)std::max(2 * q1, std::min(q3, (B / (2LL * wave_grid_waves(true))) / 128 * 128));
-    // A set with many tiles per worker gets a GRADED quantum (raft_types.hpp Quantum): most of each eighth of the set in ranges of
-    // eight tiles' worth, its last tenth in ranges of two -- half the boundaries tile_desc_kernel has to look up, and the kernel's end
-    // waits for a short draw.  (RAFT_GRADED_QUANTUM=0: uniform, as until round 6.)
-    static const bool graded_off = [] { const char *e = getenv("RAFT_GRADED_QUANTUM"); return e && atoi(e) == 0; }();
-    const bool graded = !c->tile_q && !graded_off && B / kTileCap >= 64LL * wave_grid_waves(true) && (B + 7) / 8 + 128 < (1LL << 31);
-    P.qz = graded ? graded_quantum(B, 8 * (int)q1, 2 * (int)q1, 0.9) : uniform_quantum(Q);
+    P.qz = quantum_for(c, P.sw, B);
+    if (P.qz.share) c->sum.flags |= RAFT_HIP_SUM_GRADED_RANGES;
     P.n_tiles = P.qz.n_ranges(B);
     // delta4: a tile lists windows in slots of its own, named by a tile id; the number bounds the ids that have slots (the tiles are
     // cut by the workers -- a tile is closed by a full array, 63 reads, a long read or the end of a range; ids are drawn 32 at a time;
@@ -661,7 +680,7 @@ static int decide_source(raft_hip_ctx *c, PassPlan &P)
         c->shape.valid = P.fast && P.table_ok && P.N > 0;
         c->shape.n_reads = P.n_reads; c->shape.n_rec = P.n_rec; c->shape.len = P.d_len; c->shape.qid = P.d_qid;
         c->shape.reso = c->prm.reso; c->shape.minbins = c->minbins; c->shape.interval_length = c->prm.interval_length;
-        c->shape.symmetric_mode = c->prm.symmetric_mode; c->shape.tile_q = c->tile_q;
+        c->shape.symmetric_mode = c->prm.symmetric_mode; c->shape.tile_q = c->tile_q; c->shape.qz = P.qz;
         c->shape.B = P.B; c->shape.RU = P.RU; c->shape.CU = P.CU; c->shape.n_desc = P.n_desc; c->shape.geom_id = c->geom_id;
         for (int i = 0; i < kMaxSeg; ++i) c->shape.desc[i] = i < P.n_desc ? P.desc[i] : 0;
     } else if (!P.speculate && !P.grouped) c->shape.valid = false;
@@ -763,7 +782,8 @@ static int bucket_sides(raft_hip_ctx *c, PassPlan &P, PileupArgs &pa)
         for (int s2 = 0; s2 < kMaxSeg; ++s2) pa.grp.adj[s2] = 0;
     }
     c->sum.interval_path = 1; c->sum.n_segments = P.n_desc + 1; c->sum.n_intervals = -1; // read back in finish
-    c->sum.flags = P.bwin ? RAFT_HIP_SUM_BUCKET_WINDOWS : 0;   // (an assignment: a pass that comes here was neither speculated nor did it keep its geometry)
+    // (an assignment but for the quantum's bit: a pass that comes here was neither speculated nor did it keep its geometry)
+    c->sum.flags = (c->sum.flags & RAFT_HIP_SUM_GRADED_RANGES) | (P.bwin ? RAFT_HIP_SUM_BUCKET_WINDOWS : 0);
     return RAFT_HIP_OK;
 }
 

@@ -426,6 +426,7 @@ struct raft_hip_ctx {
     struct Shape {
         bool valid = false;
         int32_t n_reads = 0, reso = 0, minbins = 0, interval_length = 0, symmetric_mode = 0, tile_q = 0;
+        Quantum qz{};                  // the quantum that pass cut its ranges by (run_pass reads its switches at every pass: tile_first is that quantum's)
         int64_t n_rec = 0;
         const void *len = nullptr, *qid = nullptr;
         long long B = 0, RU = 0, CU = 0;

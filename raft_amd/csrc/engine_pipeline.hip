@@ -387,7 +387,7 @@ bool routed_chunk(Routed &R, raft_hip_ctx *jc, int k)
     R.base_bins += s.n_bins; R.base_rep += s.n_repeats; R.base_frag += s.n_fragments; R.base_exc += n_exc;
     tot.n_bins += s.n_bins; tot.n_repeats += s.n_repeats; tot.n_fragments += s.n_fragments; tot.n_cuts += s.n_cuts;
     tot.n_intervals += s.n_intervals; tot.total_coverage += s.total_coverage; tot.total_repeat_length += s.total_repeat_length;
-    tot.total_read_length += s.total_read_length;
+    tot.total_read_length += s.total_read_length; tot.flags |= s.flags & RAFT_HIP_SUM_GRADED_RANGES;
     R.chain.hand_on(R.published, k);
     return true;
 }
@@ -479,6 +479,7 @@ struct ChunkResult {
     long long n_bins = 0, n_rep = 0, n_frag = 0, n_exc = 0, n_cuts = 0, n_iv = 0;
     long long tot_cov = 0, tot_rep = 0, tot_len = 0;
     int path = 0;
+    int graded = 0;          // RAFT_HIP_SUM_GRADED_RANGES of the chunk's pass
 };
 
 struct PipeShared : TicketChain {                   // the chain of one context's chunks (positions within the context's job)
@@ -911,7 +912,7 @@ Step Lane::run_pass_on_chunk()
     P.stamp(k, "packed");
     cr->n_bins = s.n_bins; cr->n_rep = s.n_repeats; cr->n_frag = s.n_fragments; cr->n_exc = l->n_exc; cr->n_cuts = s.n_cuts;
     cr->n_iv = s.n_intervals; cr->tot_cov = s.total_coverage; cr->tot_rep = s.total_repeat_length; cr->tot_len = s.total_read_length;
-    cr->path = s.interval_path;
+    cr->path = s.interval_path; cr->graded = s.flags & RAFT_HIP_SUM_GRADED_RANGES;
     return Step::kGoOn;
 }
 
@@ -1074,7 +1075,7 @@ int drain_and_collect(PipelinePlan &P)
     for (const ChunkResult &cr : P.res) {
         s.n_bins += cr.n_bins; s.n_repeats += cr.n_rep; s.n_fragments += cr.n_frag; s.n_cuts += cr.n_cuts; s.n_intervals += cr.n_iv;
         s.total_coverage += cr.tot_cov; s.total_repeat_length += cr.tot_rep; s.total_read_length += cr.tot_len;
-        s.interval_path |= cr.path;
+        s.interval_path |= cr.path; s.flags |= cr.graded;
     }
     s.total_windows = s.n_bins;
     if (P.summary) *P.summary = s;

@@ -21,7 +21,7 @@ _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "lib
 
 OK, ERR_PARAM, ERR_READ_ID, ERR_COORD, ERR_FRAGMENT, ERR_NOMEM, ERR_DEVICE, ERR_STATE, ERR_TOO_LARGE = range(9)
 # Summary.flags (RAFT_HIP_SUM_*)
-SUM_BUCKET_WINDOWS, SUM_SPECULATED, SUM_DEEP_TILES, SUM_RERUN, SUM_KEPT_GEOMETRY = 1, 2, 4, 8, 16
+SUM_BUCKET_WINDOWS, SUM_SPECULATED, SUM_DEEP_TILES, SUM_RERUN, SUM_KEPT_GEOMETRY, SUM_GRADED_RANGES = 1, 2, 4, 8, 16, 32
 
 COV_HIST_BINS = 4096              # RAFT_HIP_COV_HIST_BINS
 LOW_INTERIOR, LOW_HEAD, LOW_TAIL, LOW_UNCOVERED = 1, 2, 4, 8    # RAFT_HIP_LOW_*: bits of low_flags (Engine.low_coverage)

@@ -115,3 +115,15 @@ def test_the_parser_reads_every_class():
 def test_a_missing_declaration_is_seen():
     """An entry point bound by name only (ctypes' defaults) differs from any function that takes a parameter."""
     assert (_ctypes_class(_Fn.restype), list(_Fn.argtypes or [])) == (I32, [])
+
+
+def test_summary_flags_mirror_the_header():
+    """Every RAFT_HIP_SUM_* of include/raft_hip.h has its SUM_* in raft_amd/engine.py with the same value, each a bit of its own."""
+    text = open(os.path.join(ROOT, "include", "raft_hip.h")).read()
+    flags = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define RAFT_HIP_SUM_([A-Z0-9_]+)\s+(\d+)\b", text, flags=re.M)}
+    assert set(flags) == {"BUCKET_WINDOWS", "SPECULATED", "DEEP_TILES", "RERUN", "KEPT_GEOMETRY", "GRADED_RANGES"}
+    assert sorted(flags.values()) == [1 << i for i in range(len(flags))]
+    assert flags["GRADED_RANGES"] == 32
+    for name, value in flags.items():
+        assert getattr(engine, "SUM_" + name) == value, name
+    assert {n for n in dir(engine) if n.startswith("SUM_")} == {"SUM_" + n for n in flags}
