@@ -582,8 +582,10 @@ int raft_hip_read_stats(raft_hip_ctx *ctx, int32_t threshold, int64_t *cov_sum, 
  *     contained[r]   bit 0: some record has qid == r, qs == 0, qe == len[r] and len[tid] > len[r]
  *                    bit 1: some record has tid == r, ts == 0, te == len[r] and len[qid] > len[r]; looked at only when symmetric == 0
  *     *n_contained = reads with contained[r] != 0
- * This is the awk of the reference's bash_scripts/map_mm_noncontained.sh:15-16 WITHOUT its identity filter: PAF columns 10 and 11
- * are not tokenised, so a read is flagged whatever the identity of the overlap that contains it.  A record of a read with itself
+ * This is the awk of the reference's bash_scripts/map_mm_noncontained.sh:15-16 WITHOUT its identity filter: the call sees no PAF
+ * column 10 or 11, so a read is flagged whatever the identity of the overlap that contains it.  On a stream that went through
+ * raft_hip_filter_overlaps_* first (raft_hip_flt.h; `raft --min-identity`) it is that script's rule WITH its MINIDENTITY: the
+ * overlaps below it are not in the stream.  A record of a read with itself
  * counts once and never flags (the lengths are equal).
  * intervals, contained: host arrays [n_reads], either may be NULL; n_contained, error_index, kernel_seconds may be NULL.
  * d_tid is required whenever n_rec > 0 (containment compares the two reads' lengths in either mode); d_ts and d_te may be NULL

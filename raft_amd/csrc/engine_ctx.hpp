@@ -371,7 +371,7 @@ struct raft_hip_ctx {
     DevBuf cov8{bufs, DevBuf::kBig}, exc_idx{bufs}, exc_val{bufs}, exc_cnt{bufs};   // transfer encoding of cov[] (raft_hip_fetch_packed)
     DevBuf cov_hist{bufs};             // raft_hip_cov_histogram: RAFT_HIP_COV_HIST_BINS 64-bit counts, cleared at every call
     DevBuf rs_sum{bufs}, rs_max{bufs}, rs_high{bufs};   // raft_hip_read_stats: one value per read each, cleared at every call
-    // The queries beside the engine (libraft_hip_low.so, _ovl.so, _frag.so, _rst.so; all plain allocations: those libraries keep no chunk
+    // The queries beside the engine (libraft_hip_low.so, _ovl.so, _frag.so, _rst.so, _flt.so; all plain allocations: those libraries keep no chunk
     // pool) share what none of them keeps between calls.  q_len, q_col, q_csr_a, q_csr_b: the staging of a host form -- lengths, the six
     // columns, the three arrays of a table the caller gave (repeat_overlaps, repeat_stats: the repeats in q_csr_a; fragment_overlaps:
     // the fragment table in q_csr_a, the repeats in q_csr_b).  q_cov, q_abs: for a pass that holds no int32 array where a query needs
@@ -401,6 +401,12 @@ struct raft_hip_ctx {
     DevBuf rst_digest{bufs}, rst_run_read{bufs}, rst_slot{bufs}, rst_ctl{bufs}, rst_sum{bufs}, rst_flags{bufs};
     DevBuf rst_cnt[3] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
     DevBuf rst_win[4] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
+    // raft_hip_filter_overlaps_* (filter_lib.hip): the keep bitmap, the kept records of every tile and their prefix, the scan's partial
+    // sums, the control words; the host form's staging of PAF columns 10 and 11 (the six columns: q_col) and the kept columns before
+    // they go to the caller
+    DevBuf fl_bits{bufs}, fl_tile_cnt{bufs}, fl_tile_base{bufs}, fl_scan{bufs}, fl_ctl{bufs};
+    DevBuf fl_quality[2] = {DevBuf{bufs}, DevBuf{bufs}};
+    DevBuf fl_out[6] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
     // raft_hip_census_*: counts and flag words per read, the flags as bytes, {first bad record, reads with a flag}; staging of the host form --
     // the census's own and not q_*: it lives in the engine library, whose chunk pool backs the columns (kBig), which the side libraries' must not be
     DevBuf cen_cnt{bufs}, cen_flags{bufs}, cen_out{bufs}, cen_ctl{bufs}, cen_len{bufs};

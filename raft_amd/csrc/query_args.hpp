@@ -58,5 +58,10 @@ inline bool aligned16(const RecordCols &r)
     for (int k = 0; k < 6; ++k) bits |= reinterpret_cast<uintptr_t>(r.col[k]);
     return (bits & 15) == 0;
 }
+// ... and two columns beside the six (filter_overlaps: matches, block)
+inline bool aligned16(const RecordCols &r, const void *a, const void *b)
+{
+    return aligned16(r) && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
+}
 
 } // namespace raft

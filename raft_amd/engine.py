@@ -96,6 +96,10 @@ class _RstSummary(C.Structure):
                                          "sides_touch", "sides_span", "sides_inside", "windows", "cov_sum")]
 
 
+class _FltSummary(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_records", "n_kept", "below_identity", "below_span", "first_kept", "symmetric")]
+
+
 class _Outputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("cov_offset", "cov", "rep_offset", "rep_s", "rep_e", "cut_offset", "cuts",
                                           "frag_offset", "frag_read", "frag_begin", "frag_end")]
@@ -202,6 +206,14 @@ RST_ABI = {
 }
 RST_EMPTY, RST_AT_START, RST_AT_END = 1, 2, 4
 
+# ... and those of include/raft_hip_flt.h (libraft_hip_flt.so): load_flt_library declares these
+_FLT_CALL = [_vp, _i64] + [_vp] * 8 + [_i32, _i32] + [_vp] * 6 + [_P(_FltSummary), _P(_f64)]
+FLT_ABI = {
+    "raft_hip_flt_abi": (C.c_int, []),
+    "raft_hip_filter_overlaps_device": (C.c_int, _FLT_CALL),
+    "raft_hip_filter_overlaps_host": (C.c_int, _FLT_CALL),
+}
+
 
 @dataclass
 class Summary:
@@ -272,7 +284,8 @@ def load_library(path: str | None = None) -> C.CDLL:
 
 # The libraries beside libraft_hip.so: tag -> (file, its ABI table, the function that says which engine ABI it was built beside)
 _SIDE = {"low": ("libraft_hip_low.so", LOW_ABI, "raft_hip_low_abi"), "ovl": ("libraft_hip_ovl.so", OVL_ABI, "raft_hip_ovl_abi"),
-         "frag": ("libraft_hip_frag.so", FRAG_ABI, "raft_hip_frag_abi"), "rst": ("libraft_hip_rst.so", RST_ABI, "raft_hip_rst_abi")}
+         "frag": ("libraft_hip_frag.so", FRAG_ABI, "raft_hip_frag_abi"), "rst": ("libraft_hip_rst.so", RST_ABI, "raft_hip_rst_abi"),
+         "flt": ("libraft_hip_flt.so", FLT_ABI, "raft_hip_flt_abi")}
 _side_libs: dict = {}
 
 
@@ -314,6 +327,11 @@ def load_frag_library() -> C.CDLL:
 def load_rst_library() -> C.CDLL:
     """libraft_hip_rst.so with every entry point of include/raft_hip_rst.h declared."""
     return _load_side_library("rst")
+
+
+def load_flt_library() -> C.CDLL:
+    """libraft_hip_flt.so with every entry point of include/raft_hip_flt.h declared."""
+    return _load_side_library("flt")
 
 
 def _cparams(p: RaftParams) -> _Params:
@@ -1017,6 +1035,55 @@ class Engine:
         self.last_repeat_stats_seconds = secs.value
         out.update(_summary_dict(sm))
         return out
+
+    # -- which records go into a job at all -------------------------------------------------------
+    last_filter_overlaps_seconds = 0.0   # device time of the launches of the last filter_overlaps()
+
+    def filter_overlaps(self, qid, qs, qe, tid, ts, te, matches=None, block=None, *, min_identity_permille: int = 0, min_span: int = 0,
+                        out=None) -> dict:
+        """raft_hip_filter_overlaps_device / _host (libraft_hip_flt.so): the records with ``matches * 1000 >= min_identity_permille *
+        block`` (``block`` > 0, ``matches`` >= 0; PAF columns 10 and 11) and ``qe - qs >= min_span and te - ts >= min_span``, in
+        their order; 0 switches a rule off, and ``matches`` / ``block`` may be None without the identity rule.  -> ``columns`` (the
+        six kept columns, views of length ``n_kept``: what ``run_device`` / ``run_host`` / ``census`` take), ``n_kept``,
+        ``below_identity``, ``below_span`` (a record may count in both), ``first_kept`` (index in the input, -1 = none),
+        ``symmetric`` (the symmetric flag of the kept stream) and ``kernel_seconds``.  The columns are int32 torch tensors on this
+        engine's device -- the kept columns then go into ``out`` (six such tensors of the input's length that overlap no input) or
+        into tensors from ``device_tensor``, which live until ``device_free`` or the context's end -- or numpy arrays (staged by the library), where ``out`` may be the input arrays
+        themselves: the stream is then compacted in place."""
+        cols = [qid, qs, qe, tid, ts, te, matches, block]
+        given = [x for x in cols if x is not None]
+        on_device = bool(given) and all(hasattr(x, "is_cuda") and x.is_cuda for x in given)
+        n_rec = M.count(given[0]) if given else 0
+        if out is not None and len(out) != 6:
+            raise ValueError("filter_overlaps: out is six columns")
+        flt = load_flt_library()
+        if on_device:
+            import torch
+            _need_int32_cuda("filter_overlaps needs", cols + list(out or []))
+            self.use_torch_stream()
+            if out is None:
+                out = [self.device_tensor(n_rec, torch.int32) for _ in range(6)]
+            fn = flt.raft_hip_filter_overlaps_device
+        else:
+            cols = _host_columns([x.cpu() if hasattr(x, "is_cuda") else x for x in cols])
+            if out is None:
+                out = [np.empty(n_rec, np.int32) for _ in range(6)]
+            elif any(not isinstance(o, np.ndarray) or o.dtype != np.int32 or not o.flags["C_CONTIGUOUS"] for o in out):
+                raise TypeError("filter_overlaps needs out as contiguous int32 numpy arrays")
+            fn = flt.raft_hip_filter_overlaps_host
+        _need_equal_lengths(cols, n_rec)
+        if any(M.count(o) < n_rec for o in out):
+            raise ValueError("filter_overlaps: every out column needs room for all records")
+        sm, secs = _FltSummary(), C.c_double(0.0)
+        rc = fn(self._ctx, n_rec, *[M.ptr(x) for x in cols], int(min_identity_permille), int(min_span), *[M.ptr(o) for o in out],
+                C.byref(sm), C.byref(secs))
+        self._check(rc)
+        self.last_filter_overlaps_seconds = secs.value
+        res = _summary_dict(sm)
+        del res["n_records"]
+        res["kernel_seconds"] = secs.value
+        res["columns"] = tuple(o[: res["n_kept"]] for o in out)
+        return res
 
     def census(self, read_len, qid, qs, qe, tid, ts=None, te=None, symmetric: bool = False) -> dict:
         """raft_hip_census_device / _host: ``intervals`` (int32 [n_reads]: what a pass piles up on each read under ``symmetric``),

@@ -210,6 +210,44 @@ inline std::string repeat_stats_line(int64_t runs, int64_t interior, int64_t spa
            ", sides inside a repeat = " + std::to_string(sides_inside);
 }
 
+// --min-identity PCT: digits with at most one decimal digit ("99", "99.5", "100", "0.1"), 0 < PCT <= 100, into per mille (the
+// min_identity_permille of raft_hip_filter_overlaps_*).  No sign, no blank, no exponent, nothing behind a point but one digit, and no
+// strtod: the text is the number.
+inline bool parse_min_identity(const char *text, int32_t *permille)
+{
+    if (!text || *text < '0' || *text > '9') return false;
+    int64_t v = 0;
+    const char *q = text;
+    for (; *q >= '0' && *q <= '9'; ++q) {
+        v = v * 10 + (*q - '0');
+        if (v > 100) return false;
+    }
+    v *= 10;
+    if (*q == '.') {
+        if (q[1] < '0' || q[1] > '9') return false;
+        v += q[1] - '0';
+        q += 2;
+    }
+    if (*q || v < 1 || v > 1000) return false;
+    *permille = (int32_t)v;
+    return true;
+}
+
+// --min-overlap BASES: BASES (min_span of raft_hip_filter_overlaps_*) is a whole number >= 1 written in digits alone, at most INT32_MAX.
+inline bool parse_min_overlap(const char *text, int32_t *min_span) { return parse_min_anchor(text, min_span); }
+
+// Either option makes the job tokenise PAF columns 10 and 11 and filter its records before anything else sees them.
+inline bool filter_wanted(int32_t permille, int32_t min_span) { return permille > 0 || min_span > 0; }
+
+// ... the options' stdout line, directly behind the reference's own last line and before the lines of the other options, from
+// raft_hip_flt_summary's counts
+inline std::string filter_overlaps_line(int32_t permille, int32_t min_span, int64_t records, int64_t kept, int64_t below_identity, int64_t below_span)
+{
+    return "INFO, filter_overlaps(), min_identity = " + std::to_string(permille) + " per mille, min_overlap = " + std::to_string(min_span) +
+           ", records = " + std::to_string(records) + ", kept = " + std::to_string(kept) + ", below identity = " + std::to_string(below_identity) +
+           ", below overlap = " + std::to_string(below_span);
+}
+
 // ... a read counts as uncovered when more than this many thousandths of its bases lie in low runs (yacrd's default for "not covered")
 constexpr int32_t kLowUncoveredPermille = 800;
 

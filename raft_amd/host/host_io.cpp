@@ -16,6 +16,7 @@
 #include "../../include/raft_host_ovl.h"
 #include "../../include/raft_host_frag.h"
 #include "../../include/raft_host_rst.h"
+#include "../../include/raft_host_flt.h"
 
 #include <emmintrin.h>
 #include <zlib.h>
@@ -36,6 +37,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -492,6 +494,7 @@ struct raft_host_text {                  // a file's bytes in memory (inflated i
 
 struct raft_host_paf {
     std::unique_ptr<int32_t[]> col[6];   // allocated untouched: the workers' copies are the first writes
+    std::unique_ptr<int32_t[]> quality[2];   // PAF fields 10 and 11, only from raft_host_paf_parse_quality (raft_host_flt.h)
     size_t n = 0;
     int symmetric = 0;                   // chop.hpp:175-184: some record after the first mirrors the first
 };
@@ -876,7 +879,19 @@ int raft_host_paf_load(const char *path, const raft_host_reads *reads, raft_host
     return rc;
 }
 
-int raft_host_paf_parse(raft_host_text *text, const raft_host_reads *reads, raft_host_paf **out, char *err_name, int err_cap)
+} // extern "C"
+
+namespace {
+
+// What kQuality adds to a line that waits for its names: where field 10 ends and where field 11 lies (empty on a ten-field line).
+struct NoQuality {};
+struct QualityEnds { size_t e10, b11, e11; };
+
+// raft_host_paf_parse (kQuality = false) and raft_host_paf_parse_quality (true: fields 10 and 11 as two more columns,
+// include/raft_host_flt.h).  One body, so that the two cannot drift apart; everything the second adds stands behind `if constexpr`,
+// and the first compiles to what it was.
+template <bool kQuality>
+int paf_parse(raft_host_text *text, const raft_host_reads *reads, raft_host_paf **out, char *err_name, int err_cap)
 {
     if (!text || !reads || !out) return RAFT_HOST_ERR_ARG;
     *out = nullptr;
@@ -954,8 +969,12 @@ int raft_host_paf_parse(raft_host_text *text, const raft_host_reads *reads, raft
     for (int t = 0; t < T; ++t) off[(size_t)t + 1] = off[(size_t)t] + chunks[(size_t)t].lines;
     std::unique_ptr<raft_host_paf> P(new raft_host_paf());
     for (int k = 0; k < 6; ++k) P->col[k].reset(new int32_t[off[(size_t)T] ? off[(size_t)T] : 1]);
+    if constexpr (kQuality)
+        for (int k = 0; k < 2; ++k) P->quality[k].reset(new int32_t[off[(size_t)T] ? off[(size_t)T] : 1]);
     parallel_for(T, [&](int t) {
         Chunk &C = chunks[(size_t)t];
+        int32_t *const out_quality[2] = {kQuality ? P->quality[0].get() + off[(size_t)t] : nullptr, kQuality ? P->quality[1].get() + off[(size_t)t] : nullptr};
+        (void)out_quality;
         int32_t *const out_col[6] = {P->col[0].get() + off[(size_t)t], P->col[1].get() + off[(size_t)t], P->col[2].get() + off[(size_t)t],
                                      P->col[3].get() + off[(size_t)t], P->col[4].get() + off[(size_t)t], P->col[5].get() + off[(size_t)t]};
         const char *lastq = nullptr, *lastt = nullptr;
@@ -995,13 +1014,14 @@ int raft_host_paf_parse(raft_host_text *text, const raft_host_reads *reads, raft
             if (i == b || i - b == 19) return num(std::string(data + b, e - b).c_str());       // blanks, signs, overflow: strtol's rules
             return (int32_t)(uint32_t)v;       // trailing garbage ends the number, as in strtol
         };
-        size_t line_start = pos0, tab[10];
+        constexpr int kTabs = kQuality ? 11 : 10;         // tab positions kept per line (field 11 ends at the eleventh)
+        size_t line_start = pos0, tab[kTabs];
         int nt = 0;
         bool stop = false;
         // Lines wait in groups of eight for their target names: the hashes first (each fetching its slot of the name table), then the
         // slots (each fetching its name's bytes), then the lines in file order -- two cache misses per group where there were two per
         // line.  The query name is the line before's nearly always (a PAF grouped by query).
-        struct Pending { size_t ls, tab[9]; unsigned long long hv; };
+        struct Pending : std::conditional_t<kQuality, QualityEnds, NoQuality> { size_t ls, tab[9]; unsigned long long hv; };
         constexpr int kGroup = 8;
         Pending pend[kGroup];
         int np = 0;
@@ -1028,6 +1048,10 @@ int raft_host_paf_parse(raft_host_text *text, const raft_host_reads *reads, raft
                 const size_t at = C.n++;
                 out_col[0][at] = a; out_col[1][at] = v_qs; out_col[2][at] = v_qe;
                 out_col[3][at] = b; out_col[4][at] = v_ts; out_col[5][at] = v_te;
+                if constexpr (kQuality) {
+                    out_quality[0][at] = field_num(L.tab[8] + 1, L.e10);
+                    out_quality[1][at] = field_num(L.b11, L.e11);
+                }
                 if (have0 && a == r0[3] && b == r0[0] && v_ts == r0[1] && v_te == r0[2] && v_qs == r0[4] && v_qe == r0[5] && L.ls != rec0_pos)
                     C.mirror = true;
             }
@@ -1041,10 +1065,16 @@ int raft_host_paf_parse(raft_host_text *text, const raft_host_reads *reads, raft
             Pending &L = pend[np++];
             L.ls = ls;
             for (int k = 0; k < 9; ++k) L.tab[k] = tab[k];
+            if constexpr (kQuality) {
+                const size_t eol = nl > ls && data[nl - 1] == '\r' ? nl - 1 : nl;
+                L.e10 = ntabs >= 10 ? tab[9] : eol;
+                L.b11 = ntabs >= 10 ? tab[9] + 1 : eol;
+                L.e11 = ntabs >= 11 ? tab[10] : eol;
+            }
             if (np == kGroup) flush();
         };
         auto delim = [&](size_t p) {
-            if (data[p] == '\t') { if (nt < 10) tab[nt] = p; ++nt; }
+            if (data[p] == '\t') { if (nt < kTabs) tab[nt] = p; ++nt; }
             else line_done(p);
         };
         size_t i = pos0;
@@ -1073,14 +1103,44 @@ int raft_host_paf_parse(raft_host_text *text, const raft_host_reads *reads, raft
     size_t n_rec = 0;
     for (int t = 0; t < T; ++t) {                         // (gaps: lines that were no records)
         const Chunk &C = chunks[(size_t)t];
-        if (n_rec != off[(size_t)t] && C.n)
+        if (n_rec != off[(size_t)t] && C.n) {
             for (int k = 0; k < 6; ++k) memmove(P->col[k].get() + n_rec, P->col[k].get() + off[(size_t)t], C.n * sizeof(int32_t));
+            if constexpr (kQuality)
+                for (int k = 0; k < 2; ++k) memmove(P->quality[k].get() + n_rec, P->quality[k].get() + off[(size_t)t], C.n * sizeof(int32_t));
+        }
         n_rec += C.n;
     }
     P->n = n_rec;
     *out = P.release();
     return RAFT_HOST_OK;
 }
+
+} // namespace
+
+extern "C" {
+
+int raft_host_paf_parse(raft_host_text *text, const raft_host_reads *reads, raft_host_paf **out, char *err_name, int err_cap)
+{
+    return paf_parse<false>(text, reads, out, err_name, err_cap);
+}
+
+int raft_host_paf_parse_quality(raft_host_text *text, const raft_host_reads *reads, raft_host_paf **out, char *err_name, int err_cap)
+{
+    return paf_parse<true>(text, reads, out, err_name, err_cap);
+}
+
+int raft_host_paf_load_quality(const char *path, const raft_host_reads *reads, raft_host_paf **out, char *err_name, int err_cap)
+{
+    if (!path || !reads || !out) return RAFT_HOST_ERR_ARG;
+    *out = nullptr;
+    raft_host_text *text = nullptr;
+    int rc = raft_host_text_read(path, &text);
+    if (rc == RAFT_HOST_OK) rc = raft_host_paf_parse_quality(text, reads, out, err_name, err_cap);
+    raft_host_text_free(text);
+    return rc;
+}
+
+const int32_t *raft_host_paf_quality(const raft_host_paf *p, int k) { return (p && k >= 0 && k < 2) ? p->quality[k].get() : nullptr; }
 
 // The grouped form of a tokenised query column (include/raft_hip.h raft_hip_run_device_grouped): hifiasm writes its PAF
 // grouped by query (reference README.md:36-38), so the column is a handful of runs sorted by read id.  Pass 1 finds the

@@ -21,6 +21,8 @@
 #include "../../include/raft_host_frag.h"
 #include "../../include/raft_hip_rst.h"
 #include "../../include/raft_host_rst.h"
+#include "../../include/raft_hip_flt.h"
+#include "../../include/raft_host_flt.h"
 #include "../../include/raft_host.h"
 #include "cli_plan.hpp"
 
@@ -53,6 +55,8 @@ struct Params {            // param.hpp:18-31
     int32_t low_cov = -1;          // --low-cov C: PREFIX.low_coverage.bed, the runs of windows with coverage <= C (raft_hip_low_coverage); -1: not asked for
     bool fragment_overlaps = false;   // --fragment-overlaps: PREFIX.fragments.tsv, the fragments against the overlaps (raft_hip_frag_overlaps_host)
     bool repeat_stats = false;     // --repeat-stats: PREFIX.long_repeats.stats.tsv, one line per repeat run (raft_hip_repeat_stats_host)
+    int32_t min_identity = 0;      // --min-identity PCT, in per mille, and --min-overlap BASES: only the records that pass go into the job
+    int32_t min_overlap = 0;       // (raft_hip_filter_overlaps_host, before anything else sees the stream); 0: not asked for
     int32_t min_anchor = 0;        // --repeat-overlaps A: PREFIX.repeat_overlaps.tsv and .records.tsv (raft_hip_repeat_overlaps_host); 0: not asked for
 };
 
@@ -86,6 +90,9 @@ struct Job {
     raft_host_paf *paf = nullptr;
     int64_t n_rec = 0;
     const int32_t *col[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};    // qid, qs, qe, tid, ts, te
+    // --min-identity / --min-overlap: what the filter counted; from then on n_rec, col and the symmetric flag are the kept stream's
+    raft_hip_flt_summary flt_sum{};
+    bool filtered = false;
     // the arrays everything comes back in (made and page-locked on out_prep)
     raft_cli::Capacities cap;
     std::vector<int64_t> cov_off, rep_off, frag_off;
@@ -196,7 +203,8 @@ void parse_options(Job &j, int argc, char *argv[])
     // (the short options and their quirks are the reference's; the long options are this program's own)
     static const struct option long_options[] = {{"read-stats", no_argument, nullptr, 1000}, {"low-cov", required_argument, nullptr, 1001},
                                                  {"repeat-overlaps", required_argument, nullptr, 1002}, {"fragment-overlaps", no_argument, nullptr, 1003},
-                                                 {"repeat-stats", no_argument, nullptr, 1004},
+                                                 {"repeat-stats", no_argument, nullptr, 1004}, {"min-identity", required_argument, nullptr, 1005},
+                                                 {"min-overlap", required_argument, nullptr, 1006},
                                                  {nullptr, 0, nullptr, 0}};
     while ((option = getopt_long(argc, argv, "r:e:m:l:i:p:f:v:o:", long_options, nullptr)) != -1) {
         switch (option) {
@@ -205,6 +213,8 @@ void parse_options(Job &j, int argc, char *argv[])
         case 1002: if (!raft_cli::parse_min_anchor(optarg, &p.min_anchor)) print_help(p); break;
         case 1003: p.fragment_overlaps = true; break;
         case 1004: p.repeat_stats = true; break;
+        case 1005: if (!raft_cli::parse_min_identity(optarg, &p.min_identity)) print_help(p); break;
+        case 1006: if (!raft_cli::parse_min_overlap(optarg, &p.min_overlap)) print_help(p); break;
         case 'r': p.reso = atoi(optarg); break;
         case 'e': p.auto_cov = strcmp(optarg, "auto") == 0; p.est_cov = p.auto_cov ? 0 : atoi(optarg); break;
         case 'm': p.cov_mul = std::stod(optarg); break;
@@ -395,7 +405,8 @@ void parse_paf(Job &j)
     j.paf_reader.join();
     stage(j, "paf_read (rest)");
     int rc = j.paf_text_rc;
-    if (rc == RAFT_HOST_OK) rc = raft_host_paf_parse(j.paf_text, j.reads, &j.paf, bad, sizeof bad);
+    const bool quality = raft_cli::filter_wanted(j.p.min_identity, j.p.min_overlap);       // (the filter reads PAF columns 10 and 11)
+    if (rc == RAFT_HOST_OK) rc = (quality ? raft_host_paf_parse_quality : raft_host_paf_parse)(j.paf_text, j.reads, &j.paf, bad, sizeof bad);
     // (a big file's GBs of touched pages are left to the process exit: unmapping them here -- or beside the pass, where it holds
     // the address space's lock against the page-locking -- cost 0.3 s of a 4 s run)
     if (raft_host_paf_count(j.paf) < (1 << 22)) { raft_host_text_free(j.paf_text); j.paf_text = nullptr; }
@@ -415,16 +426,37 @@ void await_devices(Job &j)
     stage(j, "device_wait");
 }
 
+// --min-identity / --min-overlap: the records that pass (include/raft_hip_flt.h) are compacted in place, on the first context, before
+// anything else sees the stream -- the survey, the census, the split of a multi-device or pre-split job, every query: the job is the
+// job on a file of the kept lines.  Without the options nothing happens here.
+void filter_overlaps(Job &j)
+{
+    if (!raft_cli::filter_wanted(j.p.min_identity, j.p.min_overlap)) return;
+    j.out_prep.join();                                  // (its raft_hip_reserve uses the context this call runs on)
+    int32_t *out[6];
+    for (int k = 0; k < 6; ++k) out[k] = const_cast<int32_t *>(j.col[k]);
+    const int rc = raft_hip_filter_overlaps_host(j.ctxs[0], j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.col[4], j.col[5],
+                                                 raft_host_paf_quality(j.paf, 0), raft_host_paf_quality(j.paf, 1), j.p.min_identity, j.p.min_overlap,
+                                                 out[0], out[1], out[2], out[3], out[4], out[5], &j.flt_sum, nullptr);
+    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, -1));
+    j.n_rec = j.flt_sum.n_kept;
+    j.filtered = true;
+    stage(j, "filter_overlaps");
+}
+
+// the symmetric flag of the stream the job runs on: the tokeniser's, or the filter's for the kept stream
+bool stream_symmetric(const Job &j) { return j.filtered ? j.flt_sum.symmetric != 0 : raft_host_paf_symmetric(j.paf) != 0; }
+
 // The tokeniser already knows whether the PAF is symmetric (chop.hpp:171-184, found while the lines were in
 // registers): the engine is told, so it neither scans for the mirror of record 0 nor -- for a symmetric PAF -- is
 // handed the target columns at all (half of the upload).  bring_up is joined: j.hp may be written.
 void hand_over_symmetric_flag(Job &j)
 {
-    j.hp.symmetric_mode = j.ranks > 0 ? -1 : (raft_host_paf_symmetric(j.paf) ? 1 : 0);   // (a pre-split job finds the flag across its ranks)
-    j.out_prep.join();                                  // (its raft_hip_reserve reads the contexts' parameters: done before they change)
+    j.hp.symmetric_mode = j.ranks > 0 ? -1 : (stream_symmetric(j) ? 1 : 0);   // (a pre-split job finds the flag across its ranks)
+    if (j.out_prep.joinable()) j.out_prep.join();       // (its raft_hip_reserve reads the contexts' parameters: done before they change)
     const int rc = raft_hip_set_params(j.ctxs[0], &j.hp);
     if (rc != RAFT_HIP_OK) die(std::string("ERROR, raft_hip_set_params(), ") + raft_hip_strerror(rc));
-    j.sym = j.hp.symmetric_mode == 1 || (j.ranks > 0 && raft_host_paf_symmetric(j.paf));
+    j.sym = j.hp.symmetric_mode == 1 || (j.ranks > 0 && stream_symmetric(j));
 }
 
 // What the survey changes on the first context, and the way back: its own parameters, two-byte codes and no cut points for the
@@ -818,6 +850,9 @@ void print_totals(Job &j, int argc, char *argv[])
     for (int i = 0; i < argc; ++i) fprintf(stdout, " %s", argv[i]);
     fflush(stdout);
     std::cout << "\n";
+    if (j.filtered)
+        std::cout << raft_cli::filter_overlaps_line(j.p.min_identity, j.p.min_overlap, j.flt_sum.n_records, j.flt_sum.n_kept, j.flt_sum.below_identity,
+                                                    j.flt_sum.below_span) << "\n";
     if (j.p.read_stats) std::cout << "INFO, read_stats(), contained reads = " << j.n_contained << " of " << j.n_reads << "\n";
     if (j.p.low_cov >= 0)
         std::cout << "INFO, low_coverage(), low_cov = " << j.p.low_cov << ", runs = " << j.low_sum.n_runs << ", reads with an interior run = "
@@ -860,6 +895,7 @@ int main(int argc, char *argv[])
     start_output_prep(job);
     parse_paf(job);
     await_devices(job);
+    filter_overlaps(job);
     hand_over_symmetric_flag(job);
     survey(job);
     census(job);

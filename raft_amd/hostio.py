@@ -65,6 +65,12 @@ FRAG_ABI = {
 RST_ABI = {
     "raft_host_write_repeat_stats": (C.c_int, [_str, _i32, _P(_str)] + [_vp] * 12),
 }
+# ... and of include/raft_host_flt.h
+FLT_ABI = {
+    "raft_host_paf_parse_quality": (C.c_int, [_vp, _vp, _P(_vp), _str, C.c_int]),
+    "raft_host_paf_load_quality": (C.c_int, [_str, _vp, _P(_vp), _str, C.c_int]),
+    "raft_host_paf_quality": (_P(_i32), [_vp, C.c_int]),
+}
 
 
 class HostError(RuntimeError):
@@ -83,7 +89,7 @@ def load_library():
         if not os.path.exists(_LIB_PATH):
             raise RuntimeError(f"{_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         lib = C.CDLL(_LIB_PATH)
-        for name, (restype, argtypes) in list(ABI.items()) + list(LOW_ABI.items()) + list(OVL_ABI.items()) + list(FRAG_ABI.items()) + list(RST_ABI.items()):
+        for name, (restype, argtypes) in list(ABI.items()) + list(LOW_ABI.items()) + list(OVL_ABI.items()) + list(FRAG_ABI.items()) + list(RST_ABI.items()) + list(FLT_ABI.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -183,9 +189,12 @@ class Reads:
             pass
 
 
-def load_paf(path: str, reads: Reads, with_flag: bool = False, two_steps: bool = False):
+def load_paf(path: str, reads: Reads, with_flag: bool = False, two_steps: bool = False, quality: bool = False):
     """-> six int32 numpy columns (qid, qs, qe, tid, ts, te) [, the symmetric flag the tokeniser found].
-    ``two_steps``: raft_host_text_read + raft_host_paf_parse (what the CLI does, the first beside the loading of the reads)."""
+    ``two_steps``: raft_host_text_read + raft_host_paf_parse (what the CLI does, the first beside the loading of the reads).
+    ``quality``: the ``_quality`` parser of include/raft_host_flt.h -- eight columns, the last two PAF fields 10 and 11 (matches,
+    block; block is 0 on a ten-field line)."""
+    parse, load = ("raft_host_paf_parse_quality", "raft_host_paf_load_quality") if quality else ("raft_host_paf_parse", "raft_host_paf_load")
     lib = load_library()
     h = C.c_void_p()
     err = C.create_string_buffer(256)
@@ -193,14 +202,16 @@ def load_paf(path: str, reads: Reads, with_flag: bool = False, two_steps: bool =
         t = C.c_void_p()
         rc = lib.raft_host_text_read(path.encode(), C.byref(t))
         if rc == OK:
-            rc = lib.raft_host_paf_parse(t, reads._h, C.byref(h), err, 256)
+            rc = getattr(lib, parse)(t, reads._h, C.byref(h), err, 256)
         lib.raft_host_text_free(t)
     else:
-        rc = lib.raft_host_paf_load(path.encode(), reads._h, C.byref(h), err, 256)
+        rc = getattr(lib, load)(path.encode(), reads._h, C.byref(h), err, 256)
     if rc != OK:
         raise HostError(rc, err.value.decode())
     n = lib.raft_host_paf_count(h)
     cols = [np.ctypeslib.as_array(lib.raft_host_paf_column(h, k), shape=(n,)).copy() if n else np.empty(0, np.int32) for k in range(6)]
+    if quality:
+        cols += [np.ctypeslib.as_array(lib.raft_host_paf_quality(h, k), shape=(n,)).copy() if n else np.empty(0, np.int32) for k in range(2)]
     sym = int(lib.raft_host_paf_symmetric(h))
     lib.raft_host_paf_free(h)
     return (cols, sym) if with_flag else cols
