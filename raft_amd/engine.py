@@ -100,6 +100,11 @@ class _FltSummary(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_records", "n_kept", "below_identity", "below_span", "first_kept", "symmetric")]
 
 
+class _EndSummary(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_records", "kind_invalid", "kind_internal", "kind_query_contained", "kind_target_contained", "kind_end3",
+                                         "kind_end5", "kind_self", "reads_linked", "reads_contained", "reads_isolated", "reads_dead5", "reads_dead3")]
+
+
 class _Outputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("cov_offset", "cov", "rep_offset", "rep_s", "rep_e", "cut_offset", "cuts",
                                           "frag_offset", "frag_read", "frag_begin", "frag_end")]
@@ -214,6 +219,18 @@ FLT_ABI = {
     "raft_hip_filter_overlaps_host": (C.c_int, _FLT_CALL),
 }
 
+# ... and those of include/raft_hip_end.h (libraft_hip_end.so): load_end_library declares these
+_END_CALL = [_vp] + _COLUMNS + [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _P(_EndSummary), _P(_i64), _P(_f64)]
+END_ABI = {
+    "raft_hip_end_abi": (C.c_int, []),
+    "raft_hip_overlap_ends_device": (C.c_int, _END_CALL),
+    "raft_hip_overlap_ends_host": (C.c_int, _END_CALL),
+}
+# the kinds of a record and the statuses of a read (RAFT_HIP_END_*, RAFT_HIP_END_READ_*), and the rows of the counts table
+END_INVALID, END_INTERNAL, END_QUERY_CONTAINED, END_TARGET_CONTAINED, END_QUERY_3, END_QUERY_5, END_SELF = range(7)
+END_READ_LINKED, END_READ_CONTAINED, END_READ_ISOLATED, END_READ_DEAD5, END_READ_DEAD3 = range(5)
+END_COUNTS = ("internal", "contained_in", "contains", "end5", "end3")
+
 
 @dataclass
 class Summary:
@@ -285,7 +302,7 @@ def load_library(path: str | None = None) -> C.CDLL:
 # The libraries beside libraft_hip.so: tag -> (file, its ABI table, the function that says which engine ABI it was built beside)
 _SIDE = {"low": ("libraft_hip_low.so", LOW_ABI, "raft_hip_low_abi"), "ovl": ("libraft_hip_ovl.so", OVL_ABI, "raft_hip_ovl_abi"),
          "frag": ("libraft_hip_frag.so", FRAG_ABI, "raft_hip_frag_abi"), "rst": ("libraft_hip_rst.so", RST_ABI, "raft_hip_rst_abi"),
-         "flt": ("libraft_hip_flt.so", FLT_ABI, "raft_hip_flt_abi")}
+         "flt": ("libraft_hip_flt.so", FLT_ABI, "raft_hip_flt_abi"), "end": ("libraft_hip_end.so", END_ABI, "raft_hip_end_abi")}
 _side_libs: dict = {}
 
 
@@ -332,6 +349,11 @@ def load_rst_library() -> C.CDLL:
 def load_flt_library() -> C.CDLL:
     """libraft_hip_flt.so with every entry point of include/raft_hip_flt.h declared."""
     return _load_side_library("flt")
+
+
+def load_end_library() -> C.CDLL:
+    """libraft_hip_end.so with every entry point of include/raft_hip_end.h declared."""
+    return _load_side_library("end")
 
 
 def _cparams(p: RaftParams) -> _Params:
@@ -1083,6 +1105,55 @@ class Engine:
         del res["n_records"]
         res["kernel_seconds"] = secs.value
         res["columns"] = tuple(o[: res["n_kept"]] for o in out)
+        return res
+
+    # -- what kind of overlap each record is, which end of each read it supports ---------------------
+    last_overlap_ends_seconds = 0.0      # device time of the launches of the last overlap_ends()
+
+    def overlap_ends(self, read_len, qid, qs, qe, tid, ts, te, strand, *, max_overhang: int = 1000, min_ratio_permille: int = 800,
+                     symmetric: bool = False, kinds: bool = False) -> dict:
+        """raft_hip_overlap_ends_device / _host (libraft_hip_end.so): every record under the rule of include/raft_hip_end.h -- an
+        internal match, a containment, a dovetail at the query's 5' or 3' end -- with ``strand`` one uint8 per record (1: PAF field 5
+        begins with '-'; ``hostio.load_paf(strand=True)`` gives it).  -> ``counts`` (int32 [5, n_reads]: the rows ``END_COUNTS``),
+        ``status`` (uint8 [n_reads]: ``END_READ_*``), the summary's counts (``kind_*``, ``reads_*``, ``n_records``),
+        ``kernel_seconds`` and, with ``kinds=True``, ``kinds`` (uint8 per record, ``END_*``: a torch tensor on the input's
+        device, else a numpy array).  The columns are torch tensors on this engine's device (int32; strand uint8) or numpy
+        arrays (staged by the library).  Unless ``symmetric`` a record counts on its target's row as well.  Independent of any pass."""
+        cols = [read_len, qid, qs, qe, tid, ts, te]
+        if any(x is None for x in cols) or strand is None:
+            raise ValueError("overlap_ends needs read_len, the six columns and strand")
+        on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in cols + [strand])
+        end = load_end_library()
+        if on_device:
+            import torch
+            _need_int32_cuda("overlap_ends needs", cols)
+            if strand.dtype != torch.uint8 or not strand.is_contiguous():
+                raise TypeError("overlap_ends needs strand as a contiguous uint8 CUDA tensor")
+            self.use_torch_stream()
+            fn = end.raft_hip_overlap_ends_device
+        else:
+            cols = _host_columns([x.cpu() if hasattr(x, "is_cuda") else x for x in cols])
+            strand = M.carray(strand.cpu() if hasattr(strand, "is_cuda") else strand, np.uint8)
+            fn = end.raft_hip_overlap_ends_host
+        n_reads, n_rec = M.count(cols[0]), M.count(cols[1])
+        _need_equal_lengths(cols[1:] + [strand], n_rec)
+        kind_out = None
+        if kinds:
+            if on_device:
+                import torch
+                kind_out = torch.empty(n_rec, dtype=torch.uint8, device=strand.device)
+            else:
+                kind_out = np.zeros(n_rec, np.uint8)
+        counts, status = np.zeros((5, n_reads), np.int32), np.zeros(n_reads, np.uint8)
+        sm, err, secs = _EndSummary(), C.c_int64(-1), C.c_double(0.0)
+        rc = fn(self._ctx, *_plain(cols), M.ptr(strand), int(max_overhang), int(min_ratio_permille), 1 if symmetric else 0, M.ptr(counts),
+                M.ptr(status), M.ptr(kind_out), C.byref(sm), C.byref(err), C.byref(secs))
+        self._check(rc, err.value)
+        self.last_overlap_ends_seconds = secs.value
+        res = {"counts": counts, "status": status, "kernel_seconds": secs.value}
+        if kinds:
+            res["kinds"] = kind_out
+        res.update(_summary_dict(sm))
         return res
 
     def census(self, read_len, qid, qs, qe, tid, ts=None, te=None, symmetric: bool = False) -> dict:

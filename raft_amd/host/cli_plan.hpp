@@ -5,6 +5,7 @@
 #pragma once
 #include "../../include/raft_hip.h"
 #include "../../include/raft_hip_low.h"
+#include "../../include/raft_host_end.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -246,6 +247,38 @@ inline std::string filter_overlaps_line(int32_t permille, int32_t min_span, int6
     return "INFO, filter_overlaps(), min_identity = " + std::to_string(permille) + " per mille, min_overlap = " + std::to_string(min_span) +
            ", records = " + std::to_string(records) + ", kept = " + std::to_string(kept) + ", below identity = " + std::to_string(below_identity) +
            ", below overlap = " + std::to_string(below_span);
+}
+
+// --overlap-ends H: H (max_overhang of raft_hip_overlap_ends_*) is a whole number >= 0 written in digits alone, at most INT32_MAX.
+inline bool parse_overlap_ends(const char *text, int32_t *max_overhang) { return parse_low_cov(text, max_overhang); }
+
+// --ends-min-ratio F: F (min_ratio_permille) is a whole number written in digits alone, 0 .. 1000; without the option it is
+constexpr int32_t kEndsMinRatioDefault = 800;
+inline bool parse_ends_min_ratio(const char *text, int32_t *permille)
+{
+    int32_t v = 0;
+    if (!parse_low_cov(text, &v) || v > 1000) return false;
+    *permille = v;
+    return true;
+}
+
+// ... which means nothing without --overlap-ends (max_overhang < 0: not asked for): a usage error
+inline bool ends_options_ok(int32_t max_overhang, bool ratio_given) { return max_overhang >= 0 || !ratio_given; }
+
+// The columns the tokeniser keeps beside the six (the mask of raft_host_paf_parse_with): fields 10 and 11 for the filter, the strand
+// for --overlap-ends.
+inline int paf_columns(bool filter, bool overlap_ends) { return (filter ? RAFT_HOST_PAF_QUALITY : 0) | (overlap_ends ? RAFT_HOST_PAF_STRAND : 0); }
+
+// ... the option's stdout line, the last one, from raft_hip_end_summary's counts (dead ends: the reads with status dead5 or dead3)
+inline std::string overlap_ends_line(int32_t max_overhang, int32_t min_ratio, int64_t records, int64_t internal, int64_t query_contained,
+                                     int64_t target_contained, int64_t dovetail, int64_t self, int64_t invalid, int64_t reads_contained,
+                                     int64_t dead_ends, int64_t reads_isolated, int32_t n_reads)
+{
+    return "INFO, overlap_ends(), max_overhang = " + std::to_string(max_overhang) + ", min_ratio = " + std::to_string(min_ratio) +
+           " per mille, records = " + std::to_string(records) + ", internal = " + std::to_string(internal) + ", query contained = " +
+           std::to_string(query_contained) + ", target contained = " + std::to_string(target_contained) + ", dovetail = " + std::to_string(dovetail) +
+           ", self = " + std::to_string(self) + ", invalid = " + std::to_string(invalid) + ", contained reads = " + std::to_string(reads_contained) +
+           ", dead ends = " + std::to_string(dead_ends) + ", isolated reads = " + std::to_string(reads_isolated) + " of " + std::to_string(n_reads);
 }
 
 // ... a read counts as uncovered when more than this many thousandths of its bases lie in low runs (yacrd's default for "not covered")

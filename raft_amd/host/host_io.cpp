@@ -17,6 +17,7 @@
 #include "../../include/raft_host_frag.h"
 #include "../../include/raft_host_rst.h"
 #include "../../include/raft_host_flt.h"
+#include "../../include/raft_host_end.h"
 
 #include <emmintrin.h>
 #include <zlib.h>
@@ -495,6 +496,7 @@ struct raft_host_text {                  // a file's bytes in memory (inflated i
 struct raft_host_paf {
     std::unique_ptr<int32_t[]> col[6];   // allocated untouched: the workers' copies are the first writes
     std::unique_ptr<int32_t[]> quality[2];   // PAF fields 10 and 11, only from raft_host_paf_parse_quality (raft_host_flt.h)
+    std::unique_ptr<uint8_t[]> strand;       // PAF field 5 begins with '-', only from raft_host_paf_parse_with (raft_host_end.h)
     size_t n = 0;
     int symmetric = 0;                   // chop.hpp:175-184: some record after the first mirrors the first
 };
@@ -889,8 +891,9 @@ struct QualityEnds { size_t e10, b11, e11; };
 
 // raft_host_paf_parse (kQuality = false) and raft_host_paf_parse_quality (true: fields 10 and 11 as two more columns,
 // include/raft_host_flt.h).  One body, so that the two cannot drift apart; everything the second adds stands behind `if constexpr`,
-// and the first compiles to what it was.
-template <bool kQuality>
+// and the first compiles to what it was.  kStrand (raft_host_paf_parse_with, include/raft_host_end.h): field 5 as one more byte per
+// record, behind `if constexpr` as well.
+template <bool kQuality, bool kStrand = false>
 int paf_parse(raft_host_text *text, const raft_host_reads *reads, raft_host_paf **out, char *err_name, int err_cap)
 {
     if (!text || !reads || !out) return RAFT_HOST_ERR_ARG;
@@ -971,10 +974,13 @@ int paf_parse(raft_host_text *text, const raft_host_reads *reads, raft_host_paf 
     for (int k = 0; k < 6; ++k) P->col[k].reset(new int32_t[off[(size_t)T] ? off[(size_t)T] : 1]);
     if constexpr (kQuality)
         for (int k = 0; k < 2; ++k) P->quality[k].reset(new int32_t[off[(size_t)T] ? off[(size_t)T] : 1]);
+    if constexpr (kStrand) P->strand.reset(new uint8_t[off[(size_t)T] ? off[(size_t)T] : 1]);
     parallel_for(T, [&](int t) {
         Chunk &C = chunks[(size_t)t];
         int32_t *const out_quality[2] = {kQuality ? P->quality[0].get() + off[(size_t)t] : nullptr, kQuality ? P->quality[1].get() + off[(size_t)t] : nullptr};
         (void)out_quality;
+        uint8_t *const out_strand = kStrand ? P->strand.get() + off[(size_t)t] : nullptr;
+        (void)out_strand;
         int32_t *const out_col[6] = {P->col[0].get() + off[(size_t)t], P->col[1].get() + off[(size_t)t], P->col[2].get() + off[(size_t)t],
                                      P->col[3].get() + off[(size_t)t], P->col[4].get() + off[(size_t)t], P->col[5].get() + off[(size_t)t]};
         const char *lastq = nullptr, *lastt = nullptr;
@@ -1052,6 +1058,7 @@ int paf_parse(raft_host_text *text, const raft_host_reads *reads, raft_host_paf 
                     out_quality[0][at] = field_num(L.tab[8] + 1, L.e10);
                     out_quality[1][at] = field_num(L.b11, L.e11);
                 }
+                if constexpr (kStrand) out_strand[at] = (L.tab[3] + 1 < L.tab[4] && data[L.tab[3] + 1] == '-') ? 1 : 0;   // paf.hpp:69
                 if (have0 && a == r0[3] && b == r0[0] && v_ts == r0[1] && v_te == r0[2] && v_qs == r0[4] && v_qe == r0[5] && L.ls != rec0_pos)
                     C.mirror = true;
             }
@@ -1107,6 +1114,7 @@ int paf_parse(raft_host_text *text, const raft_host_reads *reads, raft_host_paf 
             for (int k = 0; k < 6; ++k) memmove(P->col[k].get() + n_rec, P->col[k].get() + off[(size_t)t], C.n * sizeof(int32_t));
             if constexpr (kQuality)
                 for (int k = 0; k < 2; ++k) memmove(P->quality[k].get() + n_rec, P->quality[k].get() + off[(size_t)t], C.n * sizeof(int32_t));
+            if constexpr (kStrand) memmove(P->strand.get() + n_rec, P->strand.get() + off[(size_t)t], C.n);
         }
         n_rec += C.n;
     }
@@ -1141,6 +1149,49 @@ int raft_host_paf_load_quality(const char *path, const raft_host_reads *reads, r
 }
 
 const int32_t *raft_host_paf_quality(const raft_host_paf *p, int k) { return (p && k >= 0 && k < 2) ? p->quality[k].get() : nullptr; }
+
+// include/raft_host_end.h: the tokeniser under a mask of columns
+int raft_host_paf_parse_with(raft_host_text *text, const raft_host_reads *reads, int columns, raft_host_paf **out, char *err_name, int err_cap)
+{
+    switch (columns) {
+    case 0: return paf_parse<false>(text, reads, out, err_name, err_cap);
+    case RAFT_HOST_PAF_QUALITY: return paf_parse<true>(text, reads, out, err_name, err_cap);
+    case RAFT_HOST_PAF_STRAND: return paf_parse<false, true>(text, reads, out, err_name, err_cap);
+    case RAFT_HOST_PAF_QUALITY | RAFT_HOST_PAF_STRAND: return paf_parse<true, true>(text, reads, out, err_name, err_cap);
+    }
+    if (out) *out = nullptr;
+    return RAFT_HOST_ERR_ARG;
+}
+
+int raft_host_paf_load_with(const char *path, const raft_host_reads *reads, int columns, raft_host_paf **out, char *err_name, int err_cap)
+{
+    if (!path || !reads || !out) return RAFT_HOST_ERR_ARG;
+    *out = nullptr;
+    if (columns & ~(RAFT_HOST_PAF_QUALITY | RAFT_HOST_PAF_STRAND)) return RAFT_HOST_ERR_ARG;
+    raft_host_text *text = nullptr;
+    int rc = raft_host_text_read(path, &text);
+    if (rc == RAFT_HOST_OK) rc = raft_host_paf_parse_with(text, reads, columns, out, err_name, err_cap);
+    raft_host_text_free(text);
+    return rc;
+}
+
+const uint8_t *raft_host_paf_strand(const raft_host_paf *p) { return p ? p->strand.get() : nullptr; }
+
+// PREFIX.overlap_ends.tsv: name, length, the five counts, the status
+int raft_host_write_overlap_ends(const char *path, const raft_host_reads *reads, const int32_t *counts, const uint8_t *status)
+{
+    if (!path || !reads) return RAFT_HOST_ERR_ARG;
+    const long long n = (long long)reads->lens.size();
+    if (n > 0 && (!counts || !status)) return RAFT_HOST_ERR_ARG;
+    return write_ordered(path, n, 1 << 16, [](long long) { return 1LL; },
+                         [&](long long i, std::string &o) {
+                             o.append(reads->names.name((int32_t)i), reads->names.name_len((int32_t)i));
+                             o.push_back('\t'); put_num(o, reads->lens[(size_t)i]);
+                             for (int k = 0; k < 5; ++k) { o.push_back('\t'); put_num(o, counts[(long long)k * n + i]); }
+                             o.push_back('\t'); put_num(o, status[i]);
+                             o.push_back('\n');
+                         });
+}
 
 // The grouped form of a tokenised query column (include/raft_hip.h raft_hip_run_device_grouped): hifiasm writes its PAF
 // grouped by query (reference README.md:36-38), so the column is a handful of runs sorted by read id.  Pass 1 finds the

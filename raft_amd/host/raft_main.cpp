@@ -23,6 +23,8 @@
 #include "../../include/raft_host_rst.h"
 #include "../../include/raft_hip_flt.h"
 #include "../../include/raft_host_flt.h"
+#include "../../include/raft_hip_end.h"
+#include "../../include/raft_host_end.h"
 #include "../../include/raft_host.h"
 #include "cli_plan.hpp"
 
@@ -57,6 +59,9 @@ struct Params {            // param.hpp:18-31
     bool repeat_stats = false;     // --repeat-stats: PREFIX.long_repeats.stats.tsv, one line per repeat run (raft_hip_repeat_stats_host)
     int32_t min_identity = 0;      // --min-identity PCT, in per mille, and --min-overlap BASES: only the records that pass go into the job
     int32_t min_overlap = 0;       // (raft_hip_filter_overlaps_host, before anything else sees the stream); 0: not asked for
+    int32_t overlap_ends = -1;     // --overlap-ends H: PREFIX.overlap_ends.tsv, the kind of every record and the ends of every read (raft_hip_overlap_ends_host); -1: not asked for
+    int32_t ends_min_ratio = raft_cli::kEndsMinRatioDefault;   // --ends-min-ratio F, in per mille
+    bool ends_ratio_given = false;
     int32_t min_anchor = 0;        // --repeat-overlaps A: PREFIX.repeat_overlaps.tsv and .records.tsv (raft_hip_repeat_overlaps_host); 0: not asked for
 };
 
@@ -93,6 +98,11 @@ struct Job {
     // --min-identity / --min-overlap: what the filter counted; from then on n_rec, col and the symmetric flag are the kept stream's
     raft_hip_flt_summary flt_sum{};
     bool filtered = false;
+    // --overlap-ends: the strand byte of every record (the tokeniser's, or strand_kept for the kept stream), the reads' counts and status
+    const uint8_t *strand = nullptr;
+    std::vector<uint8_t> strand_kept, end_status;
+    std::vector<int32_t> end_counts;
+    raft_hip_end_summary end_sum{};
     // the arrays everything comes back in (made and page-locked on out_prep)
     raft_cli::Capacities cap;
     std::vector<int64_t> cov_off, rep_off, frag_off;
@@ -205,6 +215,7 @@ void parse_options(Job &j, int argc, char *argv[])
                                                  {"repeat-overlaps", required_argument, nullptr, 1002}, {"fragment-overlaps", no_argument, nullptr, 1003},
                                                  {"repeat-stats", no_argument, nullptr, 1004}, {"min-identity", required_argument, nullptr, 1005},
                                                  {"min-overlap", required_argument, nullptr, 1006},
+                                                 {"overlap-ends", required_argument, nullptr, 1007}, {"ends-min-ratio", required_argument, nullptr, 1008},
                                                  {nullptr, 0, nullptr, 0}};
     while ((option = getopt_long(argc, argv, "r:e:m:l:i:p:f:v:o:", long_options, nullptr)) != -1) {
         switch (option) {
@@ -215,6 +226,8 @@ void parse_options(Job &j, int argc, char *argv[])
         case 1004: p.repeat_stats = true; break;
         case 1005: if (!raft_cli::parse_min_identity(optarg, &p.min_identity)) print_help(p); break;
         case 1006: if (!raft_cli::parse_min_overlap(optarg, &p.min_overlap)) print_help(p); break;
+        case 1007: if (!raft_cli::parse_overlap_ends(optarg, &p.overlap_ends)) print_help(p); break;
+        case 1008: if (!raft_cli::parse_ends_min_ratio(optarg, &p.ends_min_ratio)) print_help(p); p.ends_ratio_given = true; break;
         case 'r': p.reso = atoi(optarg); break;
         case 'e': p.auto_cov = strcmp(optarg, "auto") == 0; p.est_cov = p.auto_cov ? 0 : atoi(optarg); break;
         case 'm': p.cov_mul = std::stod(optarg); break;
@@ -227,6 +240,7 @@ void parse_options(Job &j, int argc, char *argv[])
         default: print_help(p);
         }
     }
+    if (!raft_cli::ends_options_ok(p.overlap_ends, p.ends_ratio_given)) print_help(p);
     if (argc < optind + 2) print_help(p);
     if (p.est_cov <= 0 && !p.auto_cov) {
         std::cout << "ERROR, main(), estimated coverage must be set properly\n";
@@ -405,8 +419,9 @@ void parse_paf(Job &j)
     j.paf_reader.join();
     stage(j, "paf_read (rest)");
     int rc = j.paf_text_rc;
-    const bool quality = raft_cli::filter_wanted(j.p.min_identity, j.p.min_overlap);       // (the filter reads PAF columns 10 and 11)
-    if (rc == RAFT_HOST_OK) rc = (quality ? raft_host_paf_parse_quality : raft_host_paf_parse)(j.paf_text, j.reads, &j.paf, bad, sizeof bad);
+    // (the filter reads PAF columns 10 and 11, --overlap-ends the strand; neither: the plain parser)
+    const int columns = raft_cli::paf_columns(raft_cli::filter_wanted(j.p.min_identity, j.p.min_overlap), j.p.overlap_ends >= 0);
+    if (rc == RAFT_HOST_OK) rc = raft_host_paf_parse_with(j.paf_text, j.reads, columns, &j.paf, bad, sizeof bad);
     // (a big file's GBs of touched pages are left to the process exit: unmapping them here -- or beside the pass, where it holds
     // the address space's lock against the page-locking -- cost 0.3 s of a 4 s run)
     if (raft_host_paf_count(j.paf) < (1 << 22)) { raft_host_text_free(j.paf_text); j.paf_text = nullptr; }
@@ -414,6 +429,7 @@ void parse_paf(Job &j)
     if (rc != RAFT_HOST_OK) die(std::string("ERROR, create_pileup(), cannot read ") + j.paf_fn);
     j.n_rec = raft_host_paf_count(j.paf);
     for (int k = 0; k < 6; ++k) j.col[k] = raft_host_paf_column(j.paf, k);
+    j.strand = raft_host_paf_strand(j.paf);
     stage(j, "paf_load");
 }
 
@@ -426,6 +442,22 @@ void await_devices(Job &j)
     stage(j, "device_wait");
 }
 
+// --overlap-ends beside the filter: the strand must follow the kept records.  The filter copies its id columns without using them as
+// indices (include/raft_hip_flt.h), so one more call of its host form under the same P and L, with the strand bytes widened to int32
+// in the query-id slot, compacts them; what it writes for the other five columns is dropped.
+void keep_strand(Job &j)
+{
+    std::vector<int32_t> wide(j.strand, j.strand + j.n_rec), drop[5];
+    for (auto &d : drop) d.resize((size_t)j.n_rec);
+    raft_hip_flt_summary sum{};
+    const int rc = raft_hip_filter_overlaps_host(j.ctxs[0], j.n_rec, wide.data(), j.col[1], j.col[2], j.col[3], j.col[4], j.col[5],
+                                                 raft_host_paf_quality(j.paf, 0), raft_host_paf_quality(j.paf, 1), j.p.min_identity, j.p.min_overlap,
+                                                 wide.data(), drop[0].data(), drop[1].data(), drop[2].data(), drop[3].data(), drop[4].data(), &sum, nullptr);
+    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, -1));
+    j.strand_kept.assign(wide.begin(), wide.begin() + sum.n_kept);
+    j.strand = j.strand_kept.data();
+}
+
 // --min-identity / --min-overlap: the records that pass (include/raft_hip_flt.h) are compacted in place, on the first context, before
 // anything else sees the stream -- the survey, the census, the split of a multi-device or pre-split job, every query: the job is the
 // job on a file of the kept lines.  Without the options nothing happens here.
@@ -435,6 +467,7 @@ void filter_overlaps(Job &j)
     j.out_prep.join();                                  // (its raft_hip_reserve uses the context this call runs on)
     int32_t *out[6];
     for (int k = 0; k < 6; ++k) out[k] = const_cast<int32_t *>(j.col[k]);
+    if (j.p.overlap_ends >= 0) keep_strand(j);          // (first: it reads the columns as tokenised)
     const int rc = raft_hip_filter_overlaps_host(j.ctxs[0], j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.col[4], j.col[5],
                                                  raft_host_paf_quality(j.paf, 0), raft_host_paf_quality(j.paf, 1), j.p.min_identity, j.p.min_overlap,
                                                  out[0], out[1], out[2], out[3], out[4], out[5], &j.flt_sum, nullptr);
@@ -602,6 +635,21 @@ void census(Job &j)
                                         j.sym ? nullptr : j.col[5], j.sym ? 1 : 0, j.cen_intervals.data(), j.cen_contained.data(), &j.n_contained, &bad_index, nullptr);
     if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
     stage(j, "census");
+}
+
+// --overlap-ends: the kind of every record and the ends of every read it supports (raft_hip_overlap_ends_host), on the first context
+// over the whole job's stream -- a multi-device or pre-split job is classified whole, before the split -- under the job's final
+// symmetric flag, before prepare_input() writes window records over the query column.
+void overlap_ends(Job &j)
+{
+    if (j.p.overlap_ends < 0) return;
+    j.end_counts.resize((size_t)j.n_reads * 5); j.end_status.resize((size_t)j.n_reads);
+    int64_t bad_index = -1;
+    const int rc = raft_hip_overlap_ends_host(j.ctxs[0], j.n_reads, j.rl, j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.col[4], j.col[5], j.strand,
+                                              j.p.overlap_ends, j.p.ends_min_ratio, j.sym ? 1 : 0, j.end_counts.data(), j.end_status.data(), nullptr,
+                                              &j.end_sum, &bad_index, nullptr);
+    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
+    stage(j, "overlap_ends");
 }
 
 // hifiasm writes its PAF grouped by query (reference README.md:36-38): a symmetric stream of at most four runs sorted by
@@ -828,6 +876,9 @@ void write_outputs(Job &j)
     if (p.min_anchor > 0) write_repeat_overlaps(j);
     if (p.fragment_overlaps) write_fragment_overlaps(j);
     if (p.repeat_stats) write_repeat_stats(j);
+    if (p.overlap_ends >= 0 &&
+        raft_host_write_overlap_ends((p.prefix + ".overlap_ends.tsv").c_str(), j.reads, j.end_counts.data(), j.end_status.data()) != RAFT_HOST_OK)
+        die("ERROR, overlap_ends(), cannot write output files");
     stage(j, "write_tables");
     // repeat.hpp:173-178 (total_windows is an int in the reference; identical below 2^31 windows)
     const double cpw = (double)s.total_coverage / (double)s.total_windows;
@@ -868,6 +919,11 @@ void print_totals(Job &j, int argc, char *argv[])
     if (j.p.repeat_stats)
         std::cout << raft_cli::repeat_stats_line(j.rst_sum.n_runs, j.rst_sum.runs_interior, j.rst_sum.runs_spanned, j.rst_sum.interior_spanned,
                                                  j.rst_sum.runs_touched, j.rst_sum.sides_inside) << "\n";
+    if (j.p.overlap_ends >= 0)
+        std::cout << raft_cli::overlap_ends_line(j.p.overlap_ends, j.p.ends_min_ratio, j.end_sum.n_records, j.end_sum.kind_internal,
+                                                 j.end_sum.kind_query_contained, j.end_sum.kind_target_contained, j.end_sum.kind_end3 + j.end_sum.kind_end5,
+                                                 j.end_sum.kind_self, j.end_sum.kind_invalid, j.end_sum.reads_contained,
+                                                 j.end_sum.reads_dead5 + j.end_sum.reads_dead3, j.end_sum.reads_isolated, j.n_reads) << "\n";
     stage(j, "stdout");
     if (j.sw.timing) {
         timespec ts{};
@@ -899,6 +955,7 @@ int main(int argc, char *argv[])
     hand_over_symmetric_flag(job);
     survey(job);
     census(job);
+    overlap_ends(job);
     prepare_input(job);
     lock_inputs(job);
     choose_encoding(job);

@@ -71,6 +71,14 @@ FLT_ABI = {
     "raft_host_paf_load_quality": (C.c_int, [_str, _vp, _P(_vp), _str, C.c_int]),
     "raft_host_paf_quality": (_P(_i32), [_vp, C.c_int]),
 }
+# ... and of include/raft_host_end.h
+END_ABI = {
+    "raft_host_paf_parse_with": (C.c_int, [_vp, _vp, C.c_int, _P(_vp), _str, C.c_int]),
+    "raft_host_paf_load_with": (C.c_int, [_str, _vp, C.c_int, _P(_vp), _str, C.c_int]),
+    "raft_host_paf_strand": (_P(C.c_uint8), [_vp]),
+    "raft_host_write_overlap_ends": (C.c_int, [_str, _vp, _vp, _vp]),
+}
+PAF_QUALITY, PAF_STRAND = 1, 2       # RAFT_HOST_PAF_*: the bits of ``columns``
 
 
 class HostError(RuntimeError):
@@ -89,7 +97,7 @@ def load_library():
         if not os.path.exists(_LIB_PATH):
             raise RuntimeError(f"{_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         lib = C.CDLL(_LIB_PATH)
-        for name, (restype, argtypes) in list(ABI.items()) + list(LOW_ABI.items()) + list(OVL_ABI.items()) + list(FRAG_ABI.items()) + list(RST_ABI.items()) + list(FLT_ABI.items()):
+        for name, (restype, argtypes) in list(ABI.items()) + list(LOW_ABI.items()) + list(OVL_ABI.items()) + list(FRAG_ABI.items()) + list(RST_ABI.items()) + list(FLT_ABI.items()) + list(END_ABI.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -189,32 +197,51 @@ class Reads:
             pass
 
 
-def load_paf(path: str, reads: Reads, with_flag: bool = False, two_steps: bool = False, quality: bool = False):
+def load_paf(path: str, reads: Reads, with_flag: bool = False, two_steps: bool = False, quality: bool = False, strand: bool = False):
     """-> six int32 numpy columns (qid, qs, qe, tid, ts, te) [, the symmetric flag the tokeniser found].
     ``two_steps``: raft_host_text_read + raft_host_paf_parse (what the CLI does, the first beside the loading of the reads).
     ``quality``: the ``_quality`` parser of include/raft_host_flt.h -- eight columns, the last two PAF fields 10 and 11 (matches,
-    block; block is 0 on a ten-field line)."""
-    parse, load = ("raft_host_paf_parse_quality", "raft_host_paf_load_quality") if quality else ("raft_host_paf_parse", "raft_host_paf_load")
+    block; block is 0 on a ten-field line).
+    ``strand``: the ``_with`` parser of include/raft_host_end.h -- one more column, the last: uint8, 1 where PAF field 5 begins with
+    '-'; combines with ``quality``."""
     lib = load_library()
+    if strand:                                             # (the parser under a mask of columns)
+        mask = (C.c_int(PAF_STRAND | (PAF_QUALITY if quality else 0)),)
+        parse, load = lib.raft_host_paf_parse_with, lib.raft_host_paf_load_with
+    else:
+        mask = ()
+        parse, load = (lib.raft_host_paf_parse_quality, lib.raft_host_paf_load_quality) if quality else (lib.raft_host_paf_parse, lib.raft_host_paf_load)
     h = C.c_void_p()
     err = C.create_string_buffer(256)
     if two_steps:
         t = C.c_void_p()
         rc = lib.raft_host_text_read(path.encode(), C.byref(t))
         if rc == OK:
-            rc = getattr(lib, parse)(t, reads._h, C.byref(h), err, 256)
+            rc = parse(t, reads._h, *mask, C.byref(h), err, 256)
         lib.raft_host_text_free(t)
     else:
-        rc = getattr(lib, load)(path.encode(), reads._h, C.byref(h), err, 256)
+        rc = load(path.encode(), reads._h, *mask, C.byref(h), err, 256)
     if rc != OK:
         raise HostError(rc, err.value.decode())
     n = lib.raft_host_paf_count(h)
     cols = [np.ctypeslib.as_array(lib.raft_host_paf_column(h, k), shape=(n,)).copy() if n else np.empty(0, np.int32) for k in range(6)]
     if quality:
         cols += [np.ctypeslib.as_array(lib.raft_host_paf_quality(h, k), shape=(n,)).copy() if n else np.empty(0, np.int32) for k in range(2)]
+    if strand:
+        cols.append(np.ctypeslib.as_array(lib.raft_host_paf_strand(h), shape=(n,)).copy() if n else np.empty(0, np.uint8))
     sym = int(lib.raft_host_paf_symmetric(h))
     lib.raft_host_paf_free(h)
     return (cols, sym) if with_flag else cols
+
+
+def write_overlap_ends(path: str, reads: Reads, counts, status):
+    """raft_host_write_overlap_ends: PREFIX.overlap_ends.tsv from ``Engine.overlap_ends``' ``counts`` ([5, n_reads]) and ``status``."""
+    c, s = carray(counts, np.int32), carray(status, np.uint8)
+    if c.size != 5 * reads.n or s.size != reads.n:
+        raise ValueError("write_overlap_ends: counts is [5, n_reads], status [n_reads]")
+    rc = load_library().raft_host_write_overlap_ends(path.encode(), reads._h, ptr(c), ptr(s))
+    if rc != OK:
+        raise HostError(rc, path)
 
 
 def pack_coverage(cov, width: int = 1):
