@@ -371,7 +371,7 @@ struct raft_hip_ctx {
     DevBuf cov8{bufs, DevBuf::kBig}, exc_idx{bufs}, exc_val{bufs}, exc_cnt{bufs};   // transfer encoding of cov[] (raft_hip_fetch_packed)
     DevBuf cov_hist{bufs};             // raft_hip_cov_histogram: RAFT_HIP_COV_HIST_BINS 64-bit counts, cleared at every call
     DevBuf rs_sum{bufs}, rs_max{bufs}, rs_high{bufs};   // raft_hip_read_stats: one value per read each, cleared at every call
-    // The queries beside the engine (libraft_hip_low.so, _ovl.so, _frag.so, _rst.so, _flt.so, _end.so; all plain allocations: those libraries keep no chunk
+    // The queries beside the engine (libraft_hip_low.so, _ovl.so, _frag.so, _rst.so, _flt.so, _end.so, _best.so; all plain allocations: those libraries keep no chunk
     // pool) share what none of them keeps between calls.  q_len, q_col, q_csr_a, q_csr_b: the staging of a host form -- lengths, the six
     // columns, the three arrays of a table the caller gave (repeat_overlaps, repeat_stats: the repeats in q_csr_a; fragment_overlaps:
     // the fragment table in q_csr_a, the repeats in q_csr_b).  q_cov, q_abs: for a pass that holds no int32 array where a query needs
@@ -410,6 +410,9 @@ struct raft_hip_ctx {
     // raft_hip_overlap_ends_* (ovl_ends_lib.hip): the five counts of every read, the status bytes, the control words; the host form's
     // staging of the strand bytes (lengths and columns: q_len, q_col) and the kind bytes before they go to the caller
     DevBuf en_cnt{bufs}, en_status{bufs}, en_ctl{bufs}, en_strand{bufs}, en_kinds{bufs};
+    // raft_hip_best_overlaps_* (best_ovl_lib.hip): len | skipped << 31 of every read, the table of keys (two 64-bit slots per read), what
+    // the pairs kernel writes (partner, span, the flag bytes), the control words; the host form's staging of the strand and the skip bytes
+    DevBuf bo_dig{bufs}, bo_tab{bufs}, bo_partner{bufs}, bo_span{bufs}, bo_flags{bufs}, bo_ctl{bufs}, bo_strand{bufs}, bo_skip{bufs};
     // raft_hip_census_*: counts and flag words per read, the flags as bytes, {first bad record, reads with a flag}; staging of the host form --
     // the census's own and not q_*: it lives in the engine library, whose chunk pool backs the columns (kBig), which the side libraries' must not be
     DevBuf cen_cnt{bufs}, cen_flags{bufs}, cen_out{bufs}, cen_ctl{bufs}, cen_len{bufs};

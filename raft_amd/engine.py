@@ -105,6 +105,11 @@ class _EndSummary(C.Structure):
                                          "kind_end5", "kind_self", "reads_linked", "reads_contained", "reads_isolated", "reads_dead5", "reads_dead3")]
 
 
+class _BestSummary(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_records", "candidates", "left_out", "ends_best", "ends_mutual", "reads_both_best", "reads_both_mutual",
+                                         "reads_no_best", "reads_skipped")]
+
+
 class _Outputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("cov_offset", "cov", "rep_offset", "rep_s", "rep_e", "cut_offset", "cuts",
                                           "frag_offset", "frag_read", "frag_begin", "frag_end")]
@@ -231,6 +236,16 @@ END_INVALID, END_INTERNAL, END_QUERY_CONTAINED, END_TARGET_CONTAINED, END_QUERY_
 END_READ_LINKED, END_READ_CONTAINED, END_READ_ISOLATED, END_READ_DEAD5, END_READ_DEAD3 = range(5)
 END_COUNTS = ("internal", "contained_in", "contains", "end5", "end3")
 
+# ... and those of include/raft_hip_best.h (libraft_hip_best.so): load_best_library declares these
+_BEST_CALL = [_vp] + _COLUMNS + [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _P(_BestSummary), _P(_i64), _P(_f64)]
+BEST_ABI = {
+    "raft_hip_best_abi": (C.c_int, []),
+    "raft_hip_best_overlaps_device": (C.c_int, _BEST_CALL),
+    "raft_hip_best_overlaps_host": (C.c_int, _BEST_CALL),
+}
+# the bits of a read's flag byte (RAFT_HIP_BEST_*)
+BEST_REV5, BEST_MUTUAL5, BEST_REV3, BEST_MUTUAL3, BEST_SKIPPED = 1, 2, 4, 8, 16
+
 
 @dataclass
 class Summary:
@@ -303,14 +318,17 @@ def load_library(path: str | None = None) -> C.CDLL:
 _SIDE = {"low": ("libraft_hip_low.so", LOW_ABI, "raft_hip_low_abi"), "ovl": ("libraft_hip_ovl.so", OVL_ABI, "raft_hip_ovl_abi"),
          "frag": ("libraft_hip_frag.so", FRAG_ABI, "raft_hip_frag_abi"), "rst": ("libraft_hip_rst.so", RST_ABI, "raft_hip_rst_abi"),
          "flt": ("libraft_hip_flt.so", FLT_ABI, "raft_hip_flt_abi"), "end": ("libraft_hip_end.so", END_ABI, "raft_hip_end_abi")}
+# ... and a second table of the same shape for the libraries added since: ``_SIDE`` is a closed set of six that the tests of those
+# six pin by its length, as they pin the entry points of raft_hip.h, so a new library is registered here and ``_SIDE`` stays as it is.
+_SIDE_MORE = {"best": ("libraft_hip_best.so", BEST_ABI, "raft_hip_best_abi")}
 _side_libs: dict = {}
 
 
 def _load_side_library(tag: str) -> C.CDLL:
-    """Loads one library of ``_SIDE`` (behind libraft_hip.so, whose contexts it takes) and declares every entry point of its header;
+    """Loads one library of ``_SIDE`` or ``_SIDE_MORE`` (behind libraft_hip.so, whose contexts it takes) and declares every entry point of its header;
     the two must have been built beside each other."""
     if tag not in _side_libs:
-        file, abi, abi_fn = _SIDE[tag]
+        file, abi, abi_fn = _SIDE[tag] if tag in _SIDE else _SIDE_MORE[tag]
         main = load_library()
         p = os.path.join(os.path.dirname(_LIB_PATH), file)
         if not os.path.exists(p):
@@ -354,6 +372,11 @@ def load_flt_library() -> C.CDLL:
 def load_end_library() -> C.CDLL:
     """libraft_hip_end.so with every entry point of include/raft_hip_end.h declared."""
     return _load_side_library("end")
+
+
+def load_best_library() -> C.CDLL:
+    """libraft_hip_best.so with every entry point of include/raft_hip_best.h declared."""
+    return _load_side_library("best")
 
 
 def _cparams(p: RaftParams) -> _Params:
@@ -1153,6 +1176,51 @@ class Engine:
         res = {"counts": counts, "status": status, "kernel_seconds": secs.value}
         if kinds:
             res["kinds"] = kind_out
+        res.update(_summary_dict(sm))
+        return res
+
+    # -- the best overlap of every read end, and whether it is mutual ----------------------------------
+    last_best_overlaps_seconds = 0.0     # device time of the launches of the last best_overlaps()
+
+    def best_overlaps(self, read_len, qid, qs, qe, tid, ts, te, strand, *, max_overhang: int = 1000, min_ratio_permille: int = 800,
+                      symmetric: bool = False, skip=None) -> dict:
+        """raft_hip_best_overlaps_device / _host (libraft_hip_best.so): per read and end (0 = 5', 1 = 3') the longest dovetail, under
+        the rule of include/raft_hip_best.h, to a read that ``skip`` (uint8 per read, non-zero: left out; ``None``: nobody) does not
+        flag -- ``overlap_ends``' ``status == END_READ_CONTAINED`` is the usual mask.  -> ``partner`` (int32 [n_reads, 2], -1: none),
+        ``span`` (int32 [n_reads, 2], 0: none), ``flags`` (uint8 [n_reads]: ``BEST_*``), the summary's counts (``candidates``,
+        ``left_out``, ``ends_best``, ``ends_mutual``, ``reads_*``, ``n_records``) and ``kernel_seconds``.  The columns are torch tensors
+        on this engine's device (int32; strand and skip uint8) or numpy arrays (staged by the library).  Unless ``symmetric`` a record
+        is a candidate at its target's end as well.  Independent of any pass."""
+        cols = [read_len, qid, qs, qe, tid, ts, te]
+        if any(x is None for x in cols) or strand is None:
+            raise ValueError("best_overlaps needs read_len, the six columns and strand")
+        on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in cols + [strand] + ([] if skip is None else [skip]))
+        best = load_best_library()
+        if on_device:
+            import torch
+            _need_int32_cuda("best_overlaps needs", cols)
+            for name, x in (("strand", strand), ("skip", skip)):
+                if x is not None and (x.dtype != torch.uint8 or not x.is_contiguous()):
+                    raise TypeError(f"best_overlaps needs {name} as a contiguous uint8 CUDA tensor")
+            self.use_torch_stream()
+            fn = best.raft_hip_best_overlaps_device
+        else:
+            cols = _host_columns([x.cpu() if hasattr(x, "is_cuda") else x for x in cols])
+            strand = M.carray(strand.cpu() if hasattr(strand, "is_cuda") else strand, np.uint8)
+            if skip is not None:
+                skip = M.carray(skip.cpu() if hasattr(skip, "is_cuda") else skip, np.uint8)
+            fn = best.raft_hip_best_overlaps_host
+        n_reads, n_rec = M.count(cols[0]), M.count(cols[1])
+        _need_equal_lengths(cols[1:] + [strand], n_rec)
+        if skip is not None and M.count(skip) != n_reads:
+            raise ValueError("best_overlaps: skip is one byte per read")
+        partner, span, flags = np.zeros((n_reads, 2), np.int32), np.zeros((n_reads, 2), np.int32), np.zeros(n_reads, np.uint8)
+        sm, err, secs = _BestSummary(), C.c_int64(-1), C.c_double(0.0)
+        rc = fn(self._ctx, *_plain(cols), M.ptr(strand), M.ptr(skip), int(max_overhang), int(min_ratio_permille), 1 if symmetric else 0,
+                M.ptr(partner), M.ptr(span), M.ptr(flags), C.byref(sm), C.byref(err), C.byref(secs))
+        self._check(rc, err.value)
+        self.last_best_overlaps_seconds = secs.value
+        res = {"partner": partner, "span": span, "flags": flags, "kernel_seconds": secs.value}
         res.update(_summary_dict(sm))
         return res
 

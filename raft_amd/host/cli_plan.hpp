@@ -281,6 +281,19 @@ inline std::string overlap_ends_line(int32_t max_overhang, int32_t min_ratio, in
            ", dead ends = " + std::to_string(dead_ends) + ", isolated reads = " + std::to_string(reads_isolated) + " of " + std::to_string(n_reads);
 }
 
+// --best-overlaps takes its H and F from --overlap-ends and its mask from that option's status bytes: a usage error without it
+inline bool best_options_ok(bool best_overlaps, int32_t max_overhang) { return !best_overlaps || max_overhang >= 0; }
+
+// ... the option's stdout line, the last one (behind overlap_ends'), from raft_hip_best_summary's counts
+inline std::string best_overlaps_line(int64_t records, int64_t candidates, int64_t left_out, int64_t ends_best, int64_t ends_mutual,
+                                      int64_t reads_both_mutual, int64_t reads_no_best, int64_t reads_skipped, int32_t n_reads)
+{
+    return "INFO, best_overlaps(), records = " + std::to_string(records) + ", candidates = " + std::to_string(candidates) + ", left out = " +
+           std::to_string(left_out) + ", ends with a best overlap = " + std::to_string(ends_best) + ", mutual = " + std::to_string(ends_mutual) +
+           ", reads with both ends mutual = " + std::to_string(reads_both_mutual) + ", reads without a best overlap = " + std::to_string(reads_no_best) +
+           ", reads left out = " + std::to_string(reads_skipped) + " of " + std::to_string(n_reads);
+}
+
 // ... a read counts as uncovered when more than this many thousandths of its bases lie in low runs (yacrd's default for "not covered")
 constexpr int32_t kLowUncoveredPermille = 800;
 

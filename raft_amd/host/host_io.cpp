@@ -18,6 +18,7 @@
 #include "../../include/raft_host_rst.h"
 #include "../../include/raft_host_flt.h"
 #include "../../include/raft_host_end.h"
+#include "../../include/raft_host_best.h"
 
 #include <emmintrin.h>
 #include <zlib.h>
@@ -1189,6 +1190,34 @@ int raft_host_write_overlap_ends(const char *path, const raft_host_reads *reads,
                              o.push_back('\t'); put_num(o, reads->lens[(size_t)i]);
                              for (int k = 0; k < 5; ++k) { o.push_back('\t'); put_num(o, counts[(long long)k * n + i]); }
                              o.push_back('\t'); put_num(o, status[i]);
+                             o.push_back('\n');
+                         });
+}
+
+// PREFIX.best_overlaps.tsv (include/raft_host_best.h): name, length, per end the partner's name, the strand, the span and whether the
+// choice is mutual, whether the read was left out.  A partner that is no read of the set is refused before anything is written.
+int raft_host_write_best_overlaps(const char *path, const raft_host_reads *reads, const int32_t *partner, const int32_t *span, const uint8_t *flags)
+{
+    if (!path || !reads) return RAFT_HOST_ERR_ARG;
+    const long long n = (long long)reads->lens.size();
+    if (n > 0 && (!partner || !span || !flags)) return RAFT_HOST_ERR_ARG;
+    for (long long i = 0; i < 2 * n; ++i)
+        if (partner[i] < -1 || partner[i] >= n) return RAFT_HOST_ERR_ARG;
+    return write_ordered(path, n, 1 << 16, [](long long) { return 1LL; },
+                         [&](long long i, std::string &o) {
+                             o.append(reads->names.name((int32_t)i), reads->names.name_len((int32_t)i));
+                             o.push_back('\t'); put_num(o, reads->lens[(size_t)i]);
+                             for (int e = 0; e < 2; ++e) {
+                                 const int32_t p = partner[2 * i + e];
+                                 const unsigned f = (unsigned)flags[i] >> (2 * e);
+                                 o.push_back('\t');
+                                 if (p < 0) { o.append("*\t*\t0\t0"); continue; }
+                                 o.append(reads->names.name(p), reads->names.name_len(p));
+                                 o.push_back('\t'); o.push_back((f & 1u) ? '-' : '+');
+                                 o.push_back('\t'); put_num(o, span[2 * i + e]);
+                                 o.push_back('\t'); o.push_back((f & 2u) ? '1' : '0');
+                             }
+                             o.push_back('\t'); o.push_back((flags[i] & 16u) ? '1' : '0');
                              o.push_back('\n');
                          });
 }

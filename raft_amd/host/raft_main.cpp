@@ -25,6 +25,8 @@
 #include "../../include/raft_host_flt.h"
 #include "../../include/raft_hip_end.h"
 #include "../../include/raft_host_end.h"
+#include "../../include/raft_hip_best.h"
+#include "../../include/raft_host_best.h"
 #include "../../include/raft_host.h"
 #include "cli_plan.hpp"
 
@@ -62,6 +64,7 @@ struct Params {            // param.hpp:18-31
     int32_t overlap_ends = -1;     // --overlap-ends H: PREFIX.overlap_ends.tsv, the kind of every record and the ends of every read (raft_hip_overlap_ends_host); -1: not asked for
     int32_t ends_min_ratio = raft_cli::kEndsMinRatioDefault;   // --ends-min-ratio F, in per mille
     bool ends_ratio_given = false;
+    bool best_overlaps = false;    // --best-overlaps: PREFIX.best_overlaps.tsv, the best overlap of every read end under --overlap-ends' H and F (raft_hip_best_overlaps_host)
     int32_t min_anchor = 0;        // --repeat-overlaps A: PREFIX.repeat_overlaps.tsv and .records.tsv (raft_hip_repeat_overlaps_host); 0: not asked for
 };
 
@@ -103,6 +106,10 @@ struct Job {
     std::vector<uint8_t> strand_kept, end_status;
     std::vector<int32_t> end_counts;
     raft_hip_end_summary end_sum{};
+    // --best-overlaps: per read end the partner and the span, per read the flag byte
+    std::vector<int32_t> best_partner, best_span;
+    std::vector<uint8_t> best_flags;
+    raft_hip_best_summary best_sum{};
     // the arrays everything comes back in (made and page-locked on out_prep)
     raft_cli::Capacities cap;
     std::vector<int64_t> cov_off, rep_off, frag_off;
@@ -216,6 +223,7 @@ void parse_options(Job &j, int argc, char *argv[])
                                                  {"repeat-stats", no_argument, nullptr, 1004}, {"min-identity", required_argument, nullptr, 1005},
                                                  {"min-overlap", required_argument, nullptr, 1006},
                                                  {"overlap-ends", required_argument, nullptr, 1007}, {"ends-min-ratio", required_argument, nullptr, 1008},
+                                                 {"best-overlaps", no_argument, nullptr, 1009},
                                                  {nullptr, 0, nullptr, 0}};
     while ((option = getopt_long(argc, argv, "r:e:m:l:i:p:f:v:o:", long_options, nullptr)) != -1) {
         switch (option) {
@@ -228,6 +236,7 @@ void parse_options(Job &j, int argc, char *argv[])
         case 1006: if (!raft_cli::parse_min_overlap(optarg, &p.min_overlap)) print_help(p); break;
         case 1007: if (!raft_cli::parse_overlap_ends(optarg, &p.overlap_ends)) print_help(p); break;
         case 1008: if (!raft_cli::parse_ends_min_ratio(optarg, &p.ends_min_ratio)) print_help(p); p.ends_ratio_given = true; break;
+        case 1009: p.best_overlaps = true; break;
         case 'r': p.reso = atoi(optarg); break;
         case 'e': p.auto_cov = strcmp(optarg, "auto") == 0; p.est_cov = p.auto_cov ? 0 : atoi(optarg); break;
         case 'm': p.cov_mul = std::stod(optarg); break;
@@ -241,6 +250,7 @@ void parse_options(Job &j, int argc, char *argv[])
         }
     }
     if (!raft_cli::ends_options_ok(p.overlap_ends, p.ends_ratio_given)) print_help(p);
+    if (!raft_cli::best_options_ok(p.best_overlaps, p.overlap_ends)) print_help(p);
     if (argc < optind + 2) print_help(p);
     if (p.est_cov <= 0 && !p.auto_cov) {
         std::cout << "ERROR, main(), estimated coverage must be set properly\n";
@@ -652,6 +662,23 @@ void overlap_ends(Job &j)
     stage(j, "overlap_ends");
 }
 
+// --best-overlaps: the best overlap of every read end and whether it is mutual (raft_hip_best_overlaps_host), directly behind
+// overlap_ends(): on the first context over the same whole stream under the same H, F and symmetric flag, with the reads that phase
+// found contained left out (their status byte is the mask).
+void best_overlaps(Job &j)
+{
+    if (!j.p.best_overlaps) return;
+    j.best_partner.resize((size_t)j.n_reads * 2); j.best_span.resize((size_t)j.n_reads * 2); j.best_flags.resize((size_t)j.n_reads);
+    std::vector<uint8_t> skip(j.end_status.size());
+    for (size_t r = 0; r < skip.size(); ++r) skip[r] = j.end_status[r] == RAFT_HIP_END_READ_CONTAINED ? 1 : 0;
+    int64_t bad_index = -1;
+    const int rc = raft_hip_best_overlaps_host(j.ctxs[0], j.n_reads, j.rl, j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.col[4], j.col[5], j.strand,
+                                               skip.data(), j.p.overlap_ends, j.p.ends_min_ratio, j.sym ? 1 : 0, j.best_partner.data(), j.best_span.data(),
+                                               j.best_flags.data(), &j.best_sum, &bad_index, nullptr);
+    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
+    stage(j, "best_overlaps");
+}
+
 // hifiasm writes its PAF grouped by query (reference README.md:36-38): a symmetric stream of at most four runs sorted by
 // read id is handed over in its grouped form -- per run, where every read's records begin -- and the query column stays
 // on the host (a third of the upload); any other stream goes up as it is.
@@ -879,6 +906,9 @@ void write_outputs(Job &j)
     if (p.overlap_ends >= 0 &&
         raft_host_write_overlap_ends((p.prefix + ".overlap_ends.tsv").c_str(), j.reads, j.end_counts.data(), j.end_status.data()) != RAFT_HOST_OK)
         die("ERROR, overlap_ends(), cannot write output files");
+    if (p.best_overlaps &&
+        raft_host_write_best_overlaps((p.prefix + ".best_overlaps.tsv").c_str(), j.reads, j.best_partner.data(), j.best_span.data(), j.best_flags.data()) != RAFT_HOST_OK)
+        die("ERROR, best_overlaps(), cannot write output files");
     stage(j, "write_tables");
     // repeat.hpp:173-178 (total_windows is an int in the reference; identical below 2^31 windows)
     const double cpw = (double)s.total_coverage / (double)s.total_windows;
@@ -924,6 +954,10 @@ void print_totals(Job &j, int argc, char *argv[])
                                                  j.end_sum.kind_query_contained, j.end_sum.kind_target_contained, j.end_sum.kind_end3 + j.end_sum.kind_end5,
                                                  j.end_sum.kind_self, j.end_sum.kind_invalid, j.end_sum.reads_contained,
                                                  j.end_sum.reads_dead5 + j.end_sum.reads_dead3, j.end_sum.reads_isolated, j.n_reads) << "\n";
+    if (j.p.best_overlaps)
+        std::cout << raft_cli::best_overlaps_line(j.best_sum.n_records, j.best_sum.candidates, j.best_sum.left_out, j.best_sum.ends_best,
+                                                  j.best_sum.ends_mutual, j.best_sum.reads_both_mutual, j.best_sum.reads_no_best,
+                                                  j.best_sum.reads_skipped, j.n_reads) << "\n";
     stage(j, "stdout");
     if (j.sw.timing) {
         timespec ts{};
@@ -956,6 +990,7 @@ int main(int argc, char *argv[])
     survey(job);
     census(job);
     overlap_ends(job);
+    best_overlaps(job);
     prepare_input(job);
     lock_inputs(job);
     choose_encoding(job);

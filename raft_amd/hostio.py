@@ -78,6 +78,10 @@ END_ABI = {
     "raft_host_paf_strand": (_P(C.c_uint8), [_vp]),
     "raft_host_write_overlap_ends": (C.c_int, [_str, _vp, _vp, _vp]),
 }
+# ... and of include/raft_host_best.h
+BEST_ABI = {
+    "raft_host_write_best_overlaps": (C.c_int, [_str, _vp, _vp, _vp, _vp]),
+}
 PAF_QUALITY, PAF_STRAND = 1, 2       # RAFT_HOST_PAF_*: the bits of ``columns``
 
 
@@ -97,7 +101,7 @@ def load_library():
         if not os.path.exists(_LIB_PATH):
             raise RuntimeError(f"{_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         lib = C.CDLL(_LIB_PATH)
-        for name, (restype, argtypes) in list(ABI.items()) + list(LOW_ABI.items()) + list(OVL_ABI.items()) + list(FRAG_ABI.items()) + list(RST_ABI.items()) + list(FLT_ABI.items()) + list(END_ABI.items()):
+        for name, (restype, argtypes) in list(ABI.items()) + list(LOW_ABI.items()) + list(OVL_ABI.items()) + list(FRAG_ABI.items()) + list(RST_ABI.items()) + list(FLT_ABI.items()) + list(END_ABI.items()) + list(BEST_ABI.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -240,6 +244,17 @@ def write_overlap_ends(path: str, reads: Reads, counts, status):
     if c.size != 5 * reads.n or s.size != reads.n:
         raise ValueError("write_overlap_ends: counts is [5, n_reads], status [n_reads]")
     rc = load_library().raft_host_write_overlap_ends(path.encode(), reads._h, ptr(c), ptr(s))
+    if rc != OK:
+        raise HostError(rc, path)
+
+
+def write_best_overlaps(path: str, reads: Reads, partner, span, flags):
+    """raft_host_write_best_overlaps: PREFIX.best_overlaps.tsv from ``Engine.best_overlaps``' ``partner``, ``span`` ([n_reads, 2] each)
+    and ``flags``."""
+    p, s, f = carray(partner, np.int32), carray(span, np.int32), carray(flags, np.uint8)
+    if p.size != 2 * reads.n or s.size != 2 * reads.n or f.size != reads.n:
+        raise ValueError("write_best_overlaps: partner and span are [n_reads, 2], flags [n_reads]")
+    rc = load_library().raft_host_write_best_overlaps(path.encode(), reads._h, ptr(p), ptr(s), ptr(f))
     if rc != OK:
         raise HostError(rc, path)
 
