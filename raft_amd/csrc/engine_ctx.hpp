@@ -371,7 +371,7 @@ struct raft_hip_ctx {
     DevBuf cov8{bufs, DevBuf::kBig}, exc_idx{bufs}, exc_val{bufs}, exc_cnt{bufs};   // transfer encoding of cov[] (raft_hip_fetch_packed)
     DevBuf cov_hist{bufs};             // raft_hip_cov_histogram: RAFT_HIP_COV_HIST_BINS 64-bit counts, cleared at every call
     DevBuf rs_sum{bufs}, rs_max{bufs}, rs_high{bufs};   // raft_hip_read_stats: one value per read each, cleared at every call
-    // The queries beside the engine (libraft_hip_low.so, _ovl.so, _frag.so, _rst.so, _flt.so, _end.so, _best.so; all plain allocations: those libraries keep no chunk
+    // The queries beside the engine (libraft_hip_low.so, _ovl.so, _frag.so, _rst.so, _flt.so, _end.so, _best.so, _utg.so; all plain allocations: those libraries keep no chunk
     // pool) share what none of them keeps between calls.  q_len, q_col, q_csr_a, q_csr_b: the staging of a host form -- lengths, the six
     // columns, the three arrays of a table the caller gave (repeat_overlaps, repeat_stats: the repeats in q_csr_a; fragment_overlaps:
     // the fragment table in q_csr_a, the repeats in q_csr_b).  q_cov, q_abs: for a pass that holds no int32 array where a query needs
@@ -413,6 +413,13 @@ struct raft_hip_ctx {
     // raft_hip_best_overlaps_* (best_ovl_lib.hip): len | skipped << 31 of every read, the table of keys (two 64-bit slots per read), what
     // the pairs kernel writes (partner, span, the flag bytes), the control words; the host form's staging of the strand and the skip bytes
     DevBuf bo_dig{bufs}, bo_tab{bufs}, bo_partner{bufs}, bo_span{bufs}, bo_flags{bufs}, bo_ctl{bufs}, bo_strand{bufs}, bo_skip{bufs};
+    // raft_hip_unitigs_* (unitig_lib.hip): the two halves of the ranking's state (32 B per half-edge each), the cycles' start reads, per
+    // read {start read, index, unitig size if it is a start} / offset / the start's length / orientation, the scan's two prefix arrays
+    // and partial sums, what goes to the caller (unitig, order; utg_off, utg_reads, utg_length, utg_circular), the control words; the
+    // host form's staging of the flag bytes (lengths: q_len; partner and span: q_col[0], q_col[1])
+    DevBuf ut_state{bufs}, ut_cut{bufs}, ut_read{bufs}, ut_offset{bufs}, ut_ulen{bufs}, ut_orient{bufs}, ut_scan{bufs}, ut_unitig{bufs}, ut_order{bufs};
+    DevBuf ut_utg[4] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
+    DevBuf ut_ctl{bufs}, ut_flags{bufs};
     // raft_hip_census_*: counts and flag words per read, the flags as bytes, {first bad record, reads with a flag}; staging of the host form --
     // the census's own and not q_*: it lives in the engine library, whose chunk pool backs the columns (kBig), which the side libraries' must not be
     DevBuf cen_cnt{bufs}, cen_flags{bufs}, cen_out{bufs}, cen_ctl{bufs}, cen_len{bufs};

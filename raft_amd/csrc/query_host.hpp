@@ -1,5 +1,5 @@
 // query_host.hpp -- the host side that the queries about a finished pass or a record stream share (engine.hip: cov_histogram,
-// read_stats, census; low_cov_lib.hip, ovl_class_lib.hip, frag_ovl_lib.hip, repeat_stats_lib.hip, filter_lib.hip, ovl_ends_lib.hip, best_ovl_lib.hip): phases, grids, copy tables, the
+// read_stats, census; low_cov_lib.hip, ovl_class_lib.hip, frag_ovl_lib.hip, repeat_stats_lib.hip, filter_lib.hip, ovl_ends_lib.hip, best_ovl_lib.hip, unitig_lib.hip): phases, grids, copy tables, the
 // staging of a host form, the caller's table or the pass's, the event pair, the control words.  Everything works on a raft_hip_ctx
 // and its stream; no helper knows which query calls it -- what differs between them (whether the clears are timed, where a copy
 // goes, which totals make the summary) stays with the caller.  The decisions free of HIP are in query_args.hpp; the coverage decode,

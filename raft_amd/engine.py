@@ -110,6 +110,11 @@ class _BestSummary(C.Structure):
                                          "reads_no_best", "reads_skipped")]
 
 
+class _UtgSummary(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("reads_in", "reads_skipped", "unitigs", "singletons", "circular", "longest_reads", "longest_length",
+                                         "total_length")]
+
+
 class _Outputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("cov_offset", "cov", "rep_offset", "rep_s", "rep_e", "cut_offset", "cuts",
                                           "frag_offset", "frag_read", "frag_begin", "frag_end")]
@@ -246,6 +251,15 @@ BEST_ABI = {
 # the bits of a read's flag byte (RAFT_HIP_BEST_*)
 BEST_REV5, BEST_MUTUAL5, BEST_REV3, BEST_MUTUAL3, BEST_SKIPPED = 1, 2, 4, 8, 16
 
+# ... and those of include/raft_hip_utg.h (libraft_hip_utg.so): load_utg_library declares these
+_UTG_CALL = [_vp, _i32] + [_vp] * 4 + [_vp] * 9 + [_P(_UtgSummary), _P(_i64), _P(_f64), _P(_i64)]
+UTG_ABI = {
+    "raft_hip_utg_abi": (C.c_int, []),
+    "raft_hip_unitigs_device": (C.c_int, _UTG_CALL),
+    "raft_hip_unitigs_host": (C.c_int, _UTG_CALL),
+}
+UTG_MAX_READS = (1 << 30) - 1     # half-edge ids are int32
+
 
 @dataclass
 class Summary:
@@ -321,14 +335,17 @@ _SIDE = {"low": ("libraft_hip_low.so", LOW_ABI, "raft_hip_low_abi"), "ovl": ("li
 # ... and a second table of the same shape for the libraries added since: ``_SIDE`` is a closed set of six that the tests of those
 # six pin by its length, as they pin the entry points of raft_hip.h, so a new library is registered here and ``_SIDE`` stays as it is.
 _SIDE_MORE = {"best": ("libraft_hip_best.so", BEST_ABI, "raft_hip_best_abi")}
+# ... and an open one for every library after that (``_SIDE_MORE`` is compared by equality where it was added): the next library is
+# one more entry here, and its tests look for their own tag, not at the whole table.
+_SIDE_OPEN = {"utg": ("libraft_hip_utg.so", UTG_ABI, "raft_hip_utg_abi")}
 _side_libs: dict = {}
 
 
 def _load_side_library(tag: str) -> C.CDLL:
-    """Loads one library of ``_SIDE`` or ``_SIDE_MORE`` (behind libraft_hip.so, whose contexts it takes) and declares every entry point of its header;
+    """Loads one library of ``_SIDE``, ``_SIDE_MORE`` or ``_SIDE_OPEN`` (behind libraft_hip.so, whose contexts it takes) and declares every entry point of its header;
     the two must have been built beside each other."""
     if tag not in _side_libs:
-        file, abi, abi_fn = _SIDE[tag] if tag in _SIDE else _SIDE_MORE[tag]
+        file, abi, abi_fn = next(t[tag] for t in (_SIDE, _SIDE_MORE, _SIDE_OPEN) if tag in t)
         main = load_library()
         p = os.path.join(os.path.dirname(_LIB_PATH), file)
         if not os.path.exists(p):
@@ -377,6 +394,11 @@ def load_end_library() -> C.CDLL:
 def load_best_library() -> C.CDLL:
     """libraft_hip_best.so with every entry point of include/raft_hip_best.h declared."""
     return _load_side_library("best")
+
+
+def load_utg_library() -> C.CDLL:
+    """libraft_hip_utg.so with every entry point of include/raft_hip_utg.h declared."""
+    return _load_side_library("utg")
 
 
 def _cparams(p: RaftParams) -> _Params:
@@ -1223,6 +1245,51 @@ class Engine:
         res = {"partner": partner, "span": span, "flags": flags, "kernel_seconds": secs.value}
         res.update(_summary_dict(sm))
         return res
+
+    # -- the unitigs of the best overlap graph -----------------------------------------------------------
+    last_unitigs_seconds = 0.0           # device time of the launches of the last unitigs()
+    last_unitigs_launches = 0            # ... and how many there were (the second ranking runs only if the table holds a cycle)
+
+    def unitigs(self, read_len, partner, span, flags) -> dict:
+        """raft_hip_unitigs_device / _host (libraft_hip_utg.so): the chains and cycles that the mutual best overlaps form, under the
+        rule of include/raft_hip_utg.h.  ``partner``, ``span`` ([n_reads, 2] or [2 * n_reads]) and ``flags`` are what
+        ``best_overlaps`` returned, as torch tensors on this engine's device (int32; flags uint8) or numpy arrays (staged by the
+        library).  -> per read ``unitig``, ``index`` (int32; -1 for a read left out), ``offset`` (int64), ``orient`` (uint8, 1: '-');
+        ``order`` (int32, the reads in layout order) with ``utg_off`` (int64 [U + 1]); per unitig ``utg_reads``, ``utg_length``,
+        ``utg_circular``; ``summary`` (the counts of raft_hip_utg_summary), ``kernel_seconds`` and ``launches``.  A table that is not
+        consistent raises RaftError(ERR_READ_ID) with the smallest such read as its index.  Independent of any pass."""
+        arrs = [read_len, partner, span]
+        if any(x is None for x in arrs) or flags is None:
+            raise ValueError("unitigs needs read_len, partner, span and flags")
+        on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in arrs + [flags])
+        utg = load_utg_library()
+        if on_device:
+            import torch
+            _need_int32_cuda("unitigs needs", arrs)
+            if flags.dtype != torch.uint8 or not flags.is_contiguous():
+                raise TypeError("unitigs needs flags as a contiguous uint8 CUDA tensor")
+            self.use_torch_stream()
+            fn = utg.raft_hip_unitigs_device
+        else:
+            arrs = _host_columns([x.cpu() if hasattr(x, "is_cuda") else x for x in arrs])
+            flags = M.carray(flags.cpu() if hasattr(flags, "is_cuda") else flags, np.uint8)
+            fn = utg.raft_hip_unitigs_host
+        n = M.count(arrs[0])
+        if M.count(arrs[1]) != 2 * n or M.count(arrs[2]) != 2 * n or M.count(flags) != n:
+            raise ValueError("unitigs: partner and span are two values per read, flags one byte")
+        unitig, index, order, utg_reads = (np.zeros(n, np.int32) for _ in range(4))
+        offset, utg_off, utg_length = np.zeros(n, np.int64), np.zeros(n + 1, np.int64), np.zeros(n, np.int64)
+        orient, utg_circular = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        sm, err, secs, launches = _UtgSummary(), C.c_int64(-1), C.c_double(0.0), C.c_int64(0)
+        rc = fn(self._ctx, n, M.ptr(arrs[0]), M.ptr(arrs[1]), M.ptr(arrs[2]), M.ptr(flags), M.ptr(unitig), M.ptr(index), M.ptr(offset),
+                M.ptr(orient), M.ptr(order), M.ptr(utg_off), M.ptr(utg_reads), M.ptr(utg_length), M.ptr(utg_circular), C.byref(sm),
+                C.byref(err), C.byref(secs), C.byref(launches))
+        self.last_unitigs_seconds, self.last_unitigs_launches = secs.value, launches.value
+        self._check(rc, err.value)
+        n_utg, placed = int(sm.unitigs), n - int(sm.reads_skipped)
+        return {"unitig": unitig, "index": index, "offset": offset, "orient": orient, "order": order[:placed], "utg_off": utg_off[:n_utg + 1],
+                "utg_reads": utg_reads[:n_utg], "utg_length": utg_length[:n_utg], "utg_circular": utg_circular[:n_utg],
+                "summary": _summary_dict(sm), "kernel_seconds": secs.value, "launches": launches.value}
 
     def census(self, read_len, qid, qs, qe, tid, ts=None, te=None, symmetric: bool = False) -> dict:
         """raft_hip_census_device / _host: ``intervals`` (int32 [n_reads]: what a pass piles up on each read under ``symmetric``),

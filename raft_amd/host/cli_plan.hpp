@@ -294,6 +294,35 @@ inline std::string best_overlaps_line(int64_t records, int64_t candidates, int64
            ", reads left out = " + std::to_string(reads_skipped) + " of " + std::to_string(n_reads);
 }
 
+// --unitigs walks the table --best-overlaps made: a usage error without it
+inline bool unitigs_options_ok(bool unitigs, bool best_overlaps) { return !unitigs || best_overlaps; }
+
+// N50 of the unitigs, singletons included: the smallest length L such that the unitigs of length >= L hold at least half of the
+// total -- sorted descending, the length at the first prefix with 2 * cum >= total; 0 for no unitigs.
+inline int64_t unitig_n50(const int64_t *lengths, int64_t n)
+{
+    if (n <= 0 || !lengths) return 0;
+    std::vector<int64_t> v(lengths, lengths + n);
+    std::sort(v.begin(), v.end(), [](int64_t a, int64_t b) { return a > b; });
+    int64_t total = 0, cum = 0;
+    for (int64_t x : v) total += x;
+    for (int64_t x : v) {
+        cum += x;
+        if (cum >= total - cum) return x;
+    }
+    return v.back();
+}
+
+// ... the option's stdout line, the last one (behind best_overlaps'), from raft_hip_utg_summary's counts and the N50
+inline std::string unitigs_line(int64_t reads, int64_t skipped, int64_t unitigs, int64_t singletons, int64_t circular, int64_t longest_reads,
+                                int64_t longest_length, int64_t total_length, int64_t n50)
+{
+    return "INFO, unitigs(), reads = " + std::to_string(reads) + ", left out = " + std::to_string(skipped) + ", unitigs = " + std::to_string(unitigs) +
+           ", singletons = " + std::to_string(singletons) + ", circular = " + std::to_string(circular) + ", longest = " + std::to_string(longest_reads) +
+           " reads, longest length = " + std::to_string(longest_length) + ", total length = " + std::to_string(total_length) +
+           ", N50 = " + std::to_string(n50);
+}
+
 // ... a read counts as uncovered when more than this many thousandths of its bases lie in low runs (yacrd's default for "not covered")
 constexpr int32_t kLowUncoveredPermille = 800;
 

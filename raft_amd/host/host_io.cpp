@@ -19,6 +19,7 @@
 #include "../../include/raft_host_flt.h"
 #include "../../include/raft_host_end.h"
 #include "../../include/raft_host_best.h"
+#include "../../include/raft_host_utg.h"
 
 #include <emmintrin.h>
 #include <zlib.h>
@@ -1218,6 +1219,47 @@ int raft_host_write_best_overlaps(const char *path, const raft_host_reads *reads
                                  o.push_back('\t'); o.push_back((f & 2u) ? '1' : '0');
                              }
                              o.push_back('\t'); o.push_back((flags[i] & 16u) ? '1' : '0');
+                             o.push_back('\n');
+                         });
+}
+
+// PREFIX.unitigs.tsv and PREFIX.unitigs.layout.tsv (include/raft_host_utg.h): one line per unitig, one line per read in layout order.
+// A table whose offsets do not ascend from 0 or that names a read outside the set is refused before anything is written.
+int raft_host_write_unitigs(const char *prefix, const raft_host_reads *reads, int64_t n_unitigs, const int32_t *unitig, const int32_t *index,
+                            const int64_t *offset, const uint8_t *orient, const int32_t *order, const int64_t *utg_off,
+                            const int32_t *utg_reads, const int64_t *utg_length, const uint8_t *utg_circular)
+{
+    if (!prefix || !reads || n_unitigs < 0 || !utg_off) return RAFT_HOST_ERR_ARG;
+    const long long n = (long long)reads->lens.size(), n_utg = (long long)n_unitigs;
+    if (n_utg > 0 && (!utg_reads || !utg_length || !utg_circular || !order || !unitig || !index || !offset || !orient)) return RAFT_HOST_ERR_ARG;
+    if (utg_off[0] != 0) return RAFT_HOST_ERR_ARG;
+    for (long long u = 0; u < n_utg; ++u)
+        if (utg_off[u + 1] <= utg_off[u] || utg_off[u + 1] > n) return RAFT_HOST_ERR_ARG;
+    const long long placed = utg_off[n_utg];
+    for (long long i = 0; i < placed; ++i)
+        if (order[i] < 0 || order[i] >= n) return RAFT_HOST_ERR_ARG;
+    const std::string base(prefix);
+    const auto put_name = [&](std::string &o, int32_t r) { o.append(reads->names.name(r), reads->names.name_len(r)); };
+    int rc = write_ordered((base + ".unitigs.tsv").c_str(), n_utg, 1 << 16, [](long long) { return 1LL; },
+                           [&](long long u, std::string &o) {
+                               put_num(o, u);
+                               o.push_back('\t'); put_num(o, utg_reads[u]);
+                               o.push_back('\t'); put_num(o, utg_length[u]);
+                               o.push_back('\t'); o.push_back(utg_circular[u] ? '1' : '0');
+                               o.push_back('\t'); put_name(o, order[utg_off[u]]);
+                               o.push_back('\t'); put_name(o, order[utg_off[u + 1] - 1]);
+                               o.push_back('\n');
+                           });
+    if (rc != RAFT_HOST_OK) return rc;
+    return write_ordered((base + ".unitigs.layout.tsv").c_str(), placed, 1 << 16, [](long long) { return 1LL; },
+                         [&](long long i, std::string &o) {
+                             const int32_t r = order[i];
+                             put_num(o, unitig[r]);
+                             o.push_back('\t'); put_num(o, index[r]);
+                             o.push_back('\t'); put_name(o, r);
+                             o.push_back('\t'); put_num(o, reads->lens[(size_t)r]);
+                             o.push_back('\t'); o.push_back(orient[r] ? '-' : '+');
+                             o.push_back('\t'); put_num(o, offset[r]);
                              o.push_back('\n');
                          });
 }

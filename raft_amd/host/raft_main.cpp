@@ -27,6 +27,8 @@
 #include "../../include/raft_host_end.h"
 #include "../../include/raft_hip_best.h"
 #include "../../include/raft_host_best.h"
+#include "../../include/raft_hip_utg.h"
+#include "../../include/raft_host_utg.h"
 #include "../../include/raft_host.h"
 #include "cli_plan.hpp"
 
@@ -65,6 +67,7 @@ struct Params {            // param.hpp:18-31
     int32_t ends_min_ratio = raft_cli::kEndsMinRatioDefault;   // --ends-min-ratio F, in per mille
     bool ends_ratio_given = false;
     bool best_overlaps = false;    // --best-overlaps: PREFIX.best_overlaps.tsv, the best overlap of every read end under --overlap-ends' H and F (raft_hip_best_overlaps_host)
+    bool unitigs = false;          // --unitigs: PREFIX.unitigs.tsv and .unitigs.layout.tsv, the chains and cycles of --best-overlaps' mutual ends (raft_hip_unitigs_host)
     int32_t min_anchor = 0;        // --repeat-overlaps A: PREFIX.repeat_overlaps.tsv and .records.tsv (raft_hip_repeat_overlaps_host); 0: not asked for
 };
 
@@ -110,6 +113,11 @@ struct Job {
     std::vector<int32_t> best_partner, best_span;
     std::vector<uint8_t> best_flags;
     raft_hip_best_summary best_sum{};
+    // --unitigs: per read the unitig, the place in it, the offset and the orientation; the layout order; per unitig size, length, circular
+    std::vector<int32_t> utg_unitig, utg_index, utg_order, utg_reads;
+    std::vector<int64_t> utg_offset, utg_off, utg_length;
+    std::vector<uint8_t> utg_orient, utg_circular;
+    raft_hip_utg_summary utg_sum{};
     // the arrays everything comes back in (made and page-locked on out_prep)
     raft_cli::Capacities cap;
     std::vector<int64_t> cov_off, rep_off, frag_off;
@@ -223,7 +231,7 @@ void parse_options(Job &j, int argc, char *argv[])
                                                  {"repeat-stats", no_argument, nullptr, 1004}, {"min-identity", required_argument, nullptr, 1005},
                                                  {"min-overlap", required_argument, nullptr, 1006},
                                                  {"overlap-ends", required_argument, nullptr, 1007}, {"ends-min-ratio", required_argument, nullptr, 1008},
-                                                 {"best-overlaps", no_argument, nullptr, 1009},
+                                                 {"best-overlaps", no_argument, nullptr, 1009}, {"unitigs", no_argument, nullptr, 1010},
                                                  {nullptr, 0, nullptr, 0}};
     while ((option = getopt_long(argc, argv, "r:e:m:l:i:p:f:v:o:", long_options, nullptr)) != -1) {
         switch (option) {
@@ -237,6 +245,7 @@ void parse_options(Job &j, int argc, char *argv[])
         case 1007: if (!raft_cli::parse_overlap_ends(optarg, &p.overlap_ends)) print_help(p); break;
         case 1008: if (!raft_cli::parse_ends_min_ratio(optarg, &p.ends_min_ratio)) print_help(p); p.ends_ratio_given = true; break;
         case 1009: p.best_overlaps = true; break;
+        case 1010: p.unitigs = true; break;
         case 'r': p.reso = atoi(optarg); break;
         case 'e': p.auto_cov = strcmp(optarg, "auto") == 0; p.est_cov = p.auto_cov ? 0 : atoi(optarg); break;
         case 'm': p.cov_mul = std::stod(optarg); break;
@@ -251,6 +260,7 @@ void parse_options(Job &j, int argc, char *argv[])
     }
     if (!raft_cli::ends_options_ok(p.overlap_ends, p.ends_ratio_given)) print_help(p);
     if (!raft_cli::best_options_ok(p.best_overlaps, p.overlap_ends)) print_help(p);
+    if (!raft_cli::unitigs_options_ok(p.unitigs, p.best_overlaps)) print_help(p);
     if (argc < optind + 2) print_help(p);
     if (p.est_cov <= 0 && !p.auto_cov) {
         std::cout << "ERROR, main(), estimated coverage must be set properly\n";
@@ -679,6 +689,24 @@ void best_overlaps(Job &j)
     stage(j, "best_overlaps");
 }
 
+// --unitigs: the chains and cycles of the mutual best overlaps (raft_hip_unitigs_host), directly behind best_overlaps() on the
+// arrays that phase holds.
+void unitigs(Job &j)
+{
+    if (!j.p.unitigs) return;
+    const size_t n = (size_t)j.n_reads;
+    j.utg_unitig.resize(n); j.utg_index.resize(n); j.utg_order.resize(n); j.utg_reads.resize(n);
+    j.utg_offset.resize(n); j.utg_off.resize(n + 1); j.utg_length.resize(n);
+    j.utg_orient.resize(n); j.utg_circular.resize(n);
+    int64_t bad_index = -1;
+    const int rc = raft_hip_unitigs_host(j.ctxs[0], j.n_reads, j.rl, j.best_partner.data(), j.best_span.data(), j.best_flags.data(),
+                                         j.utg_unitig.data(), j.utg_index.data(), j.utg_offset.data(), j.utg_orient.data(), j.utg_order.data(),
+                                         j.utg_off.data(), j.utg_reads.data(), j.utg_length.data(), j.utg_circular.data(), &j.utg_sum, &bad_index,
+                                         nullptr, nullptr);
+    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
+    stage(j, "unitigs");
+}
+
 // hifiasm writes its PAF grouped by query (reference README.md:36-38): a symmetric stream of at most four runs sorted by
 // read id is handed over in its grouped form -- per run, where every read's records begin -- and the query column stays
 // on the host (a third of the upload); any other stream goes up as it is.
@@ -909,6 +937,11 @@ void write_outputs(Job &j)
     if (p.best_overlaps &&
         raft_host_write_best_overlaps((p.prefix + ".best_overlaps.tsv").c_str(), j.reads, j.best_partner.data(), j.best_span.data(), j.best_flags.data()) != RAFT_HOST_OK)
         die("ERROR, best_overlaps(), cannot write output files");
+    if (p.unitigs &&
+        raft_host_write_unitigs(p.prefix.c_str(), j.reads, j.utg_sum.unitigs, j.utg_unitig.data(), j.utg_index.data(), j.utg_offset.data(),
+                                j.utg_orient.data(), j.utg_order.data(), j.utg_off.data(), j.utg_reads.data(), j.utg_length.data(),
+                                j.utg_circular.data()) != RAFT_HOST_OK)
+        die("ERROR, unitigs(), cannot write output files");
     stage(j, "write_tables");
     // repeat.hpp:173-178 (total_windows is an int in the reference; identical below 2^31 windows)
     const double cpw = (double)s.total_coverage / (double)s.total_windows;
@@ -958,6 +991,10 @@ void print_totals(Job &j, int argc, char *argv[])
         std::cout << raft_cli::best_overlaps_line(j.best_sum.n_records, j.best_sum.candidates, j.best_sum.left_out, j.best_sum.ends_best,
                                                   j.best_sum.ends_mutual, j.best_sum.reads_both_mutual, j.best_sum.reads_no_best,
                                                   j.best_sum.reads_skipped, j.n_reads) << "\n";
+    if (j.p.unitigs)
+        std::cout << raft_cli::unitigs_line(j.utg_sum.reads_in, j.utg_sum.reads_skipped, j.utg_sum.unitigs, j.utg_sum.singletons, j.utg_sum.circular,
+                                            j.utg_sum.longest_reads, j.utg_sum.longest_length, j.utg_sum.total_length,
+                                            raft_cli::unitig_n50(j.utg_length.data(), j.utg_sum.unitigs)) << "\n";
     stage(j, "stdout");
     if (j.sw.timing) {
         timespec ts{};
@@ -991,6 +1028,7 @@ int main(int argc, char *argv[])
     census(job);
     overlap_ends(job);
     best_overlaps(job);
+    unitigs(job);
     prepare_input(job);
     lock_inputs(job);
     choose_encoding(job);

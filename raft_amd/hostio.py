@@ -82,6 +82,10 @@ END_ABI = {
 BEST_ABI = {
     "raft_host_write_best_overlaps": (C.c_int, [_str, _vp, _vp, _vp, _vp]),
 }
+# ... and of include/raft_host_utg.h
+UTG_ABI = {
+    "raft_host_write_unitigs": (C.c_int, [_str, _vp, C.c_int64] + [_vp] * 9),
+}
 PAF_QUALITY, PAF_STRAND = 1, 2       # RAFT_HOST_PAF_*: the bits of ``columns``
 
 
@@ -101,7 +105,7 @@ def load_library():
         if not os.path.exists(_LIB_PATH):
             raise RuntimeError(f"{_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         lib = C.CDLL(_LIB_PATH)
-        for name, (restype, argtypes) in list(ABI.items()) + list(LOW_ABI.items()) + list(OVL_ABI.items()) + list(FRAG_ABI.items()) + list(RST_ABI.items()) + list(FLT_ABI.items()) + list(END_ABI.items()) + list(BEST_ABI.items()):
+        for name, (restype, argtypes) in list(ABI.items()) + list(LOW_ABI.items()) + list(OVL_ABI.items()) + list(FRAG_ABI.items()) + list(RST_ABI.items()) + list(FLT_ABI.items()) + list(END_ABI.items()) + list(BEST_ABI.items()) + list(UTG_ABI.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -257,6 +261,23 @@ def write_best_overlaps(path: str, reads: Reads, partner, span, flags):
     rc = load_library().raft_host_write_best_overlaps(path.encode(), reads._h, ptr(p), ptr(s), ptr(f))
     if rc != OK:
         raise HostError(rc, path)
+
+
+def write_unitigs(prefix: str, reads: Reads, res: dict):
+    """raft_host_write_unitigs: PREFIX.unitigs.tsv and PREFIX.unitigs.layout.tsv from what ``Engine.unitigs`` returned (``unitig``,
+    ``index``, ``offset``, ``orient``, ``order``, ``utg_off``, ``utg_reads``, ``utg_length``, ``utg_circular``)."""
+    i32 = [carray(res[k], np.int32) for k in ("unitig", "index", "order", "utg_reads")]
+    i64 = [carray(res[k], np.int64) for k in ("offset", "utg_off", "utg_length")]
+    u8 = [carray(res[k], np.uint8) for k in ("orient", "utg_circular")]
+    n_utg = i64[1].size - 1
+    if any(a.size != reads.n for a in (i32[0], i32[1], i64[0], u8[0])) or n_utg < 0 or any(a.size != n_utg for a in (i32[3], i64[2], u8[1])):
+        raise ValueError("write_unitigs: the per-read arrays are [n_reads], the per-unitig arrays [U], utg_off [U + 1]")
+    if i32[2].size != (int(i64[1][-1]) if n_utg >= 0 else 0):
+        raise ValueError("write_unitigs: order holds utg_off[U] reads")
+    rc = load_library().raft_host_write_unitigs(prefix.encode(), reads._h, n_utg, ptr(i32[0]), ptr(i32[1]), ptr(i64[0]), ptr(u8[0]), ptr(i32[2]),
+                                                ptr(i64[1]), ptr(i32[3]), ptr(i64[2]), ptr(u8[1]))
+    if rc != OK:
+        raise HostError(rc, prefix)
 
 
 def pack_coverage(cov, width: int = 1):
