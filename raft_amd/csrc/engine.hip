@@ -1652,8 +1652,8 @@ static int census_run(raft_hip_ctx *c, int32_t n_reads, const int32_t *d_len, co
     if (n_rec > 0) {
         CensusArgs A{d_len, rec.col[0], rec.col[1], rec.col[2], rec.col[3], rec.col[4], rec.col[5], (long long)n_rec, n_reads,
                      symmetric ? 1 : 0, c->cen_cnt.as<unsigned>(), c->cen_flags.as<unsigned>(), ctl};
-        if (aligned16(rec)) hipLaunchKernelGGL(census_kernel<true>, dim3(census_grid(n_rec)), dim3(kCensusThreads), 0, c->stream, A);
-        else hipLaunchKernelGGL(census_kernel<false>, dim3(census_grid(n_rec)), dim3(kCensusThreads), 0, c->stream, A);
+        if (aligned16(rec)) hipLaunchKernelGGL(census_kernel<true>, dim3(stream_grid(n_rec)), dim3(kStreamThreads), 0, c->stream, A);
+        else hipLaunchKernelGGL(census_kernel<false>, dim3(stream_grid(n_rec)), dim3(kStreamThreads), 0, c->stream, A);
     }
     if (n_reads > 0)
         hipLaunchKernelGGL(census_pack_kernel, dim3((unsigned)std::min<long long>(((long long)n_reads + 255) / 256, 1024)), dim3(256), 0, c->stream,

@@ -7,7 +7,7 @@
 // and the kept records of the six columns, in their order, in six other arrays: a stream compaction.  Count, prefix, scatter, as
 // low_cov.hpp and finalize.hpp do it -- launch boundaries carry what crosses workgroups: no look-back, no workgroup waits for another
 // (device_scan.hpp: the look-back lost here at full size).  A tile is kFltTile consecutive records, one workgroup step; a lane takes
-// kFltLaneRecords consecutive records, as in the census, whose loads these are (census_load: one 16-byte load per column, 4-byte loads
+// kFltLaneRecords consecutive records with record_stream.hpp's lane loader (stream_load: one 16-byte load per column, 4-byte loads
 // for a column that is not 16-byte aligned and behind the last whole group).
 //
 //   * flt_flag_kernel streams matches, block (only when P > 0), qs, qe, ts, te ONCE and evaluates the rule.  A lane's four keep bits
@@ -23,17 +23,19 @@
 #pragma once
 #include "raft_types.hpp"
 #include "wave.hpp"
+#include "record_stream.hpp"
 #include "census.hpp"
 #include "device_scan.hpp"
 
 namespace raft {
 
 constexpr int kFltThreads = 256;
-constexpr int kFltLaneRecords = kCensusLaneRecords;                  // census_load's group: one 16-byte load per column
+constexpr int kFltLaneRecords = kCensusLaneRecords;                  // stream_load's group (kStreamLaneRecords under its earlier name, census.hpp)
 constexpr int kFltTile = kFltThreads * kFltLaneRecords;              // records of one workgroup step
 constexpr int kFltTileWords = kFltTile / 64;                         // bitmap words of a tile
 constexpr int kFltWordLanes = 64 / kFltLaneRecords;                  // lanes whose bits make one word
 constexpr int kFltMaxBlocks = 2048;                                  // eight workgroups on each of the 256 CUs, grid-stride beyond
+static_assert(kFltLaneRecords == kStreamLaneRecords, "stream_load fills kStreamLaneRecords values");
 static_assert(kFltLaneRecords == 4 && kFltTile == 1024 && kFltWordLanes == 16, "a nibble per lane, a word per 16 lanes");
 
 // control words of one call: [0] the first kept record (all ones: none; the flag kernel takes the minimum), [1] below identity,
@@ -73,13 +75,13 @@ __global__ __launch_bounds__(kFltThreads) void flt_flag_kernel(FltFlagArgs A)
     for (long long tile = blockIdx.x; tile < A.n_tiles; tile += gridDim.x) {
         const long long rec0 = tile * kFltTile + (long long)tid * R;          // (at or beyond n_rec: a lane without records)
         int a[R], b[R], s[R], e[R], m[R], d[R];
-        census_load<kVec>(A.qs, rec0, A.n_rec, 0, a);
-        census_load<kVec>(A.qe, rec0, A.n_rec, 0, b);
-        census_load<kVec>(A.ts, rec0, A.n_rec, 0, s);
-        census_load<kVec>(A.te, rec0, A.n_rec, 0, e);
+        stream_load<kVec>(A.qs, rec0, A.n_rec, 0, a);
+        stream_load<kVec>(A.qe, rec0, A.n_rec, 0, b);
+        stream_load<kVec>(A.ts, rec0, A.n_rec, 0, s);
+        stream_load<kVec>(A.te, rec0, A.n_rec, 0, e);
         if (kIdent) {
-            census_load<kVec>(A.matches, rec0, A.n_rec, 0, m);
-            census_load<kVec>(A.block, rec0, A.n_rec, 0, d);
+            stream_load<kVec>(A.matches, rec0, A.n_rec, 0, m);
+            stream_load<kVec>(A.block, rec0, A.n_rec, 0, d);
         }
         unsigned keep = 0;
 #pragma unroll
@@ -161,7 +163,7 @@ __global__ __launch_bounds__(kFltThreads) void flt_scatter_kernel(FltScatterArgs
             long long at = A.tile_base[tile] + before + incl - mine;
             int v[6][R];
 #pragma unroll
-            for (int k = 0; k < 6; ++k) census_load<kVec>(A.in[k], rec0, A.n_rec, 0, v[k]);
+            for (int k = 0; k < 6; ++k) stream_load<kVec>(A.in[k], rec0, A.n_rec, 0, v[k]);
 #pragma unroll
             for (int i = 0; i < R; ++i)
                 if (keep >> i & 1u) {

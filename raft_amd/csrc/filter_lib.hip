@@ -1,9 +1,9 @@
 // filter_lib.hip -- libraft_hip_flt.so: raft_hip_filter_overlaps_device / _host (include/raft_hip_flt.h), the kept records of a stream.
 //
-// A library of its own beside libraft_hip.so, as libraft_hip_low.so, libraft_hip_ovl.so, libraft_hip_frag.so and libraft_hip_rst.so
-// are: the set of entry points of include/raft_hip.h is closed (ABI 11), and this call needs nothing of the engine but the context it
-// is handed -- the stream, and buffers registered with the context like every other (fl_*, and the queries' shared staging q_col).
-// It reads no finished pass and leaves the context's state as it is.
+// A library of its own beside libraft_hip.so (the others: the SIDE list of raft_amd/csrc/Makefile): the set of entry points of
+// include/raft_hip.h is closed (ABI 11), and this call needs nothing of the engine but the context it is handed -- the stream, and
+// buffers registered with the context like every other (fl_*, and the queries' shared staging q_col).  It reads no finished pass and
+// leaves the context's state as it is.
 #include "query_host.hpp"
 #include "../../include/raft_hip_flt.h"
 #include "filter.hpp"

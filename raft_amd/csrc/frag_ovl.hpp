@@ -8,10 +8,8 @@
 //                           n == 1   the one row [x, y) itself -- the common case: a side is answered from this gather alone
 //                           n >  1   the hull [x, y) = [fb of the first row, fe of the last]: a side outside it touches nothing,
 //                                    one inside goes to the CSR arrays with binary searches
-//   frag_side_kernel    census_kernel's streaming shape (census.hpp: 16-byte loads of four consecutive records per lane, a 4-byte path for
-//                       columns that are not 16-byte aligned and for the records behind the last whole group, a capped grid with a
-//                       grid-stride loop).  fb and fe do not descend within a read, so each property selects a contiguous range of rows,
-//                       a suffix cut with a prefix:
+//   frag_side_kernel    a streaming kernel of record_stream.hpp's shape.  fb and fe do not descend within a read, so each property
+//                       selects a contiguous range of rows, a suffix cut with a prefix:
 //                           touched    [lt, ht)   lt = first row with fe > a, ht = first row at or behind lt with fb >= b
 //                           spanned    [ls, hs)   inside [lt, ht): ls = first row with fb >= a, hs = first row behind with fe > b
 //                           contained  [ls, hs)   when the partner is whole: the last row g of the partner with fb[g] <= c has d <= fe[g]
@@ -28,12 +26,14 @@
 #pragma once
 #include "raft_types.hpp"
 #include "wave.hpp"
+#include "record_stream.hpp"
 #include "census.hpp"
 #include "ovl_class.hpp"
 #include "device_scan.hpp"
 
 namespace raft {
 
+// (the names this header had for the launch constants; see census.hpp)
 constexpr int kFragThreads = kCensusThreads;
 constexpr int kFragLaneRecords = kCensusLaneRecords;
 constexpr int kFragMaxBlocks = kCensusMaxBlocks;
@@ -152,57 +152,40 @@ __device__ __forceinline__ void frag_side(const FragArgs &A, const FragDigest r,
 }
 
 template <bool kVec>
-__global__ __launch_bounds__(kFragThreads) void frag_side_kernel(FragArgs A)
+__global__ __launch_bounds__(kStreamThreads) void frag_side_kernel(FragArgs A)
 {
-    constexpr int R = kFragLaneRecords;
+    constexpr int R = kStreamLaneRecords;
     if (A.ctl[kFragBadTable]) return;                        // (uniform: the digest kernel's verdict, written before this launch)
     const int lane = (int)threadIdx.x & (kWave - 1);
-    const long long n_groups = (A.n_rec + R - 1) / R;
-    const long long stride = (long long)gridDim.x * blockDim.x;
     const unsigned n_reads = (unsigned)A.n_reads;
-    for (long long g0 = (long long)blockIdx.x * blockDim.x + ((int)threadIdx.x & ~(kWave - 1)); g0 < n_groups; g0 += stride) {
-        const long long first = (g0 + lane) * R;             // (at or beyond n_rec: a lane without records)
-        int q[R], t[R], a[R], b[R], ts[R], te[R];
-        census_load<kVec>(A.qid, first, A.n_rec, -1, q);
-        census_load<kVec>(A.tid, first, A.n_rec, -1, t);
-        census_load<kVec>(A.qs, first, A.n_rec, -1, a);
-        census_load<kVec>(A.qe, first, A.n_rec, -1, b);
-        census_load<kVec>(A.ts, first, A.n_rec, -1, ts);
-        census_load<kVec>(A.te, first, A.n_rec, -1, te);
+    stream_for_each_group(A.n_rec, lane, [&](const long long first) {
+        LaneRecords r;
+        stream_load_records<kVec>(A.qid, A.qs, A.qe, A.tid, A.ts, A.te, first, A.n_rec, true, r);
         // the gathers of the lane's eight sides first, all in flight together
         FragDigest dq[R], dt[R];
         bool ok[R];
 #pragma unroll
         for (int i = 0; i < R; ++i) {
-            const bool have = first + i < A.n_rec;
-            ok[i] = have && (unsigned)q[i] < n_reads && (unsigned)t[i] < n_reads;
-            if (have && !ok[i]) atomicMin(&A.ctl[kFragFirstBad], (unsigned long long)(first + i));
-            ok[i] = ok[i] && q[i] != t[i];                   // (a record of a read with itself contributes nothing)
+            const IdsValid v = stream_check_ids(first + i < A.n_rec, first + i, r.q[i], r.t[i], n_reads, &A.ctl[kFragFirstBad]);
+            ok[i] = v.q && v.t && r.q[i] != r.t[i];          // (a record of a read with itself contributes nothing)
             dq[i] = dt[i] = FragDigest{0, 0, 0, 0};
             if (ok[i]) {
-                dq[i] = A.digest[q[i]];
-                dt[i] = A.digest[t[i]];
+                dq[i] = A.digest[r.q[i]];
+                dt[i] = A.digest[r.t[i]];
             }
         }
 #pragma unroll
         for (int i = 0; i < R; ++i) {
             if (!ok[i]) continue;
-            frag_side(A, dq[i], a[i], b[i], dt[i], ts[i], te[i]);
+            frag_side(A, dq[i], r.qs[i], r.qe[i], dt[i], r.ts[i], r.te[i]);
             // the rule before fragmentation looks at the start before it gathers the length
-            if (a[i] <= 0 && b[i] > a[i] && b[i] >= A.len[q[i]]) ovl_flag(&A.whole[q[i]], 1u);
+            if (r.qs[i] <= 0 && r.qe[i] > r.qs[i] && r.qe[i] >= A.len[r.q[i]]) ovl_flag(&A.whole[r.q[i]], 1u);
             if (!A.symmetric) {
-                frag_side(A, dt[i], ts[i], te[i], dq[i], a[i], b[i]);
-                if (ts[i] <= 0 && te[i] > ts[i] && te[i] >= A.len[t[i]]) ovl_flag(&A.whole[t[i]], 1u);
+                frag_side(A, dt[i], r.ts[i], r.te[i], dq[i], r.qs[i], r.qe[i]);
+                if (r.ts[i] <= 0 && r.te[i] > r.ts[i] && r.te[i] >= A.len[r.t[i]]) ovl_flag(&A.whole[r.t[i]], 1u);
             }
         }
-    }
-}
-
-inline unsigned frag_grid(long long n_rec)
-{
-    const long long per_step = (long long)kFragThreads * kFragLaneRecords;
-    const long long want = (n_rec + per_step - 1) / per_step;
-    return (unsigned)(want < 1 ? 1 : (want > kFragMaxBlocks ? kFragMaxBlocks : want));
+    });
 }
 
 // device_scan.hpp's loader and hook: the three sums of a slot in; the inclusive sums -- the counts of row i -- out
@@ -260,7 +243,7 @@ __global__ __launch_bounds__(256) void frag_reads_kernel(FragReadsArgs A)
 {
     if (A.ctl[kFragBadTable] | A.ctl[kFragBadRepeats]) return;
     const long long stride = (long long)gridDim.x * blockDim.x;
-    int tot[7] = {0, 0, 0, 0, 0, 0, 0};
+    unsigned tot[7] = {0, 0, 0, 0, 0, 0, 0};
     for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < A.n_reads; r += stride) {
         const long long k0 = A.off[r], k1 = A.off[r + 1];
         const OvlDigest d = A.rep_off ? A.rep_digest[r] : OvlDigest{0, 0};
@@ -273,14 +256,10 @@ __global__ __launch_bounds__(256) void frag_reads_kernel(FragReadsArgs A)
             contained += c ? 1 : 0;
         }
         A.read_contained[r] = contained;
-        tot[4] += (int)(A.whole[r] & 1u); tot[5] += contained > 0 ? 1 : 0; tot[6] += (contained > 0 && contained == k1 - k0) ? 1 : 0;
+        tot[4] += A.whole[r] & 1u; tot[5] += contained > 0 ? 1 : 0; tot[6] += (contained > 0 && contained == k1 - k0) ? 1 : 0;
     }
     // (all lanes are back together here)
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-        const int total = wave_reduce_add(tot[k]);
-        if (((int)threadIdx.x & (kWave - 1)) == 0 && total) atomicAdd(&A.ctl[kFragTotals + k], (unsigned long long)total);
-    }
+    wave_flush_totals(tot, &A.ctl[kFragTotals], (int)threadIdx.x & (kWave - 1));
 }
 
 } // namespace raft

@@ -1,10 +1,10 @@
 // frag_ovl_lib.hip -- libraft_hip_frag.so: raft_hip_frag_overlaps_device / _host (include/raft_hip_frag.h), the record stream joined
 // with the fragment table.
 //
-// A library of its own beside libraft_hip.so, as libraft_hip_low.so and libraft_hip_ovl.so are: the set of entry points of
-// include/raft_hip.h is closed (ABI 11), and this query needs nothing of the engine but the context it is handed -- the fragment rows and
-// the repeat arrays a finished pass left (engine_ctx.hpp), the stream, and buffers registered with the context like every other (fo_*,
-// and the queries' shared staging q_*).
+// A library of its own beside libraft_hip.so (the others: the SIDE list of raft_amd/csrc/Makefile): the set of entry points of
+// include/raft_hip.h is closed (ABI 11), and this query needs nothing of the engine but the context it is handed -- the fragment rows
+// and the repeat arrays a finished pass left (engine_ctx.hpp), the stream, and buffers registered with the context like every other
+// (fo_*, and the queries' shared staging q_*).
 #include "query_host.hpp"
 #include "../../include/raft_hip_frag.h"
 #include "frag_ovl.hpp"
@@ -75,8 +75,8 @@ int frag_run(raft_hip_ctx *c, const FragCall &a)
     if (n_rec > 0) {
         FragArgs A{a.len, col[0], col[1], col[2], col[3], col[4], col[5], (long long)n_rec, a.n_reads, a.symmetric ? 1 : 0,
                    table.x, table.y, c->fo_digest.as<FragDigest>(), c->fo_slot.as<FragSlot>(), c->fo_whole.as<unsigned>(), ctl};
-        if (aligned16(a.rec)) hipLaunchKernelGGL(frag_side_kernel<true>, dim3(frag_grid(n_rec)), dim3(kFragThreads), 0, c->stream, A);
-        else hipLaunchKernelGGL(frag_side_kernel<false>, dim3(frag_grid(n_rec)), dim3(kFragThreads), 0, c->stream, A);
+        if (aligned16(a.rec)) hipLaunchKernelGGL(frag_side_kernel<true>, dim3(stream_grid(n_rec)), dim3(kStreamThreads), 0, c->stream, A);
+        else hipLaunchKernelGGL(frag_side_kernel<false>, dim3(stream_grid(n_rec)), dim3(kStreamThreads), 0, c->stream, A);
     }
     if (n_frag > 0) {                                         // the three difference arrays -> counts (the slot behind the last row only ends ranges)
         const FragLoader ld{c->fo_slot.as<FragSlot>()};

@@ -10,23 +10,17 @@
 //                       so a side on a read without repeats (two reads in three of a human set) is class 0 after one 8-byte gather,
 //                       a read whose runs are one piece (one run, or runs joined by their flanks) needs nothing else either, and the
 //                       rest is sent on only when the side reaches into the hull.
-//   ovl_class_kernel    census_kernel's streaming shape (census.hpp: 16-byte loads of four consecutive records per lane, a 4-byte path
-//                       for columns that are not 16-byte aligned and for the records behind the last whole group, the length gather
-//                       for the qs == 0 / ts == 0 candidates only, census_count's joins for the per-read tallies with the flags
-//                       as weight: ovl_count) with the lookup of both sides in it.  24 B in and 1 B out per record: the four class bytes of a lane
-//                       leave as one 32-bit store.
+//   ovl_class_kernel    a streaming kernel of record_stream.hpp's shape (24 B in and 1 B out per record: the four class bytes of a lane
+//                       leave as one 32-bit store) with the lookup of both sides in it, the length gather for the qs == 0 / ts == 0
+//                       candidates only, and join_runs for the per-read tallies with the flags as packed weight (ovl_count).
 //   ovl_reads_kernel    flag words -> one byte per read, tally words -> the two counts, the two totals over the reads.
 // The record kernel reads ctl[kOvlBadOffsets] first and leaves when the digest kernel found rep_offset broken: it would read out of bounds.
 #pragma once
 #include "raft_types.hpp"
 #include "wave.hpp"
-#include "census.hpp"
+#include "record_stream.hpp"
 
 namespace raft {
-
-constexpr int kOvlThreads = kCensusThreads;
-constexpr int kOvlLaneRecords = kCensusLaneRecords;
-constexpr int kOvlMaxBlocks = kCensusMaxBlocks;
 
 // control words (unsigned long long each)
 constexpr int kOvlFirstBad = 0;          // smallest record index with an id out of range; ~0 = none
@@ -106,148 +100,81 @@ __device__ __forceinline__ unsigned ovl_side(const OvlArgs &A, const OvlDigest d
     return 4u | (unique < (long long)A.min_anchor ? 1u : 0u);
 }
 
-// census_count's joins (census.hpp) for the two tallies of a read at once: w = TOUCH | REPEAT << 16 of each record, summed over equal
-// neighbouring ids within the lane and across the wave -- a wave has 256 records, so neither half overflows into the other -- and one
-// 64-bit add per run and wave, the halves 32 bits apart.  A target column is random ids: one atomic per side that touches a repeat
-// instead of one per tally.  EXEC must be all ones.
-__device__ __forceinline__ void ovl_add(unsigned long long *cnt, int id, unsigned x)
-{
-    atomicAdd(&cnt[id], (unsigned long long)(x & 0xFFFFu) | ((unsigned long long)(x >> 16) << 32));
-}
+// join_runs for the two tallies of a read at once: w = TOUCH | REPEAT << 16 of each record, summed over equal neighbouring ids -- a
+// wave has kStreamWaveRecords records, so neither half overflows into the other -- and one 64-bit add per run and wave, the halves
+// 32 bits apart.  A target column is random ids: one atomic per side that touches a repeat instead of one per tally.
+static_assert(kStreamWaveRecords < (1 << 16), "a wave's sides on one read fit a half of the packed weight");
 
-__device__ __forceinline__ void ovl_count(const int (&id)[kOvlLaneRecords], const unsigned (&w)[kOvlLaneRecords], unsigned long long *__restrict__ cnt, int lane)
+__device__ __forceinline__ void ovl_count(const int (&id)[kStreamLaneRecords], const unsigned (&w)[kStreamLaneRecords], unsigned long long *__restrict__ cnt, int lane)
 {
-    int cur = id[0];
-    unsigned n = w[0], head_n = 0;
-    bool uniform = true;
-#pragma unroll
-    for (int i = 1; i < kOvlLaneRecords; ++i) {
-        if (id[i] == cur) n += w[i];
-        else {
-            if (uniform) { head_n = n; uniform = false; }
-            else if (n) ovl_add(cnt, cur, n);              // a run that touches neither end of the lane
-            cur = id[i]; n = w[i];
-        }
-    }
-    // the lane's last run (cur, n) opens a segment unless the lane is one run that carries on what the lane before ended with
-    const int prev_tail = __shfl_up(cur, 1, kWave);
-    const bool joins = lane > 0 && id[0] == prev_tail;
-    unsigned x = n;
-    int f = (!uniform || !joins) ? 1 : 0;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const unsigned xo = __shfl_up(x, d, kWave);
-        const int fo = __shfl_up(f, d, kWave);
-        if (lane >= d && !f) { x += xo; f = fo; }
-    }
-    const unsigned before = __shfl_up(x, 1, kWave);        // the open run as the lane before left it
-    const int next_joins = __shfl_down(joins ? 1 : 0, 1, kWave);
-    if (!uniform) {
-        const unsigned h = head_n + (joins ? before : 0u);
-        if (h) ovl_add(cnt, id[0], h);
-    }
-    if ((lane == kWave - 1 || !next_joins) && x) ovl_add(cnt, cur, x);
-}
-
-// flags[r] |= bits.  A contained read is contained by many records (ten a side on a human set), neighbours in the stream: the word is
-// looked at first and the atomic goes out only while a bit is missing.  Bits are only ever set, so a stale look costs an atomic, never a bit.
-__device__ __forceinline__ void ovl_flag(unsigned *word, unsigned bits)
-{
-    if ((__atomic_load_n(word, __ATOMIC_RELAXED) & bits) != bits) atomicOr(word, bits);
+    join_runs(id, w, lane, JoinAdd{}, [cnt](int r, unsigned x) {
+        if (x) atomicAdd(&cnt[r], (unsigned long long)(x & 0xFFFFu) | ((unsigned long long)(x >> 16) << 32));
+    });
 }
 
 template <bool kVec>
-__global__ __launch_bounds__(kOvlThreads) void ovl_class_kernel(OvlArgs A)
+__global__ __launch_bounds__(kStreamThreads) void ovl_class_kernel(OvlArgs A)
 {
-    constexpr int R = kOvlLaneRecords;
+    constexpr int R = kStreamLaneRecords;
     if (A.ctl[kOvlBadOffsets]) return;                       // (uniform: the digest kernel's verdict, written before this launch)
     const int lane = (int)threadIdx.x & (kWave - 1);
-    const long long n_groups = (A.n_rec + R - 1) / R;
-    const long long stride = (long long)gridDim.x * blockDim.x;
     const unsigned n_reads = (unsigned)A.n_reads;
     const bool targets = A.ts != nullptr;
     unsigned tot[7] = {0, 0, 0, 0, 0, 0, 0};
-    // (the loop's bound is the wave's: every lane of a wave takes part in the scans)
-    for (long long g0 = (long long)blockIdx.x * blockDim.x + ((int)threadIdx.x & ~(kWave - 1)); g0 < n_groups; g0 += stride) {
-        const long long first = (g0 + lane) * R;             // (at or beyond n_rec: a lane without records)
-        int q[R], t[R], a[R], b[R], ts[R], te[R];
-        census_load<kVec>(A.qid, first, A.n_rec, -1, q);
-        census_load<kVec>(A.tid, first, A.n_rec, -1, t);
-        census_load<kVec>(A.qs, first, A.n_rec, -1, a);
-        census_load<kVec>(A.qe, first, A.n_rec, -1, b);
-        if (targets) {
-            census_load<kVec>(A.ts, first, A.n_rec, -1, ts);
-            census_load<kVec>(A.te, first, A.n_rec, -1, te);
-        }
+    stream_for_each_group(A.n_rec, lane, [&](const long long first) {
+        LaneRecords r;
+        stream_load_records<kVec>(A.qid, A.qs, A.qe, A.tid, A.ts, A.te, first, A.n_rec, targets, r);
         // the gathers of the lane's eight sides first, all in flight together: what is done with them follows
         OvlDigest dq[R], dt[R];
         bool ok[R];
 #pragma unroll
         for (int i = 0; i < R; ++i) {
-            ok[i] = first + i < A.n_rec && (unsigned)q[i] < n_reads && (unsigned)t[i] < n_reads;
+            const IdsValid v = stream_check_ids(first + i < A.n_rec, first + i, r.q[i], r.t[i], n_reads, &A.ctl[kOvlFirstBad]);
+            ok[i] = v.q && v.t;
             dq[i] = dt[i] = OvlDigest{0, 0};
             if (ok[i]) {
-                dq[i] = A.digest[q[i]];
-                if (targets) dt[i] = A.digest[t[i]];
+                dq[i] = A.digest[r.q[i]];
+                if (targets) dt[i] = A.digest[r.t[i]];
             }
         }
-        unsigned cls[R], wq[R], wt[R];
+        unsigned cls4 = 0, wq[R], wt[R];
 #pragma unroll
         for (int i = 0; i < R; ++i) {
-            const bool have = first + i < A.n_rec;
             const bool both = ok[i];
-            if (have && !both) atomicMin(&A.ctl[kOvlFirstBad], (unsigned long long)(first + i));
             unsigned c = 0;
             if (both) {
-                c = ovl_side(A, dq[i], q[i], a[i], b[i]);
-                if (targets) c |= ovl_side(A, dt[i], t[i], ts[i], te[i]) << 1;
+                c = ovl_side(A, dq[i], r.q[i], r.qs[i], r.qe[i]);
+                if (targets) c |= ovl_side(A, dt[i], r.t[i], r.ts[i], r.te[i]) << 1;
                 // containment looks at the start before it gathers any length
-                if (a[i] == 0) {
-                    const int lq = A.len[q[i]];
-                    if (b[i] == lq && A.len[t[i]] > lq) {
+                if (r.qs[i] == 0) {
+                    const int lq = A.len[r.q[i]];
+                    if (r.qe[i] == lq && A.len[r.t[i]] > lq) {
                         c |= 16u;
-                        ovl_flag(&A.flags[q[i]], (c & 2u) ? 1u : 3u);          // the container is the target side
+                        ovl_flag(&A.flags[r.q[i]], (c & 2u) ? 1u : 3u);          // the container is the target side
                     }
                 }
-                if (targets && ts[i] == 0) {
-                    const int lt = A.len[t[i]];
-                    if (te[i] == lt && A.len[q[i]] > lt) {
+                if (targets && r.ts[i] == 0) {
+                    const int lt = A.len[r.t[i]];
+                    if (r.te[i] == lt && A.len[r.q[i]] > lt) {
                         c |= 32u;
-                        if (!A.symmetric) ovl_flag(&A.flags[t[i]], (c & 1u) ? 1u : 3u);   // (a side the census does not count otherwise)
+                        if (!A.symmetric) ovl_flag(&A.flags[r.t[i]], (c & 1u) ? 1u : 3u);   // (a side the census does not count otherwise)
                     }
                 }
             }
-            cls[i] = c;
+            cls4 |= c << (8 * i);
             wq[i] = ((c >> 2) & 1u) | (c & 1u) << 16;
-            const bool t_counts = both && !A.symmetric && t[i] != q[i];
+            const bool t_counts = both && !A.symmetric && r.t[i] != r.q[i];
             wt[i] = t_counts ? ((c >> 3) & 1u) | ((c >> 1) & 1u) << 16 : 0u;
             tot[0] += (c >> 2) & 1u; tot[1] += (c >> 3) & 1u; tot[2] += c & 1u; tot[3] += (c >> 1) & 1u;
             tot[4] += (c & 3u) == 3u ? 1u : 0u; tot[5] += (c >> 4) & 1u; tot[6] += (c >> 5) & 1u;
         }
-        if (A.cls) {
-            if (first + R <= A.n_rec) *reinterpret_cast<unsigned *>(A.cls + first) = cls[0] | cls[1] << 8 | cls[2] << 16 | cls[3] << 24;
-            else {
-#pragma unroll
-                for (int i = 0; i < R; ++i) if (first + i < A.n_rec) A.cls[first + i] = (uint8_t)cls[i];
-            }
-        }
+        if (A.cls) stream_store_bytes<true>(A.cls, first, A.n_rec, cls4);        // (cls is 4-byte aligned whatever the columns are)
         // the tallies: a wave none of whose sides has the flag adds nothing (the branches are the wave's: EXEC stays all ones inside)
-        if (__any((int)(wq[0] | wq[1] | wq[2] | wq[3]))) ovl_count(q, wq, A.tally, lane);
-        if (__any((int)(wt[0] | wt[1] | wt[2] | wt[3]))) ovl_count(t, wt, A.tally, lane);
-    }
+        if (__any((int)(wq[0] | wq[1] | wq[2] | wq[3]))) ovl_count(r.q, wq, A.tally, lane);
+        if (__any((int)(wt[0] | wt[1] | wt[2] | wt[3]))) ovl_count(r.t, wt, A.tally, lane);
+    });
     // (all lanes are back together here)
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-        const int total = wave_reduce_add((int)tot[k]);
-        if (lane == 0 && total) atomicAdd(&A.ctl[kOvlRecTotals + k], (unsigned long long)total);
-    }
-}
-
-inline unsigned ovl_grid(long long n_rec)
-{
-    const long long per_step = (long long)kOvlThreads * kOvlLaneRecords;
-    const long long want = (n_rec + per_step - 1) / per_step;
-    return (unsigned)(want < 1 ? 1 : (want > kOvlMaxBlocks ? kOvlMaxBlocks : want));
+    wave_flush_totals(tot, &A.ctl[kOvlRecTotals], lane);
 }
 
 // flag words -> one byte per read, the tally words -> the two counts; reads that are contained, and those contained only inside repeats

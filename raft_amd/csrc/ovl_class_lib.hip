@@ -1,9 +1,10 @@
 // ovl_class_lib.hip -- libraft_hip_ovl.so: raft_hip_repeat_overlaps_device / _host (include/raft_hip_ovl.h), the record stream
 // classified against the repeat annotation.
 //
-// A library of its own beside libraft_hip.so, as libraft_hip_low.so is: the set of entry points of include/raft_hip.h is closed
-// (ABI 11), and this query needs nothing of the engine but the context it is handed -- the repeat arrays a finished pass left
-// (engine_ctx.hpp), the stream, and buffers registered with the context like every other (oc_*, and the queries' shared staging q_*).
+// A library of its own beside libraft_hip.so (the others: the SIDE list of raft_amd/csrc/Makefile): the set of entry points of
+// include/raft_hip.h is closed (ABI 11), and this query needs nothing of the engine but the context it is handed -- the repeat arrays
+// a finished pass left (engine_ctx.hpp), the stream, and buffers registered with the context like every other (oc_*, and the queries'
+// shared staging q_*).
 #include "query_host.hpp"
 #include "../../include/raft_hip_ovl.h"
 #include "ovl_class.hpp"
@@ -63,8 +64,8 @@ int ovl_run(raft_hip_ctx *c, const OvlCall &a)
         OvlArgs A{a.len, col[0], col[1], col[2], col[3], col[4], col[5], (long long)n_rec, a.n_reads, a.symmetric ? 1 : 0, a.min_anchor,
                   rep.off, rep.x, rep.y, c->oc_digest.as<OvlDigest>(), a.cls ? c->oc_cls.as<uint8_t>() : nullptr,
                   c->oc_tally.as<unsigned long long>(), c->oc_flagw.as<unsigned>(), ctl};
-        if (aligned16(a.rec)) hipLaunchKernelGGL(ovl_class_kernel<true>, dim3(ovl_grid(n_rec)), dim3(kOvlThreads), 0, c->stream, A);
-        else hipLaunchKernelGGL(ovl_class_kernel<false>, dim3(ovl_grid(n_rec)), dim3(kOvlThreads), 0, c->stream, A);
+        if (aligned16(a.rec)) hipLaunchKernelGGL(ovl_class_kernel<true>, dim3(stream_grid(n_rec)), dim3(kStreamThreads), 0, c->stream, A);
+        else hipLaunchKernelGGL(ovl_class_kernel<false>, dim3(stream_grid(n_rec)), dim3(kStreamThreads), 0, c->stream, A);
     }
     if (a.n_reads > 0)
         hipLaunchKernelGGL(ovl_reads_kernel, dim3((unsigned)std::min<long long>(((long long)a.n_reads + 255) / 256, 1024)), dim3(256), 0, c->stream,

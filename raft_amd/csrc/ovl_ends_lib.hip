@@ -1,10 +1,10 @@
 // ovl_ends_lib.hip -- libraft_hip_end.so: raft_hip_overlap_ends_device / _host (include/raft_hip_end.h), the kind of every record of a
 // stream and the ends of every read the records support.
 //
-// A library of its own beside libraft_hip.so, as libraft_hip_low.so, libraft_hip_ovl.so, libraft_hip_frag.so, libraft_hip_rst.so and
-// libraft_hip_flt.so are: the set of entry points of include/raft_hip.h is closed (ABI 11), and this call needs nothing of the engine
-// but the context it is handed -- the stream, and buffers registered with the context like every other (en_*, and the queries'
-// shared staging q_len, q_col).  It reads no finished pass and leaves the context's state as it is.
+// A library of its own beside libraft_hip.so (the others: the SIDE list of raft_amd/csrc/Makefile): the set of entry points of
+// include/raft_hip.h is closed (ABI 11), and this call needs nothing of the engine but the context it is handed -- the stream, and
+// buffers registered with the context like every other (en_*, and the queries' shared staging q_len, q_col).  It reads no finished
+// pass and leaves the context's state as it is.
 #include "query_host.hpp"
 #include "../../include/raft_hip_end.h"
 #include "ovl_ends.hpp"
@@ -26,15 +26,7 @@ constexpr const char *kWho = "overlap_ends";
 // what both forms check before anything is staged
 int check_call(raft_hip_ctx *c, const EndCall &a)
 {
-    if (!c) return RAFT_HIP_ERR_PARAM;
-    if (a.max_overhang < 0) return refuse(c, RAFT_HIP_ERR_PARAM, kWho, "max_overhang is negative");
-    if (a.min_ratio < 0 || a.min_ratio > 1000) return refuse(c, RAFT_HIP_ERR_PARAM, kWho, "min_ratio_permille outside [0, 1000]");
-    if (a.n_reads < 0) return refuse(c, RAFT_HIP_ERR_PARAM, kWho, "n_reads is negative");
-    if (a.rec.n_rec < 0) return refuse(c, RAFT_HIP_ERR_PARAM, kWho, "n_rec is negative");
-    if (a.n_reads > 0 && !a.len) return refuse(c, RAFT_HIP_ERR_PARAM, kWho, "read_len is missing");
-    if (a.rec.n_rec > 0 && (!record_cols_ok(a.rec, false, TargetCols::always) || !a.strand))
-        return refuse(c, RAFT_HIP_ERR_PARAM, kWho, "a missing column (the six and strand)");
-    return RAFT_HIP_OK;
+    return check_ends_rule_call(c, kWho, a.max_overhang, a.min_ratio, a.n_reads, a.len, a.rec, a.strand);
 }
 
 // the four-record loads and stores: the six columns on 16-byte lines, strand and kinds (where given) on 4-byte ones
@@ -62,7 +54,7 @@ int end_run(raft_hip_ctx *c, const EndCall &a, uint8_t *kinds_back)
         const int32_t *const *col = a.rec.col;
         const EndsArgs A{a.len, col[0], col[1], col[2], col[3], col[4], col[5], a.strand, a.kinds, (long long)n_rec, a.n_reads,
                          a.max_overhang, a.min_ratio, a.symmetric ? 1 : 0, c->en_cnt.as<unsigned>(), ctl};
-        const dim3 grid(ends_grid(n_rec)), block(kEndsThreads);
+        const dim3 grid(stream_grid(n_rec)), block(kStreamThreads);
         if (vector_path(a)) hipLaunchKernelGGL(ends_kernel<true>, grid, block, 0, c->stream, A);
         else hipLaunchKernelGGL(ends_kernel<false>, grid, block, 0, c->stream, A);
     }

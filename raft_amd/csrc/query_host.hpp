@@ -31,6 +31,21 @@ constexpr const char *kNoPass = "the context holds no finished pass (none ran, t
 constexpr const char *kOtherReads = "n_reads is not that of the context's finished pass";
 constexpr const char *kBadArgs = "an argument out of range or a missing array";
 
+// What the calls under the rule of ovl_ends_rule.hpp (overlap_ends, best_overlaps) check, in both forms, before anything is staged.
+inline int check_ends_rule_call(raft_hip_ctx *c, const char *who, int32_t max_overhang, int32_t min_ratio, int32_t n_reads, const int32_t *read_len,
+                                const RecordCols &rec, const uint8_t *strand)
+{
+    if (!c) return RAFT_HIP_ERR_PARAM;
+    if (max_overhang < 0) return refuse(c, RAFT_HIP_ERR_PARAM, who, "max_overhang is negative");
+    if (min_ratio < 0 || min_ratio > 1000) return refuse(c, RAFT_HIP_ERR_PARAM, who, "min_ratio_permille outside [0, 1000]");
+    if (n_reads < 0) return refuse(c, RAFT_HIP_ERR_PARAM, who, "n_reads is negative");
+    if (rec.n_rec < 0) return refuse(c, RAFT_HIP_ERR_PARAM, who, "n_rec is negative");
+    if (n_reads > 0 && !read_len) return refuse(c, RAFT_HIP_ERR_PARAM, who, "read_len is missing");
+    if (rec.n_rec > 0 && (!record_cols_ok(rec, false, TargetCols::always) || !strand))
+        return refuse(c, RAFT_HIP_ERR_PARAM, who, "a missing column (the six and strand)");
+    return RAFT_HIP_OK;
+}
+
 // blocks of `per_block` items for n of them, one at least and `cap` at most
 inline unsigned grid_for(long long n, long long per_block, long long cap)
 {

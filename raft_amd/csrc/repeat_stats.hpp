@@ -9,13 +9,11 @@
 //                       runs.  A side outside the hull touches nothing.  A read with exactly ONE non-empty run is written as that run
 //                       alone (k0 = its index, n = 1: nothing counts the empty ones beside it), so its hull is the run and a side is
 //                       answered from the gather.  It also writes the read of every run (run_read) for the two kernels over the runs.
-//   rst_side_kernel     census_kernel's streaming shape (census.hpp: 16-byte loads of four consecutive records per lane, a 4-byte path for
-//                       columns that are not 16-byte aligned and for the records behind the last whole group, a capped grid with a
-//                       grid-stride loop), both digest gathers of a lane's records issued together.  A side inside the hull of a read
-//                       with several runs walks them in ascending rep_s, stops at the first s >= b, and sends its adds directly.  Sides
-//                       on single-run reads -- the hot streaks of a sorted query column -- go through census_count's join with the three
-//                       counts as packed weight (rst_count; ovl_count is the model): equal neighbouring slots are joined within the lane
-//                       and across the wave, and one pair of adds is sent per slot and wave.
+//   rst_side_kernel     a streaming kernel of record_stream.hpp's shape, both digest gathers of a lane's records issued together.
+//                       A side inside the hull of a read with several runs walks them in ascending rep_s, stops at the first
+//                       s >= b, and sends its adds directly.  Sides on single-run reads -- the hot streaks of a sorted query column --
+//                       go through join_runs with the three counts as packed weight (rst_count): equal neighbouring slots are joined
+//                       within the lane and across the wave, and one pair of adds is sent per slot and wave.
 //                       Counters are 16 bytes per run (RstSlot): touch and span share one 64-bit word, inside is the second.  All adds
 //                       are positive, so the halves stay 32 bits apart and do not mix below 2^32 sides on a run.
 //   rst_cov_kernel      a wave per run, grid-stride over the runs, the lanes striding over the run's windows of the int32 coverage:
@@ -28,21 +26,16 @@
 #pragma once
 #include "raft_types.hpp"
 #include "wave.hpp"
-#include "census.hpp"
+#include "record_stream.hpp"
 
 namespace raft {
 
-constexpr int kRstThreads = kCensusThreads;
-constexpr int kRstLaneRecords = kCensusLaneRecords;      // consecutive records of one lane per step
-constexpr int kRstWaveRecords = kRstLaneRecords * kWave; // ... of one wave: what the join sums before it adds (fits kRstFieldBits)
-constexpr int kRstBlockRecords = kRstLaneRecords * kRstThreads;   // ... of one workgroup
-constexpr int kRstMaxBlocks = kCensusMaxBlocks;
 constexpr int kRstFieldBits = 10;                        // a count of the packed weight: touch | span << 10 | inside << 20
 constexpr int kRstCovVec = 4;                            // windows of one 16-byte load
 constexpr int kRstCovStep = kRstCovVec * kWave;          // windows one wave takes per step of the coverage kernel
 constexpr int kRstCovThreads = 256;
 constexpr int kRstCovMaxBlocks = 8192;
-static_assert(kRstWaveRecords < (1 << kRstFieldBits), "a wave's sides on one slot must fit one field of the packed weight");
+static_assert(kStreamWaveRecords < (1 << kRstFieldBits), "a wave's sides on one slot must fit one field of the packed weight");
 
 // control words (unsigned long long each)
 constexpr int kRstFirstBad = 0;          // smallest record index with an id out of range; ~0 = none
@@ -108,41 +101,12 @@ __device__ __forceinline__ void rst_add(RstSlot *__restrict__ slot, int id, unsi
     if (inside) atomicAdd(&slot[id].c, (unsigned long long)inside);
 }
 
-// census_count's joins (census.hpp) for the three counts of a run at once: w = touch | span << 10 | inside << 20 of each record, summed
-// over equal neighbouring slot ids within the lane and across the wave -- a wave has kRstWaveRecords records, so no field overflows into
-// the next -- and one pair of adds per slot and wave.  A record with w = 0 adds nothing whatever its id.  EXEC must be all ones.
-__device__ __forceinline__ void rst_count(const int (&id)[kRstLaneRecords], const unsigned (&w)[kRstLaneRecords], RstSlot *__restrict__ slot, int lane)
+// join_runs for the three counts of a run at once: w = touch | span << 10 | inside << 20 of each record, summed over equal
+// neighbouring slot ids -- a wave has kStreamWaveRecords records, so no field overflows into the next -- and one pair of adds per
+// slot and wave.  A record with w = 0 adds nothing whatever its id: a side without a slot comes with id -1.
+__device__ __forceinline__ void rst_count(const int (&id)[kStreamLaneRecords], const unsigned (&w)[kStreamLaneRecords], RstSlot *__restrict__ slot, int lane)
 {
-    int cur = id[0];
-    unsigned n = w[0], head_n = 0;
-    bool uniform = true;
-#pragma unroll
-    for (int i = 1; i < kRstLaneRecords; ++i) {
-        if (id[i] == cur) n += w[i];
-        else {
-            if (uniform) { head_n = n; uniform = false; }
-            else if (n) rst_add(slot, cur, n);               // a run that touches neither end of the lane
-            cur = id[i]; n = w[i];
-        }
-    }
-    // the lane's last run (cur, n) opens a segment unless the lane is one run that carries on what the lane before ended with
-    const int prev_tail = __shfl_up(cur, 1, kWave);
-    const bool joins = lane > 0 && id[0] == prev_tail;
-    unsigned x = n;
-    int f = (!uniform || !joins) ? 1 : 0;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const unsigned xo = __shfl_up(x, d, kWave);
-        const int fo = __shfl_up(f, d, kWave);
-        if (lane >= d && !f) { x += xo; f = fo; }
-    }
-    const unsigned before = __shfl_up(x, 1, kWave);          // the open run as the lane before left it
-    const int next_joins = __shfl_down(joins ? 1 : 0, 1, kWave);
-    if (!uniform) {
-        const unsigned h = head_n + (joins ? before : 0u);
-        if (h) rst_add(slot, id[0], h);
-    }
-    if ((lane == kWave - 1 || !next_joins) && x) rst_add(slot, cur, x);
+    join_runs(id, w, lane, JoinAdd{}, [slot](int k, unsigned x) { if (x) rst_add(slot, k, x); });
 }
 
 // One counted side [a, b) on the read with digest d.  A single-run read: the packed weight for the join comes back and *id is the
@@ -168,59 +132,39 @@ __device__ __forceinline__ unsigned rst_side(const RstArgs &A, const RstDigest d
 }
 
 template <bool kVec>
-__global__ __launch_bounds__(kRstThreads) void rst_side_kernel(RstArgs A)
+__global__ __launch_bounds__(kStreamThreads) void rst_side_kernel(RstArgs A)
 {
-    constexpr int R = kRstLaneRecords;
+    constexpr int R = kStreamLaneRecords;
     if (A.ctl[kRstBadOffsets]) return;                       // (uniform: the digest kernel's verdict, written before this launch)
     const int lane = (int)threadIdx.x & (kWave - 1);
-    const long long n_groups = (A.n_rec + R - 1) / R;
-    const long long stride = (long long)gridDim.x * blockDim.x;
     const unsigned n_reads = (unsigned)A.n_reads;
     const bool targets = !A.symmetric;
-    // (the loop's bound is the wave's: every lane of a wave takes part in the scans)
-    for (long long g0 = (long long)blockIdx.x * blockDim.x + ((int)threadIdx.x & ~(kWave - 1)); g0 < n_groups; g0 += stride) {
-        const long long first = (g0 + lane) * R;             // (at or beyond n_rec: a lane without records)
-        int q[R], t[R], a[R], b[R], ts[R], te[R];
-        census_load<kVec>(A.qid, first, A.n_rec, -1, q);
-        census_load<kVec>(A.tid, first, A.n_rec, -1, t);
-        census_load<kVec>(A.qs, first, A.n_rec, -1, a);
-        census_load<kVec>(A.qe, first, A.n_rec, -1, b);
-        if (targets) {
-            census_load<kVec>(A.ts, first, A.n_rec, -1, ts);
-            census_load<kVec>(A.te, first, A.n_rec, -1, te);
-        }
+    stream_for_each_group(A.n_rec, lane, [&](const long long first) {
+        LaneRecords r;
+        stream_load_records<kVec>(A.qid, A.qs, A.qe, A.tid, A.ts, A.te, first, A.n_rec, targets, r);
         // the gathers of the lane's eight sides first, all in flight together
         RstDigest dq[R], dt[R];
-        bool ok[R];
 #pragma unroll
         for (int i = 0; i < R; ++i) {
-            const bool have = first + i < A.n_rec;
-            ok[i] = have && (unsigned)q[i] < n_reads && (unsigned)t[i] < n_reads;
-            if (have && !ok[i]) atomicMin(&A.ctl[kRstFirstBad], (unsigned long long)(first + i));
+            const IdsValid v = stream_check_ids(first + i < A.n_rec, first + i, r.q[i], r.t[i], n_reads, &A.ctl[kRstFirstBad]);
             dq[i] = dt[i] = RstDigest{0, 0, 0, 0};
-            if (ok[i]) {
-                dq[i] = A.digest[q[i]];
-                if (targets && t[i] != q[i]) dt[i] = A.digest[t[i]];     // (a target side on its query's own read is not counted)
+            if (v.q && v.t) {
+                dq[i] = A.digest[r.q[i]];
+                if (targets && r.t[i] != r.q[i]) dt[i] = A.digest[r.t[i]];   // (a target side on its query's own read is not counted)
             }
         }
         int iq[R], it[R];
         unsigned wq[R], wt[R];
 #pragma unroll
         for (int i = 0; i < R; ++i) {
-            wq[i] = rst_side(A, dq[i], a[i], b[i], &iq[i]);
+            wq[i] = rst_side(A, dq[i], r.qs[i], r.qe[i], &iq[i]);
             it[i] = -1; wt[i] = 0u;
-            if (targets) wt[i] = rst_side(A, dt[i], ts[i], te[i], &it[i]);
+            if (targets) wt[i] = rst_side(A, dt[i], r.ts[i], r.te[i], &it[i]);
         }
         // a wave none of whose sides is on a single-run read adds nothing (the branches are the wave's: EXEC stays all ones inside)
         if (__any((int)(wq[0] | wq[1] | wq[2] | wq[3]))) rst_count(iq, wq, A.slot, lane);
         if (__any((int)(wt[0] | wt[1] | wt[2] | wt[3]))) rst_count(it, wt, A.slot, lane);
-    }
-}
-
-inline unsigned rst_grid(long long n_rec)
-{
-    const long long want = (n_rec + kRstBlockRecords - 1) / kRstBlockRecords;
-    return (unsigned)(want < 1 ? 1 : (want > kRstMaxBlocks ? kRstMaxBlocks : want));
+    });
 }
 
 struct RstCovOut { int32_t *windows, *cov_min, *cov_max, *high; long long *cov_sum; };

@@ -1,9 +1,9 @@
 // repeat_stats_lib.hip -- libraft_hip_rst.so: raft_hip_repeat_stats_device / _host (include/raft_hip_rst.h), one row per repeat run.
 //
-// A library of its own beside libraft_hip.so, as libraft_hip_low.so, libraft_hip_ovl.so and libraft_hip_frag.so are: the set of entry
-// points of include/raft_hip.h is closed (ABI 11), and this query needs nothing of the engine but the context it is handed -- the
-// coverage and the repeat arrays a finished pass left (engine_ctx.hpp), the stream, and buffers registered with the context like
-// every other (rst_*, and the queries' shared staging and decoded coverage q_*).
+// A library of its own beside libraft_hip.so (the others: the SIDE list of raft_amd/csrc/Makefile): the set of entry points of
+// include/raft_hip.h is closed (ABI 11), and this query needs nothing of the engine but the context it is handed -- the coverage and
+// the repeat arrays a finished pass left (engine_ctx.hpp), the stream, and buffers registered with the context like every other
+// (rst_*, and the queries' shared staging and decoded coverage q_*).
 #include "cov_decode.hpp"
 #include "../../include/raft_hip_rst.h"
 #include "repeat_stats.hpp"
@@ -80,8 +80,8 @@ int rst_run(raft_hip_ctx *c, const RstCall &a)
     if (n_rec > 0) {                                          // (without a run too: the ids are checked)
         RstArgs A{col[0], col[1], col[2], col[3], col[4], col[5], (long long)n_rec, a.n_reads, a.symmetric ? 1 : 0,
                   rep.x, rep.y, c->rst_digest.as<RstDigest>(), slot, ctl};
-        if (aligned16(a.rec)) hipLaunchKernelGGL(rst_side_kernel<true>, dim3(rst_grid(n_rec)), dim3(kRstThreads), 0, c->stream, A);
-        else hipLaunchKernelGGL(rst_side_kernel<false>, dim3(rst_grid(n_rec)), dim3(kRstThreads), 0, c->stream, A);
+        if (aligned16(a.rec)) hipLaunchKernelGGL(rst_side_kernel<true>, dim3(stream_grid(n_rec)), dim3(kStreamThreads), 0, c->stream, A);
+        else hipLaunchKernelGGL(rst_side_kernel<false>, dim3(stream_grid(n_rec)), dim3(kStreamThreads), 0, c->stream, A);
     }
     RstCovOut co{c->rst_win[0].as<int32_t>(), c->rst_win[1].as<int32_t>(), c->rst_win[2].as<int32_t>(), c->rst_win[3].as<int32_t>(), c->rst_sum.as<long long>()};
     if (n_rep > 0) {

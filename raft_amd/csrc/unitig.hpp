@@ -186,12 +186,7 @@ __global__ __launch_bounds__(kUtgThreads) void utg_emit_kernel(const UtgPlace *_
     }
     // (all lanes are back together here)
     const unsigned counts[4] = {skipped, unitigs, singletons, circular};
-    unsigned long long mine = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const unsigned total = (unsigned)wave_reduce_add((int)counts[k]);
-        if (lane == k) mine = total;
-    }
+    unsigned long long mine = wave_lane_totals(counts, lane);
     const long long tl = wave_reduce_add64(total_length), lr = utg_wave_max(longest_reads), ll = utg_wave_max(longest_length);
     if (lane == kUtgTotalLength) mine = (unsigned long long)tl;
     if (lane < kUtgLongestReads) { if (mine) atomicAdd(&ctl[kUtgCtlTotals + lane], mine); }

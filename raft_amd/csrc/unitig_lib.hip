@@ -1,7 +1,7 @@
 // unitig_lib.hip -- libraft_hip_utg.so: raft_hip_unitigs_device / _host (include/raft_hip_utg.h), the unitigs of the best overlap
 // graph.
 //
-// A library of its own beside libraft_hip.so, as libraft_hip_best.so and the six before it are: the set of entry points of
+// A library of its own beside libraft_hip.so (the others: the SIDE list of raft_amd/csrc/Makefile): the set of entry points of
 // include/raft_hip.h is closed (ABI 11), and this call needs nothing of the engine but the context it is handed -- the stream, and
 // buffers registered with the context like every other (ut_*, and the queries' shared staging q_len, q_col).  It reads no finished
 // pass and leaves the context's state as it is.

@@ -95,6 +95,28 @@ __device__ __forceinline__ int wave_reduce_add(int v)
     return __builtin_amdgcn_readlane(wave_incl_scan_add(v), kWave - 1);
 }
 
+// N per-lane totals of a kernel, summed over the wave: lane k < N comes back with the sum of tot[k], every other lane with 0 -- so
+// that the totals leave with ONE atomic instruction per wave (wave_flush_totals: ctl[k] += sum k where it is not 0) instead of N from
+// one lane.  EXEC must be all ones.
+template <int N>
+__device__ __forceinline__ unsigned wave_lane_totals(const unsigned (&tot)[N], int lane)
+{
+    static_assert(N <= kWave, "a lane per total");
+    unsigned mine = 0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const unsigned total = (unsigned)wave_reduce_add((int)tot[k]);
+        if (lane == k) mine = total;
+    }
+    return mine;
+}
+template <int N>
+__device__ __forceinline__ void wave_flush_totals(const unsigned (&tot)[N], unsigned long long *ctl, int lane)
+{
+    const unsigned mine = wave_lane_totals(tot, lane);
+    if (lane < N && mine) atomicAdd(&ctl[lane], (unsigned long long)mine);
+}
+
 // Values that are the same in every lane but were fetched with vector loads (the compiler cannot prove the
 // memory is not clobbered by the kernel's own stores, so it will not use scalar loads): move them to SGPRs so
 // that everything computed from them -- loop bounds, branch conditions, addresses -- stays scalar.

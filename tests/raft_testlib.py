@@ -2119,3 +2119,10 @@ def delta4_reference(cov):
     xi = np.flatnonzero(np.abs(step) > 7).astype(np.int64)
     anchor = np.concatenate([[0], cov[D4_BLOCK - 1::D4_BLOCK]])[: (n + D4_BLOCK - 1) // D4_BLOCK].astype(np.int32)
     return (code[0::2] | (code[1::2] << 4)).astype(np.uint8), anchor, xi, cov[xi].astype(np.int32)
+
+
+# ---- record streams ---------------------------------------------------------------------------------------------------------------------
+
+def runs_of(lengths, first_id=0, lead=0):
+    """A query column of sorted runs: `lead` records of read first_id, then runs of the given lengths on the reads behind it."""
+    return np.concatenate([np.full(lead, first_id)] + [np.full(n, first_id + 1 + k) for k, n in enumerate(lengths)]).astype(np.int64)

@@ -34,9 +34,10 @@ def source_units():
     """The unit sizes of the record kernel and of the scan, read back from the sources: records per lane, wave, workgroup and turn of
     the grid-stride loop; slots per tile of the scan and per turn of its loop over the tiles before."""
     frag = open(os.path.join(ROOT, "raft_amd", "csrc", "frag_ovl.hpp")).read()
-    for mine, theirs in (("kFragThreads", "kCensusThreads"), ("kFragLaneRecords", "kCensusLaneRecords"), ("kFragMaxBlocks", "kCensusMaxBlocks")):
-        assert re.search(r"constexpr int " + mine + r"\s*=\s*" + theirs + r"\s*;", frag), mine
-    threads, lane, blocks = (_constant("census.hpp", n) for n in ("kCensusThreads", "kCensusLaneRecords", "kCensusMaxBlocks"))
+    # the record kernel is launched with the shared constants and has no grid function of its own
+    assert '#include "record_stream.hpp"' in frag and "__launch_bounds__(kStreamThreads) void frag_side_kernel" in frag
+    assert "frag_grid" not in frag
+    threads, lane, blocks = (_constant("record_stream.hpp", n) for n in ("kStreamThreads", "kStreamLaneRecords", "kStreamMaxBlocks"))
     scan_threads, scan_items = _constant("device_scan.hpp", "kScanThreads"), _constant("device_scan.hpp", "kScanItems")
     return {"lane": lane, "wave": 64 * lane, "workgroup": threads * lane, "grid": blocks * threads * lane,
             "tile": scan_threads * scan_items, "segment": scan_threads * scan_threads * scan_items}

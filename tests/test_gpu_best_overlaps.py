@@ -7,8 +7,8 @@ import re
 
 import numpy as np
 import pytest
-from raft_testlib import ROOT
-from test_gpu_overlap_ends import make_stream, mirrored, runs_of, want_all, want_kinds
+from raft_testlib import ROOT, runs_of
+from test_gpu_overlap_ends import make_stream, mirrored, want_all, want_kinds
 
 from raft_amd.params import RaftParams
 
@@ -24,17 +24,20 @@ def _constant(header, name):
     return int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1))
 
 
-# T: the records one workgroup takes per step (best_ovl.hpp: kBestThreads lanes of kCensusLaneRecords records each); beyond
-# kBestMaxBlocks workgroups the grid strides
-T = _constant("best_ovl.hpp", "kBestThreads") * _constant("census.hpp", "kCensusLaneRecords")
-STRIDE = T * _constant("best_ovl.hpp", "kBestMaxBlocks")
+# T: the records one workgroup takes per step (record_stream.hpp: kStreamThreads lanes of kStreamLaneRecords records each); beyond
+# kStreamMaxBlocks workgroups the grid strides
+T = _constant("record_stream.hpp", "kStreamThreads") * _constant("record_stream.hpp", "kStreamLaneRecords")
+STRIDE = T * _constant("record_stream.hpp", "kStreamMaxBlocks")
 SIZES = [0, 1, 3, 4, 5, 63, 64, 65, 255, 256, 257, T - 1, T, T + 1, 2 * T + 3, STRIDE + 2 * T + 5]
 
 
 def test_the_constants_are_the_expected_ones():
     assert (T, STRIDE) == (1024, 2048 * 1024)
-    text = open(os.path.join(ROOT, "raft_amd", "csrc", "best_ovl.hpp")).read()
-    assert "const long long per_step = (long long)kBestThreads * kCensusLaneRecords;" in text
+    shared = open(os.path.join(ROOT, "raft_amd", "csrc", "record_stream.hpp")).read()
+    assert "const long long per_step = (long long)kStreamThreads * kStreamLaneRecords;" in shared
+    text = open(os.path.join(ROOT, "raft_amd", "csrc", "best_ovl.hpp")).read()      # launched with the shared ones, no grid of its own
+    assert '#include "record_stream.hpp"' in text and "__launch_bounds__(kStreamThreads) void best_kernel" in text
+    assert "_grid(" not in text
 
 
 # ---- the rule, restated over whole columns

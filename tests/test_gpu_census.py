@@ -5,7 +5,7 @@ import re
 
 import numpy as np
 import pytest
-from raft_testlib import ROOT
+from raft_testlib import ROOT, runs_of
 
 from raft_amd.params import RaftParams
 
@@ -13,9 +13,9 @@ pytestmark = pytest.mark.gpu
 
 
 def launch_constants():
-    text = open(os.path.join(ROOT, "raft_amd", "csrc", "census.hpp")).read()
-    k = {name: int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1)) for name in ("kCensusThreads", "kCensusLaneRecords", "kCensusMaxBlocks")}
-    return k["kCensusThreads"], k["kCensusLaneRecords"], k["kCensusMaxBlocks"]
+    text = open(os.path.join(ROOT, "raft_amd", "csrc", "record_stream.hpp")).read()
+    k = {name: int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1)) for name in ("kStreamThreads", "kStreamLaneRecords", "kStreamMaxBlocks")}
+    return k["kStreamThreads"], k["kStreamLaneRecords"], k["kStreamMaxBlocks"]
 
 
 def want_census(rl, qid, qs, qe, tid, ts, te, symmetric):
@@ -172,6 +172,27 @@ def test_every_record_on_one_read(eng):
         assert got["intervals"][17] >= n_rec
     cols = records(rl, tid, qid, 4)                        # ... and every target side on one read
     check(eng, cols, False, "one target read")
+
+
+RUNS = [63, 64, 65, 257, 1, 2, 257, 65, 64, 63, 5, 257, 4, 4, 4, 3, 1, 1, 256, 1024, 7]
+
+
+@pytest.mark.parametrize("lead", [0, 1, 3, 62, 255, 1024 - 1])
+def test_runs_across_lane_wave_and_workgroup_edges(eng, lead):
+    """Runs of 63 / 64 / 65 / 257 records on one read, begun at every kind of offset (the last: T - 1, T the records of a workgroup
+    step), against a random target column and against the target column in runs as well."""
+    threads, lane_records, _ = launch_constants()
+    assert threads * lane_records == 1024
+    rng = np.random.default_rng(lead)
+    n_reads = 65
+    rl = rng.integers(100, 5000, n_reads).astype(np.int32)
+    rl[::7] = rl[3]                                        # equal lengths among the reads
+    qid = runs_of(RUNS, first_id=2, lead=lead)
+    assert qid.max() < n_reads
+    for what, tid in (("runs, random targets", rng.integers(0, n_reads, qid.size)), ("runs on both sides", qid[::-1].copy())):
+        cols = records(rl, qid, tid, 11 + lead)
+        for symmetric in (False, True):
+            check(eng, cols, symmetric, what)
 
 
 def test_more_records_than_the_capped_grid_takes_in_one_step(eng):

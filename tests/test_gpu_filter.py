@@ -23,12 +23,14 @@ def _constant(header, name):
 
 
 def tile_and_scan():
-    """T: the records of a tile (filter.hpp: kFltTile = kFltThreads * kFltLaneRecords, kFltLaneRecords = census.hpp's
-    kCensusLaneRecords); S: the tiles one workgroup of the scan takes (device_scan.hpp: kScanTile = kScanThreads * kScanItems)."""
+    """T: the records of a tile (filter.hpp: kFltTile = kFltThreads * kFltLaneRecords, kFltLaneRecords = record_stream.hpp's
+    kStreamLaneRecords, by that name or by the one census.hpp has for it); S: the tiles one workgroup of the scan takes
+    (device_scan.hpp: kScanTile = kScanThreads * kScanItems)."""
     text = open(os.path.join(ROOT, "raft_amd", "csrc", "filter.hpp")).read()
-    assert "constexpr int kFltLaneRecords = kCensusLaneRecords;" in text and "constexpr int kFltTile = kFltThreads * kFltLaneRecords;" in text
+    assert re.search(r"constexpr int kFltLaneRecords = k(Stream|Census)LaneRecords;", text) and "constexpr int kFltTile = kFltThreads * kFltLaneRecords;" in text
+    assert "static_assert(kFltLaneRecords == kStreamLaneRecords" in text and '#include "record_stream.hpp"' in text
     assert "constexpr int kScanTile = kScanThreads * kScanItems;" in open(os.path.join(ROOT, "raft_amd", "csrc", "device_scan.hpp")).read()
-    T = _constant("filter.hpp", "kFltThreads") * _constant("census.hpp", "kCensusLaneRecords")
+    T = _constant("filter.hpp", "kFltThreads") * _constant("record_stream.hpp", "kStreamLaneRecords")
     S = _constant("device_scan.hpp", "kScanThreads") * _constant("device_scan.hpp", "kScanItems")
     return T, S
 

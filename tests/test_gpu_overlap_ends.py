@@ -7,7 +7,7 @@ import re
 
 import numpy as np
 import pytest
-from raft_testlib import ROOT
+from raft_testlib import ROOT, runs_of
 
 from raft_amd.params import RaftParams
 
@@ -23,17 +23,20 @@ def _constant(header, name):
     return int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1))
 
 
-# T: the records one workgroup takes per step (ovl_ends.hpp: kEndsThreads lanes of kCensusLaneRecords records each); beyond
-# kEndsMaxBlocks workgroups the grid strides
-T = _constant("ovl_ends.hpp", "kEndsThreads") * _constant("census.hpp", "kCensusLaneRecords")
-STRIDE = T * _constant("ovl_ends.hpp", "kEndsMaxBlocks")
+# T: the records one workgroup takes per step (record_stream.hpp: kStreamThreads lanes of kStreamLaneRecords records each); beyond
+# kStreamMaxBlocks workgroups the grid strides
+T = _constant("record_stream.hpp", "kStreamThreads") * _constant("record_stream.hpp", "kStreamLaneRecords")
+STRIDE = T * _constant("record_stream.hpp", "kStreamMaxBlocks")
 SIZES = [0, 1, 3, 4, 5, 63, 64, 65, 255, 256, 257, T - 1, T, T + 1, 2 * T + 3, STRIDE + 2 * T + 5]
 
 
 def test_the_constants_are_the_expected_ones():
     assert (T, STRIDE) == (1024, 2048 * 1024)
-    text = open(os.path.join(ROOT, "raft_amd", "csrc", "ovl_ends.hpp")).read()
-    assert "const long long per_step = (long long)kEndsThreads * kCensusLaneRecords;" in text
+    shared = open(os.path.join(ROOT, "raft_amd", "csrc", "record_stream.hpp")).read()
+    assert "const long long per_step = (long long)kStreamThreads * kStreamLaneRecords;" in shared
+    text = open(os.path.join(ROOT, "raft_amd", "csrc", "ovl_ends.hpp")).read()      # launched with the shared ones, no grid of its own
+    assert '#include "record_stream.hpp"' in text and "__launch_bounds__(kStreamThreads) void ends_kernel" in text
+    assert "_grid(" not in text
 
 
 # ---- the rule, restated over whole columns (int64 throughout; np.select takes the first condition that holds)
@@ -119,11 +122,6 @@ def make_stream(rng, n_reads, n_rec, qid=None, tid=None, template=None):
     put(tpl == 7, 0 * lq, ovl, lq - ovl, lq)
     cols = [c.astype(np.int32) for c in (qid, qs, qe, tid, ts, te)]
     return L, cols, rev.astype(np.uint8)
-
-
-def runs_of(lengths, first_id=0, lead=0):
-    """A query column of sorted runs: `lead` records of read first_id, then runs of the given lengths on the reads behind it."""
-    return np.concatenate([np.full(lead, first_id)] + [np.full(n, first_id + 1 + k) for k, n in enumerate(lengths)]).astype(np.int64)
 
 
 @pytest.fixture(scope="module")

@@ -264,18 +264,21 @@ def streak_case(n, column, lead=3):
 # ---- the tests ------------------------------------------------------------------------------------------------------------------------------
 
 def test_the_constants_the_cases_are_built_on():
-    rst, cen = open(os.path.join(CSRC, "repeat_stats.hpp")).read(), open(os.path.join(CSRC, "census.hpp")).read()
+    rst, shared = open(os.path.join(CSRC, "repeat_stats.hpp")).read(), open(os.path.join(CSRC, "record_stream.hpp")).read()
 
     def one(pattern, text):
         m = re.findall(pattern, text)
         assert len(m) == 1, (pattern, m)
         return m[0]
-    assert int(one(r"constexpr int kCensusLaneRecords = (\d+);", cen)) == LANE_RECORDS
-    threads = int(one(r"constexpr int kCensusThreads = (\d+);", cen))
-    one(r"constexpr int kRstThreads = kCensusThreads;", rst)
-    one(r"constexpr int kRstLaneRecords = kCensusLaneRecords;", rst)
-    one(r"constexpr int kRstWaveRecords = kRstLaneRecords \* kWave;", rst)
-    one(r"constexpr int kRstBlockRecords = kRstLaneRecords \* kRstThreads;", rst)
+    assert int(one(r"constexpr int kStreamLaneRecords = (\d+);", shared)) == LANE_RECORDS
+    threads = int(one(r"constexpr int kStreamThreads = (\d+);", shared))
+    one(r"constexpr int kStreamWaveRecords = kStreamLaneRecords \* kWave;", shared)
+    one(r"const long long per_step = \(long long\)kStreamThreads \* kStreamLaneRecords;", shared)
+    # the record kernel has no launch constant of its own: the shared ones, and the packed weight's field is sized by the shared wave
+    one(r'#include "record_stream.hpp"', rst)
+    one(r"__launch_bounds__\(kStreamThreads\) void rst_side_kernel", rst)
+    assert not re.search(r"constexpr int kRst(Threads|LaneRecords|WaveRecords|BlockRecords|MaxBlocks)\b", rst)
+    one(r"static_assert\(kStreamWaveRecords < \(1 << kRstFieldBits\)", rst)
     assert LANE_RECORDS * 64 == WAVE_RECORDS and LANE_RECORDS * threads == WG_RECORDS
     assert int(one(r"constexpr int kRstCovVec = (\d+);", rst)) * 64 == COV_STEP
     one(r"constexpr int kRstCovStep = kRstCovVec \* kWave;", rst)
