@@ -420,6 +420,11 @@ struct raft_hip_ctx {
     DevBuf ut_state{bufs}, ut_cut{bufs}, ut_read{bufs}, ut_offset{bufs}, ut_ulen{bufs}, ut_orient{bufs}, ut_scan{bufs}, ut_unitig{bufs}, ut_order{bufs};
     DevBuf ut_utg[4] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
     DevBuf ut_ctl{bufs}, ut_flags{bufs};
+    // raft_hip_lift_overlaps_* (lift_lib.hip): the digest of every read's rows, the outputs of every tile and of every lane, the tiles' prefix, the scan's
+    // partial sums, the control words; the host form's staging of the strand bytes (columns and table: q_col, q_csr_a) and the eight
+    // output columns before they go to the caller
+    DevBuf lf_digest{bufs}, lf_tile_cnt{bufs}, lf_lane_cnt{bufs}, lf_tile_base{bufs}, lf_scan{bufs}, lf_ctl{bufs}, lf_strand{bufs};
+    DevBuf lf_out[8] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
     // raft_hip_census_*: counts and flag words per read, the flags as bytes, {first bad record, reads with a flag}; staging of the host form --
     // the census's own and not q_*: it lives in the engine library, whose chunk pool backs the columns (kBig), which the side libraries' must not be
     DevBuf cen_cnt{bufs}, cen_flags{bufs}, cen_out{bufs}, cen_ctl{bufs}, cen_len{bufs};

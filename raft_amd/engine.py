@@ -115,6 +115,10 @@ class _UtgSummary(C.Structure):
                                          "total_length")]
 
 
+class _LiftSummary(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_records", "n_out", "records_none", "records_cut", "pairs_dropped", "most_per_record")]
+
+
 class _Outputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("cov_offset", "cov", "rep_offset", "rep_s", "rep_e", "cut_offset", "cuts",
                                           "frag_offset", "frag_read", "frag_begin", "frag_end")]
@@ -260,6 +264,15 @@ UTG_ABI = {
 }
 UTG_MAX_READS = (1 << 30) - 1     # half-edge ids are int32
 
+# ... and those of include/raft_hip_lift.h (libraft_hip_lift.so): load_lift_library declares these
+_LIFT_CALL = [_vp, _i32, _P(_Records), _vp, _P(_FragTable), _i32, _i64] + [_vp] * 8 + [_P(_LiftSummary), _P(_i64), _P(_f64)]
+LIFT_ABI = {
+    "raft_hip_lift_abi": (C.c_int, []),
+    "raft_hip_lift_overlaps_device": (C.c_int, _LIFT_CALL),
+    "raft_hip_lift_overlaps_host": (C.c_int, _LIFT_CALL),
+}
+LIFT_COLUMNS = ("qfrag", "qs", "qe", "tfrag", "ts", "te", "rev", "src")      # int32, but for rev: uint8
+
 
 @dataclass
 class Summary:
@@ -337,7 +350,8 @@ _SIDE = {"low": ("libraft_hip_low.so", LOW_ABI, "raft_hip_low_abi"), "ovl": ("li
 _SIDE_MORE = {"best": ("libraft_hip_best.so", BEST_ABI, "raft_hip_best_abi")}
 # ... and an open one for every library after that (``_SIDE_MORE`` is compared by equality where it was added): the next library is
 # one more entry here, and its tests look for their own tag, not at the whole table.
-_SIDE_OPEN = {"utg": ("libraft_hip_utg.so", UTG_ABI, "raft_hip_utg_abi")}
+_SIDE_OPEN = {"utg": ("libraft_hip_utg.so", UTG_ABI, "raft_hip_utg_abi"),
+              "lift": ("libraft_hip_lift.so", LIFT_ABI, "raft_hip_lift_abi")}
 _side_libs: dict = {}
 
 
@@ -399,6 +413,11 @@ def load_best_library() -> C.CDLL:
 def load_utg_library() -> C.CDLL:
     """libraft_hip_utg.so with every entry point of include/raft_hip_utg.h declared."""
     return _load_side_library("utg")
+
+
+def load_lift_library() -> C.CDLL:
+    """libraft_hip_lift.so with every entry point of include/raft_hip_lift.h declared."""
+    return _load_side_library("lift")
 
 
 def _cparams(p: RaftParams) -> _Params:
@@ -1290,6 +1309,72 @@ class Engine:
         return {"unitig": unitig, "index": index, "offset": offset, "orient": orient, "order": order[:placed], "utg_off": utg_off[:n_utg + 1],
                 "utg_reads": utg_reads[:n_utg], "utg_length": utg_length[:n_utg], "utg_circular": utg_circular[:n_utg],
                 "summary": _summary_dict(sm), "kernel_seconds": secs.value, "launches": launches.value}
+
+    # -- the overlaps between the fragments ------------------------------------------------------------------
+    last_lift_overlaps_seconds = 0.0     # device time of the launches of the last lift_overlaps()
+
+    def lift_overlaps(self, qid, qs, qe, tid, ts, te, strand, fragments=None, min_len: int = 1) -> dict:
+        """raft_hip_lift_overlaps_device / _host (libraft_hip_lift.so): every record cut at the fragment bounds of both of its reads
+        and shifted into fragment coordinates, under the rule of include/raft_hip_lift.h; pairs shorter than ``min_len`` on either
+        side are dropped.  ``strand`` is one uint8 per record (1: PAF field 5 begins with '-').  -> the eight columns ``LIFT_COLUMNS``
+        of length ``n_out`` (``qfrag`` / ``tfrag``: global row indices of the table; ``src``: the record an output came from), the
+        summary's counts (``n_records``, ``n_out``, ``records_none``, ``records_cut``, ``pairs_dropped``, ``most_per_record``) and
+        ``kernel_seconds``.  The columns are torch tensors on this engine's device (int32; strand uint8; the outputs are then tensors
+        there and ``fragments`` must be tensors too) or numpy arrays (staged by the library).  ``fragments``: None = the rows of this
+        context's finished pass, else (frag_offset int64 [n_reads + 1], frag_begin, frag_end int32).  Two calls: the size query, then
+        the one that fills."""
+        cols = [qid, qs, qe, tid, ts, te]
+        if any(x is None for x in cols) or strand is None:
+            raise ValueError("lift_overlaps needs the six columns and strand")
+        tab = [None, None, None] if fragments is None else list(fragments)
+        if len(tab) != 3:
+            raise ValueError("fragments is (frag_offset, frag_begin, frag_end)")
+        on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in cols + [strand] + [a for a in tab if a is not None])
+        lift = load_lift_library()
+        if on_device:
+            import torch
+            _need_int32_cuda("lift_overlaps needs", cols + tab[1:])
+            if strand.dtype != torch.uint8 or not strand.is_contiguous():
+                raise TypeError("lift_overlaps needs strand as a contiguous uint8 CUDA tensor")
+            if tab[0] is not None and (tab[0].dtype != torch.int64 or not tab[0].is_contiguous()):
+                raise TypeError("lift_overlaps needs frag_offset as a contiguous int64 CUDA tensor")
+            self.use_torch_stream()
+            fn = lift.raft_hip_lift_overlaps_device
+        else:
+            host = [x.cpu() if hasattr(x, "is_cuda") else x for x in cols + [strand] + tab]
+            cols = _host_columns(host[:6])
+            strand = M.carray(host[6], np.uint8)
+            tab = [None if host[7] is None else M.carray(host[7], np.int64)] + _host_columns(host[8:])
+            fn = lift.raft_hip_lift_overlaps_host
+        n_rec = M.count(cols[0])
+        _need_equal_lengths(cols + [strand], n_rec)
+        if fragments is None:
+            last = getattr(self, "summary", None)
+            n_reads = int(last.n_reads) if last is not None else 0       # (the library checks the state)
+        else:
+            if tab[0] is None or (tab[1] is None) != (tab[2] is None) or M.count(tab[0]) < 1 or (tab[1] is not None and M.count(tab[1]) != M.count(tab[2])):
+                raise ValueError("fragments is (offsets [n_reads + 1], two arrays of one length)")
+            n_reads = M.count(tab[0]) - 1
+        records = _Records(n_rec, *[M.address(c) for c in cols])
+        table = _FragTable(_csr_count(fragments is not None, tab), *[M.address(a) for a in tab])
+        sm, err, secs = _LiftSummary(), C.c_int64(-1), C.c_double(0.0)
+        null = [C.c_void_p(0)] * 8
+        rc = fn(self._ctx, n_reads, C.byref(records), M.ptr(strand), C.byref(table), int(min_len), 0, *null, C.byref(sm), C.byref(err), C.byref(secs))
+        self._check(rc, err.value)
+        n_out, seconds = int(sm.n_out), secs.value
+        if on_device:
+            out = {k: torch.empty(n_out, dtype=torch.uint8 if k == "rev" else torch.int32, device=qid.device) for k in LIFT_COLUMNS}
+        else:
+            out = {k: np.empty(n_out, np.uint8 if k == "rev" else np.int32) for k in LIFT_COLUMNS}
+        if n_out > 0:
+            rc = fn(self._ctx, n_reads, C.byref(records), M.ptr(strand), C.byref(table), int(min_len), n_out, *[M.ptr(a) for a in out.values()],
+                    C.byref(sm), C.byref(err), C.byref(secs))
+            self._check(rc, err.value)
+            seconds = secs.value
+        self.last_lift_overlaps_seconds = seconds
+        out.update(_summary_dict(sm))
+        out["kernel_seconds"] = seconds
+        return out
 
     def census(self, read_len, qid, qs, qe, tid, ts=None, te=None, symmetric: bool = False) -> dict:
         """raft_hip_census_device / _host: ``intervals`` (int32 [n_reads]: what a pass piles up on each read under ``symmetric``),

@@ -323,6 +323,34 @@ inline std::string unitigs_line(int64_t reads, int64_t skipped, int64_t unitigs,
            ", N50 = " + std::to_string(n50);
 }
 
+// --fragment-paf: PREFIX.fragments.paf, the job's overlaps lifted onto its fragments (raft_hip_lift_overlaps_host).
+// --fragment-paf-min L: L (min_len of that call) is a whole number >= 1 written in digits alone, at most INT32_MAX; without the option it is
+constexpr int32_t kFragmentPafMinDefault = 1;
+inline bool parse_fragment_paf_min(const char *text, int32_t *min_len) { return parse_min_anchor(text, min_len); }
+
+// ... which means nothing without --fragment-paf: a usage error
+inline bool fragment_paf_options_ok(bool fragment_paf, bool min_given) { return fragment_paf || !min_given; }
+
+// The lift reads the strand as --overlap-ends does: the tokeniser keeps it for either, and beside the filter it follows the kept records.
+inline bool strand_wanted(int32_t max_overhang, bool fragment_paf) { return max_overhang >= 0 || fragment_paf; }
+
+// ... paf_columns with that: the mask of raft_host_paf_parse_with for a job that may lift
+inline int paf_columns_with_lift(bool filter, int32_t max_overhang, bool fragment_paf) { return paf_columns(filter, strand_wanted(max_overhang, fragment_paf)); }
+
+// ... and keeps_query_ids: the lift reads the query ids after the job, as --fragment-overlaps does
+inline bool keeps_query_ids_with_lift(bool prepare, int32_t min_anchor, bool fragment_overlaps, bool fragment_paf)
+{
+    return keeps_query_ids(prepare, min_anchor, fragment_overlaps || fragment_paf);
+}
+
+// ... the option's stdout line, the last one of all, from raft_hip_lift_summary's counts
+inline std::string fragment_paf_line(int32_t min_len, int64_t records, int64_t lifted, int64_t cut, int64_t none, int64_t dropped, int64_t most)
+{
+    return "INFO, fragment_paf(), min_len = " + std::to_string(min_len) + ", records = " + std::to_string(records) + ", lifted = " + std::to_string(lifted) +
+           ", cut = " + std::to_string(cut) + ", without a fragment pair = " + std::to_string(none) + ", dropped pairs = " + std::to_string(dropped) +
+           ", most from one record = " + std::to_string(most);
+}
+
 // ... a read counts as uncovered when more than this many thousandths of its bases lie in low runs (yacrd's default for "not covered")
 constexpr int32_t kLowUncoveredPermille = 800;
 

@@ -20,6 +20,7 @@
 #include "../../include/raft_host_end.h"
 #include "../../include/raft_host_best.h"
 #include "../../include/raft_host_utg.h"
+#include "../../include/raft_host_lift.h"
 
 #include <emmintrin.h>
 #include <zlib.h>
@@ -1482,40 +1483,50 @@ int raft_host_write_repeats(const char *txt_path, const char *bed_path, const ra
     return (ok1 && ok2) ? RAFT_HOST_OK : RAFT_HOST_ERR_IO;
 }
 
-// chop.hpp:250-322: one FASTA record per fragment, read_num counts from 1 over the whole file
+// The text of the header of fragment f of read i in PREFIX.reads.fasta, between the '>' and the end of the line (chop.hpp:250-322;
+// read_num counts from 1 over the whole file).  false, and nothing appended: chop.hpp:293-311 writes no header for that orientation.
+// raft_host_write_fasta's headers and raft_host_write_fragment_paf's names both come from here.
+static bool fragment_header_text(const raft_host_reads *reads, const int64_t *frag_offset, const int32_t *frag_begin, const int32_t *frag_end,
+                                 long long i, int64_t f, std::string &o)
+{
+    const char *name = reads->names.name((int32_t)i);
+    const size_t name_n = reads->names.name_len((int32_t)i);
+    const int64_t f0 = frag_offset[i], f1 = frag_offset[i + 1];
+    const bool whole = (f1 - f0) == 1;             // kept in one piece (chop.hpp:250-267)
+    const long long read_num = f + 1;
+    const int32_t b = frag_begin[f], e = frag_end[f];
+    if (reads->real_reads) {
+        o.append("read=", 5); put_num(o, read_num); o.push_back(','); o.append(name, name_n);
+        o.append(",pos_on_original_read=", 22); put_num(o, b); o.push_back('-'); put_num(o, e);
+        return true;
+    }
+    // tail = name.substr(name.find_last_of(','))  -> ",<contig>"
+    const std::string nm(name, name_n);
+    const size_t lc = nm.find_last_of(',');
+    const std::string tail = lc == std::string::npos ? std::string() : nm.substr(lc);
+    const std::string &al = reads->align[(size_t)i];
+    const int32_t sp = reads->start_pos[(size_t)i], ep = reads->end_pos[(size_t)i];
+    long long p0 = 0, p1 = 0, ln = 0;
+    if (whole) { p0 = sp; p1 = ep; ln = reads->lens[(size_t)i]; }
+    else if (al == "forward") { p0 = (long long)sp + b; p1 = (long long)sp + e; ln = e - b; }
+    else if (al == "reverse") { p0 = (long long)ep - e; p1 = (long long)ep - b; ln = e - b; }
+    else return false;                             // chop.hpp:293-311 writes no header for other orientations
+    o.append("read=", 5); put_num(o, read_num); o.push_back(','); o.append(al); o.append(",position=", 10);
+    put_num(o, p0); o.push_back('-'); put_num(o, p1); o.append(",length=", 8); put_num(o, ln); o.append(tail);
+    return true;
+}
+
+// chop.hpp:250-322: one FASTA record per fragment
 int raft_host_write_fasta(const char *path, const raft_host_reads *reads, const int64_t *frag_offset,
                           const int32_t *frag_begin, const int32_t *frag_end)
 {
     const int32_t n = (int32_t)reads->lens.size();
-    // the header line of fragment f of read i (empty: chop.hpp:293-311 writes none for that orientation)
+    // the header line of fragment f of read i (none where fragment_header_text gives none)
     auto one_header = [&](long long i, int64_t f, std::string &o) {
-        const char *name = reads->names.name((int32_t)i);
-        const size_t name_n = reads->names.name_len((int32_t)i);
-        const int64_t f0 = frag_offset[i], f1 = frag_offset[i + 1];
-        const bool whole = (f1 - f0) == 1;             // kept in one piece (chop.hpp:250-267)
-        const long long read_num = f + 1;
-        const int32_t b = frag_begin[f], e = frag_end[f];
-        if (reads->real_reads) {
-            o.append(">read=", 6); put_num(o, read_num); o.push_back(','); o.append(name, name_n);
-            o.append(",pos_on_original_read=", 22); put_num(o, b); o.push_back('-'); put_num(o, e); o.push_back('\n');
-        } else {
-            // tail = name.substr(name.find_last_of(','))  -> ",<contig>"
-            const std::string nm(name, name_n);
-            const size_t lc = nm.find_last_of(',');
-            const std::string tail = lc == std::string::npos ? std::string() : nm.substr(lc);
-            const std::string &al = reads->align[(size_t)i];
-            const int32_t sp = reads->start_pos[(size_t)i], ep = reads->end_pos[(size_t)i];
-            bool header = true;
-            long long p0 = 0, p1 = 0, ln = 0;
-            if (whole) { p0 = sp; p1 = ep; ln = reads->lens[(size_t)i]; }
-            else if (al == "forward") { p0 = (long long)sp + b; p1 = (long long)sp + e; ln = e - b; }
-            else if (al == "reverse") { p0 = (long long)ep - e; p1 = (long long)ep - b; ln = e - b; }
-            else header = false;                     // chop.hpp:293-311 writes no header for other orientations
-            if (header) {
-                o.append(">read=", 6); put_num(o, read_num); o.push_back(','); o.append(al); o.append(",position=", 10);
-                put_num(o, p0); o.push_back('-'); put_num(o, p1); o.append(",length=", 8); put_num(o, ln); o.append(tail); o.push_back('\n');
-            }
-        }
+        const size_t mark = o.size();
+        o.push_back('>');
+        if (fragment_header_text(reads, frag_offset, frag_begin, frag_end, i, f, o)) o.push_back('\n');
+        else o.resize(mark);
     };
     auto one_read = [&](long long i, std::string &o) {
         const char *seq = reads->base_ptr() + reads->base_off[(size_t)i];
@@ -1530,6 +1541,51 @@ int raft_host_write_fasta(const char *path, const raft_host_reads *reads, const 
     // on the file's mapping and drag the table writers that run beside them down with them: write_fasta 1.36 -> 3.0 s,
     // write_tables 0.76 -> 6.9 s (profiles/r05_cli_s500k_mapped_writer.txt).  The single write() per block stays.)
     return write_ordered(path, n, 8 << 20, [&](long long i) { return (long long)reads->lens[(size_t)i] + 64; }, one_read);
+}
+
+// PREFIX.fragments.paf (include/raft_host_lift.h): one 12-field line per lifted overlap; a fragment's name is the first word of its
+// header in PREFIX.reads.fasta.  A row outside the table is refused before anything is written.
+int raft_host_write_fragment_paf(const char *path, const raft_host_reads *reads, const int64_t *frag_offset, const int32_t *frag_begin,
+                                 const int32_t *frag_end, int64_t n_out, const int32_t *qfrag, const int32_t *qs, const int32_t *qe,
+                                 const int32_t *tfrag, const int32_t *ts, const int32_t *te, const uint8_t *rev, const int32_t *src,
+                                 const int32_t *matches, const int32_t *block)
+{
+    if (!path || !reads || !frag_offset || n_out < 0) return RAFT_HOST_ERR_ARG;
+    if (n_out > 0 && (!frag_begin || !frag_end || !qfrag || !qs || !qe || !tfrag || !ts || !te || !rev)) return RAFT_HOST_ERR_ARG;
+    if (matches && n_out > 0 && (!block || !src)) return RAFT_HOST_ERR_ARG;
+    const long long n_reads = (long long)reads->lens.size();
+    const int64_t n_frag = frag_offset[n_reads];
+    for (int64_t k = 0; k < n_out; ++k)
+        if (qfrag[k] < 0 || qfrag[k] >= n_frag || tfrag[k] < 0 || tfrag[k] >= n_frag || (matches && src[k] < 0)) return RAFT_HOST_ERR_ARG;
+    // name and length of row f: its read is the last one whose rows begin at or before f
+    const auto put_fragment = [&](std::string &o, int64_t f) {
+        const long long i = (long long)(std::upper_bound(frag_offset, frag_offset + n_reads + 1, f) - frag_offset) - 1;
+        const size_t mark = o.size();
+        if (fragment_header_text(reads, frag_offset, frag_begin, frag_end, i, f, o)) {
+            size_t end = mark;
+            while (end < o.size() && o[end] != ' ' && o[end] != '\t') ++end;
+            o.resize(end);
+        } else {
+            o.append("read=", 5); put_num(o, (long long)f + 1);
+        }
+        o.push_back('\t'); put_num(o, (long long)frag_end[f] - frag_begin[f]);
+    };
+    return write_ordered(path, n_out, 1 << 14, [](long long) { return 1LL; },
+                         [&](long long k, std::string &o) {
+                             put_fragment(o, qfrag[k]);
+                             o.push_back('\t'); put_num(o, qs[k]); o.push_back('\t'); put_num(o, qe[k]);
+                             o.push_back('\t'); o.push_back(rev[k] ? '-' : '+'); o.push_back('\t');
+                             put_fragment(o, tfrag[k]);
+                             o.push_back('\t'); put_num(o, ts[k]); o.push_back('\t'); put_num(o, te[k]);
+                             const long long sq = (long long)qe[k] - qs[k], st = (long long)te[k] - ts[k];
+                             const long long big = sq > st ? sq : st, small = sq > st ? st : sq;
+                             long long m = small;
+                             if (matches) {
+                                 const long long b = block[src[k]], mm = matches[src[k]] > 0 ? matches[src[k]] : 0;
+                                 m = b <= 0 ? 0 : std::min(big, mm * big / b);      // (both below 2^31: the product fits)
+                             }
+                             o.push_back('\t'); put_num(o, m); o.push_back('\t'); put_num(o, big); o.append("\t255\n", 5);
+                         });
 }
 
 // The per-read table of `raft --read-stats`: a header line, then one line per read, tab-separated, integers only (see raft_host.h)

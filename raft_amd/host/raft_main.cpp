@@ -29,6 +29,8 @@
 #include "../../include/raft_host_best.h"
 #include "../../include/raft_hip_utg.h"
 #include "../../include/raft_host_utg.h"
+#include "../../include/raft_hip_lift.h"
+#include "../../include/raft_host_lift.h"
 #include "../../include/raft_host.h"
 #include "cli_plan.hpp"
 
@@ -69,6 +71,9 @@ struct Params {            // param.hpp:18-31
     bool best_overlaps = false;    // --best-overlaps: PREFIX.best_overlaps.tsv, the best overlap of every read end under --overlap-ends' H and F (raft_hip_best_overlaps_host)
     bool unitigs = false;          // --unitigs: PREFIX.unitigs.tsv and .unitigs.layout.tsv, the chains and cycles of --best-overlaps' mutual ends (raft_hip_unitigs_host)
     int32_t min_anchor = 0;        // --repeat-overlaps A: PREFIX.repeat_overlaps.tsv and .records.tsv (raft_hip_repeat_overlaps_host); 0: not asked for
+    bool fragment_paf = false;     // --fragment-paf: PREFIX.fragments.paf, the job's overlaps lifted onto its fragments (raft_hip_lift_overlaps_host)
+    int32_t fragment_paf_min = raft_cli::kFragmentPafMinDefault;   // --fragment-paf-min L: pairs shorter than L on either side are dropped
+    bool fragment_paf_min_given = false;
 };
 
 struct Switches {                  // the environment, as read_switches() found it
@@ -118,6 +123,11 @@ struct Job {
     std::vector<int64_t> utg_offset, utg_off, utg_length;
     std::vector<uint8_t> utg_orient, utg_circular;
     raft_hip_utg_summary utg_sum{};
+    // --fragment-paf: the eight columns of the lifted stream; PAF fields 10 and 11 of the kept records where the filter tokenised them
+    std::vector<int32_t> lift_col[6], lift_src, matches_kept, block_kept;
+    std::vector<uint8_t> lift_rev;
+    const int32_t *lift_matches = nullptr, *lift_block = nullptr;
+    raft_hip_lift_summary lift_sum{};
     // the arrays everything comes back in (made and page-locked on out_prep)
     raft_cli::Capacities cap;
     std::vector<int64_t> cov_off, rep_off, frag_off;
@@ -232,6 +242,7 @@ void parse_options(Job &j, int argc, char *argv[])
                                                  {"min-overlap", required_argument, nullptr, 1006},
                                                  {"overlap-ends", required_argument, nullptr, 1007}, {"ends-min-ratio", required_argument, nullptr, 1008},
                                                  {"best-overlaps", no_argument, nullptr, 1009}, {"unitigs", no_argument, nullptr, 1010},
+                                                 {"fragment-paf", no_argument, nullptr, 1011}, {"fragment-paf-min", required_argument, nullptr, 1012},
                                                  {nullptr, 0, nullptr, 0}};
     while ((option = getopt_long(argc, argv, "r:e:m:l:i:p:f:v:o:", long_options, nullptr)) != -1) {
         switch (option) {
@@ -246,6 +257,8 @@ void parse_options(Job &j, int argc, char *argv[])
         case 1008: if (!raft_cli::parse_ends_min_ratio(optarg, &p.ends_min_ratio)) print_help(p); p.ends_ratio_given = true; break;
         case 1009: p.best_overlaps = true; break;
         case 1010: p.unitigs = true; break;
+        case 1011: p.fragment_paf = true; break;
+        case 1012: if (!raft_cli::parse_fragment_paf_min(optarg, &p.fragment_paf_min)) print_help(p); p.fragment_paf_min_given = true; break;
         case 'r': p.reso = atoi(optarg); break;
         case 'e': p.auto_cov = strcmp(optarg, "auto") == 0; p.est_cov = p.auto_cov ? 0 : atoi(optarg); break;
         case 'm': p.cov_mul = std::stod(optarg); break;
@@ -261,6 +274,7 @@ void parse_options(Job &j, int argc, char *argv[])
     if (!raft_cli::ends_options_ok(p.overlap_ends, p.ends_ratio_given)) print_help(p);
     if (!raft_cli::best_options_ok(p.best_overlaps, p.overlap_ends)) print_help(p);
     if (!raft_cli::unitigs_options_ok(p.unitigs, p.best_overlaps)) print_help(p);
+    if (!raft_cli::fragment_paf_options_ok(p.fragment_paf, p.fragment_paf_min_given)) print_help(p);
     if (argc < optind + 2) print_help(p);
     if (p.est_cov <= 0 && !p.auto_cov) {
         std::cout << "ERROR, main(), estimated coverage must be set properly\n";
@@ -439,8 +453,8 @@ void parse_paf(Job &j)
     j.paf_reader.join();
     stage(j, "paf_read (rest)");
     int rc = j.paf_text_rc;
-    // (the filter reads PAF columns 10 and 11, --overlap-ends the strand; neither: the plain parser)
-    const int columns = raft_cli::paf_columns(raft_cli::filter_wanted(j.p.min_identity, j.p.min_overlap), j.p.overlap_ends >= 0);
+    // (the filter reads PAF columns 10 and 11, --overlap-ends and --fragment-paf the strand; none of them: the plain parser)
+    const int columns = raft_cli::paf_columns_with_lift(raft_cli::filter_wanted(j.p.min_identity, j.p.min_overlap), j.p.overlap_ends, j.p.fragment_paf);
     if (rc == RAFT_HOST_OK) rc = raft_host_paf_parse_with(j.paf_text, j.reads, columns, &j.paf, bad, sizeof bad);
     // (a big file's GBs of touched pages are left to the process exit: unmapping them here -- or beside the pass, where it holds
     // the address space's lock against the page-locking -- cost 0.3 s of a 4 s run)
@@ -478,6 +492,23 @@ void keep_strand(Job &j)
     j.strand = j.strand_kept.data();
 }
 
+// --fragment-paf beside the filter: PAF fields 10 and 11 of the kept records, for the writer, by the same means -- matches in the
+// query-id slot, block in the target-id slot.
+void keep_quality(Job &j)
+{
+    const int32_t *m = raft_host_paf_quality(j.paf, 0), *b = raft_host_paf_quality(j.paf, 1);
+    j.matches_kept.assign(m, m + j.n_rec); j.block_kept.assign(b, b + j.n_rec);
+    std::vector<int32_t> drop[4];
+    for (auto &d : drop) d.resize((size_t)j.n_rec);
+    raft_hip_flt_summary sum{};
+    const int rc = raft_hip_filter_overlaps_host(j.ctxs[0], j.n_rec, j.matches_kept.data(), j.col[1], j.col[2], j.block_kept.data(), j.col[4], j.col[5], m, b,
+                                                 j.p.min_identity, j.p.min_overlap, j.matches_kept.data(), drop[0].data(), drop[1].data(),
+                                                 j.block_kept.data(), drop[2].data(), drop[3].data(), &sum, nullptr);
+    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, -1));
+    j.matches_kept.resize((size_t)sum.n_kept); j.block_kept.resize((size_t)sum.n_kept);
+    j.lift_matches = j.matches_kept.data(); j.lift_block = j.block_kept.data();
+}
+
 // --min-identity / --min-overlap: the records that pass (include/raft_hip_flt.h) are compacted in place, on the first context, before
 // anything else sees the stream -- the survey, the census, the split of a multi-device or pre-split job, every query: the job is the
 // job on a file of the kept lines.  Without the options nothing happens here.
@@ -487,7 +518,8 @@ void filter_overlaps(Job &j)
     j.out_prep.join();                                  // (its raft_hip_reserve uses the context this call runs on)
     int32_t *out[6];
     for (int k = 0; k < 6; ++k) out[k] = const_cast<int32_t *>(j.col[k]);
-    if (j.p.overlap_ends >= 0) keep_strand(j);          // (first: it reads the columns as tokenised)
+    if (raft_cli::strand_wanted(j.p.overlap_ends, j.p.fragment_paf)) keep_strand(j);   // (first: it reads the columns as tokenised)
+    if (j.p.fragment_paf) keep_quality(j);
     const int rc = raft_hip_filter_overlaps_host(j.ctxs[0], j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.col[4], j.col[5],
                                                  raft_host_paf_quality(j.paf, 0), raft_host_paf_quality(j.paf, 1), j.p.min_identity, j.p.min_overlap,
                                                  out[0], out[1], out[2], out[3], out[4], out[5], &j.flt_sum, nullptr);
@@ -717,7 +749,7 @@ void unitigs(Job &j)
 void prepare_input(Job &j)
 {
     const bool prepare = j.sw.cli_prepare && j.ranks == 0;
-    if (raft_cli::keeps_query_ids(prepare, j.p.min_anchor, j.p.fragment_overlaps)) j.ovl_qid.assign(j.col[0], j.col[0] + j.n_rec);   // (--repeat-overlaps and --fragment-overlaps read the query ids after the job)
+    if (raft_cli::keeps_query_ids_with_lift(prepare, j.p.min_anchor, j.p.fragment_overlaps, j.p.fragment_paf)) j.ovl_qid.assign(j.col[0], j.col[0] + j.n_rec);   // (--repeat-overlaps, --fragment-overlaps and --fragment-paf read the query ids after the job)
     if (prepare && j.sym && j.n_rec > 0 && !j.sw.no_grouped) {
         j.rec_off.reset(new int64_t[(size_t)4 * ((size_t)j.n_reads + 1)]);
         if (raft_host_group_offsets(j.n_reads, j.n_rec, j.col[0], 4, &j.n_runs, j.rec_off.get()) != RAFT_HOST_OK) j.n_runs = 0;
@@ -845,6 +877,39 @@ void fragment_overlaps(Job &j)
     stage(j, "fragment_overlaps");
 }
 
+// --fragment-paf: the job's kept stream lifted onto the job's own fragment rows -- the host arrays reads.fasta is written from, so it
+// is the same call whichever way the job ran (one device or several, ranks, -e auto): the whole-job arrays go to the first context.
+// A size query, the eight columns at that size, the call.
+void fragment_paf(Job &j)
+{
+    if (!j.p.fragment_paf) return;
+    if (!j.ovl_qid.empty()) j.col[0] = j.ovl_qid.data();
+    const raft_hip_records rec{j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.col[4], j.col[5]};
+    const raft_hip_frag_table table{j.frag_off[(size_t)j.n_reads], j.frag_off.data(), j.fb.get(), j.fe.get()};
+    int64_t bad_index = -1;
+    int rc = raft_hip_lift_overlaps_host(j.ctxs[0], j.n_reads, &rec, j.strand, &table, j.p.fragment_paf_min, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                         nullptr, nullptr, nullptr, &j.lift_sum, &bad_index, nullptr);
+    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
+    const size_t n_out = (size_t)j.lift_sum.n_out;
+    if (n_out > 0) {
+        for (auto &c : j.lift_col) c.resize(n_out);
+        j.lift_rev.resize(n_out); j.lift_src.resize(n_out);
+        rc = raft_hip_lift_overlaps_host(j.ctxs[0], j.n_reads, &rec, j.strand, &table, j.p.fragment_paf_min, (int64_t)n_out, j.lift_col[0].data(),
+                                         j.lift_col[1].data(), j.lift_col[2].data(), j.lift_col[3].data(), j.lift_col[4].data(), j.lift_col[5].data(),
+                                         j.lift_rev.data(), j.lift_src.data(), &j.lift_sum, &bad_index, nullptr);
+        if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
+    }
+    stage(j, "fragment_paf");
+}
+
+void write_fragment_paf(Job &j)
+{
+    if (raft_host_write_fragment_paf((j.p.prefix + ".fragments.paf").c_str(), j.reads, j.frag_off.data(), j.fb.get(), j.fe.get(), j.lift_sum.n_out,
+                                     j.lift_col[0].data(), j.lift_col[1].data(), j.lift_col[2].data(), j.lift_col[3].data(), j.lift_col[4].data(),
+                                     j.lift_col[5].data(), j.lift_rev.data(), j.lift_src.data(), j.lift_matches, j.lift_block) != RAFT_HOST_OK)
+        die("ERROR, fragment_paf(), cannot write output files");
+}
+
 void write_fragment_overlaps(Job &j)
 {
     std::vector<const char *> names((size_t)j.n_reads);
@@ -942,6 +1007,7 @@ void write_outputs(Job &j)
                                 j.utg_orient.data(), j.utg_order.data(), j.utg_off.data(), j.utg_reads.data(), j.utg_length.data(),
                                 j.utg_circular.data()) != RAFT_HOST_OK)
         die("ERROR, unitigs(), cannot write output files");
+    if (p.fragment_paf) write_fragment_paf(j);
     stage(j, "write_tables");
     // repeat.hpp:173-178 (total_windows is an int in the reference; identical below 2^31 windows)
     const double cpw = (double)s.total_coverage / (double)s.total_windows;
@@ -995,6 +1061,9 @@ void print_totals(Job &j, int argc, char *argv[])
         std::cout << raft_cli::unitigs_line(j.utg_sum.reads_in, j.utg_sum.reads_skipped, j.utg_sum.unitigs, j.utg_sum.singletons, j.utg_sum.circular,
                                             j.utg_sum.longest_reads, j.utg_sum.longest_length, j.utg_sum.total_length,
                                             raft_cli::unitig_n50(j.utg_length.data(), j.utg_sum.unitigs)) << "\n";
+    if (j.p.fragment_paf)
+        std::cout << raft_cli::fragment_paf_line(j.p.fragment_paf_min, j.lift_sum.n_records, j.lift_sum.n_out, j.lift_sum.records_cut,
+                                                 j.lift_sum.records_none, j.lift_sum.pairs_dropped, j.lift_sum.most_per_record) << "\n";
     stage(j, "stdout");
     if (j.sw.timing) {
         timespec ts{};
@@ -1035,6 +1104,7 @@ int main(int argc, char *argv[])
     run_engine(job);
     repeat_overlaps(job);
     fragment_overlaps(job);
+    fragment_paf(job);
     report(job);
     write_outputs(job);
     print_totals(job, argc, argv);

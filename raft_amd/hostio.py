@@ -86,7 +86,11 @@ BEST_ABI = {
 UTG_ABI = {
     "raft_host_write_unitigs": (C.c_int, [_str, _vp, C.c_int64] + [_vp] * 9),
 }
-PAF_QUALITY, PAF_STRAND = 1, 2       # RAFT_HOST_PAF_*: the bits of ``columns``
+# ... and of include/raft_host_lift.h
+LIFT_ABI = {
+    "raft_host_write_fragment_paf": (C.c_int, [_str, _vp, _vp, _vp, _vp, C.c_int64] + [_vp] * 10),
+}
+PAF_QUALITY, PAF_STRAND = 1, 2      # RAFT_HOST_PAF_*: the bits of ``columns``
 
 
 class HostError(RuntimeError):
@@ -105,7 +109,7 @@ def load_library():
         if not os.path.exists(_LIB_PATH):
             raise RuntimeError(f"{_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         lib = C.CDLL(_LIB_PATH)
-        for name, (restype, argtypes) in list(ABI.items()) + list(LOW_ABI.items()) + list(OVL_ABI.items()) + list(FRAG_ABI.items()) + list(RST_ABI.items()) + list(FLT_ABI.items()) + list(END_ABI.items()) + list(BEST_ABI.items()) + list(UTG_ABI.items()):
+        for name, (restype, argtypes) in list(ABI.items()) + list(LOW_ABI.items()) + list(OVL_ABI.items()) + list(FRAG_ABI.items()) + list(RST_ABI.items()) + list(FLT_ABI.items()) + list(END_ABI.items()) + list(BEST_ABI.items()) + list(UTG_ABI.items()) + list(LIFT_ABI.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
@@ -278,6 +282,28 @@ def write_unitigs(prefix: str, reads: Reads, res: dict):
                                                 ptr(i64[1]), ptr(i32[3]), ptr(i64[2]), ptr(u8[1]))
     if rc != OK:
         raise HostError(rc, prefix)
+
+
+def write_fragment_paf(path: str, reads: Reads, fragments, res: dict, matches=None, block=None):
+    """raft_host_write_fragment_paf: one 12-field PAF line per output of ``Engine.lift_overlaps`` (``res``: its eight columns), the
+    names being the first words of the headers ``write_outputs`` gives the same ``fragments`` (frag_offset, frag_begin, frag_end) in
+    PREFIX.reads.fasta.  ``matches`` / ``block`` (PAF fields 10 and 11 of the lifted stream, both or neither): field 10 is scaled
+    from them through ``src``; without them it is the smaller span."""
+    if (matches is None) != (block is None):
+        raise ValueError("write_fragment_paf: matches and block are given together")
+    off, fb, fe = carray(fragments[0], np.int64), carray(fragments[1], np.int32), carray(fragments[2], np.int32)
+    cols = [carray(res[k].cpu() if hasattr(res[k], "is_cuda") else res[k], np.uint8 if k == "rev" else np.int32)
+            for k in ("qfrag", "qs", "qe", "tfrag", "ts", "te", "rev", "src")]
+    n_out = cols[0].size
+    if off.size != reads.n + 1 or fb.size != fe.size or (off.size and int(off[-1]) != fb.size) or any(c.size != n_out for c in cols):
+        raise ValueError("write_fragment_paf: fragments is (offsets [n_reads + 1], two arrays of offsets[-1] rows), the columns are of one length")
+    quality = [None, None] if matches is None else [carray(matches, np.int32), carray(block, np.int32)]
+    if matches is not None and (quality[0].size != quality[1].size or (n_out and int(cols[7].max()) >= quality[0].size)):
+        raise ValueError("write_fragment_paf: src points behind matches / block")
+    rc = load_library().raft_host_write_fragment_paf(path.encode(), reads._h, ptr(off), ptr(fb), ptr(fe), n_out, *[ptr(c) for c in cols],
+                                                     ptr(quality[0]), ptr(quality[1]))
+    if rc != OK:
+        raise HostError(rc, path)
 
 
 def pack_coverage(cov, width: int = 1):
