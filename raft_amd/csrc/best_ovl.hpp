@@ -25,10 +25,6 @@
 
 namespace raft {
 
-// (the names this header had for two of the launch constants; census.hpp says why they stay)
-constexpr int kBestThreads = 256;
-constexpr int kBestMaxBlocks = 2048;
-static_assert(kBestThreads == kStreamThreads && kBestMaxBlocks == kStreamMaxBlocks, "one launch shape under two sets of names");
 // control words: the first bad record, {candidates, left_out}, the six read totals
 constexpr int kBestCtlViews = 1, kBestCtlReads = 3, kBestReadTotals = 6, kBestCtlWords = kBestCtlReads + kBestReadTotals;
 constexpr unsigned kBestSkipBit = 0x80000000u;

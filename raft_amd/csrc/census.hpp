@@ -18,16 +18,6 @@
 
 namespace raft {
 
-// TRANSITIONAL, to be deleted by the next change to this file: record_stream.hpp's launch constants under the names they had while
-// they were the census's own.  No kernel and no launch uses them.  tests/ of the commit before this header existed reads these lines
-// (and kFrag* / kEnds* / kBest* / kFltLaneRecords, which refer here) out of the source text WHEN ITS MODULES ARE IMPORTED, and a commit's
-// tests must still load against the next commit's tree; tests/ as it is now reads record_stream.hpp and none of these names.
-constexpr int kCensusThreads = 256;
-constexpr int kCensusLaneRecords = 4;
-constexpr int kCensusMaxBlocks = 2048;
-static_assert(kCensusThreads == kStreamThreads && kCensusLaneRecords == kStreamLaneRecords && kCensusMaxBlocks == kStreamMaxBlocks,
-              "one launch shape under two sets of names");
-
 struct CensusArgs {
     const int32_t *len, *qid, *qs, *qe, *tid, *ts, *te;
     long long n_rec;

@@ -30,7 +30,7 @@
 namespace raft {
 
 constexpr int kFltThreads = 256;
-constexpr int kFltLaneRecords = kCensusLaneRecords;                  // stream_load's group (kStreamLaneRecords under its earlier name, census.hpp)
+constexpr int kFltLaneRecords = kStreamLaneRecords;                  // stream_load's group (record_stream.hpp)
 constexpr int kFltTile = kFltThreads * kFltLaneRecords;              // records of one workgroup step
 constexpr int kFltTileWords = kFltTile / 64;                         // bitmap words of a tile
 constexpr int kFltWordLanes = 64 / kFltLaneRecords;                  // lanes whose bits make one word

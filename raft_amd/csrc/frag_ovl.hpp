@@ -33,11 +33,6 @@
 
 namespace raft {
 
-// (the names this header had for the launch constants; see census.hpp)
-constexpr int kFragThreads = kCensusThreads;
-constexpr int kFragLaneRecords = kCensusLaneRecords;
-constexpr int kFragMaxBlocks = kCensusMaxBlocks;
-
 // control words (unsigned long long each)
 constexpr int kFragFirstBad = 0;         // smallest record index with an id out of range; ~0 = none
 constexpr int kFragBadTable = 1;         // != 0: the fragment table is not what the header asks for

@@ -18,10 +18,6 @@
 
 namespace raft {
 
-// (the names this header had for two of the launch constants; census.hpp says why they stay)
-constexpr int kEndsThreads = 256;
-constexpr int kEndsMaxBlocks = 2048;
-static_assert(kEndsThreads == kStreamThreads && kEndsMaxBlocks == kStreamMaxBlocks, "one launch shape under two sets of names");
 constexpr int kEndsFieldBits = 12;           // a count's field in the joined word: 5 * 12 bits, each holding up to 4095
 // control words: the first bad record, the records by kind, the reads by status
 constexpr int kEndsCtlKinds = 1, kEndsCtlStatus = kEndsCtlKinds + kEndKinds, kEndsCtlWords = kEndsCtlStatus + kEndStatuses;

@@ -73,50 +73,30 @@ class _CovEstimate(C.Structure):
                 ("windows_clamped", C.c_int64), ("mean", C.c_double)]
 
 
-class _LowSummary(C.Structure):
-    _fields_ = [(n, C.c_int64) for n in ("n_runs", "low_windows", "low_bases", "reads_with_runs", "reads_interior", "reads_uncovered")]
+def _counts_struct(name: str, *fields):
+    """A summary structure of a query: 64-bit counts, in the order of its header."""
+    return type(name, (C.Structure,), {"_fields_": [(f, C.c_int64) for f in fields]})
 
 
-class _OvlSummary(C.Structure):
-    _fields_ = [(n, C.c_int64) for n in ("n_records", "q_touch", "t_touch", "q_repeat", "t_repeat", "both_repeat", "q_contained", "t_contained",
-                                         "reads_contained", "reads_repeat_contained")]
+_LowSummary = _counts_struct("_LowSummary", "n_runs", "low_windows", "low_bases", "reads_with_runs", "reads_interior", "reads_uncovered")
+_OvlSummary = _counts_struct("_OvlSummary", "n_records", "q_touch", "t_touch", "q_repeat", "t_repeat", "both_repeat", "q_contained", "t_contained",
+                             "reads_contained", "reads_repeat_contained")
+_FragSummary = _counts_struct("_FragSummary", "n_records", "n_fragments", "frags_untouched", "frags_spanned", "frags_contained",
+                              "frags_contained_repeat", "reads_whole_spanned", "reads_any_contained", "reads_all_contained")
+_RstSummary = _counts_struct("_RstSummary", "n_runs", "runs_empty", "runs_interior", "runs_touched", "runs_spanned", "interior_spanned",
+                             "sides_touch", "sides_span", "sides_inside", "windows", "cov_sum")
+_FltSummary = _counts_struct("_FltSummary", "n_records", "n_kept", "below_identity", "below_span", "first_kept", "symmetric")
+_EndSummary = _counts_struct("_EndSummary", "n_records", "kind_invalid", "kind_internal", "kind_query_contained", "kind_target_contained", "kind_end3",
+                             "kind_end5", "kind_self", "reads_linked", "reads_contained", "reads_isolated", "reads_dead5", "reads_dead3")
+_BestSummary = _counts_struct("_BestSummary", "n_records", "candidates", "left_out", "ends_best", "ends_mutual", "reads_both_best",
+                              "reads_both_mutual", "reads_no_best", "reads_skipped")
+_UtgSummary = _counts_struct("_UtgSummary", "reads_in", "reads_skipped", "unitigs", "singletons", "circular", "longest_reads", "longest_length",
+                             "total_length")
+_LiftSummary = _counts_struct("_LiftSummary", "n_records", "n_out", "records_none", "records_cut", "pairs_dropped", "most_per_record")
 
 
 class _FragTable(C.Structure):      # raft_hip_frag_table and raft_hip_frag_repeats: a count and the three arrays of a CSR table
     _fields_ = [("n", C.c_int64), ("offset", C.c_void_p), ("first", C.c_void_p), ("second", C.c_void_p)]
-
-
-class _FragSummary(C.Structure):
-    _fields_ = [(n, C.c_int64) for n in ("n_records", "n_fragments", "frags_untouched", "frags_spanned", "frags_contained", "frags_contained_repeat",
-                                         "reads_whole_spanned", "reads_any_contained", "reads_all_contained")]
-
-
-class _RstSummary(C.Structure):
-    _fields_ = [(n, C.c_int64) for n in ("n_runs", "runs_empty", "runs_interior", "runs_touched", "runs_spanned", "interior_spanned",
-                                         "sides_touch", "sides_span", "sides_inside", "windows", "cov_sum")]
-
-
-class _FltSummary(C.Structure):
-    _fields_ = [(n, C.c_int64) for n in ("n_records", "n_kept", "below_identity", "below_span", "first_kept", "symmetric")]
-
-
-class _EndSummary(C.Structure):
-    _fields_ = [(n, C.c_int64) for n in ("n_records", "kind_invalid", "kind_internal", "kind_query_contained", "kind_target_contained", "kind_end3",
-                                         "kind_end5", "kind_self", "reads_linked", "reads_contained", "reads_isolated", "reads_dead5", "reads_dead3")]
-
-
-class _BestSummary(C.Structure):
-    _fields_ = [(n, C.c_int64) for n in ("n_records", "candidates", "left_out", "ends_best", "ends_mutual", "reads_both_best", "reads_both_mutual",
-                                         "reads_no_best", "reads_skipped")]
-
-
-class _UtgSummary(C.Structure):
-    _fields_ = [(n, C.c_int64) for n in ("reads_in", "reads_skipped", "unitigs", "singletons", "circular", "longest_reads", "longest_length",
-                                         "total_length")]
-
-
-class _LiftSummary(C.Structure):
-    _fields_ = [(n, C.c_int64) for n in ("n_records", "n_out", "records_none", "records_cut", "pairs_dropped", "most_per_record")]
 
 
 class _Outputs(C.Structure):
@@ -194,13 +174,13 @@ ABI = {
 }
 EXPORTS = tuple(ABI)
 
-# ... and the entry points of include/raft_hip_low.h (libraft_hip_low.so, beside libraft_hip.so): load_low_library declares these
+# ... and the entry points of include/raft_hip_low.h (libraft_hip_low.so, beside libraft_hip.so): load_side_library("low") declares these
 LOW_ABI = {
     "raft_hip_low_abi": (C.c_int, []),
     "raft_hip_low_coverage": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _P(_LowSummary), _P(_f64)]),
 }
 
-# ... and those of include/raft_hip_ovl.h (libraft_hip_ovl.so): load_ovl_library declares these
+# ... and those of include/raft_hip_ovl.h (libraft_hip_ovl.so): load_side_library("ovl") declares these
 _OVL_CALL = [_vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(_OvlSummary), _P(_i64), _P(_f64)]
 OVL_ABI = {
     "raft_hip_ovl_abi": (C.c_int, []),
@@ -208,7 +188,7 @@ OVL_ABI = {
     "raft_hip_repeat_overlaps_host": (C.c_int, _OVL_CALL),
 }
 
-# ... and those of include/raft_hip_frag.h (libraft_hip_frag.so): load_frag_library declares these
+# ... and those of include/raft_hip_frag.h (libraft_hip_frag.so): load_side_library("frag") declares these
 _FRAG_CALL = [_vp, _i32, _vp, _P(_Records), _i32, _P(_FragTable), _P(_FragTable), _vp, _vp, _vp, _vp, _vp, _P(_FragSummary), _P(_i64), _P(_f64)]
 FRAG_ABI = {
     "raft_hip_frag_abi": (C.c_int, []),
@@ -216,7 +196,7 @@ FRAG_ABI = {
     "raft_hip_frag_overlaps_host": (C.c_int, _FRAG_CALL),
 }
 
-# ... and those of include/raft_hip_rst.h (libraft_hip_rst.so): load_rst_library declares these
+# ... and those of include/raft_hip_rst.h (libraft_hip_rst.so): load_side_library("rst") declares these
 _RST_CALL = [_vp, _i32, _vp, _P(_Records), _i32, _i64, _vp, _vp, _vp, _i32] + [_vp] * 9 + [_P(_RstSummary), _P(_i64), _P(_f64)]
 RST_ABI = {
     "raft_hip_rst_abi": (C.c_int, []),
@@ -225,7 +205,7 @@ RST_ABI = {
 }
 RST_EMPTY, RST_AT_START, RST_AT_END = 1, 2, 4
 
-# ... and those of include/raft_hip_flt.h (libraft_hip_flt.so): load_flt_library declares these
+# ... and those of include/raft_hip_flt.h (libraft_hip_flt.so): load_side_library("flt") declares these
 _FLT_CALL = [_vp, _i64] + [_vp] * 8 + [_i32, _i32] + [_vp] * 6 + [_P(_FltSummary), _P(_f64)]
 FLT_ABI = {
     "raft_hip_flt_abi": (C.c_int, []),
@@ -233,7 +213,7 @@ FLT_ABI = {
     "raft_hip_filter_overlaps_host": (C.c_int, _FLT_CALL),
 }
 
-# ... and those of include/raft_hip_end.h (libraft_hip_end.so): load_end_library declares these
+# ... and those of include/raft_hip_end.h (libraft_hip_end.so): load_side_library("end") declares these
 _END_CALL = [_vp] + _COLUMNS + [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _P(_EndSummary), _P(_i64), _P(_f64)]
 END_ABI = {
     "raft_hip_end_abi": (C.c_int, []),
@@ -245,7 +225,7 @@ END_INVALID, END_INTERNAL, END_QUERY_CONTAINED, END_TARGET_CONTAINED, END_QUERY_
 END_READ_LINKED, END_READ_CONTAINED, END_READ_ISOLATED, END_READ_DEAD5, END_READ_DEAD3 = range(5)
 END_COUNTS = ("internal", "contained_in", "contains", "end5", "end3")
 
-# ... and those of include/raft_hip_best.h (libraft_hip_best.so): load_best_library declares these
+# ... and those of include/raft_hip_best.h (libraft_hip_best.so): load_side_library("best") declares these
 _BEST_CALL = [_vp] + _COLUMNS + [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _P(_BestSummary), _P(_i64), _P(_f64)]
 BEST_ABI = {
     "raft_hip_best_abi": (C.c_int, []),
@@ -255,7 +235,7 @@ BEST_ABI = {
 # the bits of a read's flag byte (RAFT_HIP_BEST_*)
 BEST_REV5, BEST_MUTUAL5, BEST_REV3, BEST_MUTUAL3, BEST_SKIPPED = 1, 2, 4, 8, 16
 
-# ... and those of include/raft_hip_utg.h (libraft_hip_utg.so): load_utg_library declares these
+# ... and those of include/raft_hip_utg.h (libraft_hip_utg.so): load_side_library("utg") declares these
 _UTG_CALL = [_vp, _i32] + [_vp] * 4 + [_vp] * 9 + [_P(_UtgSummary), _P(_i64), _P(_f64), _P(_i64)]
 UTG_ABI = {
     "raft_hip_utg_abi": (C.c_int, []),
@@ -264,7 +244,7 @@ UTG_ABI = {
 }
 UTG_MAX_READS = (1 << 30) - 1     # half-edge ids are int32
 
-# ... and those of include/raft_hip_lift.h (libraft_hip_lift.so): load_lift_library declares these
+# ... and those of include/raft_hip_lift.h (libraft_hip_lift.so): load_side_library("lift") declares these
 _LIFT_CALL = [_vp, _i32, _P(_Records), _vp, _P(_FragTable), _i32, _i64] + [_vp] * 8 + [_P(_LiftSummary), _P(_i64), _P(_f64)]
 LIFT_ABI = {
     "raft_hip_lift_abi": (C.c_int, []),
@@ -341,25 +321,23 @@ def load_library(path: str | None = None) -> C.CDLL:
     return lib
 
 
-# The libraries beside libraft_hip.so: tag -> (file, its ABI table, the function that says which engine ABI it was built beside)
-_SIDE = {"low": ("libraft_hip_low.so", LOW_ABI, "raft_hip_low_abi"), "ovl": ("libraft_hip_ovl.so", OVL_ABI, "raft_hip_ovl_abi"),
-         "frag": ("libraft_hip_frag.so", FRAG_ABI, "raft_hip_frag_abi"), "rst": ("libraft_hip_rst.so", RST_ABI, "raft_hip_rst_abi"),
-         "flt": ("libraft_hip_flt.so", FLT_ABI, "raft_hip_flt_abi"), "end": ("libraft_hip_end.so", END_ABI, "raft_hip_end_abi")}
-# ... and a second table of the same shape for the libraries added since: ``_SIDE`` is a closed set of six that the tests of those
-# six pin by its length, as they pin the entry points of raft_hip.h, so a new library is registered here and ``_SIDE`` stays as it is.
-_SIDE_MORE = {"best": ("libraft_hip_best.so", BEST_ABI, "raft_hip_best_abi")}
-# ... and an open one for every library after that (``_SIDE_MORE`` is compared by equality where it was added): the next library is
-# one more entry here, and its tests look for their own tag, not at the whole table.
-_SIDE_OPEN = {"utg": ("libraft_hip_utg.so", UTG_ABI, "raft_hip_utg_abi"),
-              "lift": ("libraft_hip_lift.so", LIFT_ABI, "raft_hip_lift_abi")}
+# The libraries beside libraft_hip.so, in the order they came: tag -> (file, its ABI table, the function that says which engine ABI
+# it was built beside).  The next library is one more entry here.
+_SIDE = {
+    "low": ("libraft_hip_low.so", LOW_ABI, "raft_hip_low_abi"), "ovl": ("libraft_hip_ovl.so", OVL_ABI, "raft_hip_ovl_abi"),
+    "frag": ("libraft_hip_frag.so", FRAG_ABI, "raft_hip_frag_abi"), "rst": ("libraft_hip_rst.so", RST_ABI, "raft_hip_rst_abi"),
+    "flt": ("libraft_hip_flt.so", FLT_ABI, "raft_hip_flt_abi"), "end": ("libraft_hip_end.so", END_ABI, "raft_hip_end_abi"),
+    "best": ("libraft_hip_best.so", BEST_ABI, "raft_hip_best_abi"), "utg": ("libraft_hip_utg.so", UTG_ABI, "raft_hip_utg_abi"),
+    "lift": ("libraft_hip_lift.so", LIFT_ABI, "raft_hip_lift_abi"),
+}
 _side_libs: dict = {}
 
 
-def _load_side_library(tag: str) -> C.CDLL:
-    """Loads one library of ``_SIDE``, ``_SIDE_MORE`` or ``_SIDE_OPEN`` (behind libraft_hip.so, whose contexts it takes) and declares every entry point of its header;
-    the two must have been built beside each other."""
+def load_side_library(tag: str) -> C.CDLL:
+    """libraft_hip_<tag>.so of ``_SIDE`` (behind libraft_hip.so, whose contexts it takes) with every entry point of
+    include/raft_hip_<tag>.h declared; the two must have been built beside each other."""
     if tag not in _side_libs:
-        file, abi, abi_fn = next(t[tag] for t in (_SIDE, _SIDE_MORE, _SIDE_OPEN) if tag in t)
+        file, abi, abi_fn = _SIDE[tag]
         main = load_library()
         p = os.path.join(os.path.dirname(_LIB_PATH), file)
         if not os.path.exists(p):
@@ -373,51 +351,6 @@ def _load_side_library(tag: str) -> C.CDLL:
             raise RuntimeError(f"{p} was built beside ABI {built_beside}, libraft_hip.so is ABI {main.raft_hip_abi_version()}")
         _side_libs[tag] = lib
     return _side_libs[tag]
-
-
-def load_low_library() -> C.CDLL:
-    """libraft_hip_low.so with every entry point of include/raft_hip_low.h declared."""
-    return _load_side_library("low")
-
-
-def load_ovl_library() -> C.CDLL:
-    """libraft_hip_ovl.so with every entry point of include/raft_hip_ovl.h declared."""
-    return _load_side_library("ovl")
-
-
-def load_frag_library() -> C.CDLL:
-    """libraft_hip_frag.so with every entry point of include/raft_hip_frag.h declared."""
-    return _load_side_library("frag")
-
-
-def load_rst_library() -> C.CDLL:
-    """libraft_hip_rst.so with every entry point of include/raft_hip_rst.h declared."""
-    return _load_side_library("rst")
-
-
-def load_flt_library() -> C.CDLL:
-    """libraft_hip_flt.so with every entry point of include/raft_hip_flt.h declared."""
-    return _load_side_library("flt")
-
-
-def load_end_library() -> C.CDLL:
-    """libraft_hip_end.so with every entry point of include/raft_hip_end.h declared."""
-    return _load_side_library("end")
-
-
-def load_best_library() -> C.CDLL:
-    """libraft_hip_best.so with every entry point of include/raft_hip_best.h declared."""
-    return _load_side_library("best")
-
-
-def load_utg_library() -> C.CDLL:
-    """libraft_hip_utg.so with every entry point of include/raft_hip_utg.h declared."""
-    return _load_side_library("utg")
-
-
-def load_lift_library() -> C.CDLL:
-    """libraft_hip_lift.so with every entry point of include/raft_hip_lift.h declared."""
-    return _load_side_library("lift")
 
 
 def _cparams(p: RaftParams) -> _Params:
@@ -534,6 +467,14 @@ _CSR_DTYPES = (np.int64, np.int32, np.int32)      # a CSR table by read: offsets
 def _csr_count(given: bool, table) -> int:
     """The count a library takes with the three arrays of a table: -1 = the context's own pass, else its rows (0 without row arrays)."""
     return -1 if not given else (M.count(table[1]) if table[1] is not None else 0)
+
+
+def _twin(n: int, dtype, like=None, zeroed: bool = True):
+    """``n`` elements of a numpy dtype where a query's inputs are: a tensor on the device of the input ``like``, or (None) a numpy array."""
+    if like is None:
+        return (np.zeros if zeroed else np.empty)(n, dtype)
+    import torch
+    return (torch.zeros if zeroed else torch.empty)(n, dtype=getattr(torch, np.dtype(dtype).name), device=like.device)
 
 
 def _summary_dict(sm) -> dict:
@@ -921,8 +862,7 @@ class Engine:
         cov[] is not downloaded."""
         if threshold is None:
             threshold = int(self.params.est_cov * self.params.cov_mul)
-        last = getattr(self, "summary", None)
-        n = max(int(last.n_reads), 0) if last is not None else 0
+        n = max(self._own_rows("n_reads"), 0)
         out = {"cov_sum": np.zeros(n, np.int64), "cov_max": np.zeros(n, np.int32), "high_windows": np.zeros(n, np.int32)}
         secs = C.c_double(0.0)
         self._check(self._lib.raft_hip_read_stats(self._ctx, int(threshold), *[M.ptr(a) for a in out.values()],
@@ -940,12 +880,11 @@ class Engine:
         ``total_low_windows``, ``low_bases``, ``reads_with_runs``, ``reads_interior``, ``reads_uncovered``.  Computed on the device
         from the form the pass wrote; cov[] is not downloaded.  Two calls of the library: the size query, then the fetch into arrays
         of that size."""
-        last = getattr(self, "summary", None)
-        n = max(int(last.n_reads), 0) if last is not None else 0
+        n = max(self._own_rows("n_reads"), 0)
         sm, secs = _LowSummary(), C.c_double(0.0)
         null = C.c_void_p(0)
         args = (int(low_cov), int(uncovered_permille))
-        low = load_low_library()
+        low = load_side_library("low")
         self._check(low.raft_hip_low_coverage(self._ctx, *args, 0, null, null, null, null, null, C.byref(sm), C.byref(secs)))
         out = {"low_offset": M.empty(n + 1, np.int64), "low_s": M.empty(int(sm.n_runs), np.int32), "low_e": M.empty(int(sm.n_runs), np.int32),
                "low_windows": M.empty(n, np.int32), "low_flags": M.empty(n, np.uint8)}
@@ -957,33 +896,57 @@ class Engine:
         return out
 
     # -- the queries about a record stream ------------------------------------------------
-    def _record_query(self, who: str, cols, tables: dict, offsets_error: str = "") -> tuple:
-        """The input of a query about a record stream, ready for its library.  ``cols``: read_len and the record columns that there
-        are; ``tables``: by name the three arrays of a CSR table the caller gave, or three None.  All columns on the device: the
-        device form, every array then a contiguous CUDA tensor of its dtype, on the engine's torch stream; else the host form, every
-        array a contiguous numpy array.  Columns are of one length, a table is (offsets [n_reads + 1], two arrays of one length) --
-        the library is told no lengths: what it will read must be there.  -> on_device, cols, tables' arrays, n_reads, n_rec"""
-        tabs = list(tables.values())
-        on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in cols if x is not None)
+    def _own_rows(self, field: str) -> int:
+        """Rows of the context's own pass -- ``n_fragments``, ``n_repeats`` or ``n_reads`` of the last summary --, 0 with no pass: what
+        the outputs need; the library checks the state."""
+        last = getattr(self, "summary", None)
+        return int(getattr(last, field)) if last is not None else 0
+
+    def _record_query(self, who: str, cols, *, lead: int = 1, rec_u8=None, read_u8=None, tables=None, tables_vote: bool = False,
+                      offsets_error: str = "", device_out=()) -> tuple:
+        """The input of a query, ready for its library.  ``cols``: the int32 arrays (None = absent) -- ``lead`` arrays the method
+        measures itself (read_len; none; read_len and the two per-end arrays of unitigs), then the record columns that there are.
+        ``lead == 0`` also says that there is no read_len: ``n_reads`` is then None and no table is measured here -- the method does it.
+        ``rec_u8`` / ``read_u8``: by name the uint8 arrays with a byte per record (as long as the columns) / per read (the method checks
+        their length: the words differ).  ``tables``: by name the three arrays of a CSR table the caller gave, or three None.
+        ``device_out``: int32 outputs of the caller's, which in the device form must be tensors like the columns (refused with them,
+        before the stream is touched); they have no say in the form and the host form leaves them to the method.
+        The form: all int32 and uint8 arrays on the device -- and, under ``tables_vote``, the tables' -- is the device form, every array
+        then a contiguous CUDA tensor of its dtype, on the engine's torch stream; else the host form, every array a contiguous numpy
+        array.  Record columns are of one length; with a read_len a table is (offsets [n_reads + 1], two arrays of one length) -- the
+        library is told no lengths: what it will read must be there.
+        -> on_device, cols, the uint8 arrays (per record, then per read), the tables' arrays, n_reads (None without read_len), n_rec"""
+        rec_u8, read_u8, tables = rec_u8 or {}, read_u8 or {}, tables or {}
+        u8 = {**rec_u8, **read_u8}
+        tabs = [list(t) for t in tables.values()]
+        voters = [x for x in [*cols, *u8.values()] + ([a for t in tabs for a in t] if tables_vote else []) if x is not None]
+        on_device = bool(voters) and all(hasattr(x, "is_cuda") and x.is_cuda for x in voters)
         if on_device:
             import torch
-            _need_int32_cuda(f"{who} needs", list(cols) + [a for t in tabs for a in t[1:]])
+            _need_int32_cuda(f"{who} needs", list(cols) + [a for t in tabs for a in t[1:]] + list(device_out))
+            for name, x in u8.items():          # (it voted: it is on the device)
+                if x is not None and (x.dtype != torch.uint8 or not x.is_contiguous()):
+                    raise TypeError(f"{who} needs {name} as a contiguous uint8 CUDA tensor")
             for t in tabs:
                 if t[0] is not None and (t[0].dtype != torch.int64 or not t[0].is_cuda or not t[0].is_contiguous()):
                     raise TypeError(offsets_error)
             self.use_torch_stream()
+            u8 = list(u8.values())
         else:
-            host = lambda a: a.cpu() if hasattr(a, "is_cuda") else a
-            cols = _host_columns([None if x is None else host(x) for x in cols])
-            tabs = [[None if a is None else M.carray(host(a), dt) for a, dt in zip(t, _CSR_DTYPES)] for t in tabs]
-        n_reads = M.count(cols[0])
-        n_rec = M.count(cols[1]) if len(cols) > 1 else 0
-        _need_equal_lengths(cols[2:], n_rec)
-        for what, t in zip(tables, tabs):
+            host = lambda a, dt: None if a is None else M.carray(a.cpu() if hasattr(a, "is_cuda") else a, dt)
+            cols = [host(x, np.int32) for x in cols]
+            u8 = [host(x, np.uint8) for x in u8.values()]
+            tabs = [[host(a, dt) for a, dt in zip(t, _CSR_DTYPES)] for t in tabs]
+        has_read_len = lead > 0
+        records = [c for c in cols[lead:] if c is not None]
+        n_reads = M.count(cols[0]) if has_read_len else None
+        n_rec = M.count(records[0]) if records else 0
+        _need_equal_lengths(records[1:] + u8[:len(rec_u8)], n_rec)
+        for what, t in zip(tables, tabs) if has_read_len else ():
             if any(a is not None for a in t) and (t[0] is None or (t[1] is None) != (t[2] is None) or M.count(t[0]) != n_reads + 1
                                                   or (t[1] is not None and M.count(t[1]) != M.count(t[2]))):
                 raise ValueError(f"{what} is (offsets [n_reads + 1], two arrays of one length)")
-        return (on_device, cols, *tabs, n_reads, n_rec)
+        return on_device, cols, u8, tabs, n_reads, n_rec
 
     # -- which overlaps lie inside repeats ----------------------------------------------
     last_repeat_overlaps_seconds = 0.0   # device time of the launches of the last repeat_overlaps()
@@ -1004,18 +967,13 @@ class Engine:
         rep = [None, None, None] if repeats is None else list(repeats)
         if len(rep) != 3:
             raise ValueError("repeats is (rep_offset, rep_s, rep_e)")
-        ovl = load_ovl_library()
-        on_device, cols, rep, n_reads, n_rec = self._record_query("repeat_overlaps", cols, {"repeats": rep},
-                                                                  "repeat_overlaps needs rep_offset as a contiguous int64 CUDA tensor")
-        if on_device:
-            import torch
-            fn = ovl.raft_hip_repeat_overlaps_device
-            cls = torch.zeros(n_rec, dtype=torch.uint8, device=qid.device)
-        else:
-            fn = ovl.raft_hip_repeat_overlaps_host
-            cls = np.zeros(n_rec, np.uint8)
+        ovl = load_side_library("ovl")
+        on_device, cols, _, (rep,), n_reads, n_rec = self._record_query(
+            "repeat_overlaps", cols, tables={"repeats": rep}, offsets_error="repeat_overlaps needs rep_offset as a contiguous int64 CUDA tensor")
+        fn = ovl.raft_hip_repeat_overlaps_device if on_device else ovl.raft_hip_repeat_overlaps_host
         args = _plain(cols) + ((C.c_void_p(0),) * 2 if ts is None else ())
-        out = {"cls": cls, "read_touch": np.zeros(n_reads, np.int32), "read_repeat": np.zeros(n_reads, np.int32), "read_flags": np.zeros(n_reads, np.uint8)}
+        out = {"cls": _twin(n_rec, np.uint8, qid if on_device else None), "read_touch": np.zeros(n_reads, np.int32),
+               "read_repeat": np.zeros(n_reads, np.int32), "read_flags": np.zeros(n_reads, np.uint8)}
         sm, err, secs = _OvlSummary(), C.c_int64(-1), C.c_double(0.0)
         rc = fn(self._ctx, *args, 1 if symmetric else 0, int(min_anchor), _csr_count(repeats is not None, rep), *[M.ptr(a) for a in rep],
                 *[M.ptr(a) for a in out.values()], C.byref(sm), C.byref(err), C.byref(secs))
@@ -1044,22 +1002,15 @@ class Engine:
         rep = [None, None, None] if repeats is None or len(repeats) == 0 else list(repeats)
         if len(tab) != 3 or len(rep) != 3:
             raise ValueError("fragments is (frag_offset, frag_begin, frag_end), repeats is (rep_offset, rep_s, rep_e)")
-        frag = load_frag_library()
-        on_device, cols, tab, rep, n_reads, n_rec = self._record_query(
-            "fragment_overlaps", cols, {"fragments": tab, "repeats": rep},
-            "fragment_overlaps needs frag_offset and rep_offset as contiguous int64 CUDA tensors")
+        frag = load_side_library("frag")
+        on_device, cols, _, (tab, rep), n_reads, n_rec = self._record_query(
+            "fragment_overlaps", cols, tables={"fragments": tab, "repeats": rep},
+            offsets_error="fragment_overlaps needs frag_offset and rep_offset as contiguous int64 CUDA tensors")
         fn = frag.raft_hip_frag_overlaps_device if on_device else frag.raft_hip_frag_overlaps_host
-        n_frag = rows = _csr_count(fragments is not None, tab)
-        if fragments is None:
-            last = getattr(self, "summary", None)
-            rows = int(last.n_fragments) if last is not None else 0      # (what the outputs need; the library checks the state)
+        n_frag = _csr_count(fragments is not None, tab)
+        rows = self._own_rows("n_fragments") if fragments is None else n_frag
         n_rep = _csr_count(repeats is not None, rep)
-        names = ("frag_touch", "frag_span", "frag_contained", "frag_repeat")
-        if on_device:
-            import torch
-            out = {k: torch.zeros(rows, dtype=torch.int32, device=qid.device) for k in names}
-        else:
-            out = {k: np.zeros(rows, np.int32) for k in names}
+        out = {k: _twin(rows, np.int32, qid if on_device else None) for k in ("frag_touch", "frag_span", "frag_contained", "frag_repeat")}
         out["read_contained"] = np.zeros(n_reads, np.int32)
         records = _Records(n_rec, *[M.address(c) for c in cols[1:]])
         table, annotation = _FragTable(n_frag, *[M.address(a) for a in tab]), _FragTable(n_rep, *[M.address(a) for a in rep])
@@ -1101,14 +1052,13 @@ class Engine:
         rep = [None, None, None] if repeats is None else list(repeats)
         if len(rep) != 3:
             raise ValueError("repeats is (rep_offset, rep_s, rep_e)")
-        rst = load_rst_library()
-        on_device, cols, rep, n_reads, n_rec = self._record_query("repeat_stats", [read_len] + [x for x in rec if x is not None], {"repeats": rep},
-                                                                  "repeat_stats needs rep_offset as a contiguous int64 CUDA tensor")
+        rst = load_side_library("rst")
+        on_device, cols, _, (rep,), n_reads, n_rec = self._record_query(
+            "repeat_stats", [read_len] + [x for x in rec if x is not None], tables={"repeats": rep},
+            offsets_error="repeat_stats needs rep_offset as a contiguous int64 CUDA tensor")
         fn = rst.raft_hip_repeat_stats_device if on_device else rst.raft_hip_repeat_stats_host
-        n_rep = rows = _csr_count(repeats is not None, rep)
-        if repeats is None:
-            last = getattr(self, "summary", None)
-            rows = int(last.n_repeats) if last is not None else 0        # (what the outputs need; the library checks the state)
+        n_rep = _csr_count(repeats is not None, rep)
+        rows = self._own_rows("n_repeats") if repeats is None else n_rep
         out = {k: np.zeros(rows, np.int32) for k in self.RUN_COUNTS}
         out.update({k: (np.zeros(rows, np.int64 if k == "run_cov_sum" else np.int32) if threshold != 0 else None) for k in self.RUN_COVERAGE})
         out["run_flags"] = np.zeros(rows, np.uint8)
@@ -1137,27 +1087,20 @@ class Engine:
         into tensors from ``device_tensor``, which live until ``device_free`` or the context's end -- or numpy arrays (staged by the library), where ``out`` may be the input arrays
         themselves: the stream is then compacted in place."""
         cols = [qid, qs, qe, tid, ts, te, matches, block]
-        given = [x for x in cols if x is not None]
-        on_device = bool(given) and all(hasattr(x, "is_cuda") and x.is_cuda for x in given)
-        n_rec = M.count(given[0]) if given else 0
         if out is not None and len(out) != 6:
             raise ValueError("filter_overlaps: out is six columns")
-        flt = load_flt_library()
+        flt = load_side_library("flt")
+        on_device, cols, _, _, _, n_rec = self._record_query("filter_overlaps", cols, lead=0, device_out=out or ())
+        fn = flt.raft_hip_filter_overlaps_device if on_device else flt.raft_hip_filter_overlaps_host
+        # (``out`` is no input: it comes from the engine's allocator, or is the caller's and a numpy array in the host form)
         if on_device:
-            import torch
-            _need_int32_cuda("filter_overlaps needs", cols + list(out or []))
-            self.use_torch_stream()
             if out is None:
+                import torch
                 out = [self.device_tensor(n_rec, torch.int32) for _ in range(6)]
-            fn = flt.raft_hip_filter_overlaps_device
-        else:
-            cols = _host_columns([x.cpu() if hasattr(x, "is_cuda") else x for x in cols])
-            if out is None:
-                out = [np.empty(n_rec, np.int32) for _ in range(6)]
-            elif any(not isinstance(o, np.ndarray) or o.dtype != np.int32 or not o.flags["C_CONTIGUOUS"] for o in out):
-                raise TypeError("filter_overlaps needs out as contiguous int32 numpy arrays")
-            fn = flt.raft_hip_filter_overlaps_host
-        _need_equal_lengths(cols, n_rec)
+        elif out is None:
+            out = [np.empty(n_rec, np.int32) for _ in range(6)]
+        elif any(not isinstance(o, np.ndarray) or o.dtype != np.int32 or not o.flags["C_CONTIGUOUS"] for o in out):
+            raise TypeError("filter_overlaps needs out as contiguous int32 numpy arrays")
         if any(M.count(o) < n_rec for o in out):
             raise ValueError("filter_overlaps: every out column needs room for all records")
         sm, secs = _FltSummary(), C.c_double(0.0)
@@ -1186,28 +1129,10 @@ class Engine:
         cols = [read_len, qid, qs, qe, tid, ts, te]
         if any(x is None for x in cols) or strand is None:
             raise ValueError("overlap_ends needs read_len, the six columns and strand")
-        on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in cols + [strand])
-        end = load_end_library()
-        if on_device:
-            import torch
-            _need_int32_cuda("overlap_ends needs", cols)
-            if strand.dtype != torch.uint8 or not strand.is_contiguous():
-                raise TypeError("overlap_ends needs strand as a contiguous uint8 CUDA tensor")
-            self.use_torch_stream()
-            fn = end.raft_hip_overlap_ends_device
-        else:
-            cols = _host_columns([x.cpu() if hasattr(x, "is_cuda") else x for x in cols])
-            strand = M.carray(strand.cpu() if hasattr(strand, "is_cuda") else strand, np.uint8)
-            fn = end.raft_hip_overlap_ends_host
-        n_reads, n_rec = M.count(cols[0]), M.count(cols[1])
-        _need_equal_lengths(cols[1:] + [strand], n_rec)
-        kind_out = None
-        if kinds:
-            if on_device:
-                import torch
-                kind_out = torch.empty(n_rec, dtype=torch.uint8, device=strand.device)
-            else:
-                kind_out = np.zeros(n_rec, np.uint8)
+        end = load_side_library("end")
+        on_device, cols, (strand,), _, n_reads, n_rec = self._record_query("overlap_ends", cols, rec_u8={"strand": strand})
+        fn = end.raft_hip_overlap_ends_device if on_device else end.raft_hip_overlap_ends_host
+        kind_out = _twin(n_rec, np.uint8, strand if on_device else None, zeroed=not on_device) if kinds else None   # (the kernel writes every byte)
         counts, status = np.zeros((5, n_reads), np.int32), np.zeros(n_reads, np.uint8)
         sm, err, secs = _EndSummary(), C.c_int64(-1), C.c_double(0.0)
         rc = fn(self._ctx, *_plain(cols), M.ptr(strand), int(max_overhang), int(min_ratio_permille), 1 if symmetric else 0, M.ptr(counts),
@@ -1235,24 +1160,9 @@ class Engine:
         cols = [read_len, qid, qs, qe, tid, ts, te]
         if any(x is None for x in cols) or strand is None:
             raise ValueError("best_overlaps needs read_len, the six columns and strand")
-        on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in cols + [strand] + ([] if skip is None else [skip]))
-        best = load_best_library()
-        if on_device:
-            import torch
-            _need_int32_cuda("best_overlaps needs", cols)
-            for name, x in (("strand", strand), ("skip", skip)):
-                if x is not None and (x.dtype != torch.uint8 or not x.is_contiguous()):
-                    raise TypeError(f"best_overlaps needs {name} as a contiguous uint8 CUDA tensor")
-            self.use_torch_stream()
-            fn = best.raft_hip_best_overlaps_device
-        else:
-            cols = _host_columns([x.cpu() if hasattr(x, "is_cuda") else x for x in cols])
-            strand = M.carray(strand.cpu() if hasattr(strand, "is_cuda") else strand, np.uint8)
-            if skip is not None:
-                skip = M.carray(skip.cpu() if hasattr(skip, "is_cuda") else skip, np.uint8)
-            fn = best.raft_hip_best_overlaps_host
-        n_reads, n_rec = M.count(cols[0]), M.count(cols[1])
-        _need_equal_lengths(cols[1:] + [strand], n_rec)
+        best = load_side_library("best")
+        on_device, cols, (strand, skip), _, n_reads, _ = self._record_query("best_overlaps", cols, rec_u8={"strand": strand}, read_u8={"skip": skip})
+        fn = best.raft_hip_best_overlaps_device if on_device else best.raft_hip_best_overlaps_host
         if skip is not None and M.count(skip) != n_reads:
             raise ValueError("best_overlaps: skip is one byte per read")
         partner, span, flags = np.zeros((n_reads, 2), np.int32), np.zeros((n_reads, 2), np.int32), np.zeros(n_reads, np.uint8)
@@ -1280,20 +1190,10 @@ class Engine:
         arrs = [read_len, partner, span]
         if any(x is None for x in arrs) or flags is None:
             raise ValueError("unitigs needs read_len, partner, span and flags")
-        on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in arrs + [flags])
-        utg = load_utg_library()
-        if on_device:
-            import torch
-            _need_int32_cuda("unitigs needs", arrs)
-            if flags.dtype != torch.uint8 or not flags.is_contiguous():
-                raise TypeError("unitigs needs flags as a contiguous uint8 CUDA tensor")
-            self.use_torch_stream()
-            fn = utg.raft_hip_unitigs_device
-        else:
-            arrs = _host_columns([x.cpu() if hasattr(x, "is_cuda") else x for x in arrs])
-            flags = M.carray(flags.cpu() if hasattr(flags, "is_cuda") else flags, np.uint8)
-            fn = utg.raft_hip_unitigs_host
-        n = M.count(arrs[0])
+        utg = load_side_library("utg")
+        # (no record columns: partner and span are per read end, and one sentence refuses all three lengths, so they are checked here)
+        on_device, arrs, (flags,), _, n, _ = self._record_query("unitigs", arrs, lead=3, read_u8={"flags": flags})
+        fn = utg.raft_hip_unitigs_device if on_device else utg.raft_hip_unitigs_host
         if M.count(arrs[1]) != 2 * n or M.count(arrs[2]) != 2 * n or M.count(flags) != n:
             raise ValueError("unitigs: partner and span are two values per read, flags one byte")
         unitig, index, order, utg_reads = (np.zeros(n, np.int32) for _ in range(4))
@@ -1329,28 +1229,14 @@ class Engine:
         tab = [None, None, None] if fragments is None else list(fragments)
         if len(tab) != 3:
             raise ValueError("fragments is (frag_offset, frag_begin, frag_end)")
-        on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in cols + [strand] + [a for a in tab if a is not None])
-        lift = load_lift_library()
-        if on_device:
-            import torch
-            _need_int32_cuda("lift_overlaps needs", cols + tab[1:])
-            if strand.dtype != torch.uint8 or not strand.is_contiguous():
-                raise TypeError("lift_overlaps needs strand as a contiguous uint8 CUDA tensor")
-            if tab[0] is not None and (tab[0].dtype != torch.int64 or not tab[0].is_contiguous()):
-                raise TypeError("lift_overlaps needs frag_offset as a contiguous int64 CUDA tensor")
-            self.use_torch_stream()
-            fn = lift.raft_hip_lift_overlaps_device
-        else:
-            host = [x.cpu() if hasattr(x, "is_cuda") else x for x in cols + [strand] + tab]
-            cols = _host_columns(host[:6])
-            strand = M.carray(host[6], np.uint8)
-            tab = [None if host[7] is None else M.carray(host[7], np.int64)] + _host_columns(host[8:])
-            fn = lift.raft_hip_lift_overlaps_host
-        n_rec = M.count(cols[0])
-        _need_equal_lengths(cols + [strand], n_rec)
+        lift = load_side_library("lift")
+        on_device, cols, (strand,), (tab,), _, n_rec = self._record_query(
+            "lift_overlaps", cols, lead=0, rec_u8={"strand": strand}, tables={"fragments": tab}, tables_vote=True,
+            offsets_error="lift_overlaps needs frag_offset as a contiguous int64 CUDA tensor")
+        fn = lift.raft_hip_lift_overlaps_device if on_device else lift.raft_hip_lift_overlaps_host
+        # (no read_len to measure the table against: the offsets say how many reads there are, and the table is checked here)
         if fragments is None:
-            last = getattr(self, "summary", None)
-            n_reads = int(last.n_reads) if last is not None else 0       # (the library checks the state)
+            n_reads = self._own_rows("n_reads")
         else:
             if tab[0] is None or (tab[1] is None) != (tab[2] is None) or M.count(tab[0]) < 1 or (tab[1] is not None and M.count(tab[1]) != M.count(tab[2])):
                 raise ValueError("fragments is (offsets [n_reads + 1], two arrays of one length)")
@@ -1362,10 +1248,7 @@ class Engine:
         rc = fn(self._ctx, n_reads, C.byref(records), M.ptr(strand), C.byref(table), int(min_len), 0, *null, C.byref(sm), C.byref(err), C.byref(secs))
         self._check(rc, err.value)
         n_out, seconds = int(sm.n_out), secs.value
-        if on_device:
-            out = {k: torch.empty(n_out, dtype=torch.uint8 if k == "rev" else torch.int32, device=qid.device) for k in LIFT_COLUMNS}
-        else:
-            out = {k: np.empty(n_out, np.uint8 if k == "rev" else np.int32) for k in LIFT_COLUMNS}
+        out = {k: _twin(n_out, np.uint8 if k == "rev" else np.int32, qid if on_device else None, zeroed=False) for k in LIFT_COLUMNS}
         if n_out > 0:
             rc = fn(self._ctx, n_reads, C.byref(records), M.ptr(strand), C.byref(table), int(min_len), n_out, *[M.ptr(a) for a in out.values()],
                     C.byref(sm), C.byref(err), C.byref(secs))
@@ -1384,7 +1267,7 @@ class Engine:
         cols = [read_len, qid, qs, qe, tid] + ([] if symmetric else [ts, te])
         if any(x is None for x in cols[:4]) or (not symmetric and (ts is None or te is None)):
             raise ValueError("census needs read_len, qid, qs, qe (and ts, te unless symmetric)")
-        on_device, cols, n_reads, _ = self._record_query("census", cols, {})
+        on_device, cols, _, _, n_reads, _ = self._record_query("census", cols)
         fn = self._lib.raft_hip_census_device if on_device else self._lib.raft_hip_census_host
         args = _plain(cols) + ((C.c_void_p(0),) * 2 if symmetric else ())
         intervals, contained = np.zeros(n_reads, np.int32), np.zeros(n_reads, np.uint8)

@@ -109,9 +109,10 @@ def load_library():
         if not os.path.exists(_LIB_PATH):
             raise RuntimeError(f"{_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         lib = C.CDLL(_LIB_PATH)
-        for name, (restype, argtypes) in list(ABI.items()) + list(LOW_ABI.items()) + list(OVL_ABI.items()) + list(FRAG_ABI.items()) + list(RST_ABI.items()) + list(FLT_ABI.items()) + list(END_ABI.items()) + list(BEST_ABI.items()) + list(UTG_ABI.items()) + list(LIFT_ABI.items()):
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, argtypes
+        for table in (ABI, LOW_ABI, OVL_ABI, FRAG_ABI, RST_ABI, FLT_ABI, END_ABI, BEST_ABI, UTG_ABI, LIFT_ABI):
+            for name, (restype, argtypes) in table.items():
+                fn = getattr(lib, name)
+                fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
     return _lib
 

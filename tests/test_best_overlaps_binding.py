@@ -1,7 +1,7 @@
 """CPU: the functions of include/raft_hip_best.h and include/raft_host_best.h are declared by their bindings (``BEST_ABI`` of
 raft_amd/engine.py and raft_amd/hostio.py) with the same parameters, class by class; the summary is nine int64; exports_best.map names
 the three entry points and nothing of the other tables, and libraft_hip_best.so exports exactly them.  The closed sets -- raft_hip.h,
-raft_host.h, raft_host_flt.h, raft_host_end.h, libraft_hip_end.so, ``engine._SIDE`` -- are what they were.  What
+raft_host.h, raft_host_flt.h, raft_host_end.h, libraft_hip_end.so, the tags of ``engine._SIDE`` -- are what they were.  What
 ``Engine.best_overlaps`` hands to the library, against the recording stand-in of tests/test_binding_calls.py."""
 import ctypes as C
 import fnmatch
@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 from raft_testlib import ROOT
-from test_binding_calls import CTX, D, DEV_NAMES, HOST_NAMES, QE, QID, QS, RL, TE, TID, TS, Lib, T, make_engine
+from test_binding_calls import CTX, D, DEV_NAMES, HOST_NAMES, QE, QID, QS, RL, TE, TID, TS, Lib, T, check_side_table, make_engine, side_library
 from test_binding_tables import _ctypes_class, header_functions
 
 from raft_amd import engine, hostio
@@ -77,10 +77,8 @@ def test_the_closed_sets_are_what_they_were():
     assert sorted(header_functions("raft_host_flt.h", "raft_host_")) == sorted(hostio.FLT_ABI) and len(hostio.FLT_ABI) == 3
     assert sorted(header_functions("raft_host_end.h", "raft_host_")) == sorted(hostio.END_ABI) and len(hostio.END_ABI) == 4
     assert sorted(header_functions("raft_hip_end.h", "raft_hip_")) == sorted(engine.END_ABI) and len(engine.END_ABI) == 3
-    # the new library stands in the second table; the first keeps its six
-    assert len(engine._SIDE) == 6 and "best" not in engine._SIDE
-    assert engine._SIDE_MORE == {"best": ("libraft_hip_best.so", engine.BEST_ABI, "raft_hip_best_abi")}
-    assert not set(engine._SIDE) & set(engine._SIDE_MORE)
+    # the library stands under its tag in the one table, which holds the nine libraries and no other
+    check_side_table("best", engine.BEST_ABI)
     makefile = open(os.path.join(ROOT, "raft_amd", "csrc", "Makefile")).read()
     assert re.search(r"^SIDE = .*\bend=ovl_ends_lib best=best_ovl_lib$", makefile, flags=re.M)
 
@@ -119,7 +117,7 @@ DEV_COLS = tuple(D[k] for k in ("rl", "qid", "qs", "qe", "tid", "ts", "te"))
 def call(monkeypatch, *args, **kw):
     eng = make_engine(NAMES)
     side = Lib(NAMES)
-    monkeypatch.setattr(engine, "load_best_library", lambda: side)
+    monkeypatch.setattr(engine, "load_side_library", side_library("best", side))
     res = eng.best_overlaps(*args, **kw)
     assert len(side.calls) == 1 and eng._lib.lib_calls() == []
     return eng, side.calls[0], res
@@ -168,7 +166,7 @@ def test_no_records_and_no_reads(monkeypatch):
 def test_what_is_refused_before_any_call(monkeypatch):
     eng = make_engine(NAMES)
     side = Lib(NAMES)
-    monkeypatch.setattr(engine, "load_best_library", lambda: side)
+    monkeypatch.setattr(engine, "load_side_library", side_library("best", side))
     with pytest.raises(ValueError, match="best_overlaps needs read_len, the six columns and strand"):
         eng.best_overlaps(*HOST_COLS, None)
     with pytest.raises(ValueError, match="best_overlaps needs"):

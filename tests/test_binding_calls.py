@@ -94,6 +94,26 @@ def make_engine(names=None, ctx=CTX, **summary):
     return eng
 
 
+def side_library(tag, side):
+    """A stand-in for ``engine.load_side_library`` that hands out ``side`` and only for ``tag``."""
+    def load(asked):
+        assert asked == tag, f"asked for the library {asked!r}, not {tag!r}"
+        return side
+    return load
+
+
+SIDE_TAGS = ["low", "ovl", "frag", "rst", "flt", "end", "best", "utg", "lift"]
+
+
+def check_side_table(tag, abi):
+    """``tag`` maps to exactly (file, its ABI table, its abi function); the table's tags are exactly the nine, in the order the
+    libraries came -- none appears or vanishes unnoticed --, and no two tags share a file."""
+    assert engine._SIDE[tag] == (f"libraft_hip_{tag}.so", abi, f"raft_hip_{tag}_abi")
+    assert list(engine._SIDE) == SIDE_TAGS and len(set(SIDE_TAGS)) == 9
+    files = [row[0] for row in engine._SIDE.values()]
+    assert len(files) == len(set(files)) == 9 and all(len(row) == 3 for row in engine._SIDE.values())
+
+
 class T:
     """As much of a torch tensor as the binding looks at."""
 

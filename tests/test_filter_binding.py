@@ -10,6 +10,7 @@ import subprocess
 
 import pytest
 from raft_testlib import ROOT
+from test_binding_calls import check_side_table
 from test_binding_tables import _ctypes_class, header_functions
 
 from raft_amd import engine, hostio
@@ -51,7 +52,7 @@ def test_the_closed_sets_are_what_they_were():
     assert len(hostio.EXPORTS) == 30 and not any("quality" in n for n in hostio.EXPORTS)
     assert "RAFT_HIP_ABI_VERSION 11" in re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "raft_hip.h")).read())
     assert "quality" not in open(os.path.join(ROOT, "include", "raft_host.h")).read()
-    assert engine._SIDE["flt"] == ("libraft_hip_flt.so", engine.FLT_ABI, "raft_hip_flt_abi")
+    check_side_table("flt", engine.FLT_ABI)
 
 
 def test_the_map_and_the_library_export_them():

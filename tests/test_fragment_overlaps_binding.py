@@ -57,7 +57,7 @@ def test_the_map_and_the_library_export_them():
     assert all(any(fnmatch.fnmatchcase(n, p) for n in ENTRY_POINTS) for p in patterns)
     assert not any(fnmatch.fnmatchcase(n, p) for p in patterns for n in list(engine.ABI) + list(engine.LOW_ABI) + list(engine.OVL_ABI))
     assert hasattr(hostio.load_library(), "raft_host_write_fragments")
-    frag = engine.load_frag_library()
+    frag = engine.load_side_library("frag")
     assert frag.raft_hip_frag_abi() == engine.load_library().raft_hip_abi_version() == 11
     if shutil.which("nm") is None:
         pytest.skip("no nm")

@@ -321,7 +321,7 @@ def raw_call(eng, form, L, cols, strand, skip, H, F, symmetric, partner, span, f
     """The entry point itself, with the caller's output arrays -> (code, error_index, the context's message)"""
     import torch
     from raft_amd import engine
-    lib = engine.load_best_library()
+    lib = engine.load_side_library("best")
     arrays = [L] + list(cols) + [strand, skip]
     if form == "device":
         held = [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0") for a in arrays]

@@ -277,7 +277,7 @@ def test_refusals(eng):
     both = torch.zeros(150, dtype=torch.int32, device="cuda:0")
     refused(lambda: eng.filter_overlaps(*dev, min_identity_permille=P0, out=spare[:4] + [both[:100], both[50:]]))
     # a negative count, and a missing output, reach the library only directly
-    flt = engine.load_flt_library()
+    flt = engine.load_side_library("flt")
     for fn, given in ((flt.raft_hip_filter_overlaps_host, cols), (flt.raft_hip_filter_overlaps_device, dev)):
         ptrs = [engine.M.ptr(x) for x in given[:6]]
         outs = [engine.M.ptr(x) for x in (spare if given is dev else [np.zeros(100, np.int32) for _ in range(6)])]

@@ -142,7 +142,7 @@ def raw(eng, form, cols, sym, table, rep, skip=(), n_reads=None, n_rec=None, n_f
     for no annotation.  -> rc, error_index, [touch, span, contained, repeat], read_contained, summary"""
     from raft_amd import engine
     import torch
-    lib = engine.load_frag_library()
+    lib = engine.load_side_library("frag")
     arrays = lambda t: [None] * 3 if t == OWN or len(t) == 0 else list(t)
     count = lambda t, given: given if given is not None else (-1 if t == OWN else 0 if len(t) == 0 or t[1] is None else t[1].size)
     n_frag, n_rep = count(table, n_frag), count(rep, n_rep)

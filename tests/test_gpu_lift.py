@@ -231,7 +231,7 @@ def raw(eng, form, cols, strand, table, min_len=1, out_cap=None, skip=(), n_read
     -> rc, error_index, the eight columns (of `room` elements), summary"""
     from raft_amd import engine
     import torch
-    lib = engine.load_lift_library()
+    lib = engine.load_side_library("lift")
     tab = [None] * 3 if table == OWN else list(table)
     if n_frag is None:
         n_frag = -1 if table == OWN else (0 if tab[1] is None else tab[1].size)

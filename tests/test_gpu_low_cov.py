@@ -80,7 +80,7 @@ def _raw(eng, low_cov, permille, run_cap, n_reads, with_runs=True):
     s, e = np.full(cap + 1, -1, np.int32), np.full(cap + 1, -1, np.int32)
     win, fl = np.full(n_reads, -1, np.int32), np.full(n_reads, 255, np.uint8)
     P = lambda a: C.c_void_p(a.ctypes.data)
-    rc = engine.load_low_library().raft_hip_low_coverage(eng._ctx, low_cov, permille, run_cap, P(off), P(s) if with_runs else None, P(e) if with_runs else None,
+    rc = engine.load_side_library("low").raft_hip_low_coverage(eng._ctx, low_cov, permille, run_cap, P(off), P(s) if with_runs else None, P(e) if with_runs else None,
                                         P(win), P(fl), C.byref(sm), None)
     return rc, sm, off, s, e, win, fl
 

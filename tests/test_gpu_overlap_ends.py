@@ -251,7 +251,7 @@ def raw_call(eng, form, L, cols, strand, H, F, symmetric, counts, status, kinds,
     """The entry point itself, with the caller's output arrays -> (code, error_index, the context's message)"""
     import torch
     from raft_amd import engine
-    lib = engine.load_end_library()
+    lib = engine.load_side_library("end")
     arrays = [L] + list(cols) + [strand]
     if form == "device":
         held = [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0") for a in arrays]

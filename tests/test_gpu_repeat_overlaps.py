@@ -143,7 +143,7 @@ def raw(eng, form, cols, sym, anchor, rep, n_rep=None, skip=()):
     """The entry point as the ABI has it; outputs filled with a mark before the call.  -> rc, error_index, cls, touch, repeat, flags, summary"""
     from raft_amd import engine
     import torch
-    lib = engine.load_ovl_library()
+    lib = engine.load_side_library("ovl")
     n_reads, n_rec = cols[0].size, cols[1].size
     touch, repeat, flags = np.full(n_reads, -7, np.int32), np.full(n_reads, -7, np.int32), np.full(n_reads, 77, np.uint8)
     sm, err = engine._OvlSummary(), C.c_int64(-5)

@@ -194,7 +194,7 @@ def raw(eng, form, cols, sym, rep, threshold=0, skip=COVERAGE, n_reads=None, n_r
     """The entry point as the ABI has it; outputs filled with a mark before the call.  rep: three arrays (None = NULL) or OWN.
     -> rc, error_index, {name: array}, summary"""
     from raft_amd import engine
-    lib = engine.load_rst_library()
+    lib = engine.load_side_library("rst")
     if n_rep is None:
         n_rep = -1 if rep == OWN else 0 if rep[1] is None else rep[1].size
     rows = (max(n_rep, 0) if rep != OWN else int(eng.summary.n_repeats)) if rows is None else rows

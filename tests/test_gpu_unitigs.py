@@ -210,7 +210,7 @@ def raw_call(eng, form, table, out, n_reads=None, summary=None):
     """The entry point itself, with the caller's output arrays -> (code, error_index, the context's message)"""
     import torch
     from raft_amd import engine
-    lib = engine.load_utg_library()
+    lib = engine.load_side_library("utg")
     if form == "device":
         held = [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0") for a in table]
         eng.use_torch_stream()

@@ -1,7 +1,7 @@
 """CPU: the functions of include/raft_hip_lift.h and include/raft_host_lift.h are declared by their bindings (``LIFT_ABI`` of
 raft_amd/engine.py and raft_amd/hostio.py) with the same parameters, class by class; the summary is six int64; exports_lift.map names
 the three entry points and nothing of the other tables, and libraft_hip_lift.so exports exactly them.  The library is registered
-under its tag in the open table.  What ``Engine.lift_overlaps`` hands to the library, against the recording stand-in of
+under its tag in the one table of side libraries.  What ``Engine.lift_overlaps`` hands to the library, against the recording stand-in of
 tests/test_binding_calls.py."""
 import ctypes as C
 import fnmatch
@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 from raft_testlib import ROOT
-from test_binding_calls import CTX, Lib, T, make_engine
+from test_binding_calls import CTX, Lib, T, check_side_table, make_engine, side_library
 from test_binding_tables import _ctypes_class, header_functions
 
 from raft_amd import engine, hostio
@@ -54,11 +54,7 @@ def test_the_header_declares_the_three_entry_points_and_the_summary():
 
 
 def test_the_library_is_registered_under_its_tag():
-    assert engine._SIDE_OPEN["lift"] == ("libraft_hip_lift.so", engine.LIFT_ABI, "raft_hip_lift_abi")
-    assert "lift" not in engine._SIDE and "lift" not in engine._SIDE_MORE and list(engine._SIDE_OPEN)[0] == "utg"
-    tags = [t for table in (engine._SIDE, engine._SIDE_MORE, engine._SIDE_OPEN) for t in table]
-    files = [table[t][0] for table in (engine._SIDE, engine._SIDE_MORE, engine._SIDE_OPEN) for t in table]
-    assert len(tags) == len(set(tags)) and len(files) == len(set(files))
+    check_side_table("lift", engine.LIFT_ABI)
     makefile = open(os.path.join(ROOT, "raft_amd", "csrc", "Makefile")).read()
     assert re.search(r"^SIDE \+= lift=lift_lib$", makefile, flags=re.M)
     assert makefile.index("\nSIDE += utg=unitig_lib") < makefile.index("\nSIDE += lift=lift_lib") < makefile.index("\nSIDE_TAGS =")
@@ -70,7 +66,7 @@ def test_the_closed_sets_are_what_they_were():
     assert len(engine.EXPORTS) == 57 and not any("lift" in n for n in engine.EXPORTS)
     assert len(hostio.EXPORTS) == 30 and not any("fragment_paf" in n for n in hostio.EXPORTS)
     assert "RAFT_HIP_ABI_VERSION 11" in re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "raft_hip.h")).read())
-    assert len(engine._SIDE) == 6 and list(engine._SIDE_MORE) == ["best"]
+    check_side_table("utg", engine.UTG_ABI)
     assert sorted(header_functions("raft_hip_utg.h", "raft_hip_")) == sorted(engine.UTG_ABI) and len(engine.UTG_ABI) == 3
 
 
@@ -112,7 +108,7 @@ COLS = ("qid", "qs", "qe", "tid", "ts", "te")
 def call(monkeypatch, *args, **kw):
     eng = make_engine(NAMES, n_reads=3)
     side = Lib(NAMES)
-    monkeypatch.setattr(engine, "load_lift_library", lambda: side)
+    monkeypatch.setattr(engine, "load_side_library", side_library("lift", side))
     real_empty = torch.empty
     monkeypatch.setattr(torch, "empty", lambda *a, device=None, **k: real_empty(*a, **k))          # (no device on this machine)
     res = eng.lift_overlaps(*args, **kw)
@@ -177,7 +173,7 @@ def test_the_filling_call(monkeypatch):
                 return rc
             return wrapped
     side = Five(NAMES)
-    monkeypatch.setattr(engine, "load_lift_library", lambda: side)
+    monkeypatch.setattr(engine, "load_side_library", side_library("lift", side))
     res = eng.lift_overlaps(*[HOST[k] for k in COLS], STRAND, fragments=(OFF, FB, FE))
     assert [c[0] for c in side.calls] == ["raft_hip_lift_overlaps_host"] * 2
     first, second = side.calls[0][1], side.calls[1][1]
@@ -189,7 +185,7 @@ def test_the_filling_call(monkeypatch):
 def test_what_is_refused_before_any_call(monkeypatch):
     eng = make_engine(NAMES, n_reads=3)
     side = Lib(NAMES)
-    monkeypatch.setattr(engine, "load_lift_library", lambda: side)
+    monkeypatch.setattr(engine, "load_side_library", side_library("lift", side))
     cols = [HOST[k] for k in COLS]
     with pytest.raises(ValueError, match="the six columns and strand"):
         eng.lift_overlaps(*cols, None)

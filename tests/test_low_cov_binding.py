@@ -24,7 +24,7 @@ def test_binding_declares_what_the_header_declares(header, prefix, mod):
 
 def test_the_libraries_export_them():
     assert hasattr(hostio.load_library(), "raft_host_write_low_coverage")
-    low = engine.load_low_library()
+    low = engine.load_side_library("low")
     assert low.raft_hip_low_abi() == engine.load_library().raft_hip_abi_version() == 11
     if shutil.which("nm") is None:
         pytest.skip("no nm")

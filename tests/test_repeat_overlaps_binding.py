@@ -52,7 +52,7 @@ def test_the_map_and_the_library_export_them():
     assert all(any(fnmatch.fnmatchcase(n, p) for n in names) for p in patterns)
     assert not any(fnmatch.fnmatchcase(n, p) for p in patterns for n in list(engine.ABI) + list(engine.LOW_ABI))
     assert hasattr(hostio.load_library(), "raft_host_write_repeat_overlaps")
-    ovl = engine.load_ovl_library()
+    ovl = engine.load_side_library("ovl")
     assert ovl.raft_hip_ovl_abi() == engine.load_library().raft_hip_abi_version() == 11
     if shutil.which("nm") is None:
         pytest.skip("no nm")

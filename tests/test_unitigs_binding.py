@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 from raft_testlib import ROOT
-from test_binding_calls import CTX, Lib, T, make_engine
+from test_binding_calls import CTX, Lib, T, check_side_table, make_engine, side_library
 from test_binding_tables import _ctypes_class, header_functions
 
 from raft_amd import engine, hostio
@@ -55,12 +55,7 @@ def test_the_header_declares_the_three_entry_points_and_the_summary():
 
 
 def test_the_library_is_registered_under_its_tag():
-    assert "utg" in engine._SIDE_OPEN and engine._SIDE_OPEN["utg"] == ("libraft_hip_utg.so", engine.UTG_ABI, "raft_hip_utg_abi")
-    assert "utg" not in engine._SIDE and "utg" not in engine._SIDE_MORE
-    tags = [t for table in (engine._SIDE, engine._SIDE_MORE, engine._SIDE_OPEN) for t in table]
-    assert len(tags) == len(set(tags))
-    files = [table[t][0] for table in (engine._SIDE, engine._SIDE_MORE, engine._SIDE_OPEN) for t in table]
-    assert len(files) == len(set(files))
+    check_side_table("utg", engine.UTG_ABI)
     makefile = open(os.path.join(ROOT, "raft_amd", "csrc", "Makefile")).read()
     assert re.search(r"^SIDE \+= utg=unitig_lib$", makefile, flags=re.M)
     assert makefile.index("\nSIDE = ") < makefile.index("\nSIDE += utg=unitig_lib") < makefile.index("\nSIDE_TAGS =") < makefile.index("\nall:")
@@ -74,7 +69,7 @@ def test_the_closed_sets_are_what_they_were():
     assert "RAFT_HIP_ABI_VERSION 11" in re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "raft_hip.h")).read())
     assert "unitig" not in open(os.path.join(ROOT, "include", "raft_host.h")).read()
     assert sorted(header_functions("raft_hip_best.h", "raft_hip_")) == sorted(engine.BEST_ABI) and len(engine.BEST_ABI) == 3
-    assert len(engine._SIDE) == 6 and list(engine._SIDE_MORE) == ["best"]
+    check_side_table("best", engine.BEST_ABI)
 
 
 def _exported(file):
@@ -111,7 +106,7 @@ NAMES = {RL.ctypes.data: "rl", PARTNER.ctypes.data: "partner", SPAN.ctypes.data:
 def call(monkeypatch, *args):
     eng = make_engine(NAMES)
     side = Lib(NAMES)
-    monkeypatch.setattr(engine, "load_utg_library", lambda: side)
+    monkeypatch.setattr(engine, "load_side_library", side_library("utg", side))
     res = eng.unitigs(*args)
     assert len(side.calls) == 1 and eng._lib.lib_calls() == []
     return eng, side.calls[0], res
@@ -161,7 +156,7 @@ def test_no_reads(monkeypatch):
 def test_what_is_refused_before_any_call(monkeypatch):
     eng = make_engine(NAMES)
     side = Lib(NAMES)
-    monkeypatch.setattr(engine, "load_utg_library", lambda: side)
+    monkeypatch.setattr(engine, "load_side_library", side_library("utg", side))
     with pytest.raises(ValueError, match="unitigs needs read_len, partner, span and flags"):
         eng.unitigs(RL, PARTNER, SPAN, None)
     with pytest.raises(ValueError, match="unitigs needs"):

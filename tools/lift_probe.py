@@ -69,7 +69,7 @@ def child(args):
     del rows
     torch.cuda.empty_cache()
 
-    lib = engine.load_lift_library()
+    lib = engine.load_side_library("lift")
     import ctypes as C
     records = engine._Records(n_rec, *[c.data_ptr() for c in cols[1:]])
     own = engine._FragTable(-1, 0, 0, 0)
