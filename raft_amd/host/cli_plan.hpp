@@ -171,12 +171,6 @@ inline bool parse_min_anchor(const char *text, int32_t *min_anchor)
     return true;
 }
 
-// The query column is written over by the window records prepare_input makes; the options that read the ids after the job keep a copy.
-inline bool keeps_query_ids(bool prepare, int32_t min_anchor, bool fragment_overlaps)
-{
-    return prepare && (min_anchor > 0 || fragment_overlaps);
-}
-
 // --fragment-overlaps: the option's stdout line, the last one, from raft_hip_frag_summary's counts
 inline std::string fragment_overlaps_line(int64_t fragments, int64_t spanned, int64_t contained, int64_t contained_repeat, int64_t reads_whole,
                                           int64_t reads_all, int32_t n_reads)
@@ -186,17 +180,7 @@ inline std::string fragment_overlaps_line(int64_t fragments, int64_t spanned, in
            std::to_string(reads_whole) + ", reads with every fragment contained = " + std::to_string(reads_all) + " of " + std::to_string(n_reads);
 }
 
-// --repeat-stats: the table needs coverage and annotation under the job's final parameters in one finished one-piece pass -- the survey's
-// recipe.  The options that make the survey run:
-inline bool survey_needed(bool auto_cov, bool read_stats, int32_t low_cov, bool repeat_stats)
-{
-    return auto_cov || read_stats || low_cov >= 0 || repeat_stats;
-}
-
-// ... with -e N the survey pass is that pass already; with -e auto it ran under a placeholder, and one more runs under the estimate
-inline bool repeat_stats_second_pass(bool auto_cov, bool repeat_stats) { return auto_cov && repeat_stats; }
-
-// ... the threshold of its high windows: the job's high_cov (repeat.hpp:89-90), at least 1
+// --repeat-stats: the threshold of the table's high windows is the job's high_cov (repeat.hpp:89-90), at least 1
 inline int32_t repeat_stats_threshold(int est_cov, double cov_mul)
 {
     const int32_t high_cov = (int32_t)(est_cov * cov_mul);
@@ -237,9 +221,6 @@ inline bool parse_min_identity(const char *text, int32_t *permille)
 // --min-overlap BASES: BASES (min_span of raft_hip_filter_overlaps_*) is a whole number >= 1 written in digits alone, at most INT32_MAX.
 inline bool parse_min_overlap(const char *text, int32_t *min_span) { return parse_min_anchor(text, min_span); }
 
-// Either option makes the job tokenise PAF columns 10 and 11 and filter its records before anything else sees them.
-inline bool filter_wanted(int32_t permille, int32_t min_span) { return permille > 0 || min_span > 0; }
-
 // ... the options' stdout line, directly behind the reference's own last line and before the lines of the other options, from
 // raft_hip_flt_summary's counts
 inline std::string filter_overlaps_line(int32_t permille, int32_t min_span, int64_t records, int64_t kept, int64_t below_identity, int64_t below_span)
@@ -262,13 +243,6 @@ inline bool parse_ends_min_ratio(const char *text, int32_t *permille)
     return true;
 }
 
-// ... which means nothing without --overlap-ends (max_overhang < 0: not asked for): a usage error
-inline bool ends_options_ok(int32_t max_overhang, bool ratio_given) { return max_overhang >= 0 || !ratio_given; }
-
-// The columns the tokeniser keeps beside the six (the mask of raft_host_paf_parse_with): fields 10 and 11 for the filter, the strand
-// for --overlap-ends.
-inline int paf_columns(bool filter, bool overlap_ends) { return (filter ? RAFT_HOST_PAF_QUALITY : 0) | (overlap_ends ? RAFT_HOST_PAF_STRAND : 0); }
-
 // ... the option's stdout line, the last one, from raft_hip_end_summary's counts (dead ends: the reads with status dead5 or dead3)
 inline std::string overlap_ends_line(int32_t max_overhang, int32_t min_ratio, int64_t records, int64_t internal, int64_t query_contained,
                                      int64_t target_contained, int64_t dovetail, int64_t self, int64_t invalid, int64_t reads_contained,
@@ -281,10 +255,7 @@ inline std::string overlap_ends_line(int32_t max_overhang, int32_t min_ratio, in
            ", dead ends = " + std::to_string(dead_ends) + ", isolated reads = " + std::to_string(reads_isolated) + " of " + std::to_string(n_reads);
 }
 
-// --best-overlaps takes its H and F from --overlap-ends and its mask from that option's status bytes: a usage error without it
-inline bool best_options_ok(bool best_overlaps, int32_t max_overhang) { return !best_overlaps || max_overhang >= 0; }
-
-// ... the option's stdout line, the last one (behind overlap_ends'), from raft_hip_best_summary's counts
+// --best-overlaps: the option's stdout line, the last one (behind overlap_ends'), from raft_hip_best_summary's counts
 inline std::string best_overlaps_line(int64_t records, int64_t candidates, int64_t left_out, int64_t ends_best, int64_t ends_mutual,
                                       int64_t reads_both_mutual, int64_t reads_no_best, int64_t reads_skipped, int32_t n_reads)
 {
@@ -294,10 +265,7 @@ inline std::string best_overlaps_line(int64_t records, int64_t candidates, int64
            ", reads left out = " + std::to_string(reads_skipped) + " of " + std::to_string(n_reads);
 }
 
-// --unitigs walks the table --best-overlaps made: a usage error without it
-inline bool unitigs_options_ok(bool unitigs, bool best_overlaps) { return !unitigs || best_overlaps; }
-
-// N50 of the unitigs, singletons included: the smallest length L such that the unitigs of length >= L hold at least half of the
+// --unitigs: N50 of the unitigs, singletons included: the smallest length L such that the unitigs of length >= L hold at least half of the
 // total -- sorted descending, the length at the first prefix with 2 * cum >= total; 0 for no unitigs.
 inline int64_t unitig_n50(const int64_t *lengths, int64_t n)
 {
@@ -328,27 +296,91 @@ inline std::string unitigs_line(int64_t reads, int64_t skipped, int64_t unitigs,
 constexpr int32_t kFragmentPafMinDefault = 1;
 inline bool parse_fragment_paf_min(const char *text, int32_t *min_len) { return parse_min_anchor(text, min_len); }
 
-// ... which means nothing without --fragment-paf: a usage error
-inline bool fragment_paf_options_ok(bool fragment_paf, bool min_given) { return fragment_paf || !min_given; }
-
-// The lift reads the strand as --overlap-ends does: the tokeniser keeps it for either, and beside the filter it follows the kept records.
-inline bool strand_wanted(int32_t max_overhang, bool fragment_paf) { return max_overhang >= 0 || fragment_paf; }
-
-// ... paf_columns with that: the mask of raft_host_paf_parse_with for a job that may lift
-inline int paf_columns_with_lift(bool filter, int32_t max_overhang, bool fragment_paf) { return paf_columns(filter, strand_wanted(max_overhang, fragment_paf)); }
-
-// ... and keeps_query_ids: the lift reads the query ids after the job, as --fragment-overlaps does
-inline bool keeps_query_ids_with_lift(bool prepare, int32_t min_anchor, bool fragment_overlaps, bool fragment_paf)
-{
-    return keeps_query_ids(prepare, min_anchor, fragment_overlaps || fragment_paf);
-}
-
 // ... the option's stdout line, the last one of all, from raft_hip_lift_summary's counts
 inline std::string fragment_paf_line(int32_t min_len, int64_t records, int64_t lifted, int64_t cut, int64_t none, int64_t dropped, int64_t most)
 {
     return "INFO, fragment_paf(), min_len = " + std::to_string(min_len) + ", records = " + std::to_string(records) + ", lifted = " + std::to_string(lifted) +
            ", cut = " + std::to_string(cut) + ", without a fragment pair = " + std::to_string(none) + ", dropped pairs = " + std::to_string(dropped) +
            ", most from one record = " + std::to_string(most);
+}
+
+// What the command line says, as parse_options (raft_main.cpp) leaves it: the reference's parameters (param.hpp:18-31; -e auto: est_cov
+// is read from the data before the job), and one value per long option of this program's own -- kLongOptions says what each asks for.
+struct Options {
+    int reso = 50, est_cov = 0;
+    double cov_mul = 1.5;
+    int repeat_length = 10000, interval_length = 10000, read_length = 20000, overlap_length = 500, flanking_length = 1000;
+    std::string prefix = "raft";
+    bool auto_cov = false;
+    bool read_stats = false, fragment_overlaps = false, repeat_stats = false, best_overlaps = false, unitigs = false, fragment_paf = false;
+    int32_t low_cov = -1, overlap_ends = -1;                            // -1: not asked for
+    int32_t min_anchor = 0, min_identity = 0, min_overlap = 0;          // 0: not asked for; the identity in per mille
+    int32_t ends_min_ratio = kEndsMinRatioDefault, fragment_paf_min = kFragmentPafMinDefault;
+    bool ends_ratio_given = false, fragment_paf_min_given = false;
+};
+
+// The long options, one row each: the text's parser (none: a flag, which takes no argument), the value it writes, and the flag
+// that is set -- the option itself for a flag, the "given" mark of a value that has one.  The short options are the reference's and
+// stay a switch in parse_options, quirks and all.
+struct LongOption { const char *name; bool (*parse)(const char *, int32_t *); int32_t Options::*value; bool Options::*flag; };
+
+inline constexpr LongOption kLongOptions[] = {
+    {"read-stats", nullptr, nullptr, &Options::read_stats},                 // PREFIX.read_stats.tsv, the per-read table (raft_hip_read_stats, raft_hip_census_host)
+    {"low-cov", parse_low_cov, &Options::low_cov, nullptr},                 // C: PREFIX.low_coverage.bed, the runs of windows with coverage <= C (raft_hip_low_coverage)
+    {"repeat-overlaps", parse_min_anchor, &Options::min_anchor, nullptr},   // A: PREFIX.repeat_overlaps.tsv and .records.tsv (raft_hip_repeat_overlaps_host)
+    {"fragment-overlaps", nullptr, nullptr, &Options::fragment_overlaps},   // PREFIX.fragments.tsv, the fragments against the overlaps (raft_hip_frag_overlaps_host)
+    {"repeat-stats", nullptr, nullptr, &Options::repeat_stats},             // PREFIX.long_repeats.stats.tsv, one line per repeat run (raft_hip_repeat_stats_host)
+    {"min-identity", parse_min_identity, &Options::min_identity, nullptr},  // PCT, and --min-overlap BASES: only the records that pass go into the job
+    {"min-overlap", parse_min_overlap, &Options::min_overlap, nullptr},     // (raft_hip_filter_overlaps_host, before anything else sees the stream)
+    {"overlap-ends", parse_overlap_ends, &Options::overlap_ends, nullptr},  // H: PREFIX.overlap_ends.tsv, the kind of every record and the ends of every read
+    {"ends-min-ratio", parse_ends_min_ratio, &Options::ends_min_ratio, &Options::ends_ratio_given},   // F, in per mille
+    {"best-overlaps", nullptr, nullptr, &Options::best_overlaps},           // PREFIX.best_overlaps.tsv, the best overlap of every read end under --overlap-ends' H and F
+    {"unitigs", nullptr, nullptr, &Options::unitigs},                       // PREFIX.unitigs.tsv and .unitigs.layout.tsv, the chains and cycles of --best-overlaps' mutual ends
+    {"fragment-paf", nullptr, nullptr, &Options::fragment_paf},             // PREFIX.fragments.paf, the job's overlaps lifted onto its fragments (raft_hip_lift_overlaps_host)
+    {"fragment-paf-min", parse_fragment_paf_min, &Options::fragment_paf_min, &Options::fragment_paf_min_given},   // L: pairs shorter than L on either side are dropped
+};
+
+// One long option as getopt found it (text: its argument, NULL for a flag).  false: the text is not what the option takes -- a
+// usage error, and the value is left alone.
+inline bool set_long_option(const LongOption &o, const char *text, Options *p)
+{
+    if (o.parse && !o.parse(text, &(p->*o.value))) return false;
+    if (o.flag) p->*o.flag = true;
+    return true;
+}
+
+// The options that mean nothing without another: --ends-min-ratio needs --overlap-ends; --best-overlaps needs it too (it takes its H
+// and F from it and its mask from that option's status bytes); --unitigs needs --best-overlaps, whose table it walks;
+// --fragment-paf-min needs --fragment-paf.  false: a usage error.
+inline bool usage_ok(const Options &o)
+{
+    return (o.overlap_ends >= 0 || !o.ends_ratio_given) && (!o.best_overlaps || o.overlap_ends >= 0) && (!o.unitigs || o.best_overlaps) &&
+           (o.fragment_paf || !o.fragment_paf_min_given);
+}
+
+// What the options ask of the job between them, decided once (prepare: the group offsets and window records are made by the
+// command line, RAFT_CLI_PREPARE on a job without ranks).
+struct Request {
+    bool filter;                    // --min-identity or --min-overlap: the records are filtered before anything else sees them
+    bool strand;                    // the strand byte is tokenised: --overlap-ends and --fragment-paf read it
+    bool quality_kept;              // PAF fields 10 and 11 follow the kept records: --fragment-paf writes them beside the filter
+    int paf_columns;                // the mask of raft_host_paf_parse_with: fields 10 and 11 for the filter, the strand
+    bool keep_query_ids;            // prepare_input writes window records over the query column, which three options read after the job
+    bool survey;                    // one one-piece pass before the job: -e auto, --read-stats, --low-cov, --repeat-stats
+    bool repeat_stats_second_pass;  // -e auto: the survey ran under a placeholder, the stats pass runs under the estimate
+};
+
+inline Request request(const Options &o, bool prepare)
+{
+    Request r{};
+    r.filter = o.min_identity > 0 || o.min_overlap > 0;
+    r.strand = o.overlap_ends >= 0 || o.fragment_paf;
+    r.quality_kept = r.filter && o.fragment_paf;
+    r.paf_columns = (r.filter ? RAFT_HOST_PAF_QUALITY : 0) | (r.strand ? RAFT_HOST_PAF_STRAND : 0);
+    r.keep_query_ids = prepare && (o.min_anchor > 0 || o.fragment_overlaps || o.fragment_paf);
+    r.survey = o.auto_cov || o.read_stats || o.low_cov >= 0 || o.repeat_stats;
+    r.repeat_stats_second_pass = o.auto_cov && o.repeat_stats;
+    return r;
 }
 
 // ... a read counts as uncovered when more than this many thousandths of its bases lie in low runs (yacrd's default for "not covered")

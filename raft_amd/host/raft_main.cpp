@@ -53,28 +53,7 @@
 
 namespace {
 
-struct Params {            // param.hpp:18-31
-    int reso = 50, est_cov = 0;
-    double cov_mul = 1.5;
-    int repeat_length = 10000, interval_length = 10000, read_length = 20000, overlap_length = 500, flanking_length = 1000;
-    std::string prefix = "raft";
-    bool auto_cov = false;         // -e auto: est_cov is read from the data (a survey pass and its coverage histogram) before the job
-    bool read_stats = false;       // --read-stats: PREFIX.read_stats.tsv, the per-read table (raft_hip_read_stats, raft_hip_census_host)
-    int32_t low_cov = -1;          // --low-cov C: PREFIX.low_coverage.bed, the runs of windows with coverage <= C (raft_hip_low_coverage); -1: not asked for
-    bool fragment_overlaps = false;   // --fragment-overlaps: PREFIX.fragments.tsv, the fragments against the overlaps (raft_hip_frag_overlaps_host)
-    bool repeat_stats = false;     // --repeat-stats: PREFIX.long_repeats.stats.tsv, one line per repeat run (raft_hip_repeat_stats_host)
-    int32_t min_identity = 0;      // --min-identity PCT, in per mille, and --min-overlap BASES: only the records that pass go into the job
-    int32_t min_overlap = 0;       // (raft_hip_filter_overlaps_host, before anything else sees the stream); 0: not asked for
-    int32_t overlap_ends = -1;     // --overlap-ends H: PREFIX.overlap_ends.tsv, the kind of every record and the ends of every read (raft_hip_overlap_ends_host); -1: not asked for
-    int32_t ends_min_ratio = raft_cli::kEndsMinRatioDefault;   // --ends-min-ratio F, in per mille
-    bool ends_ratio_given = false;
-    bool best_overlaps = false;    // --best-overlaps: PREFIX.best_overlaps.tsv, the best overlap of every read end under --overlap-ends' H and F (raft_hip_best_overlaps_host)
-    bool unitigs = false;          // --unitigs: PREFIX.unitigs.tsv and .unitigs.layout.tsv, the chains and cycles of --best-overlaps' mutual ends (raft_hip_unitigs_host)
-    int32_t min_anchor = 0;        // --repeat-overlaps A: PREFIX.repeat_overlaps.tsv and .records.tsv (raft_hip_repeat_overlaps_host); 0: not asked for
-    bool fragment_paf = false;     // --fragment-paf: PREFIX.fragments.paf, the job's overlaps lifted onto its fragments (raft_hip_lift_overlaps_host)
-    int32_t fragment_paf_min = raft_cli::kFragmentPafMinDefault;   // --fragment-paf-min L: pairs shorter than L on either side are dropped
-    bool fragment_paf_min_given = false;
-};
+using raft_cli::Options;            // the command line as parsed (cli_plan.hpp)
 
 struct Switches {                  // the environment, as read_switches() found it
     bool timing = false, no_warm_up = false, no_pin = false, no_delta4 = false, cli_prepare = false, no_grouped = false, no_windows = false;
@@ -82,12 +61,30 @@ struct Switches {                  // the environment, as read_switches() found 
     int chunks = 0;                // 0: the engine decides (one piece for small inputs)
 };
 
+// What each optional output owns: one struct per row of kExtras (below), one member of the Job each.
+// --min-identity / --min-overlap: what the filter counted, and the side columns of the kept records (strand; PAF fields 10 and 11)
+struct FilterOut { raft_hip_flt_summary sum{}; std::vector<uint8_t> strand; std::vector<int32_t> matches, block; };
+// --read-stats: the survey's coverage summary and the census of the record stream
+struct ReadStatsOut { std::vector<int64_t> sum; std::vector<int32_t> max, high, intervals; std::vector<uint8_t> contained; int64_t n_contained = 0; };
+struct LowCovOut { std::vector<int64_t> off; std::vector<int32_t> s, e; raft_hip_low_summary sum{}; };   // --low-cov: the survey's low-coverage runs
+struct RepeatOverlapsOut { std::vector<uint8_t> cls, flags; std::vector<int32_t> touch, repeat; raft_hip_ovl_summary sum{}; };   // --repeat-overlaps: per record, per read
+struct FragmentOverlapsOut { std::vector<int32_t> touch, span, contained, repeat; raft_hip_frag_summary sum{}; };   // --fragment-overlaps: per fragment
+// --repeat-stats: per repeat run of the stats pass the sides that touch, span and lie inside it, its coverage, its flags
+struct RepeatStatsOut { std::vector<int32_t> touch, span, inside, windows, min, max, high; std::vector<int64_t> cov_sum; std::vector<uint8_t> flags; raft_hip_rst_summary sum{}; bool done = false; };
+struct EndsOut { std::vector<int32_t> counts; std::vector<uint8_t> status; raft_hip_end_summary sum{}; };   // --overlap-ends: the reads' counts and status
+struct BestOut { std::vector<int32_t> partner, span; std::vector<uint8_t> flags; raft_hip_best_summary sum{}; };   // --best-overlaps: per read end, per read
+// --unitigs: per read the unitig, the place in it, the offset and the orientation; the layout order; per unitig size, length, circular
+struct UnitigOut { std::vector<int32_t> unitig, index, order, reads; std::vector<int64_t> offset, off, length; std::vector<uint8_t> orient, circular; raft_hip_utg_summary sum{}; };
+struct LiftOut { std::vector<int32_t> col[6], src; std::vector<uint8_t> rev; raft_hip_lift_summary sum{}; };   // --fragment-paf: the eight columns of the lifted stream
+
 struct Job {
-    Params p;
+    Options p;
+    raft_cli::Request rq{};        // what the options ask for between them (read_switches)
     const char *reads_fn = nullptr, *paf_fn = nullptr;
     std::string fasta_out;
     raft_hip_params hp{};
     Switches sw;
+    bool prepare = false;          // group offsets and window records are made here (RAFT_CLI_PREPARE on a job without ranks)
     std::chrono::system_clock::time_point t_start;              // the reference's timer
     std::chrono::steady_clock::time_point t_main, t_prev;       // the stage clock
     // the devices: context d is on devices[d]; ranks > 0: the pre-split job
@@ -97,37 +94,22 @@ struct Job {
     std::vector<int> create_rc;
     std::promise<void> devices_up_p;
     std::shared_future<void> devices_up;
-    // the inputs
+    // the inputs; behind the filter n_rec, col, the symmetric flag and the side columns are the kept stream's
     raft_host_text *paf_text = nullptr;
     int paf_text_rc = RAFT_HOST_OK;
     raft_host_reads *reads = nullptr;
     int32_t n_reads = 0;
     const int32_t *rl = nullptr;
+    std::vector<const char *> names;                            // the reads' names, for the writers that take them (names())
     raft_host_paf *paf = nullptr;
     int64_t n_rec = 0;
     const int32_t *col[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};    // qid, qs, qe, tid, ts, te
-    // --min-identity / --min-overlap: what the filter counted; from then on n_rec, col and the symmetric flag are the kept stream's
-    raft_hip_flt_summary flt_sum{};
-    bool filtered = false;
-    // --overlap-ends: the strand byte of every record (the tokeniser's, or strand_kept for the kept stream), the reads' counts and status
-    const uint8_t *strand = nullptr;
-    std::vector<uint8_t> strand_kept, end_status;
-    std::vector<int32_t> end_counts;
-    raft_hip_end_summary end_sum{};
-    // --best-overlaps: per read end the partner and the span, per read the flag byte
-    std::vector<int32_t> best_partner, best_span;
-    std::vector<uint8_t> best_flags;
-    raft_hip_best_summary best_sum{};
-    // --unitigs: per read the unitig, the place in it, the offset and the orientation; the layout order; per unitig size, length, circular
-    std::vector<int32_t> utg_unitig, utg_index, utg_order, utg_reads;
-    std::vector<int64_t> utg_offset, utg_off, utg_length;
-    std::vector<uint8_t> utg_orient, utg_circular;
-    raft_hip_utg_summary utg_sum{};
-    // --fragment-paf: the eight columns of the lifted stream; PAF fields 10 and 11 of the kept records where the filter tokenised them
-    std::vector<int32_t> lift_col[6], lift_src, matches_kept, block_kept;
-    std::vector<uint8_t> lift_rev;
-    const int32_t *lift_matches = nullptr, *lift_block = nullptr;
-    raft_hip_lift_summary lift_sum{};
+    const uint8_t *strand = nullptr;                            // the strand byte of every record, where Request::strand asked for it
+    const int32_t *matches = nullptr, *block = nullptr;         // PAF fields 10 and 11 of the kept records (Request::quality_kept)
+    std::vector<int32_t> qid_kept;                              // the query column as tokenised, where prepare_input writes over it (Request::keep_query_ids)
+    // the optional outputs, in the order of kExtras
+    FilterOut flt; ReadStatsOut rs; LowCovOut low; RepeatOverlapsOut ovl; FragmentOverlapsOut frag;
+    RepeatStatsOut rst; EndsOut ends; BestOut best; UnitigOut utg; LiftOut lift;
     // the arrays everything comes back in (made and page-locked on out_prep)
     raft_cli::Capacities cap;
     std::vector<int64_t> cov_off, rep_off, frag_off;
@@ -137,28 +119,6 @@ struct Job {
     std::vector<int64_t> exc_i;
     std::vector<int32_t> exc_v;
     std::vector<int32_t> cov_anchor;          // the four-bit step encoding's block anchors (cov_width = RAFT_HIP_COV_DELTA4)
-    // --read-stats: the survey's coverage summary and the census of the record stream
-    std::vector<int64_t> rs_sum;
-    std::vector<int32_t> rs_max, rs_high, cen_intervals;
-    std::vector<uint8_t> cen_contained;
-    int64_t n_contained = 0;
-    // --low-cov: the survey's low-coverage runs
-    std::vector<int64_t> low_off;
-    std::vector<int32_t> low_s, low_e;
-    raft_hip_low_summary low_sum{};
-    // --repeat-overlaps: the records' class bytes, the reads' tallies and flags; the query column as tokenised where prepare_input writes over it
-    std::vector<uint8_t> ovl_cls, ovl_flags;
-    std::vector<int32_t> ovl_touch, ovl_repeat, ovl_qid;
-    raft_hip_ovl_summary ovl_sum{};
-    // --fragment-overlaps: per fragment the sides that touch, span and contain it, its bases inside repeats
-    std::vector<int32_t> frag_touch, frag_span, frag_contained, frag_repeat;
-    raft_hip_frag_summary frag_sum{};
-    // --repeat-stats: per repeat run of the stats pass the sides that touch, span and lie inside it, its coverage, its flags
-    std::vector<int32_t> rst_touch, rst_span, rst_inside, rst_windows, rst_min, rst_max, rst_high;
-    std::vector<int64_t> rst_cov_sum;
-    std::vector<uint8_t> rst_flags;
-    raft_hip_rst_summary rst_sum{};
-    bool rst_done = false;
     // the form the job is handed over in, and what it brought back
     std::unique_ptr<int64_t[]> rec_off;
     int32_t n_runs = 0;
@@ -174,7 +134,7 @@ struct Job {
 
 Job *g_job = nullptr;      // for die()
 
-[[noreturn]] void print_help(const Params &p) // main.cpp:7-19
+[[noreturn]] void print_help(const Options &p) // main.cpp:7-19
 {
     std::cout << "Usage: raft [options] <input-reads.fa> <in.paf>\n";
     std::cout << "  -r NUM     resolution of coverage " << p.reso << "\n";
@@ -231,34 +191,41 @@ void pin(const Job &j, const void *ptr, size_t bytes)
     if (!j.sw.no_pin && ptr && bytes >= (size_t)(64u << 10)) (void)raft_hip_host_register(const_cast<void *>(ptr), bytes);
 }
 
+// How a phase on the device ends: an error is the engine's, in its words; else the stage clock moves on.
+void done(Job &j, int rc, int64_t bad_index, const char *label)
+{
+    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
+    stage(j, label);
+}
+
+// The stream's columns as a call takes them: all six; without the target's coordinates for a call that counts sides under the
+// symmetric flag; without the target columns for a pass over a symmetric stream.
+enum class Targets { all, ids, none };
+
+raft_hip_records records(const Job &j, Targets t = Targets::all)
+{
+    return {j.n_rec, j.col[0], j.col[1], j.col[2], t == Targets::none ? nullptr : j.col[3], t == Targets::all ? j.col[4] : nullptr, t == Targets::all ? j.col[5] : nullptr};
+}
+
+// the reads' names for the writers that take them as an array: made at the first call
+const char *const *names(Job &j)
+{
+    for (int32_t i = (int32_t)j.names.size(); i < j.n_reads; ++i) j.names.push_back(raft_host_reads_name(j.reads, i));
+    return j.names.data();
+}
+
 void parse_options(Job &j, int argc, char *argv[])
 {
-    Params &p = j.p;
-    int option;
-    // (the short options and their quirks are the reference's; the long options are this program's own)
-    static const struct option long_options[] = {{"read-stats", no_argument, nullptr, 1000}, {"low-cov", required_argument, nullptr, 1001},
-                                                 {"repeat-overlaps", required_argument, nullptr, 1002}, {"fragment-overlaps", no_argument, nullptr, 1003},
-                                                 {"repeat-stats", no_argument, nullptr, 1004}, {"min-identity", required_argument, nullptr, 1005},
-                                                 {"min-overlap", required_argument, nullptr, 1006},
-                                                 {"overlap-ends", required_argument, nullptr, 1007}, {"ends-min-ratio", required_argument, nullptr, 1008},
-                                                 {"best-overlaps", no_argument, nullptr, 1009}, {"unitigs", no_argument, nullptr, 1010},
-                                                 {"fragment-paf", no_argument, nullptr, 1011}, {"fragment-paf-min", required_argument, nullptr, 1012},
-                                                 {nullptr, 0, nullptr, 0}};
-    while ((option = getopt_long(argc, argv, "r:e:m:l:i:p:f:v:o:", long_options, nullptr)) != -1) {
+    Options &p = j.p;
+    // (the short options and their quirks are the reference's; the long options are this program's own, the rows of cli_plan.hpp
+    // kLongOptions: getopt_long returns 0 for them and says which row)
+    constexpr size_t n_long = std::size(raft_cli::kLongOptions);
+    struct option long_options[n_long + 1] = {};
+    for (size_t k = 0; k < n_long; ++k) long_options[k] = {raft_cli::kLongOptions[k].name, raft_cli::kLongOptions[k].parse ? required_argument : no_argument, nullptr, 0};
+    int option, row = 0;
+    while ((option = getopt_long(argc, argv, "r:e:m:l:i:p:f:v:o:", long_options, &row)) != -1) {
         switch (option) {
-        case 1000: p.read_stats = true; break;
-        case 1001: if (!raft_cli::parse_low_cov(optarg, &p.low_cov)) print_help(p); break;
-        case 1002: if (!raft_cli::parse_min_anchor(optarg, &p.min_anchor)) print_help(p); break;
-        case 1003: p.fragment_overlaps = true; break;
-        case 1004: p.repeat_stats = true; break;
-        case 1005: if (!raft_cli::parse_min_identity(optarg, &p.min_identity)) print_help(p); break;
-        case 1006: if (!raft_cli::parse_min_overlap(optarg, &p.min_overlap)) print_help(p); break;
-        case 1007: if (!raft_cli::parse_overlap_ends(optarg, &p.overlap_ends)) print_help(p); break;
-        case 1008: if (!raft_cli::parse_ends_min_ratio(optarg, &p.ends_min_ratio)) print_help(p); p.ends_ratio_given = true; break;
-        case 1009: p.best_overlaps = true; break;
-        case 1010: p.unitigs = true; break;
-        case 1011: p.fragment_paf = true; break;
-        case 1012: if (!raft_cli::parse_fragment_paf_min(optarg, &p.fragment_paf_min)) print_help(p); p.fragment_paf_min_given = true; break;
+        case 0: if (!raft_cli::set_long_option(raft_cli::kLongOptions[row], optarg, &p)) print_help(p); break;
         case 'r': p.reso = atoi(optarg); break;
         case 'e': p.auto_cov = strcmp(optarg, "auto") == 0; p.est_cov = p.auto_cov ? 0 : atoi(optarg); break;
         case 'm': p.cov_mul = std::stod(optarg); break;
@@ -271,10 +238,7 @@ void parse_options(Job &j, int argc, char *argv[])
         default: print_help(p);
         }
     }
-    if (!raft_cli::ends_options_ok(p.overlap_ends, p.ends_ratio_given)) print_help(p);
-    if (!raft_cli::best_options_ok(p.best_overlaps, p.overlap_ends)) print_help(p);
-    if (!raft_cli::unitigs_options_ok(p.unitigs, p.best_overlaps)) print_help(p);
-    if (!raft_cli::fragment_paf_options_ok(p.fragment_paf, p.fragment_paf_min_given)) print_help(p);
+    if (!raft_cli::usage_ok(p)) print_help(p);
     if (argc < optind + 2) print_help(p);
     if (p.est_cov <= 0 && !p.auto_cov) {
         std::cout << "ERROR, main(), estimated coverage must be set properly\n";
@@ -287,7 +251,7 @@ void parse_options(Job &j, int argc, char *argv[])
 
 void print_params(Job &j) // param.hpp:33-43, and main.cpp's timer
 {
-    const Params &p = j.p;
+    const Options &p = j.p;
     std::cout << "INFO, printParams(), reso = " << p.reso << "\n";
     if (p.auto_cov) std::cout << "INFO, printParams(), est_cov = auto\n";
     else std::cout << "INFO, printParams(), est_cov = " << p.est_cov << "\n";
@@ -312,7 +276,7 @@ void check_inputs(Job &j)
 // what the contexts are created under; symmetric_mode follows once the overlaps are tokenised (hand_over_symmetric_flag)
 void fill_engine_params(Job &j)
 {
-    const Params &p = j.p;
+    const Options &p = j.p;
     raft_hip_params &hp = j.hp;
     hp.reso = p.reso; hp.est_cov = p.auto_cov ? 1 : p.est_cov;   // (-e auto: a placeholder until the survey -- create rejects 0)
     hp.cov_mul = p.cov_mul; hp.repeat_length = p.repeat_length;
@@ -338,6 +302,9 @@ void read_switches(Job &j)
     sw.no_windows = getenv("RAFT_NO_WINDOWS") != nullptr;      // ... but no window records: the coordinate columns go up
     const char *chunks = getenv("RAFT_CHUNKS");                // pieces of the chunked pipeline; 0 / unset: the engine decides
     sw.chunks = chunks ? atoi(chunks) : 0;
+    // ... and what the options ask for between them, under these switches: decided here, read everywhere else
+    j.prepare = sw.cli_prepare && j.ranks == 0;
+    j.rq = raft_cli::request(j.p, j.prepare);
 }
 
 // What the stage clock cannot see from inside (1.4 s of a 4.8 s run appeared in no stage): how old the process was
@@ -413,7 +380,7 @@ void load_reads(Job &j)
 // page-locked for the byte width of the first attempt; an attempt of the ladder that needs more registers it anew (run_engine).
 void prepare_outputs(Job &j)
 {
-    const Params &p = j.p;
+    const Options &p = j.p;
     j.cap = raft_cli::output_capacities(j.n_reads, j.rl, p.reso, p.repeat_length, p.interval_length);
     const raft_cli::Capacities &c = j.cap;
     j.cov8.reset(new uint8_t[(size_t)c.cov8_bytes]);                              // (not value-initialised: no zero fill)
@@ -454,8 +421,7 @@ void parse_paf(Job &j)
     stage(j, "paf_read (rest)");
     int rc = j.paf_text_rc;
     // (the filter reads PAF columns 10 and 11, --overlap-ends and --fragment-paf the strand; none of them: the plain parser)
-    const int columns = raft_cli::paf_columns_with_lift(raft_cli::filter_wanted(j.p.min_identity, j.p.min_overlap), j.p.overlap_ends, j.p.fragment_paf);
-    if (rc == RAFT_HOST_OK) rc = raft_host_paf_parse_with(j.paf_text, j.reads, columns, &j.paf, bad, sizeof bad);
+    if (rc == RAFT_HOST_OK) rc = raft_host_paf_parse_with(j.paf_text, j.reads, j.rq.paf_columns, &j.paf, bad, sizeof bad);
     // (a big file's GBs of touched pages are left to the process exit: unmapping them here -- or beside the pass, where it holds
     // the address space's lock against the page-locking -- cost 0.3 s of a 4 s run)
     if (raft_host_paf_count(j.paf) < (1 << 22)) { raft_host_text_free(j.paf_text); j.paf_text = nullptr; }
@@ -476,61 +442,55 @@ void await_devices(Job &j)
     stage(j, "device_wait");
 }
 
-// --overlap-ends beside the filter: the strand must follow the kept records.  The filter copies its id columns without using them as
-// indices (include/raft_hip_flt.h), so one more call of its host form under the same P and L, with the strand bytes widened to int32
-// in the query-id slot, compacts them; what it writes for the other five columns is dropped.
-void keep_strand(Job &j)
+// Side columns that must follow the kept records ride through the filter in its id slots: the filter copies its id columns without
+// using them as indices (include/raft_hip_flt.h), so one more call of its host form under the same P and L compacts `q` in the
+// query-id slot and, where there is one, `t` in the target-id slot; what it writes for the other columns is dropped.
+void keep_side_columns(Job &j, std::vector<int32_t> &q, std::vector<int32_t> *t)
 {
-    std::vector<int32_t> wide(j.strand, j.strand + j.n_rec), drop[5];
-    for (auto &d : drop) d.resize((size_t)j.n_rec);
+    std::vector<int32_t> drop[5];
+    for (int k = 0; k < (t ? 4 : 5); ++k) drop[k].resize((size_t)j.n_rec);
     raft_hip_flt_summary sum{};
-    const int rc = raft_hip_filter_overlaps_host(j.ctxs[0], j.n_rec, wide.data(), j.col[1], j.col[2], j.col[3], j.col[4], j.col[5],
+    const int rc = raft_hip_filter_overlaps_host(j.ctxs[0], j.n_rec, q.data(), j.col[1], j.col[2], t ? t->data() : j.col[3], j.col[4], j.col[5],
                                                  raft_host_paf_quality(j.paf, 0), raft_host_paf_quality(j.paf, 1), j.p.min_identity, j.p.min_overlap,
-                                                 wide.data(), drop[0].data(), drop[1].data(), drop[2].data(), drop[3].data(), drop[4].data(), &sum, nullptr);
+                                                 q.data(), drop[0].data(), drop[1].data(), t ? t->data() : drop[4].data(), drop[2].data(), drop[3].data(),
+                                                 &sum, nullptr);
     if (rc != RAFT_HIP_OK) die(engine_error(j, rc, -1));
-    j.strand_kept.assign(wide.begin(), wide.begin() + sum.n_kept);
-    j.strand = j.strand_kept.data();
-}
-
-// --fragment-paf beside the filter: PAF fields 10 and 11 of the kept records, for the writer, by the same means -- matches in the
-// query-id slot, block in the target-id slot.
-void keep_quality(Job &j)
-{
-    const int32_t *m = raft_host_paf_quality(j.paf, 0), *b = raft_host_paf_quality(j.paf, 1);
-    j.matches_kept.assign(m, m + j.n_rec); j.block_kept.assign(b, b + j.n_rec);
-    std::vector<int32_t> drop[4];
-    for (auto &d : drop) d.resize((size_t)j.n_rec);
-    raft_hip_flt_summary sum{};
-    const int rc = raft_hip_filter_overlaps_host(j.ctxs[0], j.n_rec, j.matches_kept.data(), j.col[1], j.col[2], j.block_kept.data(), j.col[4], j.col[5], m, b,
-                                                 j.p.min_identity, j.p.min_overlap, j.matches_kept.data(), drop[0].data(), drop[1].data(),
-                                                 j.block_kept.data(), drop[2].data(), drop[3].data(), &sum, nullptr);
-    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, -1));
-    j.matches_kept.resize((size_t)sum.n_kept); j.block_kept.resize((size_t)sum.n_kept);
-    j.lift_matches = j.matches_kept.data(); j.lift_block = j.block_kept.data();
+    q.resize((size_t)sum.n_kept);
+    if (t) t->resize((size_t)sum.n_kept);
 }
 
 // --min-identity / --min-overlap: the records that pass (include/raft_hip_flt.h) are compacted in place, on the first context, before
 // anything else sees the stream -- the survey, the census, the split of a multi-device or pre-split job, every query: the job is the
-// job on a file of the kept lines.  Without the options nothing happens here.
+// job on a file of the kept lines.  Without the options nothing happens here.  The strand (--overlap-ends, --fragment-paf) and PAF
+// fields 10 and 11 (--fragment-paf, for the writer) follow the kept records.
 void filter_overlaps(Job &j)
 {
-    if (!raft_cli::filter_wanted(j.p.min_identity, j.p.min_overlap)) return;
+    if (!j.rq.filter) return;
     j.out_prep.join();                                  // (its raft_hip_reserve uses the context this call runs on)
+    FilterOut &f = j.flt;
+    if (j.rq.strand) {                                  // (first: the side columns go through beside the columns as tokenised)
+        std::vector<int32_t> wide(j.strand, j.strand + j.n_rec);           // the strand bytes widened to int32
+        keep_side_columns(j, wide, nullptr);
+        f.strand.assign(wide.begin(), wide.end());
+        j.strand = f.strand.data();
+    }
+    if (j.rq.quality_kept) {
+        const int32_t *m = raft_host_paf_quality(j.paf, 0), *b = raft_host_paf_quality(j.paf, 1);
+        f.matches.assign(m, m + j.n_rec); f.block.assign(b, b + j.n_rec);
+        keep_side_columns(j, f.matches, &f.block);
+        j.matches = f.matches.data(); j.block = f.block.data();
+    }
     int32_t *out[6];
     for (int k = 0; k < 6; ++k) out[k] = const_cast<int32_t *>(j.col[k]);
-    if (raft_cli::strand_wanted(j.p.overlap_ends, j.p.fragment_paf)) keep_strand(j);   // (first: it reads the columns as tokenised)
-    if (j.p.fragment_paf) keep_quality(j);
     const int rc = raft_hip_filter_overlaps_host(j.ctxs[0], j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.col[4], j.col[5],
                                                  raft_host_paf_quality(j.paf, 0), raft_host_paf_quality(j.paf, 1), j.p.min_identity, j.p.min_overlap,
-                                                 out[0], out[1], out[2], out[3], out[4], out[5], &j.flt_sum, nullptr);
-    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, -1));
-    j.n_rec = j.flt_sum.n_kept;
-    j.filtered = true;
-    stage(j, "filter_overlaps");
+                                                 out[0], out[1], out[2], out[3], out[4], out[5], &f.sum, nullptr);
+    if (rc == RAFT_HIP_OK) j.n_rec = f.sum.n_kept;
+    done(j, rc, -1, "filter_overlaps");
 }
 
 // the symmetric flag of the stream the job runs on: the tokeniser's, or the filter's for the kept stream
-bool stream_symmetric(const Job &j) { return j.filtered ? j.flt_sum.symmetric != 0 : raft_host_paf_symmetric(j.paf) != 0; }
+bool stream_symmetric(const Job &j) { return j.rq.filter ? j.flt.sum.symmetric != 0 : raft_host_paf_symmetric(j.paf) != 0; }
 
 // The tokeniser already knows whether the PAF is symmetric (chop.hpp:171-184, found while the lines were in
 // registers): the engine is told, so it neither scans for the mirror of record 0 nor -- for a symmetric PAF -- is
@@ -568,11 +528,12 @@ struct SurveySettings {
 // --read-stats: the coverage summary of the pass that has just run, under threshold = (int)(est_cov * cov_mul)
 int survey_read_stats(Job &j, int est_cov)
 {
-    j.rs_sum.resize((size_t)j.n_reads); j.rs_max.resize((size_t)j.n_reads); j.rs_high.resize((size_t)j.n_reads);
+    ReadStatsOut &o = j.rs;
+    o.sum.resize((size_t)j.n_reads); o.max.resize((size_t)j.n_reads); o.high.resize((size_t)j.n_reads);
     const int32_t high_cov = (int32_t)(est_cov * j.p.cov_mul);          // (the job's: repeat.hpp:89-90)
-    const int rc = raft_hip_read_stats(j.ctxs[0], std::max(high_cov, 1), j.rs_sum.data(), j.rs_max.data(), j.rs_high.data(), nullptr);
+    const int rc = raft_hip_read_stats(j.ctxs[0], std::max(high_cov, 1), o.sum.data(), o.max.data(), o.high.data(), nullptr);
     if (high_cov < 1)                                                    // (every window is at or above a threshold below 1)
-        for (int32_t i = 0; i < j.n_reads; ++i) j.rs_high[(size_t)i] = (int32_t)(((int64_t)j.rl[i] + j.p.reso - 1) / j.p.reso);
+        for (int32_t i = 0; i < j.n_reads; ++i) o.high[(size_t)i] = (int32_t)(((int64_t)j.rl[i] + j.p.reso - 1) / j.p.reso);
     return rc;
 }
 
@@ -580,15 +541,16 @@ int survey_read_stats(Job &j, int est_cov)
 // runs says so (RAFT_HIP_ERR_TOO_LARGE and the number) and is asked once more.
 int survey_low_coverage(Job &j, int64_t n_win)
 {
-    j.low_off.resize((size_t)j.n_reads + 1);
+    LowCovOut &o = j.low;
+    o.off.resize((size_t)j.n_reads + 1);
     int64_t cap = raft_cli::low_run_capacity0(n_win, j.n_reads);
     int rc = RAFT_HIP_OK;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        j.low_s.resize((size_t)cap); j.low_e.resize((size_t)cap);
-        rc = raft_hip_low_coverage(j.ctxs[0], j.p.low_cov, raft_cli::kLowUncoveredPermille, cap, j.low_off.data(), j.low_s.data(), j.low_e.data(), nullptr,
-                                   nullptr, &j.low_sum, nullptr);
+        o.s.resize((size_t)cap); o.e.resize((size_t)cap);
+        rc = raft_hip_low_coverage(j.ctxs[0], j.p.low_cov, raft_cli::kLowUncoveredPermille, cap, o.off.data(), o.s.data(), o.e.data(), nullptr, nullptr,
+                                   &o.sum, nullptr);
         if (rc != RAFT_HIP_ERR_TOO_LARGE) break;
-        cap = j.low_sum.n_runs;
+        cap = o.sum.n_runs;
     }
     return rc;
 }
@@ -597,14 +559,24 @@ int survey_low_coverage(Job &j, int64_t n_win)
 // under the job's symmetric flag as census() hands them over --, before prepare_input() writes window records over the query column.
 int survey_repeat_stats(Job &j, int est_cov, int64_t n_repeats, int64_t *bad_index)
 {
-    for (std::vector<int32_t> *v : {&j.rst_touch, &j.rst_span, &j.rst_inside, &j.rst_windows, &j.rst_min, &j.rst_max, &j.rst_high}) v->resize((size_t)n_repeats);
-    j.rst_cov_sum.resize((size_t)n_repeats); j.rst_flags.resize((size_t)n_repeats);
-    const raft_hip_records rec{j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.sym ? nullptr : j.col[4], j.sym ? nullptr : j.col[5]};
-    j.rst_done = true;
+    RepeatStatsOut &o = j.rst;
+    for (std::vector<int32_t> *v : {&o.touch, &o.span, &o.inside, &o.windows, &o.min, &o.max, &o.high}) v->resize((size_t)n_repeats);
+    o.cov_sum.resize((size_t)n_repeats); o.flags.resize((size_t)n_repeats);
+    const raft_hip_records rec = records(j, j.sym ? Targets::ids : Targets::all);
+    o.done = true;
     return raft_hip_repeat_stats_host(j.ctxs[0], j.n_reads, j.rl, &rec, j.sym ? 1 : 0, -1, nullptr, nullptr, nullptr,
-                                      raft_cli::repeat_stats_threshold(est_cov, j.p.cov_mul), j.rst_touch.data(), j.rst_span.data(), j.rst_inside.data(),
-                                      j.rst_windows.data(), j.rst_min.data(), j.rst_max.data(), j.rst_high.data(), j.rst_cov_sum.data(), j.rst_flags.data(),
-                                      &j.rst_sum, bad_index, nullptr);
+                                      raft_cli::repeat_stats_threshold(est_cov, j.p.cov_mul), o.touch.data(), o.span.data(), o.inside.data(),
+                                      o.windows.data(), o.min.data(), o.max.data(), o.high.data(), o.cov_sum.data(), o.flags.data(), &o.sum, bad_index,
+                                      nullptr);
+}
+
+// one one-piece pass of the survey on the first context (rc: of the settings it runs under), the columns as its symmetric flag has them
+void survey_pass(Job &j, int rc, raft_hip_summary *ss)
+{
+    const raft_hip_records r = records(j, j.hp.symmetric_mode != 1 ? Targets::all : Targets::none);
+    if (rc == RAFT_HIP_OK) rc = raft_hip_run_host(j.ctxs[0], j.n_reads, j.rl, r.n_rec, r.d_qid, r.d_qs, r.d_qe, r.d_tid, r.d_ts, r.d_te);
+    if (rc == RAFT_HIP_OK) rc = raft_hip_finish(j.ctxs[0], ss);
+    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, ss->error_index));
 }
 
 // -e auto: the survey.  cov[] does not depend on est_cov, so one one-piece pass on the first context under the placeholder holds
@@ -613,30 +585,23 @@ int survey_repeat_stats(Job &j, int est_cov, int64_t n_repeats, int64_t *bad_ind
 // overlap_length is 0: which fragments there are depends on the repeats, hence on the placeholder, and RAFT_HIP_ERR_FRAGMENT of
 // the survey would not be the job's.  Every other data error (ids, coordinates, lengths) is the one the job would report, in
 // its words.  With several devices or ranks the survey still runs in one piece on the first: one more upload of the columns.
-//
 // --read-stats: the per-read table.  Its coverage summary (raft_hip_read_stats) is taken from the same survey pass, right behind
 // the histogram; without -e auto one such pass -- the survey's recipe -- runs here for it.  The job itself runs as it does
 // without the option.  --low-cov: the same, for the low-coverage runs (raft_hip_low_coverage), behind the two.
 // --repeat-stats: the table of the repeat runs (raft_hip_repeat_stats_host) needs coverage AND annotation under the job's final est_cov:
-// with -e N the survey pass is that pass; with -e auto one more pass of the same recipe runs under the estimate (one more upload of
-// the columns), and the table is taken right behind it.
+// with -e auto one more pass of the same recipe runs under the estimate (one more upload of the columns), the table right behind it.
 void survey(Job &j)
 {
-    Params &p = j.p;
-    if (!raft_cli::survey_needed(p.auto_cov, p.read_stats, p.low_cov, p.repeat_stats)) return;
+    Options &p = j.p;
+    if (!j.rq.survey) return;
     raft_hip_ctx *ctx = j.ctxs[0];
     SurveySettings settings{ctx, j.sw.context_width};
     raft_hip_params sp = j.hp;
     sp.overlap_length = 0;
-    const bool targets = j.hp.symmetric_mode != 1;
     raft_hip_summary ss{};
     ss.error_index = -1;
-    int rc = settings.apply(sp);
-    if (rc == RAFT_HIP_OK)
-        rc = raft_hip_run_host(ctx, j.n_reads, j.rl, j.n_rec, j.col[0], j.col[1], j.col[2], targets ? j.col[3] : nullptr, targets ? j.col[4] : nullptr,
-                               targets ? j.col[5] : nullptr);
-    if (rc == RAFT_HIP_OK) rc = raft_hip_finish(ctx, &ss);
-    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, ss.error_index));
+    survey_pass(j, settings.apply(sp), &ss);
+    int rc = RAFT_HIP_OK;
     raft_hip_cov_estimate est{};
     est.est_cov = p.est_cov;
     if (p.auto_cov) {
@@ -647,22 +612,16 @@ void survey(Job &j)
     if (rc == RAFT_HIP_OK && p.read_stats && est.est_cov > 0) rc = survey_read_stats(j, est.est_cov);
     if (rc == RAFT_HIP_OK && p.low_cov >= 0) rc = survey_low_coverage(j, ss.n_bins);
     if (rc == RAFT_HIP_OK && p.repeat_stats && est.est_cov > 0) {
-        if (raft_cli::repeat_stats_second_pass(p.auto_cov, p.repeat_stats)) {
+        if (j.rq.repeat_stats_second_pass) {
             sp.est_cov = est.est_cov;
-            rc = raft_hip_set_params(ctx, &sp);
-            if (rc == RAFT_HIP_OK)
-                rc = raft_hip_run_host(ctx, j.n_reads, j.rl, j.n_rec, j.col[0], j.col[1], j.col[2], targets ? j.col[3] : nullptr, targets ? j.col[4] : nullptr,
-                                       targets ? j.col[5] : nullptr);
-            if (rc == RAFT_HIP_OK) rc = raft_hip_finish(ctx, &ss);
-            if (rc != RAFT_HIP_OK) die(engine_error(j, rc, ss.error_index));
+            survey_pass(j, raft_hip_set_params(ctx, &sp), &ss);
         }
         int64_t bad_index = -1;
         rc = survey_repeat_stats(j, est.est_cov, ss.n_repeats, &bad_index);
         if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
     }
     if (rc == RAFT_HIP_OK) rc = settings.restore_outputs();
-    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, -1));
-    stage(j, "estimate");
+    done(j, rc, -1, "estimate");
     if (p.auto_cov) {
         if (est.est_cov <= 0) {                              // no window anybody overlaps: as for -e 0
             std::cout << "ERROR, main(), estimated coverage must be set properly\n";
@@ -680,13 +639,13 @@ void survey(Job &j)
 // flag, before prepare_input() writes window records over the query column.
 void census(Job &j)
 {
-    if (!j.p.read_stats) return;
-    j.cen_intervals.resize((size_t)j.n_reads); j.cen_contained.resize((size_t)j.n_reads);
+    ReadStatsOut &o = j.rs;
+    o.intervals.resize((size_t)j.n_reads); o.contained.resize((size_t)j.n_reads);
+    const raft_hip_records r = records(j, j.sym ? Targets::ids : Targets::all);
     int64_t bad_index = -1;
-    const int rc = raft_hip_census_host(j.ctxs[0], j.n_reads, j.rl, j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.sym ? nullptr : j.col[4],
-                                        j.sym ? nullptr : j.col[5], j.sym ? 1 : 0, j.cen_intervals.data(), j.cen_contained.data(), &j.n_contained, &bad_index, nullptr);
-    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
-    stage(j, "census");
+    const int rc = raft_hip_census_host(j.ctxs[0], j.n_reads, j.rl, r.n_rec, r.d_qid, r.d_qs, r.d_qe, r.d_tid, r.d_ts, r.d_te, j.sym ? 1 : 0,
+                                        o.intervals.data(), o.contained.data(), &o.n_contained, &bad_index, nullptr);
+    done(j, rc, bad_index, "census");
 }
 
 // --overlap-ends: the kind of every record and the ends of every read it supports (raft_hip_overlap_ends_host), on the first context
@@ -694,14 +653,14 @@ void census(Job &j)
 // symmetric flag, before prepare_input() writes window records over the query column.
 void overlap_ends(Job &j)
 {
-    if (j.p.overlap_ends < 0) return;
-    j.end_counts.resize((size_t)j.n_reads * 5); j.end_status.resize((size_t)j.n_reads);
+    EndsOut &o = j.ends;
+    o.counts.resize((size_t)j.n_reads * 5); o.status.resize((size_t)j.n_reads);
+    const raft_hip_records r = records(j);
     int64_t bad_index = -1;
-    const int rc = raft_hip_overlap_ends_host(j.ctxs[0], j.n_reads, j.rl, j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.col[4], j.col[5], j.strand,
-                                              j.p.overlap_ends, j.p.ends_min_ratio, j.sym ? 1 : 0, j.end_counts.data(), j.end_status.data(), nullptr,
-                                              &j.end_sum, &bad_index, nullptr);
-    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
-    stage(j, "overlap_ends");
+    const int rc = raft_hip_overlap_ends_host(j.ctxs[0], j.n_reads, j.rl, r.n_rec, r.d_qid, r.d_qs, r.d_qe, r.d_tid, r.d_ts, r.d_te, j.strand,
+                                              j.p.overlap_ends, j.p.ends_min_ratio, j.sym ? 1 : 0, o.counts.data(), o.status.data(), nullptr, &o.sum,
+                                              &bad_index, nullptr);
+    done(j, rc, bad_index, "overlap_ends");
 }
 
 // --best-overlaps: the best overlap of every read end and whether it is mutual (raft_hip_best_overlaps_host), directly behind
@@ -709,34 +668,32 @@ void overlap_ends(Job &j)
 // found contained left out (their status byte is the mask).
 void best_overlaps(Job &j)
 {
-    if (!j.p.best_overlaps) return;
-    j.best_partner.resize((size_t)j.n_reads * 2); j.best_span.resize((size_t)j.n_reads * 2); j.best_flags.resize((size_t)j.n_reads);
-    std::vector<uint8_t> skip(j.end_status.size());
-    for (size_t r = 0; r < skip.size(); ++r) skip[r] = j.end_status[r] == RAFT_HIP_END_READ_CONTAINED ? 1 : 0;
+    BestOut &o = j.best;
+    o.partner.resize((size_t)j.n_reads * 2); o.span.resize((size_t)j.n_reads * 2); o.flags.resize((size_t)j.n_reads);
+    std::vector<uint8_t> skip(j.ends.status.size());
+    for (size_t r = 0; r < skip.size(); ++r) skip[r] = j.ends.status[r] == RAFT_HIP_END_READ_CONTAINED ? 1 : 0;
+    const raft_hip_records r = records(j);
     int64_t bad_index = -1;
-    const int rc = raft_hip_best_overlaps_host(j.ctxs[0], j.n_reads, j.rl, j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.col[4], j.col[5], j.strand,
-                                               skip.data(), j.p.overlap_ends, j.p.ends_min_ratio, j.sym ? 1 : 0, j.best_partner.data(), j.best_span.data(),
-                                               j.best_flags.data(), &j.best_sum, &bad_index, nullptr);
-    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
-    stage(j, "best_overlaps");
+    const int rc = raft_hip_best_overlaps_host(j.ctxs[0], j.n_reads, j.rl, r.n_rec, r.d_qid, r.d_qs, r.d_qe, r.d_tid, r.d_ts, r.d_te, j.strand, skip.data(),
+                                               j.p.overlap_ends, j.p.ends_min_ratio, j.sym ? 1 : 0, o.partner.data(), o.span.data(), o.flags.data(), &o.sum,
+                                               &bad_index, nullptr);
+    done(j, rc, bad_index, "best_overlaps");
 }
 
 // --unitigs: the chains and cycles of the mutual best overlaps (raft_hip_unitigs_host), directly behind best_overlaps() on the
 // arrays that phase holds.
 void unitigs(Job &j)
 {
-    if (!j.p.unitigs) return;
+    UnitigOut &o = j.utg;
     const size_t n = (size_t)j.n_reads;
-    j.utg_unitig.resize(n); j.utg_index.resize(n); j.utg_order.resize(n); j.utg_reads.resize(n);
-    j.utg_offset.resize(n); j.utg_off.resize(n + 1); j.utg_length.resize(n);
-    j.utg_orient.resize(n); j.utg_circular.resize(n);
+    o.unitig.resize(n); o.index.resize(n); o.order.resize(n); o.reads.resize(n);
+    o.offset.resize(n); o.off.resize(n + 1); o.length.resize(n);
+    o.orient.resize(n); o.circular.resize(n);
     int64_t bad_index = -1;
-    const int rc = raft_hip_unitigs_host(j.ctxs[0], j.n_reads, j.rl, j.best_partner.data(), j.best_span.data(), j.best_flags.data(),
-                                         j.utg_unitig.data(), j.utg_index.data(), j.utg_offset.data(), j.utg_orient.data(), j.utg_order.data(),
-                                         j.utg_off.data(), j.utg_reads.data(), j.utg_length.data(), j.utg_circular.data(), &j.utg_sum, &bad_index,
-                                         nullptr, nullptr);
-    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
-    stage(j, "unitigs");
+    const int rc = raft_hip_unitigs_host(j.ctxs[0], j.n_reads, j.rl, j.best.partner.data(), j.best.span.data(), j.best.flags.data(), o.unitig.data(),
+                                         o.index.data(), o.offset.data(), o.orient.data(), o.order.data(), o.off.data(), o.reads.data(), o.length.data(),
+                                         o.circular.data(), &o.sum, &bad_index, nullptr, nullptr);
+    done(j, rc, bad_index, "unitigs");
 }
 
 // hifiasm writes its PAF grouped by query (reference README.md:36-38): a symmetric stream of at most four runs sorted by
@@ -748,9 +705,8 @@ void unitigs(Job &j)
 // RAFT_CLI_PREPARE=1 keeps them (A/B, and the grouped / window-record entry points through the CLI).
 void prepare_input(Job &j)
 {
-    const bool prepare = j.sw.cli_prepare && j.ranks == 0;
-    if (raft_cli::keeps_query_ids_with_lift(prepare, j.p.min_anchor, j.p.fragment_overlaps, j.p.fragment_paf)) j.ovl_qid.assign(j.col[0], j.col[0] + j.n_rec);   // (--repeat-overlaps, --fragment-overlaps and --fragment-paf read the query ids after the job)
-    if (prepare && j.sym && j.n_rec > 0 && !j.sw.no_grouped) {
+    if (j.rq.keep_query_ids) j.qid_kept.assign(j.col[0], j.col[0] + j.n_rec);   // (put back behind run_engine)
+    if (j.prepare && j.sym && j.n_rec > 0 && !j.sw.no_grouped) {
         j.rec_off.reset(new int64_t[(size_t)4 * ((size_t)j.n_reads + 1)]);
         if (raft_host_group_offsets(j.n_reads, j.n_rec, j.col[0], 4, &j.n_runs, j.rec_off.get()) != RAFT_HOST_OK) j.n_runs = 0;
         if (j.n_runs == 0 && j.devices.size() == 1 && j.n_rec < ((int64_t)1 << 29)) {
@@ -786,8 +742,7 @@ void lock_inputs(Job &j)
 // grouped input and for plain columns that look like a handful of sorted runs, else one byte per window, or two from 40x on.
 void choose_encoding(Job &j)
 {
-    const bool prepare = j.sw.cli_prepare && j.ranks == 0;
-    const bool few_runs = j.sym && !prepare && j.n_rec > 0 && raft_cli::few_sorted_runs(j.col[0], j.n_rec);
+    const bool few_runs = j.sym && !j.prepare && j.n_rec > 0 && raft_cli::few_sorted_runs(j.col[0], j.n_rec);
     j.cov_width = raft_cli::first_cov_width(j.n_runs, few_runs, j.sw.no_delta4, j.ranks, j.p.est_cov);
 }
 
@@ -796,14 +751,14 @@ int call_engine(Job &j, raft_hip_host_outputs *ho)
 {
     raft_hip_ctx **ctxs = j.ctxs.data();
     const int32_t n_ctx = (int32_t)j.ctxs.size();
+    const raft_hip_records r = records(j, j.ranks == 0 && j.sym ? Targets::none : Targets::all);
     if (j.ranks > 0)
-        return raft_hip_run_presplit_local(ctxs, n_ctx, j.n_reads, j.rl, j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.col[4], j.col[5], ho, &j.s);
+        return raft_hip_run_presplit_local(ctxs, n_ctx, j.n_reads, j.rl, r.n_rec, r.d_qid, r.d_qs, r.d_qe, r.d_tid, r.d_ts, r.d_te, ho, &j.s);
     if (j.win)
         return raft_hip_run_multi_windows(ctxs, n_ctx, j.n_reads, j.rl, j.n_rec, j.n_runs, j.rec_off.get(), j.win, j.sw.chunks, ho, &j.s);
     if (j.n_runs > 0)
         return raft_hip_run_multi_grouped(ctxs, n_ctx, j.n_reads, j.rl, j.n_rec, j.n_runs, j.rec_off.get(), j.col[1], j.col[2], j.sw.chunks, ho, &j.s);
-    return raft_hip_run_multi(ctxs, n_ctx, j.n_reads, j.rl, j.n_rec, j.col[0], j.col[1], j.col[2], j.sym ? nullptr : j.col[3], j.sym ? nullptr : j.col[4],
-                              j.sym ? nullptr : j.col[5], j.sw.chunks, ho, &j.s);
+    return raft_hip_run_multi(ctxs, n_ctx, j.n_reads, j.rl, r.n_rec, r.d_qid, r.d_qs, r.d_qe, r.d_tid, r.d_ts, r.d_te, j.sw.chunks, ho, &j.s);
 }
 
 // The job, and the ladder behind it: an attempt that meets more windows at or above the limit than the exception list holds is
@@ -837,112 +792,191 @@ void run_engine(Job &j)
         j.cov_width = next.cov_width;
         exc_cap = next.exc_cap;
     }
-    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, j.s.error_index));
-    stage(j, "engine+fetch");
+    if (!j.qid_kept.empty()) j.col[0] = j.qid_kept.data();          // (the query ids, for the options that read them after the job)
+    done(j, rc, j.s.error_index, "engine+fetch");
 }
 
-// --repeat-overlaps: the tokenised columns against the job's own repeat annotation -- the host arrays long_repeats.txt is written
-// from, so it is the same call whichever way the job ran (one device or several, ranks, -e auto).  Both sides are classified; the
-// reads' tallies follow the job's symmetric flag, as the census does.
+// The three on the job's results take the tokenised columns and the host arrays reads.fasta and long_repeats.txt are written from, on
+// the first context: the same call whichever way the job ran (one device or several, ranks, -e auto).
+// --repeat-overlaps: against the job's own repeat annotation.  Both sides are classified; the reads' tallies follow the job's
+// symmetric flag, as the census does.
 void repeat_overlaps(Job &j)
 {
-    if (j.p.min_anchor <= 0) return;
-    j.ovl_cls.resize((size_t)j.n_rec); j.ovl_flags.resize((size_t)j.n_reads);
-    j.ovl_touch.resize((size_t)j.n_reads); j.ovl_repeat.resize((size_t)j.n_reads);
-    if (!j.ovl_qid.empty()) j.col[0] = j.ovl_qid.data();
+    RepeatOverlapsOut &o = j.ovl;
+    o.cls.resize((size_t)j.n_rec); o.flags.resize((size_t)j.n_reads);
+    o.touch.resize((size_t)j.n_reads); o.repeat.resize((size_t)j.n_reads);
+    const raft_hip_records r = records(j);
     int64_t bad_index = -1;
-    const int rc = raft_hip_repeat_overlaps_host(j.ctxs[0], j.n_reads, j.rl, j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.col[4], j.col[5], j.sym ? 1 : 0,
-                                                 j.p.min_anchor, j.rep_off[(size_t)j.n_reads], j.rep_off.data(), j.rep_s.get(), j.rep_e.get(),
-                                                 j.ovl_cls.data(), j.ovl_touch.data(), j.ovl_repeat.data(), j.ovl_flags.data(), &j.ovl_sum, &bad_index, nullptr);
-    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
-    stage(j, "repeat_overlaps");
+    const int rc = raft_hip_repeat_overlaps_host(j.ctxs[0], j.n_reads, j.rl, r.n_rec, r.d_qid, r.d_qs, r.d_qe, r.d_tid, r.d_ts, r.d_te, j.sym ? 1 : 0,
+                                                 j.p.min_anchor, j.rep_off[(size_t)j.n_reads], j.rep_off.data(), j.rep_s.get(), j.rep_e.get(), o.cls.data(),
+                                                 o.touch.data(), o.repeat.data(), o.flags.data(), &o.sum, &bad_index, nullptr);
+    done(j, rc, bad_index, "repeat_overlaps");
 }
 
-// --fragment-overlaps: the tokenised columns against the job's own fragment rows and repeat annotation -- the host arrays reads.fasta and
-// long_repeats.txt are written from, so it is the same call whichever way the job ran (one device or several, ranks, -e auto): the
-// whole-job arrays go to the first context.  Sides are counted under the job's symmetric flag, as the census counts them.
+// --fragment-overlaps: against the job's own fragment rows and repeat annotation.  Sides are counted under the job's symmetric flag, as
+// the census counts them.
 void fragment_overlaps(Job &j)
 {
-    if (!j.p.fragment_overlaps) return;
-    const int64_t n_frag = j.frag_off[(size_t)j.n_reads];
-    for (std::vector<int32_t> *v : {&j.frag_touch, &j.frag_span, &j.frag_contained, &j.frag_repeat}) v->resize((size_t)n_frag);
-    if (!j.ovl_qid.empty()) j.col[0] = j.ovl_qid.data();
-    const raft_hip_records rec{j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.col[4], j.col[5]};
-    const raft_hip_frag_table table{n_frag, j.frag_off.data(), j.fb.get(), j.fe.get()};
+    FragmentOverlapsOut &o = j.frag;
+    const raft_hip_records rec = records(j);
+    const raft_hip_frag_table table{j.frag_off[(size_t)j.n_reads], j.frag_off.data(), j.fb.get(), j.fe.get()};
     const raft_hip_frag_repeats repeats{j.rep_off[(size_t)j.n_reads], j.rep_off.data(), j.rep_s.get(), j.rep_e.get()};
+    for (std::vector<int32_t> *v : {&o.touch, &o.span, &o.contained, &o.repeat}) v->resize((size_t)table.n_frag);
     int64_t bad_index = -1;
-    const int rc = raft_hip_frag_overlaps_host(j.ctxs[0], j.n_reads, j.rl, &rec, j.sym ? 1 : 0, &table, &repeats, j.frag_touch.data(), j.frag_span.data(),
-                                               j.frag_contained.data(), j.frag_repeat.data(), nullptr, &j.frag_sum, &bad_index, nullptr);
-    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
-    stage(j, "fragment_overlaps");
+    const int rc = raft_hip_frag_overlaps_host(j.ctxs[0], j.n_reads, j.rl, &rec, j.sym ? 1 : 0, &table, &repeats, o.touch.data(), o.span.data(),
+                                               o.contained.data(), o.repeat.data(), nullptr, &o.sum, &bad_index, nullptr);
+    done(j, rc, bad_index, "fragment_overlaps");
 }
 
-// --fragment-paf: the job's kept stream lifted onto the job's own fragment rows -- the host arrays reads.fasta is written from, so it
-// is the same call whichever way the job ran (one device or several, ranks, -e auto): the whole-job arrays go to the first context.
-// A size query, the eight columns at that size, the call.
+// --fragment-paf: the job's kept stream lifted onto the job's own fragment rows.  A size query, the eight columns at that size, the call.
 void fragment_paf(Job &j)
 {
-    if (!j.p.fragment_paf) return;
-    if (!j.ovl_qid.empty()) j.col[0] = j.ovl_qid.data();
-    const raft_hip_records rec{j.n_rec, j.col[0], j.col[1], j.col[2], j.col[3], j.col[4], j.col[5]};
+    LiftOut &o = j.lift;
+    const raft_hip_records rec = records(j);
     const raft_hip_frag_table table{j.frag_off[(size_t)j.n_reads], j.frag_off.data(), j.fb.get(), j.fe.get()};
     int64_t bad_index = -1;
     int rc = raft_hip_lift_overlaps_host(j.ctxs[0], j.n_reads, &rec, j.strand, &table, j.p.fragment_paf_min, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                         nullptr, nullptr, nullptr, &j.lift_sum, &bad_index, nullptr);
-    if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
-    const size_t n_out = (size_t)j.lift_sum.n_out;
+                                         nullptr, nullptr, nullptr, &o.sum, &bad_index, nullptr);
+    const size_t n_out = rc == RAFT_HIP_OK ? (size_t)o.sum.n_out : 0;
     if (n_out > 0) {
-        for (auto &c : j.lift_col) c.resize(n_out);
-        j.lift_rev.resize(n_out); j.lift_src.resize(n_out);
-        rc = raft_hip_lift_overlaps_host(j.ctxs[0], j.n_reads, &rec, j.strand, &table, j.p.fragment_paf_min, (int64_t)n_out, j.lift_col[0].data(),
-                                         j.lift_col[1].data(), j.lift_col[2].data(), j.lift_col[3].data(), j.lift_col[4].data(), j.lift_col[5].data(),
-                                         j.lift_rev.data(), j.lift_src.data(), &j.lift_sum, &bad_index, nullptr);
-        if (rc != RAFT_HIP_OK) die(engine_error(j, rc, bad_index));
+        for (auto &c : o.col) c.resize(n_out);
+        o.rev.resize(n_out); o.src.resize(n_out);
+        rc = raft_hip_lift_overlaps_host(j.ctxs[0], j.n_reads, &rec, j.strand, &table, j.p.fragment_paf_min, (int64_t)n_out, o.col[0].data(), o.col[1].data(),
+                                         o.col[2].data(), o.col[3].data(), o.col[4].data(), o.col[5].data(), o.rev.data(), o.src.data(), &o.sum, &bad_index,
+                                         nullptr);
     }
-    stage(j, "fragment_paf");
+    done(j, rc, bad_index, "fragment_paf");
 }
 
-void write_fragment_paf(Job &j)
+// The writers of the optional outputs (-> RAFT_HOST_OK or not) and their stdout lines, in the words of cli_plan.hpp where they are there.
+int write_read_stats(Job &j)
 {
-    if (raft_host_write_fragment_paf((j.p.prefix + ".fragments.paf").c_str(), j.reads, j.frag_off.data(), j.fb.get(), j.fe.get(), j.lift_sum.n_out,
-                                     j.lift_col[0].data(), j.lift_col[1].data(), j.lift_col[2].data(), j.lift_col[3].data(), j.lift_col[4].data(),
-                                     j.lift_col[5].data(), j.lift_rev.data(), j.lift_src.data(), j.lift_matches, j.lift_block) != RAFT_HOST_OK)
-        die("ERROR, fragment_paf(), cannot write output files");
+    return raft_host_write_read_stats((j.p.prefix + ".read_stats.tsv").c_str(), j.n_reads, names(j), j.rl, j.p.reso, j.rs.intervals.data(), j.rs.contained.data(),
+                                      j.rs.sum.data(), j.rs.max.data(), j.rs.high.data(), j.rep_off.data(), j.frag_off.data());
+}
+std::string line_read_stats(const Job &j) { return "INFO, read_stats(), contained reads = " + std::to_string(j.rs.n_contained) + " of " + std::to_string(j.n_reads); }
+
+int write_low_coverage(Job &j)
+{
+    return raft_host_write_low_coverage((j.p.prefix + ".low_coverage.bed").c_str(), j.n_reads, names(j), j.low.off.data(), j.low.s.data(), j.low.e.data(), j.rl,
+                                        j.p.reso);
+}
+std::string line_low_coverage(const Job &j)
+{
+    return "INFO, low_coverage(), low_cov = " + std::to_string(j.p.low_cov) + ", runs = " + std::to_string(j.low.sum.n_runs) + ", reads with an interior run = " +
+           std::to_string(j.low.sum.reads_interior) + ", uncovered reads = " + std::to_string(j.low.sum.reads_uncovered) + " of " + std::to_string(j.n_reads);
 }
 
-void write_fragment_overlaps(Job &j)
+int write_repeat_overlaps(Job &j)
 {
-    std::vector<const char *> names((size_t)j.n_reads);
-    for (int32_t i = 0; i < j.n_reads; ++i) names[(size_t)i] = raft_host_reads_name(j.reads, i);
-    if (raft_host_write_fragments((j.p.prefix + ".fragments.tsv").c_str(), j.n_reads, names.data(), j.frag_off.data(), j.fb.get(), j.fe.get(),
-                                  j.frag_touch.data(), j.frag_span.data(), j.frag_contained.data(), j.frag_repeat.data()) != RAFT_HOST_OK)
-        die("ERROR, fragment_overlaps(), cannot write output files");
+    return raft_host_write_repeat_overlaps((j.p.prefix + ".repeat_overlaps.tsv").c_str(), (j.p.prefix + ".repeat_overlaps.records.tsv").c_str(), j.n_reads,
+                                           names(j), j.rl, j.ovl.touch.data(), j.ovl.repeat.data(), j.ovl.flags.data(), j.n_rec, j.col[0], j.col[1], j.col[2],
+                                           j.col[3], j.col[4], j.col[5], j.ovl.cls.data());
+}
+std::string line_repeat_overlaps(const Job &j)
+{
+    const raft_hip_ovl_summary &s = j.ovl.sum;
+    return "INFO, repeat_overlaps(), min_anchor = " + std::to_string(j.p.min_anchor) + ", records = " + std::to_string(s.n_records) +
+           ", query side in a repeat = " + std::to_string(s.q_repeat) + ", target side = " + std::to_string(s.t_repeat) + ", both = " +
+           std::to_string(s.both_repeat) + ", contained reads = " + std::to_string(s.reads_contained) + ", contained only inside repeats = " +
+           std::to_string(s.reads_repeat_contained);
+}
+
+int write_fragment_overlaps(Job &j)
+{
+    return raft_host_write_fragments((j.p.prefix + ".fragments.tsv").c_str(), j.n_reads, names(j), j.frag_off.data(), j.fb.get(), j.fe.get(), j.frag.touch.data(),
+                                     j.frag.span.data(), j.frag.contained.data(), j.frag.repeat.data());
+}
+std::string line_fragment_overlaps(const Job &j)
+{
+    const raft_hip_frag_summary &s = j.frag.sum;
+    return raft_cli::fragment_overlaps_line(s.n_fragments, s.frags_spanned, s.frags_contained, s.frags_contained_repeat, s.reads_whole_spanned,
+                                            s.reads_all_contained, j.n_reads);
 }
 
 // --repeat-stats: the file is written from the job's own runs, beside long_repeats.txt; the rows come from the stats pass, which must
 // have found the same number of runs
-void write_repeat_stats(Job &j)
+int write_repeat_stats(Job &j)
 {
+    const RepeatStatsOut &o = j.rst;
     const int64_t n_rep = j.rep_off[(size_t)j.n_reads];
-    if (!j.rst_done || (int64_t)j.rst_flags.size() != n_rep)
-        die("ERROR, repeat_stats(), the stats pass found " + std::to_string(j.rst_flags.size()) + " repeats, the job " + std::to_string(n_rep));
-    std::vector<const char *> names((size_t)j.n_reads);
-    for (int32_t i = 0; i < j.n_reads; ++i) names[(size_t)i] = raft_host_reads_name(j.reads, i);
-    if (raft_host_write_repeat_stats((j.p.prefix + ".long_repeats.stats.tsv").c_str(), j.n_reads, names.data(), j.rep_off.data(), j.rep_s.get(), j.rep_e.get(),
-                                     j.rst_flags.data(), j.rst_windows.data(), j.rst_cov_sum.data(), j.rst_min.data(), j.rst_max.data(), j.rst_high.data(),
-                                     j.rst_touch.data(), j.rst_span.data(), j.rst_inside.data()) != RAFT_HOST_OK)
-        die("ERROR, repeat_stats(), cannot write output files");
+    if (!o.done || (int64_t)o.flags.size() != n_rep)
+        die("ERROR, repeat_stats(), the stats pass found " + std::to_string(o.flags.size()) + " repeats, the job " + std::to_string(n_rep));
+    return raft_host_write_repeat_stats((j.p.prefix + ".long_repeats.stats.tsv").c_str(), j.n_reads, names(j), j.rep_off.data(), j.rep_s.get(), j.rep_e.get(),
+                                        o.flags.data(), o.windows.data(), o.cov_sum.data(), o.min.data(), o.max.data(), o.high.data(), o.touch.data(),
+                                        o.span.data(), o.inside.data());
+}
+std::string line_repeat_stats(const Job &j) { const auto &s = j.rst.sum; return raft_cli::repeat_stats_line(s.n_runs, s.runs_interior, s.runs_spanned, s.interior_spanned, s.runs_touched, s.sides_inside); }
+
+int write_overlap_ends(Job &j) { return raft_host_write_overlap_ends((j.p.prefix + ".overlap_ends.tsv").c_str(), j.reads, j.ends.counts.data(), j.ends.status.data()); }
+std::string line_overlap_ends(const Job &j)
+{
+    const raft_hip_end_summary &s = j.ends.sum;
+    return raft_cli::overlap_ends_line(j.p.overlap_ends, j.p.ends_min_ratio, s.n_records, s.kind_internal, s.kind_query_contained, s.kind_target_contained,
+                                       s.kind_end3 + s.kind_end5, s.kind_self, s.kind_invalid, s.reads_contained, s.reads_dead5 + s.reads_dead3,
+                                       s.reads_isolated, j.n_reads);
 }
 
-void write_repeat_overlaps(Job &j)
+int write_best_overlaps(Job &j)
 {
-    const Params &p = j.p;
-    std::vector<const char *> names((size_t)j.n_reads);
-    for (int32_t i = 0; i < j.n_reads; ++i) names[(size_t)i] = raft_host_reads_name(j.reads, i);
-    if (raft_host_write_repeat_overlaps((p.prefix + ".repeat_overlaps.tsv").c_str(), (p.prefix + ".repeat_overlaps.records.tsv").c_str(), j.n_reads,
-                                        names.data(), j.rl, j.ovl_touch.data(), j.ovl_repeat.data(), j.ovl_flags.data(), j.n_rec, j.col[0], j.col[1],
-                                        j.col[2], j.col[3], j.col[4], j.col[5], j.ovl_cls.data()) != RAFT_HOST_OK)
-        die("ERROR, repeat_overlaps(), cannot write output files");
+    return raft_host_write_best_overlaps((j.p.prefix + ".best_overlaps.tsv").c_str(), j.reads, j.best.partner.data(), j.best.span.data(), j.best.flags.data());
+}
+std::string line_best_overlaps(const Job &j)
+{
+    const raft_hip_best_summary &s = j.best.sum;
+    return raft_cli::best_overlaps_line(s.n_records, s.candidates, s.left_out, s.ends_best, s.ends_mutual, s.reads_both_mutual, s.reads_no_best,
+                                        s.reads_skipped, j.n_reads);
+}
+
+int write_unitigs(Job &j)
+{
+    const UnitigOut &o = j.utg;
+    return raft_host_write_unitigs(j.p.prefix.c_str(), j.reads, o.sum.unitigs, o.unitig.data(), o.index.data(), o.offset.data(), o.orient.data(), o.order.data(),
+                                   o.off.data(), o.reads.data(), o.length.data(), o.circular.data());
+}
+std::string line_unitigs(const Job &j)
+{
+    const raft_hip_utg_summary &s = j.utg.sum;
+    return raft_cli::unitigs_line(s.reads_in, s.reads_skipped, s.unitigs, s.singletons, s.circular, s.longest_reads, s.longest_length, s.total_length,
+                                  raft_cli::unitig_n50(j.utg.length.data(), s.unitigs));
+}
+
+int write_fragment_paf(Job &j)
+{
+    const LiftOut &o = j.lift;
+    return raft_host_write_fragment_paf((j.p.prefix + ".fragments.paf").c_str(), j.reads, j.frag_off.data(), j.fb.get(), j.fe.get(), o.sum.n_out, o.col[0].data(),
+                                        o.col[1].data(), o.col[2].data(), o.col[3].data(), o.col[4].data(), o.col[5].data(), o.rev.data(), o.src.data(),
+                                        j.matches, j.block);
+}
+std::string line_fragment_paf(const Job &j) { const auto &s = j.lift.sum; return raft_cli::fragment_paf_line(j.p.fragment_paf_min, s.n_records, s.n_out, s.records_cut, s.records_none, s.pairs_dropped, s.most_per_record); }
+
+std::string line_filter_overlaps(const Job &j) { const auto &s = j.flt.sum; return raft_cli::filter_overlaps_line(j.p.min_identity, j.p.min_overlap, s.n_records, s.n_kept, s.below_identity, s.below_span); }
+
+// The optional outputs, one row each, in the one order in which they run, are written and report on stdout.  name: that of the row's
+// `ERROR, name(), cannot write output files`, of its stdout line and -- the census apart -- of its stage on the clock.  stage: where
+// run stands in main() -- on the stream before the job (prepare_input() writes window records over the query column), on the job's
+// results, or inside the survey (a phase of its own, as the filter is: it calls its three by name).  run, write and line may be null.
+enum class Stage { stream, results, survey };
+
+struct Extra { const char *name; bool (*wanted)(const Job &); Stage stage; void (*run)(Job &); int (*write)(Job &); std::string (*line)(const Job &); };
+
+const Extra kExtras[] = {
+    {"filter_overlaps", [](const Job &j) { return j.rq.filter; }, Stage::stream, nullptr, nullptr, line_filter_overlaps},
+    {"read_stats", [](const Job &j) { return j.p.read_stats; }, Stage::stream, census, write_read_stats, line_read_stats},
+    {"low_coverage", [](const Job &j) { return j.p.low_cov >= 0; }, Stage::survey, nullptr, write_low_coverage, line_low_coverage},
+    {"repeat_overlaps", [](const Job &j) { return j.p.min_anchor > 0; }, Stage::results, repeat_overlaps, write_repeat_overlaps, line_repeat_overlaps},
+    {"fragment_overlaps", [](const Job &j) { return j.p.fragment_overlaps; }, Stage::results, fragment_overlaps, write_fragment_overlaps, line_fragment_overlaps},
+    {"repeat_stats", [](const Job &j) { return j.p.repeat_stats; }, Stage::survey, nullptr, write_repeat_stats, line_repeat_stats},
+    {"overlap_ends", [](const Job &j) { return j.p.overlap_ends >= 0; }, Stage::stream, overlap_ends, write_overlap_ends, line_overlap_ends},
+    {"best_overlaps", [](const Job &j) { return j.p.best_overlaps; }, Stage::stream, best_overlaps, write_best_overlaps, line_best_overlaps},
+    {"unitigs", [](const Job &j) { return j.p.unitigs; }, Stage::stream, unitigs, write_unitigs, line_unitigs},
+    {"fragment_paf", [](const Job &j) { return j.p.fragment_paf; }, Stage::results, fragment_paf, write_fragment_paf, line_fragment_paf},
+};
+
+void run_extras(Job &j, Stage stage)
+{
+    for (const Extra &e : kExtras)
+        if (e.stage == stage && e.run && e.wanted(j)) e.run(j);
 }
 
 void report(Job &j)
@@ -955,30 +989,10 @@ void report(Job &j)
     fprintf(stdout, "high_cov %d\n", s.high_cov);                              // repeat.hpp:91
 }
 
-void write_read_stats(Job &j)
-{
-    const Params &p = j.p;
-    std::vector<const char *> names((size_t)j.n_reads);
-    for (int32_t i = 0; i < j.n_reads; ++i) names[(size_t)i] = raft_host_reads_name(j.reads, i);
-    if (raft_host_write_read_stats((p.prefix + ".read_stats.tsv").c_str(), j.n_reads, names.data(), j.rl, p.reso, j.cen_intervals.data(), j.cen_contained.data(),
-                                   j.rs_sum.data(), j.rs_max.data(), j.rs_high.data(), j.rep_off.data(), j.frag_off.data()) != RAFT_HOST_OK)
-        die("ERROR, read_stats(), cannot write output files");
-}
-
-void write_low_coverage(Job &j)
-{
-    const Params &p = j.p;
-    std::vector<const char *> names((size_t)j.n_reads);
-    for (int32_t i = 0; i < j.n_reads; ++i) names[(size_t)i] = raft_host_reads_name(j.reads, i);
-    if (raft_host_write_low_coverage((p.prefix + ".low_coverage.bed").c_str(), j.n_reads, names.data(), j.low_off.data(), j.low_s.data(), j.low_e.data(),
-                                     j.rl, p.reso) != RAFT_HOST_OK)
-        die("ERROR, low_coverage(), cannot write output files");
-}
-
 // the four output files are independent: the FASTA is written beside the coverage/repeat tables
 void write_outputs(Job &j)
 {
-    const Params &p = j.p;
+    const Options &p = j.p;
     const raft_hip_summary &s = j.s;
     j.fasta_writer = std::thread([&j] { j.fasta_rc = raft_host_write_fasta(j.fasta_out.c_str(), j.reads, j.frag_off.data(), j.fb.get(), j.fe.get()); });
     const int cov_rc = j.cov_width == RAFT_HIP_COV_DELTA4
@@ -991,23 +1005,8 @@ void write_outputs(Job &j)
                                 j.rep_off.data(), j.rep_s.get(), j.rep_e.get()) != RAFT_HOST_OK) {
         die("ERROR, repeat_annotate(), cannot write output files");
     }
-    if (p.read_stats) write_read_stats(j);
-    if (p.low_cov >= 0) write_low_coverage(j);
-    if (p.min_anchor > 0) write_repeat_overlaps(j);
-    if (p.fragment_overlaps) write_fragment_overlaps(j);
-    if (p.repeat_stats) write_repeat_stats(j);
-    if (p.overlap_ends >= 0 &&
-        raft_host_write_overlap_ends((p.prefix + ".overlap_ends.tsv").c_str(), j.reads, j.end_counts.data(), j.end_status.data()) != RAFT_HOST_OK)
-        die("ERROR, overlap_ends(), cannot write output files");
-    if (p.best_overlaps &&
-        raft_host_write_best_overlaps((p.prefix + ".best_overlaps.tsv").c_str(), j.reads, j.best_partner.data(), j.best_span.data(), j.best_flags.data()) != RAFT_HOST_OK)
-        die("ERROR, best_overlaps(), cannot write output files");
-    if (p.unitigs &&
-        raft_host_write_unitigs(p.prefix.c_str(), j.reads, j.utg_sum.unitigs, j.utg_unitig.data(), j.utg_index.data(), j.utg_offset.data(),
-                                j.utg_orient.data(), j.utg_order.data(), j.utg_off.data(), j.utg_reads.data(), j.utg_length.data(),
-                                j.utg_circular.data()) != RAFT_HOST_OK)
-        die("ERROR, unitigs(), cannot write output files");
-    if (p.fragment_paf) write_fragment_paf(j);
+    for (const Extra &e : kExtras)
+        if (e.write && e.wanted(j) && e.write(j) != RAFT_HOST_OK) die(std::string("ERROR, ") + e.name + "(), cannot write output files");
     stage(j, "write_tables");
     // repeat.hpp:173-178 (total_windows is an int in the reference; identical below 2^31 windows)
     const double cpw = (double)s.total_coverage / (double)s.total_windows;
@@ -1030,40 +1029,8 @@ void print_totals(Job &j, int argc, char *argv[])
     for (int i = 0; i < argc; ++i) fprintf(stdout, " %s", argv[i]);
     fflush(stdout);
     std::cout << "\n";
-    if (j.filtered)
-        std::cout << raft_cli::filter_overlaps_line(j.p.min_identity, j.p.min_overlap, j.flt_sum.n_records, j.flt_sum.n_kept, j.flt_sum.below_identity,
-                                                    j.flt_sum.below_span) << "\n";
-    if (j.p.read_stats) std::cout << "INFO, read_stats(), contained reads = " << j.n_contained << " of " << j.n_reads << "\n";
-    if (j.p.low_cov >= 0)
-        std::cout << "INFO, low_coverage(), low_cov = " << j.p.low_cov << ", runs = " << j.low_sum.n_runs << ", reads with an interior run = "
-                  << j.low_sum.reads_interior << ", uncovered reads = " << j.low_sum.reads_uncovered << " of " << j.n_reads << "\n";
-    if (j.p.min_anchor > 0)
-        std::cout << "INFO, repeat_overlaps(), min_anchor = " << j.p.min_anchor << ", records = " << j.ovl_sum.n_records << ", query side in a repeat = "
-                  << j.ovl_sum.q_repeat << ", target side = " << j.ovl_sum.t_repeat << ", both = " << j.ovl_sum.both_repeat << ", contained reads = "
-                  << j.ovl_sum.reads_contained << ", contained only inside repeats = " << j.ovl_sum.reads_repeat_contained << "\n";
-    if (j.p.fragment_overlaps)
-        std::cout << raft_cli::fragment_overlaps_line(j.frag_sum.n_fragments, j.frag_sum.frags_spanned, j.frag_sum.frags_contained,
-                                                      j.frag_sum.frags_contained_repeat, j.frag_sum.reads_whole_spanned, j.frag_sum.reads_all_contained,
-                                                      j.n_reads) << "\n";
-    if (j.p.repeat_stats)
-        std::cout << raft_cli::repeat_stats_line(j.rst_sum.n_runs, j.rst_sum.runs_interior, j.rst_sum.runs_spanned, j.rst_sum.interior_spanned,
-                                                 j.rst_sum.runs_touched, j.rst_sum.sides_inside) << "\n";
-    if (j.p.overlap_ends >= 0)
-        std::cout << raft_cli::overlap_ends_line(j.p.overlap_ends, j.p.ends_min_ratio, j.end_sum.n_records, j.end_sum.kind_internal,
-                                                 j.end_sum.kind_query_contained, j.end_sum.kind_target_contained, j.end_sum.kind_end3 + j.end_sum.kind_end5,
-                                                 j.end_sum.kind_self, j.end_sum.kind_invalid, j.end_sum.reads_contained,
-                                                 j.end_sum.reads_dead5 + j.end_sum.reads_dead3, j.end_sum.reads_isolated, j.n_reads) << "\n";
-    if (j.p.best_overlaps)
-        std::cout << raft_cli::best_overlaps_line(j.best_sum.n_records, j.best_sum.candidates, j.best_sum.left_out, j.best_sum.ends_best,
-                                                  j.best_sum.ends_mutual, j.best_sum.reads_both_mutual, j.best_sum.reads_no_best,
-                                                  j.best_sum.reads_skipped, j.n_reads) << "\n";
-    if (j.p.unitigs)
-        std::cout << raft_cli::unitigs_line(j.utg_sum.reads_in, j.utg_sum.reads_skipped, j.utg_sum.unitigs, j.utg_sum.singletons, j.utg_sum.circular,
-                                            j.utg_sum.longest_reads, j.utg_sum.longest_length, j.utg_sum.total_length,
-                                            raft_cli::unitig_n50(j.utg_length.data(), j.utg_sum.unitigs)) << "\n";
-    if (j.p.fragment_paf)
-        std::cout << raft_cli::fragment_paf_line(j.p.fragment_paf_min, j.lift_sum.n_records, j.lift_sum.n_out, j.lift_sum.records_cut,
-                                                 j.lift_sum.records_none, j.lift_sum.pairs_dropped, j.lift_sum.most_per_record) << "\n";
+    for (const Extra &e : kExtras)
+        if (e.line && e.wanted(j)) std::cout << e.line(j) << "\n";
     stage(j, "stdout");
     if (j.sw.timing) {
         timespec ts{};
@@ -1094,17 +1061,12 @@ int main(int argc, char *argv[])
     filter_overlaps(job);
     hand_over_symmetric_flag(job);
     survey(job);
-    census(job);
-    overlap_ends(job);
-    best_overlaps(job);
-    unitigs(job);
+    run_extras(job, Stage::stream);
     prepare_input(job);
     lock_inputs(job);
     choose_encoding(job);
     run_engine(job);
-    repeat_overlaps(job);
-    fragment_overlaps(job);
-    fragment_paf(job);
+    run_extras(job, Stage::results);
     report(job);
     write_outputs(job);
     print_totals(job, argc, argv);

@@ -1,24 +1,17 @@
 // cli_plan_best_check.cpp -- what `raft --best-overlaps` adds to raft_amd/host/cli_plan.hpp, checked on the CPU as a program of its own
 // (tests/test_cli_plan_best.py builds it under the address and undefined-behaviour sanitizers).
-#include "../raft_amd/host/cli_plan.hpp"
-
-#include <cstdio>
-#include <cstdlib>
-
-#define CHECK(cond)                                                                   \
-    do {                                                                              \
-        if (!(cond)) { printf("FAILED line %d: %s\n", __LINE__, #cond); exit(1); }    \
-    } while (0)
+#include "cli_check.hpp"
 
 int main()
 {
     using namespace raft_cli;
+    using cli_check::usage;
     // the option needs --overlap-ends (max_overhang -1: not asked for); without the option everything goes
-    CHECK(best_options_ok(false, -1) && best_options_ok(false, 0) && best_options_ok(false, 1000));
-    CHECK(best_options_ok(true, 0) && best_options_ok(true, 1000) && best_options_ok(true, 2147483647));
-    CHECK(!best_options_ok(true, -1));
+    CHECK(usage(-1, false, false, false, false, false) && usage(0, false, false, false, false, false) && usage(1000, false, false, false, false, false));
+    CHECK(usage(0, false, true, false, false, false) && usage(1000, false, true, false, false, false) && usage(2147483647, false, true, false, false, false));
+    CHECK(!usage(-1, false, true, false, false, false));
     // ... and leaves the rules of the options before it alone
-    CHECK(ends_options_ok(-1, false) && !ends_options_ok(-1, true) && paf_columns(false, true) == RAFT_HOST_PAF_STRAND);
+    CHECK(usage(-1, false, false, false, false, false) && !usage(-1, true, false, false, false, false) && cli_check::columns(false, 0, false) == RAFT_HOST_PAF_STRAND);
     // the stdout line
     CHECK(best_overlaps_line(25236, 412, 9000, 38, 28, 8, 2, 279, 300) ==
           "INFO, best_overlaps(), records = 25236, candidates = 412, left out = 9000, ends with a best overlap = 38, mutual = 28, "
@@ -29,6 +22,5 @@ int main()
     CHECK(best_overlaps_line(3000000000LL, 6000000000LL, 5999999999LL, 4294967294LL, 4294967292LL, 2147483646, 1, 2, 2147483647) ==
           "INFO, best_overlaps(), records = 3000000000, candidates = 6000000000, left out = 5999999999, ends with a best overlap = 4294967294, "
           "mutual = 4294967292, reads with both ends mutual = 2147483646, reads without a best overlap = 1, reads left out = 2 of 2147483647");
-    printf("cli_plan_best_check: ok\n");
-    return 0;
+    return cli_check::finish("cli_plan_best_check");
 }

@@ -1,22 +1,15 @@
 // cli_plan_check.cpp -- raft_amd/host/cli_plan.hpp on its own: the device list, the output capacities, the record estimate, the
 // sampled run count, the coverage widths, the ladder after an overflowing exception list, the start-time field and the two
-// descriptions of the stage clock.  No HIP: a host compiler builds it (tests/test_cli_plan.py: under the address and
-// undefined-behaviour sanitizers).  Every expected value is a literal: what the statements of the former main() (raft_main.cpp at
-// 451f851, lines 139-181, 238-267, 425-437, 469-479) gave on the same inputs.
-#include "../raft_amd/host/cli_plan.hpp"
+// descriptions of the stage clock; the table of the long options and what the options ask of a job between them (Request).  No HIP:
+// a host compiler builds it (tests/test_cli_plan.py: under the address and undefined-behaviour sanitizers).  Every expected value
+// is a literal: what the statements of the former main() (raft_main.cpp at 451f851, lines 139-181, 238-267, 425-437, 469-479) gave
+// on the same inputs; for the Request, the expressions of the functions it replaced, written out.
+#include "cli_check.hpp"
 
-#include <cstdio>
 #include <initializer_list>
+#include <set>
 
 using namespace raft_cli;
-
-static int g_failed = 0;
-#define CHECK(cond, ...)                                                                   \
-    do {                                                                                   \
-        if (!(cond)) {                                                                     \
-            if (++g_failed <= 20) { fprintf(stderr, "%s:%d: %s -- ", __FILE__, __LINE__, #cond); fprintf(stderr, __VA_ARGS__); fputc('\n', stderr); } \
-        }                                                                                  \
-    } while (0)
 
 static const char *show(const char *s) { return s ? s : "(unset)"; }
 
@@ -80,8 +73,113 @@ static void step(int cov_width, long long exc_cap, long long n_exc, long long n_
           a.cov_width, (long long)a.exc_cap);
 }
 
+// every value of an Options, as text: two are equal when these are
+static std::string fields(const Options &o)
+{
+    std::string t = o.prefix + " " + std::to_string(o.cov_mul);
+    for (long long v : {(long long)o.reso, (long long)o.est_cov, (long long)o.repeat_length, (long long)o.interval_length, (long long)o.read_length,
+                        (long long)o.overlap_length, (long long)o.flanking_length, (long long)o.auto_cov, (long long)o.read_stats, (long long)o.low_cov,
+                        (long long)o.min_anchor, (long long)o.fragment_overlaps, (long long)o.repeat_stats, (long long)o.min_identity, (long long)o.min_overlap,
+                        (long long)o.overlap_ends, (long long)o.ends_min_ratio, (long long)o.ends_ratio_given, (long long)o.best_overlaps, (long long)o.unitigs,
+                        (long long)o.fragment_paf, (long long)o.fragment_paf_min, (long long)o.fragment_paf_min_given})
+        t += " " + std::to_string(v);
+    return t;
+}
+
+// One row of kLongOptions against what the former `case` of parse_options did: a flag sets `flag` and nothing else; a value option
+// takes `good` -- a text that the other parsers of the table refuse or read differently -- into `value` (and sets `given`, where it
+// has one), refuses `bad`, and a refused text changes nothing at all.
+static void row(int k, const char *name, bool Options::*flag, int32_t Options::*value, const char *good, int32_t want, const char *bad)
+{
+    const LongOption &o = kLongOptions[k];
+    CHECK(strcmp(o.name, name) == 0, "row %d is %s, want %s", k, o.name, name);
+    CHECK((o.parse != nullptr) == (value != nullptr) && (o.value != nullptr) == (value != nullptr), "--%s: takes an argument exactly when it has a value", name);
+    Options expect, got;
+    if (value) expect.*value = want;
+    if (flag) expect.*flag = true;
+    char *text = good ? strdup(good) : nullptr;            // (a heap block of exactly the text's size)
+    CHECK(set_long_option(o, text, &got) && fields(got) == fields(expect), "--%s %s: %s", name, good ? good : "", fields(got).c_str());
+    free(text);
+    if (bad) {
+        Options untouched;
+        text = strdup(bad);
+        CHECK(!set_long_option(o, text, &untouched) && fields(untouched) == fields(Options()), "--%s %s is refused and changes nothing", name, bad);
+        free(text);
+    }
+}
+
+static void long_options()
+{
+    CHECK(sizeof kLongOptions / sizeof kLongOptions[0] == 13, "thirteen long options");
+    std::set<std::string> names;
+    for (const LongOption &o : kLongOptions) names.insert(o.name);
+    CHECK(names.size() == 13, "the names are unique");
+    row(0, "read-stats", &Options::read_stats, nullptr, nullptr, 0, nullptr);
+    row(1, "low-cov", nullptr, &Options::low_cov, "0", 0, "-1");                         // (0: parse_low_cov takes it, parse_min_anchor does not)
+    row(2, "repeat-overlaps", nullptr, &Options::min_anchor, "5", 5, "0");
+    row(3, "fragment-overlaps", &Options::fragment_overlaps, nullptr, nullptr, 0, nullptr);
+    row(4, "repeat-stats", &Options::repeat_stats, nullptr, nullptr, 0, nullptr);
+    row(5, "min-identity", nullptr, &Options::min_identity, "99.5", 995, "100.1");       // (per mille: no other parser reads a point)
+    row(6, "min-overlap", nullptr, &Options::min_overlap, "500", 500, "0");
+    row(7, "overlap-ends", nullptr, &Options::overlap_ends, "1001", 1001, "2147483648");  // (1001: beyond parse_ends_min_ratio)
+    row(8, "ends-min-ratio", &Options::ends_ratio_given, &Options::ends_min_ratio, "1000", 1000, "1001");
+    row(9, "best-overlaps", &Options::best_overlaps, nullptr, nullptr, 0, nullptr);
+    row(10, "unitigs", &Options::unitigs, nullptr, nullptr, 0, nullptr);
+    row(11, "fragment-paf", &Options::fragment_paf, nullptr, nullptr, 0, nullptr);
+    row(12, "fragment-paf-min", &Options::fragment_paf_min_given, &Options::fragment_paf_min, "501", 501, "0");
+    row(7, "overlap-ends", nullptr, &Options::overlap_ends, "0", 0, "x");                 // (0: parse_overlap_ends takes it, parse_min_anchor does not)
+    // what the command line leaves without any of them
+    const Options none;
+    CHECK(none.low_cov == -1 && none.overlap_ends == -1 && none.min_anchor == 0 && none.min_identity == 0 && none.min_overlap == 0 &&
+          none.ends_min_ratio == kEndsMinRatioDefault && none.fragment_paf_min == kFragmentPafMinDefault && usage_ok(none), "the defaults");
+    CHECK(none.reso == 50 && none.est_cov == 0 && none.cov_mul == 1.5 && none.repeat_length == 10000 && none.interval_length == 10000 &&
+          none.read_length == 20000 && none.overlap_length == 500 && none.flanking_length == 1000 && none.prefix == "raft" && !none.auto_cov, "param.hpp:18-31");
+}
+
+// usage_ok over every combination of the six values its rules read, against the four rules it took over from the functions before it, written out
+static void usage_rules()
+{
+    for (int c = 0; c < 64; ++c) {
+        Options o;
+        o.overlap_ends = (c & 1) ? 100 : -1; o.ends_ratio_given = (c & 2) != 0; o.best_overlaps = (c & 4) != 0; o.unitigs = (c & 8) != 0;
+        o.fragment_paf = (c & 16) != 0; o.fragment_paf_min_given = (c & 32) != 0;
+        const bool ends_ok = o.overlap_ends >= 0 || !o.ends_ratio_given, best_ok = !o.best_overlaps || o.overlap_ends >= 0;
+        const bool unitigs_ok = !o.unitigs || o.best_overlaps, lift_ok = o.fragment_paf || !o.fragment_paf_min_given;
+        CHECK(usage_ok(o) == (ends_ok && best_ok && unitigs_ok && lift_ok), "usage_ok, combination %d", c);
+    }
+}
+
+// Every Request field over prepare, -e auto, the filter (either option, both, none), --overlap-ends and the eight other options,
+// against the expressions of the eight functions it replaced (DESIGN.md I.21 names them) as they stood, written out over the same
+// values.
+static void requests()
+{
+    for (int c = 0; c < (1 << 13); ++c) {
+        const bool prepare = c & 1;
+        Options o;
+        o.auto_cov = (c & 2) != 0; o.est_cov = o.auto_cov ? 0 : 30;
+        o.min_identity = (c & 4) ? 990 : 0; o.min_overlap = (c & 8) ? 500 : 0;
+        o.overlap_ends = (c & 16) ? 0 : -1;
+        o.read_stats = (c & 32) != 0; o.low_cov = (c & 64) ? 0 : -1; o.min_anchor = (c & 128) ? 1 : 0; o.fragment_overlaps = (c & 256) != 0;
+        o.repeat_stats = (c & 512) != 0; o.best_overlaps = (c & 1024) != 0; o.unitigs = (c & 2048) != 0; o.fragment_paf = (c & 4096) != 0;
+        const Request r = request(o, prepare);
+        const bool filter = o.min_identity > 0 || o.min_overlap > 0;
+        const bool strand = o.overlap_ends >= 0 || o.fragment_paf;
+        CHECK(r.filter == filter, "filter, combination %d", c);
+        CHECK(r.strand == strand, "strand, combination %d", c);
+        CHECK(r.quality_kept == (filter && o.fragment_paf), "quality_kept, combination %d", c);
+        CHECK(r.paf_columns == ((filter ? RAFT_HOST_PAF_QUALITY : 0) | (strand ? RAFT_HOST_PAF_STRAND : 0)), "paf_columns, combination %d", c);
+        CHECK(r.keep_query_ids == (prepare && (o.min_anchor > 0 || (o.fragment_overlaps || o.fragment_paf))), "keep_query_ids, combination %d", c);
+        CHECK(r.survey == (o.auto_cov || o.read_stats || o.low_cov >= 0 || o.repeat_stats), "survey, combination %d", c);
+        CHECK(r.repeat_stats_second_pass == (o.auto_cov && o.repeat_stats), "repeat_stats_second_pass, combination %d", c);
+    }
+}
+
 int main()
 {
+    long_options();
+    usage_rules();
+    requests();
     // devices
     dev("0,1", nullptr, nullptr, 0, {0, 1});
     dev("0,1", "5", nullptr, 0, {0, 1});
@@ -332,7 +430,5 @@ int main()
     CHECK(strcmp(encoding_label(8), "delta4") == 0, "encoding_label");
     CHECK(strcmp(encoding_label(2), "uint16") == 0, "encoding_label");
     CHECK(strcmp(encoding_label(1), "uint8") == 0, "encoding_label");
-    if (g_failed) { fprintf(stderr, "cli_plan_check: %d checks failed\n", g_failed); return 1; }
-    printf("cli_plan_check: ok\n");
-    return 0;
+    return cli_check::finish("cli_plan_check");
 }

@@ -1,29 +1,13 @@
 // cli_plan_ends_check.cpp -- what `raft --overlap-ends / --ends-min-ratio` adds to raft_amd/host/cli_plan.hpp, checked on the CPU as a
 // program of its own (tests/test_cli_plan_ends.py builds it under the address and undefined-behaviour sanitizers).
-#include "../raft_amd/host/cli_plan.hpp"
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-
-#define CHECK(cond)                                                                   \
-    do {                                                                              \
-        if (!(cond)) { printf("FAILED line %d: %s\n", __LINE__, #cond); exit(1); }    \
-    } while (0)
-
-// the text in a heap block of exactly its size, so that a read behind its end is the sanitizer's
-template <class F> static bool parsed(F parse, const char *text, int32_t *v)
-{
-    char *copy = (char *)malloc(strlen(text) + 1);
-    strcpy(copy, text);
-    const bool ok = parse(copy, v);
-    free(copy);
-    return ok;
-}
+#include "cli_check.hpp"
 
 int main()
 {
     using namespace raft_cli;
+    using cli_check::columns;
+    using cli_check::parsed;
+    using cli_check::usage;
     int32_t v = -7;
     // --overlap-ends H: digits alone, 0 .. INT32_MAX
     CHECK(parsed(parse_overlap_ends, "0", &v) && v == 0);
@@ -52,11 +36,12 @@ int main()
     CHECK(!parse_ends_min_ratio(nullptr, &v));
     CHECK(kEndsMinRatioDefault == 800);
     // the second option needs the first (max_overhang -1: not asked for)
-    CHECK(ends_options_ok(-1, false) && ends_options_ok(0, false) && ends_options_ok(0, true) && ends_options_ok(2147483647, true));
-    CHECK(!ends_options_ok(-1, true));
+    CHECK(usage(-1, false, false, false, false, false) && usage(0, false, false, false, false, false) && usage(0, true, false, false, false, false) &&
+          usage(2147483647, true, false, false, false, false));
+    CHECK(!usage(-1, true, false, false, false, false));
     // the columns the tokeniser is asked for
-    CHECK(paf_columns(false, false) == 0 && paf_columns(true, false) == RAFT_HOST_PAF_QUALITY && paf_columns(false, true) == RAFT_HOST_PAF_STRAND);
-    CHECK(paf_columns(true, true) == (RAFT_HOST_PAF_QUALITY | RAFT_HOST_PAF_STRAND) && RAFT_HOST_PAF_QUALITY == 1 && RAFT_HOST_PAF_STRAND == 2);
+    CHECK(columns(false, -1, false) == 0 && columns(true, -1, false) == RAFT_HOST_PAF_QUALITY && columns(false, 0, false) == RAFT_HOST_PAF_STRAND);
+    CHECK(columns(true, 0, false) == (RAFT_HOST_PAF_QUALITY | RAFT_HOST_PAF_STRAND) && RAFT_HOST_PAF_QUALITY == 1 && RAFT_HOST_PAF_STRAND == 2);
     // the stdout line
     CHECK(overlap_ends_line(1000, 800, 300, 100, 20, 30, 140, 4, 6, 25, 7, 3, 40) ==
           "INFO, overlap_ends(), max_overhang = 1000, min_ratio = 800 per mille, records = 300, internal = 100, query contained = 20, target contained = 30, "
@@ -67,6 +52,5 @@ int main()
     CHECK(overlap_ends_line(2147483647, 1000, 3000000000LL, 2999999999LL, 1, 2, 3, 4, 5, 6, 7, 8, 2147483647) ==
           "INFO, overlap_ends(), max_overhang = 2147483647, min_ratio = 1000 per mille, records = 3000000000, internal = 2999999999, query contained = 1, "
           "target contained = 2, dovetail = 3, self = 4, invalid = 5, contained reads = 6, dead ends = 7, isolated reads = 8 of 2147483647");
-    printf("cli_plan_ends_check: ok\n");
-    return 0;
+    return cli_check::finish("cli_plan_ends_check");
 }

@@ -1,33 +1,16 @@
 // cli_plan_filter_check.cpp -- what `raft --min-identity / --min-overlap` adds to raft_amd/host/cli_plan.hpp, checked on the CPU as a
 // program of its own (tests/test_cli_plan_filter.py builds it under the address and undefined-behaviour sanitizers).
-#include "../raft_amd/host/cli_plan.hpp"
+#include "cli_check.hpp"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
+static bool identity(const char *text, int32_t *v) { return cli_check::parsed(raft_cli::parse_min_identity, text, v); }
+static bool overlap(const char *text, int32_t *v) { return cli_check::parsed(raft_cli::parse_min_overlap, text, v); }
 
-#define CHECK(cond)                                                                   \
-    do {                                                                              \
-        if (!(cond)) { printf("FAILED line %d: %s\n", __LINE__, #cond); exit(1); }    \
-    } while (0)
-
-// the text in a heap block of exactly its size, so that a read behind its end is the sanitizer's
-static bool identity(const char *text, int32_t *v)
+// Request::filter over the two options it reads
+static bool filters(int32_t permille, int32_t min_span)
 {
-    char *copy = (char *)malloc(strlen(text) + 1);
-    strcpy(copy, text);
-    const bool ok = raft_cli::parse_min_identity(copy, v);
-    free(copy);
-    return ok;
-}
-
-static bool overlap(const char *text, int32_t *v)
-{
-    char *copy = (char *)malloc(strlen(text) + 1);
-    strcpy(copy, text);
-    const bool ok = raft_cli::parse_min_overlap(copy, v);
-    free(copy);
-    return ok;
+    raft_cli::Options o;
+    o.min_identity = permille; o.min_overlap = min_span;
+    return raft_cli::request(o, false).filter;
 }
 
 int main()
@@ -64,7 +47,7 @@ int main()
     }
     CHECK(!parse_min_overlap(nullptr, &v));
     // either option makes the job filter
-    CHECK(!filter_wanted(0, 0) && filter_wanted(990, 0) && filter_wanted(0, 1) && filter_wanted(1000, 2147483647));
+    CHECK(!filters(0, 0) && filters(990, 0) && filters(0, 1) && filters(1000, 2147483647));
     // the stdout line
     CHECK(filter_overlaps_line(990, 0, 300, 200, 100, 0) ==
           "INFO, filter_overlaps(), min_identity = 990 per mille, min_overlap = 0, records = 300, kept = 200, below identity = 100, below overlap = 0");
@@ -73,6 +56,5 @@ int main()
     CHECK(filter_overlaps_line(995, 2147483647, 3000000000LL, 1, 2999999999LL, 2999999998LL) ==
           "INFO, filter_overlaps(), min_identity = 995 per mille, min_overlap = 2147483647, records = 3000000000, kept = 1, below identity = 2999999999, "
           "below overlap = 2999999998");
-    printf("cli_plan_filter_check: ok\n");
-    return 0;
+    return cli_check::finish("cli_plan_filter_check");
 }

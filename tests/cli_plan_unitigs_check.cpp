@@ -1,26 +1,21 @@
 // cli_plan_unitigs_check.cpp -- what `raft --unitigs` adds to raft_amd/host/cli_plan.hpp, checked on the CPU as a program of its own
 // (tests/test_cli_plan_unitigs.py builds it under the address and undefined-behaviour sanitizers).
-#include "../raft_amd/host/cli_plan.hpp"
+#include "cli_check.hpp"
 
-#include <cstdio>
-#include <cstdlib>
 #include <vector>
-
-#define CHECK(cond)                                                                   \
-    do {                                                                              \
-        if (!(cond)) { printf("FAILED line %d: %s\n", __LINE__, #cond); exit(1); }    \
-    } while (0)
 
 static int64_t n50(std::vector<int64_t> v) { return raft_cli::unitig_n50(v.data(), (int64_t)v.size()); }
 
 int main()
 {
     using namespace raft_cli;
+    using cli_check::usage;
     // the option needs --best-overlaps; without the option everything goes
-    CHECK(unitigs_options_ok(false, false) && unitigs_options_ok(false, true) && unitigs_options_ok(true, true));
-    CHECK(!unitigs_options_ok(true, false));
+    CHECK(usage(0, false, false, false, false, false) && usage(0, false, true, false, false, false) && usage(0, false, true, true, false, false));
+    CHECK(!usage(0, false, false, true, false, false));
     // ... and leaves the rules of the options before it alone
-    CHECK(best_options_ok(true, 0) && !best_options_ok(true, -1) && ends_options_ok(-1, false) && !ends_options_ok(-1, true));
+    CHECK(usage(0, false, true, false, false, false) && !usage(-1, false, true, false, false, false) && usage(-1, false, false, false, false, false) &&
+          !usage(-1, true, false, false, false, false));
     // N50: no unitigs, one, ties, the exact half, just below it, any order, lengths of 0, totals beyond 2^32
     CHECK(unitig_n50(nullptr, 0) == 0 && n50({}) == 0);
     CHECK(n50({7}) == 7 && n50({0}) == 0);
@@ -49,6 +44,5 @@ int main()
     CHECK(unitigs_line(1073741823, 2, 3000000, 2999999, 7, 1073741820, 2305843009213693951LL, 4611686018427387903LL, 4294967296LL) ==
           "INFO, unitigs(), reads = 1073741823, left out = 2, unitigs = 3000000, singletons = 2999999, circular = 7, longest = 1073741820 reads, "
           "longest length = 2305843009213693951, total length = 4611686018427387903, N50 = 4294967296");
-    printf("cli_plan_unitigs_check: ok\n");
-    return 0;
+    return cli_check::finish("cli_plan_unitigs_check");
 }

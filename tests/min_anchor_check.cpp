@@ -1,33 +1,19 @@
 // min_anchor_check.cpp -- raft_cli::parse_min_anchor (raft_amd/host/cli_plan.hpp), the argument of `raft --repeat-overlaps A`, on the
 // CPU: built by the host compiler under the address and undefined-behaviour sanitizers and run as a process of its own
 // (tests/test_min_anchor_parse.py).
-#include "../raft_amd/host/cli_plan.hpp"
+#include "cli_check.hpp"
 
-#include <cstdio>
-#include <cstring>
-#include <memory>
-#include <string>
-
-static int failures = 0;
-
-// the text in a heap block of exactly its size: a read past the terminator is the sanitizer's to see
-static bool parse(const std::string &text, int32_t *out)
-{
-    std::unique_ptr<char[]> copy(new char[text.size() + 1]);
-    memcpy(copy.get(), text.c_str(), text.size() + 1);
-    return raft_cli::parse_min_anchor(copy.get(), out);
-}
-
+// (the text in a heap block of exactly its size: a read past the terminator is the sanitizer's to see)
 static void good(const char *text, int32_t want)
 {
     int32_t v = -77;
-    if (!parse(text, &v) || v != want) { printf("FAIL: \"%s\" should give %d, gave %d\n", text, want, v); ++failures; }
+    CHECK(cli_check::parsed(raft_cli::parse_min_anchor, text, &v) && v == want, "\"%s\" should give %d, gave %d", text, want, v);
 }
 
 static void bad(const char *text)
 {
     int32_t v = -77;
-    if (parse(text, &v) || v != -77) { printf("FAIL: \"%s\" should be refused and leave the value alone (%d)\n", text, v); ++failures; }
+    CHECK(!cli_check::parsed(raft_cli::parse_min_anchor, text, &v) && v == -77, "\"%s\" should be refused and leave the value alone (%d)", text, v);
 }
 
 int main()
@@ -37,8 +23,6 @@ int main()
                           "18446744073709551617", "\t5", "5\n"})
         bad(t);
     int32_t v = 5;
-    if (raft_cli::parse_min_anchor(nullptr, &v) || v != 5) { printf("FAIL: NULL\n"); ++failures; }
-    if (failures) return 1;
-    printf("min_anchor_check: ok\n");
-    return 0;
+    CHECK(!raft_cli::parse_min_anchor(nullptr, &v) && v == 5, "NULL");
+    return cli_check::finish("min_anchor_check");
 }

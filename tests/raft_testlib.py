@@ -58,6 +58,19 @@ def build_oracle():
     subprocess.run(["make", "-s", "-C", ORACLE_DIR], check=True)
 
 
+def build_and_run_check(name, tmp_path):
+    """tests/NAME.cpp -- a check program of the host's plain-value headers, with its own main() -- built by the host compiler under
+    the address and undefined-behaviour sanitizers and run as a process of its own; it must end with `NAME: ok`."""
+    exe = str(tmp_path / name)
+    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                            "-static-libasan", "-static-libubsan", "-pthread",       # (the runtimes inside the program: nothing to load beside it)
+                            os.path.join(ROOT, "tests", name + ".cpp"), "-o", exe], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert f"{name}: ok" in run.stdout
+
+
 _olib = None
 
 

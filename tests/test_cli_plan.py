@@ -2,22 +2,12 @@
 compiler under the address and undefined-behaviour sanitizers and run as a process of its own."""
 from __future__ import annotations
 
-import os
 import shutil
-import subprocess
 
 import pytest
-
-HERE = os.path.dirname(os.path.abspath(__file__))
+from raft_testlib import build_and_run_check
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_cli_plan_check(tmp_path):
-    exe = str(tmp_path / "cli_plan_check")
-    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                            "-static-libasan", "-static-libubsan", "-pthread",       # (the runtimes inside the program: nothing to load beside it)
-                            os.path.join(HERE, "cli_plan_check.cpp"), "-o", exe], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr
-    run = subprocess.run([exe], capture_output=True, text=True)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "cli_plan_check: ok" in run.stdout
+    build_and_run_check("cli_plan_check", tmp_path)

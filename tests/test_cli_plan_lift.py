@@ -9,6 +9,7 @@ import shutil
 import subprocess
 
 import pytest
+from raft_testlib import build_and_run_check
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 RAFT = os.path.join(HERE, "..", "raft_amd", "bin", "raft")
@@ -16,14 +17,7 @@ RAFT = os.path.join(HERE, "..", "raft_amd", "bin", "raft")
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_cli_plan_lift_check(tmp_path):
-    exe = str(tmp_path / "cli_plan_lift_check")
-    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                            "-static-libasan", "-static-libubsan", "-pthread",       # (the runtimes inside the program: nothing to load beside it)
-                            os.path.join(HERE, "cli_plan_lift_check.cpp"), "-o", exe], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr
-    run = subprocess.run([exe], capture_output=True, text=True)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "cli_plan_lift_check: ok" in run.stdout
+    build_and_run_check("cli_plan_lift_check", tmp_path)
 
 
 @pytest.mark.parametrize("args", [["--fragment-paf-min", "5"], ["--fragment-paf", "--fragment-paf-min", "0"], ["--fragment-paf", "--fragment-paf-min", "x"],

@@ -59,7 +59,10 @@ def test_the_library_is_registered_under_its_tag():
     assert re.search(r"^SIDE \+= lift=lift_lib$", makefile, flags=re.M)
     assert makefile.index("\nSIDE += utg=unitig_lib") < makefile.index("\nSIDE += lift=lift_lib") < makefile.index("\nSIDE_TAGS =")
     host = open(os.path.join(ROOT, "raft_amd", "host", "Makefile")).read()
-    assert "-lraft_hip_lift" in host and host.count("raft_host_lift.h") == 2 and host.count("raft_hip_lift.h") == 1
+    # (the CLI links every library of the SIDE list, and both host targets depend on every public header)
+    assert "lift" in re.search(r"^SIDE = (.*)$", host, flags=re.M).group(1).split() and "$(SIDE:%=-lraft_hip_%)" in host
+    assert "HDRS = $(wildcard ../../include/*.h)" in host and host.count(" $(HDRS)") == 2
+    assert all(os.path.exists(os.path.join(ROOT, "include", h)) for h in ("raft_host_lift.h", "raft_hip_lift.h"))
 
 
 def test_the_closed_sets_are_what_they_were():
