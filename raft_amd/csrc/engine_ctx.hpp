@@ -425,6 +425,12 @@ struct raft_hip_ctx {
     // output columns before they go to the caller
     DevBuf lf_digest{bufs}, lf_tile_cnt{bufs}, lf_lane_cnt{bufs}, lf_tile_base{bufs}, lf_scan{bufs}, lf_ctl{bufs}, lf_strand{bufs};
     DevBuf lf_out[8] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
+    // raft_hip_components_* (components_lib.hip): the union-find's parent of every read, its root once the tree is flat, its degree, the
+    // per-root accumulators (reads, then bases and sides), the roots' prefix with the scan's partial sums, what goes to the caller (the
+    // component of every read; first, reads, bases, sides of every component), the control words; the host form's staging of the strand
+    // bytes (lengths and columns: q_len, q_col)
+    DevBuf cc_parent{bufs}, cc_root{bufs}, cc_degree{bufs}, cc_acc{bufs}, cc_scan{bufs}, cc_comp{bufs}, cc_ctl{bufs}, cc_strand{bufs};
+    DevBuf cc_rows[4] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
     // raft_hip_census_*: counts and flag words per read, the flags as bytes, {first bad record, reads with a flag}; staging of the host form --
     // the census's own and not q_*: it lives in the engine library, whose chunk pool backs the columns (kBig), which the side libraries' must not be
     DevBuf cen_cnt{bufs}, cen_flags{bufs}, cen_out{bufs}, cen_ctl{bufs}, cen_len{bufs};

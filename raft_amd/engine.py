@@ -93,6 +93,8 @@ _BestSummary = _counts_struct("_BestSummary", "n_records", "candidates", "left_o
 _UtgSummary = _counts_struct("_UtgSummary", "reads_in", "reads_skipped", "unitigs", "singletons", "circular", "longest_reads", "longest_length",
                              "total_length")
 _LiftSummary = _counts_struct("_LiftSummary", "n_records", "n_out", "records_none", "records_cut", "pairs_dropped", "most_per_record")
+_CcSummary = _counts_struct("_CcSummary", "n_reads", "n_records", "edge_records", "components", "singletons", "largest_reads", "largest_bases",
+                            "total_bases", "reads_in_largest_permille")
 
 
 class _FragTable(C.Structure):      # raft_hip_frag_table and raft_hip_frag_repeats: a count and the three arrays of a CSR table
@@ -253,6 +255,16 @@ LIFT_ABI = {
 }
 LIFT_COLUMNS = ("qfrag", "qs", "qe", "tfrag", "ts", "te", "rev", "src")      # int32, but for rev: uint8
 
+# ... and those of include/raft_hip_cc.h (libraft_hip_cc.so): load_side_library("cc") declares these
+_CC_CALL = [_vp] + _COLUMNS + [_vp, _i32, _i32, _i32, _i32] + [_vp] * 6 + [_P(_CcSummary), _P(_i64), _P(_f64), _P(_i64)]
+CC_ABI = {
+    "raft_hip_cc_abi": (C.c_int, []),
+    "raft_hip_components_device": (C.c_int, _CC_CALL),
+    "raft_hip_components_host": (C.c_int, _CC_CALL),
+}
+# the masks of kinds that count as edges (RAFT_HIP_CC_KINDS_*): containments and dovetails; those and the internal matches
+CC_KINDS_PROPER, CC_KINDS_ALL = 60, 62
+
 
 @dataclass
 class Summary:
@@ -330,14 +342,19 @@ _SIDE = {
     "best": ("libraft_hip_best.so", BEST_ABI, "raft_hip_best_abi"), "utg": ("libraft_hip_utg.so", UTG_ABI, "raft_hip_utg_abi"),
     "lift": ("libraft_hip_lift.so", LIFT_ABI, "raft_hip_lift_abi"),
 }
+# That table is closed at the nine; the libraries that came later stand here, rows of the same type under tags of their own, and the
+# next one is a row here.
+_SIDE_LATER = {
+    "cc": ("libraft_hip_cc.so", CC_ABI, "raft_hip_cc_abi"),
+}
 _side_libs: dict = {}
 
 
 def load_side_library(tag: str) -> C.CDLL:
-    """libraft_hip_<tag>.so of ``_SIDE`` (behind libraft_hip.so, whose contexts it takes) with every entry point of
-    include/raft_hip_<tag>.h declared; the two must have been built beside each other."""
+    """libraft_hip_<tag>.so of ``_SIDE`` or ``_SIDE_LATER`` (behind libraft_hip.so, whose contexts it takes) with every entry point
+    of include/raft_hip_<tag>.h declared; the two must have been built beside each other."""
     if tag not in _side_libs:
-        file, abi, abi_fn = _SIDE[tag]
+        file, abi, abi_fn = _SIDE[tag] if tag in _SIDE else _SIDE_LATER[tag]
         main = load_library()
         p = os.path.join(os.path.dirname(_LIB_PATH), file)
         if not os.path.exists(p):
@@ -1209,6 +1226,38 @@ class Engine:
         return {"unitig": unitig, "index": index, "offset": offset, "orient": orient, "order": order[:placed], "utg_off": utg_off[:n_utg + 1],
                 "utg_reads": utg_reads[:n_utg], "utg_length": utg_length[:n_utg], "utg_circular": utg_circular[:n_utg],
                 "summary": _summary_dict(sm), "kernel_seconds": secs.value, "launches": launches.value}
+
+    # -- the connected components of the overlap graph ----------------------------------------------------
+    last_components_seconds = 0.0        # device time of the launches of the last components()
+    last_components_launches = 0         # ... and how many there were
+
+    def components(self, read_len, qid, qs, qe, tid, ts, te, strand, max_overhang: int = 1000, min_ratio_permille: int = 800,
+                   kind_mask: int = CC_KINDS_PROPER, symmetric: bool = False) -> dict:
+        """raft_hip_components_device / _host (libraft_hip_cc.so): the connected components of the graph over all reads whose edges
+        are the records with a kind of ``kind_mask`` (bit k: kind ``END_*`` k; ``CC_KINDS_PROPER``, ``CC_KINDS_ALL``) under the rule of
+        include/raft_hip_end.h, as include/raft_hip_cc.h says.  -> per read ``component`` and ``degree`` (int32); per component, in
+        the order of the smallest read ids, ``comp_first``, ``comp_reads`` (int32), ``comp_bases``, ``comp_sides`` (int64);
+        ``summary`` (the counts of raft_hip_cc_summary), ``kernel_seconds`` and ``launches``.  The columns are torch tensors on this
+        engine's device (int32; strand uint8) or numpy arrays (staged by the library).  Unless ``symmetric`` an edge counts in its
+        target's degree as well.  Independent of any pass."""
+        cols = [read_len, qid, qs, qe, tid, ts, te]
+        if any(x is None for x in cols) or strand is None:
+            raise ValueError("components needs read_len, the six columns and strand")
+        cc = load_side_library("cc")
+        on_device, cols, (strand,), _, n, _ = self._record_query("components", cols, rec_u8={"strand": strand})
+        fn = cc.raft_hip_components_device if on_device else cc.raft_hip_components_host
+        component, degree, comp_first, comp_reads = (np.zeros(n, np.int32) for _ in range(4))
+        comp_bases, comp_sides = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        sm, err, secs, launches = _CcSummary(), C.c_int64(-1), C.c_double(0.0), C.c_int64(0)
+        rc = fn(self._ctx, *_plain(cols), M.ptr(strand), int(max_overhang), int(min_ratio_permille), int(kind_mask), 1 if symmetric else 0,
+                M.ptr(component), M.ptr(degree), M.ptr(comp_first), M.ptr(comp_reads), M.ptr(comp_bases), M.ptr(comp_sides), C.byref(sm),
+                C.byref(err), C.byref(secs), C.byref(launches))
+        self.last_components_seconds, self.last_components_launches = secs.value, launches.value
+        self._check(rc, err.value)
+        n_comp = int(sm.components)
+        return {"component": component, "degree": degree, "comp_first": comp_first[:n_comp], "comp_reads": comp_reads[:n_comp],
+                "comp_bases": comp_bases[:n_comp], "comp_sides": comp_sides[:n_comp], "summary": _summary_dict(sm),
+                "kernel_seconds": secs.value, "launches": launches.value}
 
     # -- the overlaps between the fragments ------------------------------------------------------------------
     last_lift_overlaps_seconds = 0.0     # device time of the launches of the last lift_overlaps()

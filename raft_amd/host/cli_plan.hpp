@@ -291,6 +291,16 @@ inline std::string unitigs_line(int64_t reads, int64_t skipped, int64_t unitigs,
            ", N50 = " + std::to_string(n50);
 }
 
+// --components: the option's stdout line, behind unitigs' and before fragment_paf's, from raft_hip_cc_summary's counts (kinds: the mask)
+inline std::string components_line(int32_t kind_mask, int64_t records, int64_t edges, int64_t components, int64_t singletons, int64_t largest_reads,
+                                   int64_t largest_bases, int64_t total_bases, int64_t permille, int64_t n_reads)
+{
+    return "INFO, components(), kinds = " + std::to_string(kind_mask) + ", records = " + std::to_string(records) + ", edges = " + std::to_string(edges) +
+           ", components = " + std::to_string(components) + ", singletons = " + std::to_string(singletons) + ", largest = " + std::to_string(largest_reads) +
+           " reads, largest bases = " + std::to_string(largest_bases) + " of " + std::to_string(total_bases) + ", reads in the largest = " +
+           std::to_string(permille) + " per mille of " + std::to_string(n_reads);
+}
+
 // --fragment-paf: PREFIX.fragments.paf, the job's overlaps lifted onto its fragments (raft_hip_lift_overlaps_host).
 // --fragment-paf-min L: L (min_len of that call) is a whole number >= 1 written in digits alone, at most INT32_MAX; without the option it is
 constexpr int32_t kFragmentPafMinDefault = 1;
@@ -313,6 +323,7 @@ struct Options {
     std::string prefix = "raft";
     bool auto_cov = false;
     bool read_stats = false, fragment_overlaps = false, repeat_stats = false, best_overlaps = false, unitigs = false, fragment_paf = false;
+    bool components = false;
     int32_t low_cov = -1, overlap_ends = -1;                            // -1: not asked for
     int32_t min_anchor = 0, min_identity = 0, min_overlap = 0;          // 0: not asked for; the identity in per mille
     int32_t ends_min_ratio = kEndsMinRatioDefault, fragment_paf_min = kFragmentPafMinDefault;
@@ -340,6 +351,16 @@ inline constexpr LongOption kLongOptions[] = {
     {"fragment-paf-min", parse_fragment_paf_min, &Options::fragment_paf_min, &Options::fragment_paf_min_given},   // L: pairs shorter than L on either side are dropped
 };
 
+// That table is closed at the thirteen; the options that came later stand here, rows of the same type, and the next one is a row here.
+// long_option(k) counts through both: what getopt_long's array is built from and what a row it found is applied with.
+inline constexpr LongOption kLaterLongOptions[] = {
+    {"components", nullptr, nullptr, &Options::components},                 // PREFIX.components.tsv and .components.summary.tsv, the connected components under --overlap-ends' H and F
+};
+
+constexpr size_t kLongOptionCount = sizeof(kLongOptions) / sizeof(kLongOptions[0]);
+constexpr size_t long_option_count() { return kLongOptionCount + sizeof(kLaterLongOptions) / sizeof(kLaterLongOptions[0]); }
+constexpr const LongOption &long_option(size_t k) { return k < kLongOptionCount ? kLongOptions[k] : kLaterLongOptions[k - kLongOptionCount]; }
+
 // One long option as getopt found it (text: its argument, NULL for a flag).  false: the text is not what the option takes -- a
 // usage error, and the value is left alone.
 inline bool set_long_option(const LongOption &o, const char *text, Options *p)
@@ -351,11 +372,11 @@ inline bool set_long_option(const LongOption &o, const char *text, Options *p)
 
 // The options that mean nothing without another: --ends-min-ratio needs --overlap-ends; --best-overlaps needs it too (it takes its H
 // and F from it and its mask from that option's status bytes); --unitigs needs --best-overlaps, whose table it walks;
-// --fragment-paf-min needs --fragment-paf.  false: a usage error.
+// --fragment-paf-min needs --fragment-paf; --components needs --overlap-ends, whose H and F it classifies under.  false: a usage error.
 inline bool usage_ok(const Options &o)
 {
     return (o.overlap_ends >= 0 || !o.ends_ratio_given) && (!o.best_overlaps || o.overlap_ends >= 0) && (!o.unitigs || o.best_overlaps) &&
-           (o.fragment_paf || !o.fragment_paf_min_given);
+           (o.fragment_paf || !o.fragment_paf_min_given) && (!o.components || o.overlap_ends >= 0);
 }
 
 // What the options ask of the job between them, decided once (prepare: the group offsets and window records are made by the

@@ -21,6 +21,7 @@
 #include "../../include/raft_host_best.h"
 #include "../../include/raft_host_utg.h"
 #include "../../include/raft_host_lift.h"
+#include "../../include/raft_host_cc.h"
 
 #include <emmintrin.h>
 #include <zlib.h>
@@ -1261,6 +1262,41 @@ int raft_host_write_unitigs(const char *prefix, const raft_host_reads *reads, in
                              o.push_back('\t'); put_num(o, reads->lens[(size_t)r]);
                              o.push_back('\t'); o.push_back(orient[r] ? '-' : '+');
                              o.push_back('\t'); put_num(o, offset[r]);
+                             o.push_back('\n');
+                         });
+}
+
+// PREFIX.components.tsv and PREFIX.components.summary.tsv (include/raft_host_cc.h): one line per read, one line per component.  A table
+// that names a component outside [0, C) or a first read outside the set is refused before anything is written.
+int raft_host_write_components(const char *prefix, const raft_host_reads *reads, int64_t n_components, const int32_t *component,
+                               const int32_t *degree, const int32_t *comp_first, const int32_t *comp_reads, const int64_t *comp_bases,
+                               const int64_t *comp_sides)
+{
+    if (!prefix || !reads || n_components < 0) return RAFT_HOST_ERR_ARG;
+    const long long n = (long long)reads->lens.size(), n_comp = (long long)n_components;
+    if (n > 0 && (!component || !degree)) return RAFT_HOST_ERR_ARG;
+    if (n_comp > 0 && (!comp_first || !comp_reads || !comp_bases || !comp_sides)) return RAFT_HOST_ERR_ARG;
+    for (long long i = 0; i < n; ++i)
+        if (component[i] < 0 || component[i] >= n_comp) return RAFT_HOST_ERR_ARG;
+    for (long long k = 0; k < n_comp; ++k)
+        if (comp_first[k] < 0 || comp_first[k] >= n) return RAFT_HOST_ERR_ARG;
+    const std::string base(prefix);
+    int rc = write_ordered((base + ".components.tsv").c_str(), n, 1 << 16, [](long long) { return 1LL; },
+                           [&](long long i, std::string &o) {
+                               o.append(reads->names.name((int32_t)i), reads->names.name_len((int32_t)i));
+                               o.push_back('\t'); put_num(o, reads->lens[(size_t)i]);
+                               o.push_back('\t'); put_num(o, component[i]);
+                               o.push_back('\t'); put_num(o, degree[i]);
+                               o.push_back('\n');
+                           });
+    if (rc != RAFT_HOST_OK) return rc;
+    return write_ordered((base + ".components.summary.tsv").c_str(), n_comp, 1 << 16, [](long long) { return 1LL; },
+                         [&](long long k, std::string &o) {
+                             put_num(o, k);
+                             o.push_back('\t'); put_num(o, comp_reads[k]);
+                             o.push_back('\t'); put_num(o, comp_bases[k]);
+                             o.push_back('\t'); put_num(o, comp_sides[k]);
+                             o.push_back('\t'); o.append(reads->names.name(comp_first[k]), reads->names.name_len(comp_first[k]));
                              o.push_back('\n');
                          });
 }

@@ -31,6 +31,8 @@
 #include "../../include/raft_host_utg.h"
 #include "../../include/raft_hip_lift.h"
 #include "../../include/raft_host_lift.h"
+#include "../../include/raft_hip_cc.h"
+#include "../../include/raft_host_cc.h"
 #include "../../include/raft_host.h"
 #include "cli_plan.hpp"
 
@@ -75,6 +77,8 @@ struct EndsOut { std::vector<int32_t> counts; std::vector<uint8_t> status; raft_
 struct BestOut { std::vector<int32_t> partner, span; std::vector<uint8_t> flags; raft_hip_best_summary sum{}; };   // --best-overlaps: per read end, per read
 // --unitigs: per read the unitig, the place in it, the offset and the orientation; the layout order; per unitig size, length, circular
 struct UnitigOut { std::vector<int32_t> unitig, index, order, reads; std::vector<int64_t> offset, off, length; std::vector<uint8_t> orient, circular; raft_hip_utg_summary sum{}; };
+// --components: per read the component and the degree; per component the smallest read, the reads, the bases, the sides
+struct ComponentsOut { std::vector<int32_t> component, degree, first, reads; std::vector<int64_t> bases, sides; raft_hip_cc_summary sum{}; };
 struct LiftOut { std::vector<int32_t> col[6], src; std::vector<uint8_t> rev; raft_hip_lift_summary sum{}; };   // --fragment-paf: the eight columns of the lifted stream
 
 struct Job {
@@ -109,7 +113,7 @@ struct Job {
     std::vector<int32_t> qid_kept;                              // the query column as tokenised, where prepare_input writes over it (Request::keep_query_ids)
     // the optional outputs, in the order of kExtras
     FilterOut flt; ReadStatsOut rs; LowCovOut low; RepeatOverlapsOut ovl; FragmentOverlapsOut frag;
-    RepeatStatsOut rst; EndsOut ends; BestOut best; UnitigOut utg; LiftOut lift;
+    RepeatStatsOut rst; EndsOut ends; BestOut best; UnitigOut utg; ComponentsOut cc; LiftOut lift;
     // the arrays everything comes back in (made and page-locked on out_prep)
     raft_cli::Capacities cap;
     std::vector<int64_t> cov_off, rep_off, frag_off;
@@ -218,14 +222,14 @@ void parse_options(Job &j, int argc, char *argv[])
 {
     Options &p = j.p;
     // (the short options and their quirks are the reference's; the long options are this program's own, the rows of cli_plan.hpp
-    // kLongOptions: getopt_long returns 0 for them and says which row)
-    constexpr size_t n_long = std::size(raft_cli::kLongOptions);
+    // kLongOptions and kLaterLongOptions, counted through by long_option(k): getopt_long returns 0 for them and says which row)
+    constexpr size_t n_long = raft_cli::long_option_count();
     struct option long_options[n_long + 1] = {};
-    for (size_t k = 0; k < n_long; ++k) long_options[k] = {raft_cli::kLongOptions[k].name, raft_cli::kLongOptions[k].parse ? required_argument : no_argument, nullptr, 0};
+    for (size_t k = 0; k < n_long; ++k) long_options[k] = {raft_cli::long_option(k).name, raft_cli::long_option(k).parse ? required_argument : no_argument, nullptr, 0};
     int option, row = 0;
     while ((option = getopt_long(argc, argv, "r:e:m:l:i:p:f:v:o:", long_options, &row)) != -1) {
         switch (option) {
-        case 0: if (!raft_cli::set_long_option(raft_cli::kLongOptions[row], optarg, &p)) print_help(p); break;
+        case 0: if (!raft_cli::set_long_option(raft_cli::long_option((size_t)row), optarg, &p)) print_help(p); break;
         case 'r': p.reso = atoi(optarg); break;
         case 'e': p.auto_cov = strcmp(optarg, "auto") == 0; p.est_cov = p.auto_cov ? 0 : atoi(optarg); break;
         case 'm': p.cov_mul = std::stod(optarg); break;
@@ -696,6 +700,22 @@ void unitigs(Job &j)
     done(j, rc, bad_index, "unitigs");
 }
 
+// --components: the connected components of the graph whose edges are the containments and the dovetails (raft_hip_components_host),
+// behind unitigs(): on the first context over the same whole stream as overlap_ends(), under its H and F and the job's symmetric flag.
+void components(Job &j)
+{
+    ComponentsOut &o = j.cc;
+    const size_t n = (size_t)j.n_reads;
+    o.component.resize(n); o.degree.resize(n); o.first.resize(n); o.reads.resize(n); o.bases.resize(n); o.sides.resize(n);
+    const raft_hip_records r = records(j);
+    int64_t bad_index = -1;
+    const int rc = raft_hip_components_host(j.ctxs[0], j.n_reads, j.rl, r.n_rec, r.d_qid, r.d_qs, r.d_qe, r.d_tid, r.d_ts, r.d_te, j.strand,
+                                            j.p.overlap_ends, j.p.ends_min_ratio, RAFT_HIP_CC_KINDS_PROPER, j.sym ? 1 : 0, o.component.data(),
+                                            o.degree.data(), o.first.data(), o.reads.data(), o.bases.data(), o.sides.data(), &o.sum, &bad_index,
+                                            nullptr, nullptr);
+    done(j, rc, bad_index, "components");
+}
+
 // hifiasm writes its PAF grouped by query (reference README.md:36-38): a symmetric stream of at most four runs sorted by
 // read id is handed over in its grouped form -- per run, where every read's records begin -- and the query column stays
 // on the host (a third of the upload); any other stream goes up as it is.
@@ -941,6 +961,19 @@ std::string line_unitigs(const Job &j)
                                   raft_cli::unitig_n50(j.utg.length.data(), s.unitigs));
 }
 
+int write_components(Job &j)
+{
+    const ComponentsOut &o = j.cc;
+    return raft_host_write_components(j.p.prefix.c_str(), j.reads, o.sum.components, o.component.data(), o.degree.data(), o.first.data(), o.reads.data(),
+                                      o.bases.data(), o.sides.data());
+}
+std::string line_components(const Job &j)
+{
+    const raft_hip_cc_summary &s = j.cc.sum;
+    return raft_cli::components_line(RAFT_HIP_CC_KINDS_PROPER, s.n_records, s.edge_records, s.components, s.singletons, s.largest_reads, s.largest_bases,
+                                     s.total_bases, s.reads_in_largest_permille, s.n_reads);
+}
+
 int write_fragment_paf(Job &j)
 {
     const LiftOut &o = j.lift;
@@ -970,6 +1003,7 @@ const Extra kExtras[] = {
     {"overlap_ends", [](const Job &j) { return j.p.overlap_ends >= 0; }, Stage::stream, overlap_ends, write_overlap_ends, line_overlap_ends},
     {"best_overlaps", [](const Job &j) { return j.p.best_overlaps; }, Stage::stream, best_overlaps, write_best_overlaps, line_best_overlaps},
     {"unitigs", [](const Job &j) { return j.p.unitigs; }, Stage::stream, unitigs, write_unitigs, line_unitigs},
+    {"components", [](const Job &j) { return j.p.components; }, Stage::stream, components, write_components, line_components},
     {"fragment_paf", [](const Job &j) { return j.p.fragment_paf; }, Stage::results, fragment_paf, write_fragment_paf, line_fragment_paf},
 };
 

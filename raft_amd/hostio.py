@@ -90,6 +90,10 @@ UTG_ABI = {
 LIFT_ABI = {
     "raft_host_write_fragment_paf": (C.c_int, [_str, _vp, _vp, _vp, _vp, C.c_int64] + [_vp] * 10),
 }
+# ... and of include/raft_host_cc.h
+CC_ABI = {
+    "raft_host_write_components": (C.c_int, [_str, _vp, C.c_int64] + [_vp] * 6),
+}
 PAF_QUALITY, PAF_STRAND = 1, 2      # RAFT_HOST_PAF_*: the bits of ``columns``
 
 
@@ -109,7 +113,7 @@ def load_library():
         if not os.path.exists(_LIB_PATH):
             raise RuntimeError(f"{_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         lib = C.CDLL(_LIB_PATH)
-        for table in (ABI, LOW_ABI, OVL_ABI, FRAG_ABI, RST_ABI, FLT_ABI, END_ABI, BEST_ABI, UTG_ABI, LIFT_ABI):
+        for table in (ABI, LOW_ABI, OVL_ABI, FRAG_ABI, RST_ABI, FLT_ABI, END_ABI, BEST_ABI, UTG_ABI, LIFT_ABI, CC_ABI):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -266,6 +270,20 @@ def write_best_overlaps(path: str, reads: Reads, partner, span, flags):
     rc = load_library().raft_host_write_best_overlaps(path.encode(), reads._h, ptr(p), ptr(s), ptr(f))
     if rc != OK:
         raise HostError(rc, path)
+
+
+def write_components(prefix: str, reads: Reads, res: dict):
+    """raft_host_write_components: PREFIX.components.tsv and PREFIX.components.summary.tsv from what ``Engine.components`` returned
+    (``component``, ``degree``, ``comp_first``, ``comp_reads``, ``comp_bases``, ``comp_sides``)."""
+    i32 = [carray(res[k], np.int32) for k in ("component", "degree", "comp_first", "comp_reads")]
+    i64 = [carray(res[k], np.int64) for k in ("comp_bases", "comp_sides")]
+    n_comp = i32[2].size
+    if any(a.size != reads.n for a in i32[:2]) or any(a.size != n_comp for a in (i32[3], *i64)):
+        raise ValueError("write_components: the per-read arrays are [n_reads], the per-component arrays [C]")
+    rc = load_library().raft_host_write_components(prefix.encode(), reads._h, n_comp, ptr(i32[0]), ptr(i32[1]), ptr(i32[2]), ptr(i32[3]),
+                                                   ptr(i64[0]), ptr(i64[1]))
+    if rc != OK:
+        raise HostError(rc, prefix)
 
 
 def write_unitigs(prefix: str, reads: Reads, res: dict):
