@@ -287,6 +287,13 @@ struct DevBuf {
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// N buffers of a context declared as one: each is on the list like a DevBuf declared alone
+template <int N> struct DevBufSet {
+    DevBuf b[N];
+    explicit DevBufSet(std::vector<DevBuf *> &owner) { for (DevBuf &x : b) owner.push_back(&x); }
+    DevBuf &operator[](int k) { return b[k]; }
+};
+constexpr int kSgBufs = 40;           // the buffers of raft_hip_string_graph_* (string_graph_lib.hip SgBuf)
 
 } // namespace raft
 
@@ -431,6 +438,10 @@ struct raft_hip_ctx {
     // bytes (lengths and columns: q_len, q_col)
     DevBuf cc_parent{bufs}, cc_root{bufs}, cc_degree{bufs}, cc_acc{bufs}, cc_scan{bufs}, cc_comp{bufs}, cc_ctl{bufs}, cc_strand{bufs};
     DevBuf cc_rows[4] = {DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}, DevBuf{bufs}};
+    // raft_hip_string_graph_* (string_graph_lib.hip): one entry for all of its buffers -- the digests, the view bits and the steps'
+    // offsets, the items and the sort's pairs, the chosen arcs with their rows, flags and states, the per-node tables, what goes to
+    // the caller, the control words, the host form's staging of strand and skip; string_graph_lib.hip names them (SgBuf)
+    DevBufSet<kSgBufs> sg{bufs};
     // raft_hip_census_*: counts and flag words per read, the flags as bytes, {first bad record, reads with a flag}; staging of the host form --
     // the census's own and not q_*: it lives in the engine library, whose chunk pool backs the columns (kBig), which the side libraries' must not be
     DevBuf cen_cnt{bufs}, cen_flags{bufs}, cen_out{bufs}, cen_ctl{bufs}, cen_len{bufs};

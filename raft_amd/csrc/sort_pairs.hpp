@@ -253,11 +253,13 @@ __global__ __launch_bounds__(kRsThreads) void rs_scatter_kernel(const uint32_t *
 }
 
 // n pairs by the low `bits` bits of the key.  Buffers a and b ping-pong; *in_b says where the result is.  tmp: rs_tmp_bytes(n) bytes.
+// launched: where given, the kernels this call launched are added to it.
 template <class V> struct RsIpt { static constexpr int v = sizeof(V) == 8 ? 16 : 32; };      // 4096 pairs of 12 bytes / 8192 of 8: 48 / 64 KB of LDS per tile
 template <class V>
 inline size_t rs_tmp_bytes(long long n) { return ((size_t)256 * (size_t)((n + RsGeom<RsIpt<V>::v>::kTile - 1) / RsGeom<RsIpt<V>::v>::kTile + 1) + (size_t)256 * kRsSegs) * 4; }
 template <class V>
-inline hipError_t radix_sort_by_key(hipStream_t st, uint32_t *key_a, V *val_a, uint32_t *key_b, V *val_b, long long n, int bits, void *tmp, bool *in_b)
+inline hipError_t radix_sort_by_key(hipStream_t st, uint32_t *key_a, V *val_a, uint32_t *key_b, V *val_b, long long n, int bits, void *tmp, bool *in_b,
+                                    long long *launched = nullptr)
 {
     constexpr int IPT = RsIpt<V>::v;
     *in_b = false;
@@ -274,6 +276,7 @@ inline hipError_t radix_sort_by_key(hipStream_t st, uint32_t *key_a, V *val_a, u
         hipLaunchKernelGGL((rs_scatter_kernel<V, IPT>), dim3(rs_grid(n_tiles)), dim3(kRsThreads), 0, st, ki, vi, n, shift, n_tiles, hist, ko, vo);
         std::swap(ki, ko); std::swap(vi, vo);
         *in_b = !*in_b;
+        if (launched) *launched += 5;
     }
     return hipGetLastError();
 }

@@ -95,6 +95,9 @@ _UtgSummary = _counts_struct("_UtgSummary", "reads_in", "reads_skipped", "unitig
 _LiftSummary = _counts_struct("_LiftSummary", "n_records", "n_out", "records_none", "records_cut", "pairs_dropped", "most_per_record")
 _CcSummary = _counts_struct("_CcSummary", "n_reads", "n_records", "edge_records", "components", "singletons", "largest_reads", "largest_bases",
                             "total_bases", "reads_in_largest_permille")
+_SgSummary = _counts_struct("_SgSummary", "records", "dovetail_views", "views_left_out", "arcs", "duplicate_arcs", "unpaired_arcs", "reducible_arcs",
+                            "edges", "removed_edges", "kept_edges", "ends_with_arc", "ends_kept_one", "ends_kept_more", "ends_mutual", "ends_dead",
+                            "reads_flagged", "longest_row")
 
 
 class _FragTable(C.Structure):      # raft_hip_frag_table and raft_hip_frag_repeats: a count and the three arrays of a CSR table
@@ -265,6 +268,16 @@ CC_ABI = {
 # the masks of kinds that count as edges (RAFT_HIP_CC_KINDS_*): containments and dovetails; those and the internal matches
 CC_KINDS_PROPER, CC_KINDS_ALL = 60, 62
 
+# ... and those of include/raft_hip_sg.h (libraft_hip_sg.so): load_side_library("sg") declares these
+_SG_CALL = [_vp] + _COLUMNS + [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64] + [_vp] * 11 + [_P(_i64), _P(_SgSummary), _P(_i64), _P(_f64), _P(_i64)]
+SG_ABI = {
+    "raft_hip_sg_abi": (C.c_int, []),
+    "raft_hip_string_graph_device": (C.c_int, _SG_CALL),
+    "raft_hip_string_graph_host": (C.c_int, _SG_CALL),
+}
+SG_EDGE_RED_U, SG_EDGE_RED_W, SG_EDGE_UNPAIRED = 1, 2, 4      # RAFT_HIP_SG_EDGE_*: the bits of ``edge_flags``
+SG_EDGE_COLUMNS = ("edge_u", "edge_w", "edge_span", "edge_ext", "edge_back", "edge_flags")      # int32, but for edge_flags: uint8
+
 
 @dataclass
 class Summary:
@@ -346,6 +359,7 @@ _SIDE = {
 # next one is a row here.
 _SIDE_LATER = {
     "cc": ("libraft_hip_cc.so", CC_ABI, "raft_hip_cc_abi"),
+    "sg": ("libraft_hip_sg.so", SG_ABI, "raft_hip_sg_abi"),
 }
 _side_libs: dict = {}
 
@@ -1257,6 +1271,47 @@ class Engine:
         n_comp = int(sm.components)
         return {"component": component, "degree": degree, "comp_first": comp_first[:n_comp], "comp_reads": comp_reads[:n_comp],
                 "comp_bases": comp_bases[:n_comp], "comp_sides": comp_sides[:n_comp], "summary": _summary_dict(sm),
+                "kernel_seconds": secs.value, "launches": launches.value}
+
+    # -- the string graph: the dovetails between the reads that stay, transitively reduced ---------------------
+    last_string_graph_seconds = 0.0      # device time of the launches of the last string_graph()
+    last_string_graph_launches = 0       # ... and how many there were
+
+    def string_graph(self, read_len, qid, qs, qe, tid, ts, te, strand, *, max_overhang: int = 1000, min_ratio_permille: int = 800,
+                     fuzz: int = 1000, symmetric: bool = False, skip=None, emit_removed: bool = False) -> dict:
+        """raft_hip_string_graph_device / _host (libraft_hip_sg.so): one arc per pair of read ends among the dovetails between the reads
+        that ``skip`` (uint8 per read, non-zero: left out; ``None``: nobody) does not flag, and which of them two nearer arcs imply
+        within ``fuzz``, under the rule of include/raft_hip_sg.h.  -> per read end ``arcs`` and ``kept`` (int32 [n_reads, 2]); the
+        table ``unitigs`` takes: ``partner``, ``span`` (int32 [n_reads, 2]) and ``flags`` (uint8 [n_reads], ``BEST_*``); the edge list
+        ``SG_EDGE_COLUMNS`` of length ``n_out`` in ascending (u, w), node u = 2 * read + end -- the surviving edges, or with
+        ``emit_removed`` every edge, ``edge_flags`` (``SG_EDGE_*``) saying what fell; ``summary`` (the counts of raft_hip_sg_summary),
+        ``kernel_seconds`` and ``launches``.  The columns are torch tensors on this engine's device (int32; strand and skip uint8) or
+        numpy arrays (staged by the library).  Two calls: the size query, then the one that fills.  Independent of any pass."""
+        cols = [read_len, qid, qs, qe, tid, ts, te]
+        if any(x is None for x in cols) or strand is None:
+            raise ValueError("string_graph needs read_len, the six columns and strand")
+        sg = load_side_library("sg")
+        on_device, cols, (strand, skip), _, n, _ = self._record_query("string_graph", cols, rec_u8={"strand": strand}, read_u8={"skip": skip})
+        fn = sg.raft_hip_string_graph_device if on_device else sg.raft_hip_string_graph_host
+        if skip is not None and M.count(skip) != n:
+            raise ValueError("string_graph: skip is one byte per read")
+        arcs, kept, partner, span = (np.zeros((n, 2), np.int32) for _ in range(4))
+        flags = np.zeros(n, np.uint8)
+        per_read = [M.ptr(a) for a in (arcs, kept, partner, span, flags)]
+        sm, err, secs, launches, n_out = _SgSummary(), C.c_int64(-1), C.c_double(0.0), C.c_int64(0), C.c_int64(0)
+        head = [self._ctx, *_plain(cols), M.ptr(strand), M.ptr(skip), int(max_overhang), int(min_ratio_permille), 1 if symmetric else 0, int(fuzz),
+                1 if emit_removed else 0]
+        tail = [C.byref(n_out), C.byref(sm), C.byref(err), C.byref(secs), C.byref(launches)]
+        rc = fn(*head, 0, *per_read, *([C.c_void_p(0)] * 6), *tail)
+        self.last_string_graph_seconds, self.last_string_graph_launches = secs.value, launches.value
+        self._check(rc, err.value)
+        m = int(n_out.value)
+        edges = {k: np.zeros(m, np.uint8 if k == "edge_flags" else np.int32) for k in SG_EDGE_COLUMNS}
+        if m > 0:
+            rc = fn(*head, m, *per_read, *[M.ptr(a) for a in edges.values()], *tail)
+            self.last_string_graph_seconds, self.last_string_graph_launches = secs.value, launches.value
+            self._check(rc, err.value)
+        return {"arcs": arcs, "kept": kept, "partner": partner, "span": span, "flags": flags, **edges, "n_out": m, "summary": _summary_dict(sm),
                 "kernel_seconds": secs.value, "launches": launches.value}
 
     # -- the overlaps between the fragments ------------------------------------------------------------------

@@ -301,6 +301,31 @@ inline std::string components_line(int32_t kind_mask, int64_t records, int64_t e
            std::to_string(permille) + " per mille of " + std::to_string(n_reads);
 }
 
+// --string-graph-fuzz Z: Z (fuzz of raft_hip_string_graph_*) is a whole number >= 0 written in digits alone, at most INT32_MAX; without the
+// option it is miniasm's gap fuzz
+constexpr int32_t kStringGraphFuzzDefault = 1000;
+inline bool parse_string_graph_fuzz(const char *text, int32_t *fuzz) { return parse_low_cov(text, fuzz); }
+
+// The edge list's first size: a string graph keeps about an edge per read -- two per read where most ends branch --, and never more
+// than two per record; at least 1, so that the arrays are there.  The call says what it needs when that is not enough.
+inline int64_t string_graph_capacity0(int64_t n_rec, int32_t n_reads)
+{
+    return std::max<int64_t>(1, std::min<int64_t>(2 * n_rec, 2 * (int64_t)n_reads + 1024));
+}
+
+// --string-graph: the option's stdout line, behind components' and before fragment_paf's, from raft_hip_sg_summary's counts
+inline std::string string_graph_line(int32_t fuzz, int64_t records, int64_t views, int64_t left_out, int64_t arcs, int64_t duplicates, int64_t unpaired,
+                                     int64_t reducible, int64_t edges, int64_t kept_edges, int64_t ends_one, int64_t ends_more, int64_t ends_dead,
+                                     int64_t ends_mutual, int64_t reads_flagged, int64_t longest_row, int64_t n_reads)
+{
+    return "INFO, string_graph(), fuzz = " + std::to_string(fuzz) + ", records = " + std::to_string(records) + ", dovetail views = " + std::to_string(views) +
+           ", left out = " + std::to_string(left_out) + ", arcs = " + std::to_string(arcs) + ", duplicates = " + std::to_string(duplicates) +
+           ", unpaired = " + std::to_string(unpaired) + ", reducible = " + std::to_string(reducible) + ", edges = " + std::to_string(edges) +
+           ", kept = " + std::to_string(kept_edges) + ", ends with one = " + std::to_string(ends_one) + ", ends that branch = " + std::to_string(ends_more) +
+           ", dead ends = " + std::to_string(ends_dead) + ", mutual ends = " + std::to_string(ends_mutual) + ", reads left out = " +
+           std::to_string(reads_flagged) + " of " + std::to_string(n_reads) + ", longest row = " + std::to_string(longest_row);
+}
+
 // --fragment-paf: PREFIX.fragments.paf, the job's overlaps lifted onto its fragments (raft_hip_lift_overlaps_host).
 // --fragment-paf-min L: L (min_len of that call) is a whole number >= 1 written in digits alone, at most INT32_MAX; without the option it is
 constexpr int32_t kFragmentPafMinDefault = 1;
@@ -323,11 +348,13 @@ struct Options {
     std::string prefix = "raft";
     bool auto_cov = false;
     bool read_stats = false, fragment_overlaps = false, repeat_stats = false, best_overlaps = false, unitigs = false, fragment_paf = false;
-    bool components = false;
+    bool components = false, string_graph = false;
     int32_t low_cov = -1, overlap_ends = -1;                            // -1: not asked for
     int32_t min_anchor = 0, min_identity = 0, min_overlap = 0;          // 0: not asked for; the identity in per mille
     int32_t ends_min_ratio = kEndsMinRatioDefault, fragment_paf_min = kFragmentPafMinDefault;
     bool ends_ratio_given = false, fragment_paf_min_given = false;
+    int32_t string_graph_fuzz = kStringGraphFuzzDefault;
+    bool string_graph_fuzz_given = false;
 };
 
 // The long options, one row each: the text's parser (none: a flag, which takes no argument), the value it writes, and the flag
@@ -361,6 +388,16 @@ constexpr size_t kLongOptionCount = sizeof(kLongOptions) / sizeof(kLongOptions[0
 constexpr size_t long_option_count() { return kLongOptionCount + sizeof(kLaterLongOptions) / sizeof(kLaterLongOptions[0]); }
 constexpr const LongOption &long_option(size_t k) { return k < kLongOptionCount ? kLongOptions[k] : kLaterLongOptions[k - kLongOptionCount]; }
 
+// Those two are what long_option counts through, and that stays so: 14 rows.  The options behind them stand in a third table, and
+// the command line is built over all three -- any_long_option(k), k < any_long_option_count().
+inline constexpr LongOption kStringGraphLongOptions[] = {
+    {"string-graph", nullptr, nullptr, &Options::string_graph},             // PREFIX.string_graph.gfa and .string_graph.tsv, the transitively reduced dovetails under --overlap-ends' H and F
+    {"string-graph-fuzz", parse_string_graph_fuzz, &Options::string_graph_fuzz, &Options::string_graph_fuzz_given},   // Z: how far a path may miss the arc it implies
+};
+
+constexpr size_t any_long_option_count() { return long_option_count() + sizeof(kStringGraphLongOptions) / sizeof(kStringGraphLongOptions[0]); }
+constexpr const LongOption &any_long_option(size_t k) { return k < long_option_count() ? long_option(k) : kStringGraphLongOptions[k - long_option_count()]; }
+
 // One long option as getopt found it (text: its argument, NULL for a flag).  false: the text is not what the option takes -- a
 // usage error, and the value is left alone.
 inline bool set_long_option(const LongOption &o, const char *text, Options *p)
@@ -372,11 +409,13 @@ inline bool set_long_option(const LongOption &o, const char *text, Options *p)
 
 // The options that mean nothing without another: --ends-min-ratio needs --overlap-ends; --best-overlaps needs it too (it takes its H
 // and F from it and its mask from that option's status bytes); --unitigs needs --best-overlaps, whose table it walks;
-// --fragment-paf-min needs --fragment-paf; --components needs --overlap-ends, whose H and F it classifies under.  false: a usage error.
+// --fragment-paf-min needs --fragment-paf; --components needs --overlap-ends, whose H and F it classifies under, and so does
+// --string-graph; --string-graph-fuzz needs --string-graph.  false: a usage error.
 inline bool usage_ok(const Options &o)
 {
     return (o.overlap_ends >= 0 || !o.ends_ratio_given) && (!o.best_overlaps || o.overlap_ends >= 0) && (!o.unitigs || o.best_overlaps) &&
-           (o.fragment_paf || !o.fragment_paf_min_given) && (!o.components || o.overlap_ends >= 0);
+           (o.fragment_paf || !o.fragment_paf_min_given) && (!o.components || o.overlap_ends >= 0) &&
+           (!o.string_graph || o.overlap_ends >= 0) && (o.string_graph || !o.string_graph_fuzz_given);
 }
 
 // What the options ask of the job between them, decided once (prepare: the group offsets and window records are made by the

@@ -22,6 +22,7 @@
 #include "../../include/raft_host_utg.h"
 #include "../../include/raft_host_lift.h"
 #include "../../include/raft_host_cc.h"
+#include "../../include/raft_host_sg.h"
 
 #include <emmintrin.h>
 #include <zlib.h>
@@ -1297,6 +1298,54 @@ int raft_host_write_components(const char *prefix, const raft_host_reads *reads,
                              o.push_back('\t'); put_num(o, comp_bases[k]);
                              o.push_back('\t'); put_num(o, comp_sides[k]);
                              o.push_back('\t'); o.append(reads->names.name(comp_first[k]), reads->names.name_len(comp_first[k]));
+                             o.push_back('\n');
+                         });
+}
+
+// PREFIX.string_graph.gfa and PREFIX.string_graph.tsv (include/raft_host_sg.h): the header, a segment per read that is not flagged and
+// a link per edge; one line per read.  A list that names a node outside the set or an end of a flagged read is refused before anything
+// is written.
+int raft_host_write_string_graph(const char *prefix, const raft_host_reads *reads, const int32_t *arcs, const int32_t *kept, const uint8_t *flags,
+                                 int64_t n_edges, const int32_t *edge_u, const int32_t *edge_w, const int32_t *edge_span)
+{
+    if (!prefix || !reads || n_edges < 0) return RAFT_HOST_ERR_ARG;
+    const long long n = (long long)reads->lens.size(), m = (long long)n_edges;
+    if (n > 0 && (!arcs || !kept || !flags)) return RAFT_HOST_ERR_ARG;
+    if (m > 0 && (!edge_u || !edge_w || !edge_span)) return RAFT_HOST_ERR_ARG;
+    constexpr uint8_t kSkipped = 16;                       // RAFT_HIP_BEST_SKIPPED
+    for (long long e = 0; e < m; ++e)
+        for (const int32_t node : {edge_u[e], edge_w[e]})
+            if (node < 0 || node >= 2 * n || (flags[node >> 1] & kSkipped)) return RAFT_HOST_ERR_ARG;
+    const std::string base(prefix);
+    const auto name = [&](std::string &o, int32_t r) { o.append(reads->names.name(r), reads->names.name_len(r)); };
+    // items: the header, the reads, the edges
+    int rc = write_ordered((base + ".string_graph.gfa").c_str(), 1 + n + m, 1 << 16, [](long long) { return 1LL; },
+                           [&](long long i, std::string &o) {
+                               if (i == 0) { o.append("H\tVN:Z:1.0\n"); return; }
+                               if (i <= n) {
+                                   const int32_t r = (int32_t)(i - 1);
+                                   if (flags[r] & kSkipped) return;
+                                   o.append("S\t"); name(o, r);
+                                   o.append("\t*\tLN:i:"); put_num(o, reads->lens[(size_t)r]);
+                                   o.push_back('\n');
+                                   return;
+                               }
+                               const long long e = i - 1 - n;
+                               const int32_t u = edge_u[e], w = edge_w[e];
+                               o.append("L\t"); name(o, u >> 1);
+                               o.append((u & 1) ? "\t+\t" : "\t-\t"); name(o, w >> 1);
+                               o.append((w & 1) ? "\t-\t" : "\t+\t"); put_num(o, edge_span[e]);
+                               o.append("M\n");
+                           });
+    if (rc != RAFT_HOST_OK) return rc;
+    return write_ordered((base + ".string_graph.tsv").c_str(), n, 1 << 16, [](long long) { return 1LL; },
+                         [&](long long i, std::string &o) {
+                             name(o, (int32_t)i);
+                             o.push_back('\t'); put_num(o, reads->lens[(size_t)i]);
+                             for (int k = 0; k < 2; ++k) {
+                                 o.push_back('\t'); put_num(o, arcs[2 * i + k]);
+                                 o.push_back('\t'); put_num(o, kept[2 * i + k]);
+                             }
                              o.push_back('\n');
                          });
 }

@@ -33,6 +33,8 @@
 #include "../../include/raft_host_lift.h"
 #include "../../include/raft_hip_cc.h"
 #include "../../include/raft_host_cc.h"
+#include "../../include/raft_hip_sg.h"
+#include "../../include/raft_host_sg.h"
 #include "../../include/raft_host.h"
 #include "cli_plan.hpp"
 
@@ -79,6 +81,8 @@ struct BestOut { std::vector<int32_t> partner, span; std::vector<uint8_t> flags;
 struct UnitigOut { std::vector<int32_t> unitig, index, order, reads; std::vector<int64_t> offset, off, length; std::vector<uint8_t> orient, circular; raft_hip_utg_summary sum{}; };
 // --components: per read the component and the degree; per component the smallest read, the reads, the bases, the sides
 struct ComponentsOut { std::vector<int32_t> component, degree, first, reads; std::vector<int64_t> bases, sides; raft_hip_cc_summary sum{}; };
+// --string-graph: per read end the arcs and the survivors, per read the flag byte; the surviving edges (nodes and span)
+struct StringGraphOut { std::vector<int32_t> arcs, kept, u, w, span; std::vector<uint8_t> flags; raft_hip_sg_summary sum{}; };
 struct LiftOut { std::vector<int32_t> col[6], src; std::vector<uint8_t> rev; raft_hip_lift_summary sum{}; };   // --fragment-paf: the eight columns of the lifted stream
 
 struct Job {
@@ -113,7 +117,7 @@ struct Job {
     std::vector<int32_t> qid_kept;                              // the query column as tokenised, where prepare_input writes over it (Request::keep_query_ids)
     // the optional outputs, in the order of kExtras
     FilterOut flt; ReadStatsOut rs; LowCovOut low; RepeatOverlapsOut ovl; FragmentOverlapsOut frag;
-    RepeatStatsOut rst; EndsOut ends; BestOut best; UnitigOut utg; ComponentsOut cc; LiftOut lift;
+    RepeatStatsOut rst; EndsOut ends; BestOut best; UnitigOut utg; ComponentsOut cc; StringGraphOut sg; LiftOut lift;
     // the arrays everything comes back in (made and page-locked on out_prep)
     raft_cli::Capacities cap;
     std::vector<int64_t> cov_off, rep_off, frag_off;
@@ -222,14 +226,14 @@ void parse_options(Job &j, int argc, char *argv[])
 {
     Options &p = j.p;
     // (the short options and their quirks are the reference's; the long options are this program's own, the rows of cli_plan.hpp
-    // kLongOptions and kLaterLongOptions, counted through by long_option(k): getopt_long returns 0 for them and says which row)
-    constexpr size_t n_long = raft_cli::long_option_count();
+    // three tables, counted through by any_long_option(k): getopt_long returns 0 for them and says which row)
+    constexpr size_t n_long = raft_cli::any_long_option_count();
     struct option long_options[n_long + 1] = {};
-    for (size_t k = 0; k < n_long; ++k) long_options[k] = {raft_cli::long_option(k).name, raft_cli::long_option(k).parse ? required_argument : no_argument, nullptr, 0};
+    for (size_t k = 0; k < n_long; ++k) long_options[k] = {raft_cli::any_long_option(k).name, raft_cli::any_long_option(k).parse ? required_argument : no_argument, nullptr, 0};
     int option, row = 0;
     while ((option = getopt_long(argc, argv, "r:e:m:l:i:p:f:v:o:", long_options, &row)) != -1) {
         switch (option) {
-        case 0: if (!raft_cli::set_long_option(raft_cli::long_option((size_t)row), optarg, &p)) print_help(p); break;
+        case 0: if (!raft_cli::set_long_option(raft_cli::any_long_option((size_t)row), optarg, &p)) print_help(p); break;
         case 'r': p.reso = atoi(optarg); break;
         case 'e': p.auto_cov = strcmp(optarg, "auto") == 0; p.est_cov = p.auto_cov ? 0 : atoi(optarg); break;
         case 'm': p.cov_mul = std::stod(optarg); break;
@@ -667,6 +671,14 @@ void overlap_ends(Job &j)
     done(j, rc, bad_index, "overlap_ends");
 }
 
+// The reads overlap_ends() found contained, a byte each: the mask --best-overlaps and --string-graph leave reads out by.
+std::vector<uint8_t> contained_reads(const Job &j)
+{
+    std::vector<uint8_t> skip(j.ends.status.size());
+    for (size_t r = 0; r < skip.size(); ++r) skip[r] = j.ends.status[r] == RAFT_HIP_END_READ_CONTAINED ? 1 : 0;
+    return skip;
+}
+
 // --best-overlaps: the best overlap of every read end and whether it is mutual (raft_hip_best_overlaps_host), directly behind
 // overlap_ends(): on the first context over the same whole stream under the same H, F and symmetric flag, with the reads that phase
 // found contained left out (their status byte is the mask).
@@ -674,8 +686,7 @@ void best_overlaps(Job &j)
 {
     BestOut &o = j.best;
     o.partner.resize((size_t)j.n_reads * 2); o.span.resize((size_t)j.n_reads * 2); o.flags.resize((size_t)j.n_reads);
-    std::vector<uint8_t> skip(j.ends.status.size());
-    for (size_t r = 0; r < skip.size(); ++r) skip[r] = j.ends.status[r] == RAFT_HIP_END_READ_CONTAINED ? 1 : 0;
+    const std::vector<uint8_t> skip = contained_reads(j);
     const raft_hip_records r = records(j);
     int64_t bad_index = -1;
     const int rc = raft_hip_best_overlaps_host(j.ctxs[0], j.n_reads, j.rl, r.n_rec, r.d_qid, r.d_qs, r.d_qe, r.d_tid, r.d_ts, r.d_te, j.strand, skip.data(),
@@ -714,6 +725,31 @@ void components(Job &j)
                                             o.degree.data(), o.first.data(), o.reads.data(), o.bases.data(), o.sides.data(), &o.sum, &bad_index,
                                             nullptr, nullptr);
     done(j, rc, bad_index, "components");
+}
+
+// --string-graph: the dovetails between the reads that are not contained, one arc per pair of read ends, transitively reduced
+// (raft_hip_string_graph_host), behind components(): on the first context over the same whole stream as overlap_ends(), under its H and
+// F, the job's symmetric flag and best_overlaps()' mask.  One call where the edge list fits the first capacity (cli_plan.hpp
+// string_graph_capacity0), which it does unless the graph branches at most ends; else the call says what it needs and runs once more.
+void string_graph(Job &j)
+{
+    StringGraphOut &o = j.sg;
+    const size_t n = (size_t)j.n_reads;
+    o.arcs.resize(2 * n); o.kept.resize(2 * n); o.flags.resize(n);
+    const std::vector<uint8_t> skip = contained_reads(j);
+    const raft_hip_records r = records(j);
+    int64_t bad_index = -1, n_out = 0;
+    const auto call = [&](int64_t cap) {
+        o.u.resize((size_t)cap); o.w.resize((size_t)cap); o.span.resize((size_t)cap);
+        return raft_hip_string_graph_host(j.ctxs[0], j.n_reads, j.rl, r.n_rec, r.d_qid, r.d_qs, r.d_qe, r.d_tid, r.d_ts, r.d_te, j.strand, skip.data(),
+                                          j.p.overlap_ends, j.p.ends_min_ratio, j.sym ? 1 : 0, j.p.string_graph_fuzz, 0, cap, o.arcs.data(), o.kept.data(),
+                                          nullptr, nullptr, o.flags.data(), o.u.data(), o.w.data(), o.span.data(), nullptr, nullptr, nullptr, &n_out,
+                                          &o.sum, &bad_index, nullptr, nullptr);
+    };
+    int rc = call(raft_cli::string_graph_capacity0(r.n_rec, j.n_reads));
+    if (rc == RAFT_HIP_ERR_TOO_LARGE && n_out > (int64_t)o.u.size()) rc = call(n_out);      // (the one refusal that names a size: out_cap below n_out)
+    if (rc == RAFT_HIP_OK) { o.u.resize((size_t)n_out); o.w.resize((size_t)n_out); o.span.resize((size_t)n_out); }
+    done(j, rc, bad_index, "string_graph");
 }
 
 // hifiasm writes its PAF grouped by query (reference README.md:36-38): a symmetric stream of at most four runs sorted by
@@ -974,6 +1010,20 @@ std::string line_components(const Job &j)
                                      s.total_bases, s.reads_in_largest_permille, s.n_reads);
 }
 
+int write_string_graph(Job &j)
+{
+    const StringGraphOut &o = j.sg;
+    return raft_host_write_string_graph(j.p.prefix.c_str(), j.reads, o.arcs.data(), o.kept.data(), o.flags.data(), (int64_t)o.u.size(), o.u.data(), o.w.data(),
+                                        o.span.data());
+}
+std::string line_string_graph(const Job &j)
+{
+    const raft_hip_sg_summary &s = j.sg.sum;
+    return raft_cli::string_graph_line(j.p.string_graph_fuzz, s.records, s.dovetail_views, s.views_left_out, s.arcs, s.duplicate_arcs, s.unpaired_arcs,
+                                       s.reducible_arcs, s.edges, s.kept_edges, s.ends_kept_one, s.ends_kept_more, s.ends_dead, s.ends_mutual,
+                                       s.reads_flagged, s.longest_row, j.n_reads);
+}
+
 int write_fragment_paf(Job &j)
 {
     const LiftOut &o = j.lift;
@@ -1004,6 +1054,7 @@ const Extra kExtras[] = {
     {"best_overlaps", [](const Job &j) { return j.p.best_overlaps; }, Stage::stream, best_overlaps, write_best_overlaps, line_best_overlaps},
     {"unitigs", [](const Job &j) { return j.p.unitigs; }, Stage::stream, unitigs, write_unitigs, line_unitigs},
     {"components", [](const Job &j) { return j.p.components; }, Stage::stream, components, write_components, line_components},
+    {"string_graph", [](const Job &j) { return j.p.string_graph; }, Stage::stream, string_graph, write_string_graph, line_string_graph},
     {"fragment_paf", [](const Job &j) { return j.p.fragment_paf; }, Stage::results, fragment_paf, write_fragment_paf, line_fragment_paf},
 };
 

@@ -94,6 +94,10 @@ LIFT_ABI = {
 CC_ABI = {
     "raft_host_write_components": (C.c_int, [_str, _vp, C.c_int64] + [_vp] * 6),
 }
+# ... and of include/raft_host_sg.h
+SG_ABI = {
+    "raft_host_write_string_graph": (C.c_int, [_str, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp]),
+}
 PAF_QUALITY, PAF_STRAND = 1, 2      # RAFT_HOST_PAF_*: the bits of ``columns``
 
 
@@ -113,7 +117,7 @@ def load_library():
         if not os.path.exists(_LIB_PATH):
             raise RuntimeError(f"{_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         lib = C.CDLL(_LIB_PATH)
-        for table in (ABI, LOW_ABI, OVL_ABI, FRAG_ABI, RST_ABI, FLT_ABI, END_ABI, BEST_ABI, UTG_ABI, LIFT_ABI, CC_ABI):
+        for table in (ABI, LOW_ABI, OVL_ABI, FRAG_ABI, RST_ABI, FLT_ABI, END_ABI, BEST_ABI, UTG_ABI, LIFT_ABI, CC_ABI, SG_ABI):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -282,6 +286,20 @@ def write_components(prefix: str, reads: Reads, res: dict):
         raise ValueError("write_components: the per-read arrays are [n_reads], the per-component arrays [C]")
     rc = load_library().raft_host_write_components(prefix.encode(), reads._h, n_comp, ptr(i32[0]), ptr(i32[1]), ptr(i32[2]), ptr(i32[3]),
                                                    ptr(i64[0]), ptr(i64[1]))
+    if rc != OK:
+        raise HostError(rc, prefix)
+
+
+def write_string_graph(prefix: str, reads: Reads, res: dict):
+    """raft_host_write_string_graph: PREFIX.string_graph.gfa and PREFIX.string_graph.tsv from what ``Engine.string_graph`` returned
+    (``arcs``, ``kept``, ``flags`` and the edge list ``edge_u``, ``edge_w``, ``edge_span``)."""
+    arcs, kept = carray(res["arcs"], np.int32), carray(res["kept"], np.int32)
+    flags = carray(res["flags"], np.uint8)
+    edges = [carray(res[k], np.int32) for k in ("edge_u", "edge_w", "edge_span")]
+    if arcs.size != 2 * reads.n or kept.size != 2 * reads.n or flags.size != reads.n or any(a.size != edges[0].size for a in edges[1:]):
+        raise ValueError("write_string_graph: arcs and kept are [2 * n_reads], flags [n_reads], the edge arrays of one length")
+    rc = load_library().raft_host_write_string_graph(prefix.encode(), reads._h, ptr(arcs), ptr(kept), ptr(flags), edges[0].size,
+                                                     ptr(edges[0]), ptr(edges[1]), ptr(edges[2]))
     if rc != OK:
         raise HostError(rc, prefix)
 
