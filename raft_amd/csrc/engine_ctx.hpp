@@ -294,6 +294,7 @@ template <int N> struct DevBufSet {
     DevBuf &operator[](int k) { return b[k]; }
 };
 constexpr int kSgBufs = 40;           // the buffers of raft_hip_string_graph_* (string_graph_lib.hip SgBuf)
+constexpr int kCtnBufs = 16;          // the buffers of raft_hip_containment_* and raft_hip_place_contained_* (containment_lib.hip CtnBuf)
 
 } // namespace raft
 
@@ -442,6 +443,10 @@ struct raft_hip_ctx {
     // offsets, the items and the sort's pairs, the chosen arcs with their rows, flags and states, the per-node tables, what goes to
     // the caller, the control words, the host form's staging of strand and skip; string_graph_lib.hip names them (SgBuf)
     DevBufSet<kSgBufs> sg{bufs};
+    // raft_hip_containment_* and raft_hip_place_contained_* (containment_lib.hip): one entry for all of their buffers -- the two key
+    // slots with the flag words, the children and the per-root accumulators, the two halves of the pointer jumping's state, what goes
+    // to the caller, the control words, the host forms' staging; containment_lib.hip names them (CtnBuf)
+    DevBufSet<kCtnBufs> ctn{bufs};
     // raft_hip_census_*: counts and flag words per read, the flags as bytes, {first bad record, reads with a flag}; staging of the host form --
     // the census's own and not q_*: it lives in the engine library, whose chunk pool backs the columns (kBig), which the side libraries' must not be
     DevBuf cen_cnt{bufs}, cen_flags{bufs}, cen_out{bufs}, cen_ctl{bufs}, cen_len{bufs};

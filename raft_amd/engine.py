@@ -98,6 +98,9 @@ _CcSummary = _counts_struct("_CcSummary", "n_reads", "n_records", "edge_records"
 _SgSummary = _counts_struct("_SgSummary", "records", "dovetail_views", "views_left_out", "arcs", "duplicate_arcs", "unpaired_arcs", "reducible_arcs",
                             "edges", "removed_edges", "kept_edges", "ends_with_arc", "ends_kept_one", "ends_kept_more", "ends_mutual", "ends_dead",
                             "reads_flagged", "longest_row")
+_CtnSummary = _counts_struct("_CtnSummary", "records", "containment_views", "views_not_longer", "reads_with_parent", "orphans", "roots",
+                             "roots_with_tree", "greatest_depth", "largest_tree_reads", "largest_tree_bases", "launches")
+_PlaceSummary = _counts_struct("_PlaceSummary", "n_reads", "n_unitigs", "placed", "unplaced", "unitigs_gained", "greatest_depth_permille")
 
 
 class _FragTable(C.Structure):      # raft_hip_frag_table and raft_hip_frag_repeats: a count and the three arrays of a CSR table
@@ -278,6 +281,26 @@ SG_ABI = {
 SG_EDGE_RED_U, SG_EDGE_RED_W, SG_EDGE_UNPAIRED = 1, 2, 4      # RAFT_HIP_SG_EDGE_*: the bits of ``edge_flags``
 SG_EDGE_COLUMNS = ("edge_u", "edge_w", "edge_span", "edge_ext", "edge_back", "edge_flags")      # int32, but for edge_flags: uint8
 
+# ... and those of include/raft_hip_ctn.h (libraft_hip_ctn.so): load_side_library("ctn") declares these
+_CTN_CALL = [_vp] + _COLUMNS + [_vp, _i32, _i32, _i32] + [_vp] * 11 + [_P(_CtnSummary), _P(_i64), _P(_f64)]
+_PLACE_CALL = [_vp, _i32] + [_vp] * 7 + [_i32, _vp] + [_vp] * 6 + [_P(_PlaceSummary), _P(_i64), _P(_f64)]
+CTN_ABI = {
+    "raft_hip_ctn_abi": (C.c_int, []),
+    "raft_hip_containment_device": (C.c_int, _CTN_CALL),
+    "raft_hip_containment_host": (C.c_int, _CTN_CALL),
+    "raft_hip_place_contained_device": (C.c_int, _PLACE_CALL),
+    "raft_hip_place_contained_host": (C.c_int, _PLACE_CALL),
+}
+# the bits of a read's flag byte (RAFT_HIP_CTN_*)
+CTN_HAS_PARENT, CTN_PARENT_REV, CTN_ROOT_REV, CTN_UNPLACED_VIEW, CTN_ORPHAN = 1, 2, 4, 8, 16
+CTN_MAX_READS = (1 << 30) - 1
+# what ``Engine.containment`` returns per read (numpy dtypes), in the order of the entry point's outputs
+CTN_PER_READ = (("parent", np.int32), ("pos", np.int32), ("span", np.int32), ("root", np.int32), ("root_pos", np.int32), ("depth", np.int32),
+                ("children", np.int32), ("flags", np.uint8), ("tree_reads", np.int32), ("tree_bases", np.int64), ("tree_depth", np.int32))
+# ... and ``Engine.place_contained``: per read, per unitig
+PLACE_PER_READ = (("placed_unitig", np.int32), ("start", np.int64), ("placed_orient", np.uint8))
+PLACE_PER_UNITIG = (("placed_reads", np.int32), ("placed_bases", np.int64), ("depth_permille", np.int64))
+
 
 @dataclass
 class Summary:
@@ -361,14 +384,20 @@ _SIDE_LATER = {
     "cc": ("libraft_hip_cc.so", CC_ABI, "raft_hip_cc_abi"),
     "sg": ("libraft_hip_sg.so", SG_ABI, "raft_hip_sg_abi"),
 }
+# ... and that one is closed at the two; a third holds what came behind them, and load_side_library looks through every table of
+# _SIDE_TABLES: the next library is a row of the last one.
+_SIDE_THIRD = {
+    "ctn": ("libraft_hip_ctn.so", CTN_ABI, "raft_hip_ctn_abi"),
+}
+_SIDE_TABLES = (_SIDE, _SIDE_LATER, _SIDE_THIRD)
 _side_libs: dict = {}
 
 
 def load_side_library(tag: str) -> C.CDLL:
-    """libraft_hip_<tag>.so of ``_SIDE`` or ``_SIDE_LATER`` (behind libraft_hip.so, whose contexts it takes) with every entry point
+    """libraft_hip_<tag>.so of a table of ``_SIDE_TABLES`` (behind libraft_hip.so, whose contexts it takes) with every entry point
     of include/raft_hip_<tag>.h declared; the two must have been built beside each other."""
     if tag not in _side_libs:
-        file, abi, abi_fn = _SIDE[tag] if tag in _SIDE else _SIDE_LATER[tag]
+        file, abi, abi_fn = next((t[tag] for t in _SIDE_TABLES[:-1] if tag in t), None) or _SIDE_TABLES[-1][tag]
         main = load_library()
         p = os.path.join(os.path.dirname(_LIB_PATH), file)
         if not os.path.exists(p):
@@ -1313,6 +1342,68 @@ class Engine:
             self._check(rc, err.value)
         return {"arcs": arcs, "kept": kept, "partner": partner, "span": span, "flags": flags, **edges, "n_out": m, "summary": _summary_dict(sm),
                 "kernel_seconds": secs.value, "launches": launches.value}
+
+    # -- the containment forest, and the forest on a unitig layout -------------------------------------------
+    last_containment_seconds = 0.0       # device time of the launches of the last containment()
+    last_place_contained_seconds = 0.0   # ... of the last place_contained()
+
+    def containment(self, read_len, qid, qs, qe, tid, ts, te, strand, *, max_overhang: int = 1000, min_ratio_permille: int = 800,
+                    symmetric: bool = False) -> dict:
+        """raft_hip_containment_device / _host (libraft_hip_ctn.so): in which read every contained read sits, where and on which
+        strand, and its place in the read its chain of containers ends in, under the rule of include/raft_hip_ctn.h.  -> per read
+        ``parent`` (int32, -1: none), ``pos``, ``span``, ``root``, ``root_pos``, ``depth``, ``children`` (int32), ``flags`` (uint8,
+        ``CTN_*``), and in the rows of the roots ``tree_reads`` (int32), ``tree_bases`` (int64), ``tree_depth`` (int32); ``summary``
+        (the counts of raft_hip_ctn_summary, ``launches`` among them) and ``kernel_seconds``.  The columns are torch tensors on this
+        engine's device (int32; strand uint8) or numpy arrays (staged by the library).  Unless ``symmetric`` a record of kind
+        ``END_TARGET_CONTAINED`` places its target as well.  Independent of any pass."""
+        cols = [read_len, qid, qs, qe, tid, ts, te]
+        if any(x is None for x in cols) or strand is None:
+            raise ValueError("containment needs read_len, the six columns and strand")
+        ctn = load_side_library("ctn")
+        on_device, cols, (strand,), _, n, _ = self._record_query("containment", cols, rec_u8={"strand": strand})
+        fn = ctn.raft_hip_containment_device if on_device else ctn.raft_hip_containment_host
+        out = {k: np.zeros(n, dt) for k, dt in CTN_PER_READ}
+        sm, err, secs = _CtnSummary(), C.c_int64(-1), C.c_double(0.0)
+        rc = fn(self._ctx, *_plain(cols), M.ptr(strand), int(max_overhang), int(min_ratio_permille), 1 if symmetric else 0,
+                *[M.ptr(a) for a in out.values()], C.byref(sm), C.byref(err), C.byref(secs))
+        self.last_containment_seconds = secs.value
+        self._check(rc, err.value)
+        return {**out, "summary": _summary_dict(sm), "kernel_seconds": secs.value}
+
+    def place_contained(self, read_len, forest, unitig, offset, orient, utg_length) -> dict:
+        """raft_hip_place_contained_device / _host (libraft_hip_ctn.so): the forest ``containment`` returned (``forest``: its dict, of
+        which ``root``, ``root_pos`` and ``flags`` are read) laid onto the layout ``unitigs`` returned (``unitig``, ``offset``,
+        ``orient`` per read; ``utg_length`` per unitig), under the rule of include/raft_hip_ctn.h.  -> per read ``placed_unitig``
+        (int32, -1: unplaced), ``start`` (int64), ``placed_orient`` (uint8, 1: '-'); per unitig ``placed_reads`` (int32, the backbone
+        included), ``placed_bases`` and ``depth_permille`` (int64); ``summary`` (the counts of raft_hip_place_summary) and
+        ``kernel_seconds``.  All arrays are torch tensors on this engine's device (int32; offset and utg_length int64; flags and
+        orient uint8) or all numpy arrays (staged by the library).  A table that names a unitig or a root outside its range raises
+        RaftError(ERR_READ_ID) with the smallest such read as its index.  No wrap on circular unitigs."""
+        given = [read_len, forest["root"], forest["root_pos"], forest["flags"], unitig, offset, orient, utg_length]
+        if any(x is None for x in given):
+            raise ValueError("place_contained needs read_len, the forest, unitig, offset, orient and utg_length")
+        ctn = load_side_library("ctn")
+        on_device = all(hasattr(x, "is_cuda") and x.is_cuda for x in given)
+        dtypes = (np.int32, np.int32, np.int32, np.uint8, np.int32, np.int64, np.uint8, np.int64)
+        if on_device:
+            import torch
+            for x, dt in zip(given, dtypes):
+                if x.dtype != getattr(torch, np.dtype(dt).name) or not x.is_contiguous():
+                    raise TypeError("place_contained needs contiguous CUDA tensors: int32, but offset and utg_length int64, flags and orient uint8")
+            self.use_torch_stream()
+        else:
+            given = [M.carray(x.cpu() if hasattr(x, "is_cuda") else x, dt) for x, dt in zip(given, dtypes)]
+        n, n_utg = M.count(given[0]), M.count(given[7])
+        if any(M.count(x) != n for x in given[1:7]):
+            raise ValueError("place_contained: root, root_pos, flags, unitig, offset and orient are one value per read")
+        fn = ctn.raft_hip_place_contained_device if on_device else ctn.raft_hip_place_contained_host
+        out = {**{k: np.zeros(n, dt) for k, dt in PLACE_PER_READ}, **{k: np.zeros(n_utg, dt) for k, dt in PLACE_PER_UNITIG}}
+        sm, err, secs = _PlaceSummary(), C.c_int64(-1), C.c_double(0.0)
+        rc = fn(self._ctx, n, *[M.ptr(x) for x in given[:7]], n_utg, M.ptr(given[7]), *[M.ptr(a) for a in out.values()], C.byref(sm),
+                C.byref(err), C.byref(secs))
+        self.last_place_contained_seconds = secs.value
+        self._check(rc, err.value)
+        return {**out, "summary": _summary_dict(sm), "kernel_seconds": secs.value}
 
     # -- the overlaps between the fragments ------------------------------------------------------------------
     last_lift_overlaps_seconds = 0.0     # device time of the launches of the last lift_overlaps()

@@ -326,6 +326,25 @@ inline std::string string_graph_line(int32_t fuzz, int64_t records, int64_t view
            std::to_string(reads_flagged) + " of " + std::to_string(n_reads) + ", longest row = " + std::to_string(longest_row);
 }
 
+// --containment: the option's stdout line, behind string_graph's and before fragment_paf's, from raft_hip_ctn_summary's counts
+inline std::string containment_line(int64_t records, int64_t views, int64_t not_longer, int64_t with_parent, int64_t orphans, int64_t roots,
+                                    int64_t roots_with_tree, int64_t deepest, int64_t largest_reads, int64_t largest_bases)
+{
+    return "INFO, containment(), records = " + std::to_string(records) + ", containment views = " + std::to_string(views) + ", not longer = " +
+           std::to_string(not_longer) + ", reads with a parent = " + std::to_string(with_parent) + ", contained without a parent = " +
+           std::to_string(orphans) + ", roots = " + std::to_string(roots) + ", roots with a tree = " + std::to_string(roots_with_tree) +
+           ", deepest = " + std::to_string(deepest) + ", largest tree = " + std::to_string(largest_reads) + " reads, largest tree bases = " +
+           std::to_string(largest_bases);
+}
+
+// ... and, with --unitigs, the line behind it, from raft_hip_place_summary's counts
+inline std::string place_contained_line(int64_t unitigs, int64_t placed, int64_t unplaced, int64_t n_reads, int64_t gained, int64_t greatest_permille)
+{
+    return "INFO, place_contained(), unitigs = " + std::to_string(unitigs) + ", placed = " + std::to_string(placed) + ", unplaced = " +
+           std::to_string(unplaced) + " of " + std::to_string(n_reads) + ", unitigs that gained reads = " + std::to_string(gained) +
+           ", greatest depth = " + std::to_string(greatest_permille) + " per mille";
+}
+
 // --fragment-paf: PREFIX.fragments.paf, the job's overlaps lifted onto its fragments (raft_hip_lift_overlaps_host).
 // --fragment-paf-min L: L (min_len of that call) is a whole number >= 1 written in digits alone, at most INT32_MAX; without the option it is
 constexpr int32_t kFragmentPafMinDefault = 1;
@@ -355,6 +374,7 @@ struct Options {
     bool ends_ratio_given = false, fragment_paf_min_given = false;
     int32_t string_graph_fuzz = kStringGraphFuzzDefault;
     bool string_graph_fuzz_given = false;
+    bool containment = false;
 };
 
 // The long options, one row each: the text's parser (none: a flag, which takes no argument), the value it writes, and the flag
@@ -389,7 +409,7 @@ constexpr size_t long_option_count() { return kLongOptionCount + sizeof(kLaterLo
 constexpr const LongOption &long_option(size_t k) { return k < kLongOptionCount ? kLongOptions[k] : kLaterLongOptions[k - kLongOptionCount]; }
 
 // Those two are what long_option counts through, and that stays so: 14 rows.  The options behind them stand in a third table, and
-// the command line is built over all three -- any_long_option(k), k < any_long_option_count().
+// any_long_option(k), k < any_long_option_count(), counts through all three (the command line itself walks kLongOptionTables, below).
 inline constexpr LongOption kStringGraphLongOptions[] = {
     {"string-graph", nullptr, nullptr, &Options::string_graph},             // PREFIX.string_graph.gfa and .string_graph.tsv, the transitively reduced dovetails under --overlap-ends' H and F
     {"string-graph-fuzz", parse_string_graph_fuzz, &Options::string_graph_fuzz, &Options::string_graph_fuzz_given},   // Z: how far a path may miss the arc it implies
@@ -397,6 +417,35 @@ inline constexpr LongOption kStringGraphLongOptions[] = {
 
 constexpr size_t any_long_option_count() { return long_option_count() + sizeof(kStringGraphLongOptions) / sizeof(kStringGraphLongOptions[0]); }
 constexpr const LongOption &any_long_option(size_t k) { return k < long_option_count() ? long_option(k) : kStringGraphLongOptions[k - long_option_count()]; }
+
+// Those three are what any_long_option counts through, and that stays so: 16 rows.  What came behind stands in a fourth table, and the
+// command line -- getopt's array, the lookup of a row it found, the check programs -- walks ONE list of tables: the next option is a
+// row of the last table, or a table more in the list, and needs no accessor of its own.
+inline constexpr LongOption kContainmentLongOptions[] = {
+    {"containment", nullptr, nullptr, &Options::containment},               // PREFIX.containment.tsv (with --unitigs also .unitigs.depth.tsv), the forest of the contained reads under --overlap-ends' H and F
+};
+
+struct LongOptionTable { const LongOption *rows; size_t count; };
+inline constexpr LongOptionTable kLongOptionTables[] = {
+    {kLongOptions, sizeof(kLongOptions) / sizeof(kLongOptions[0])},
+    {kLaterLongOptions, sizeof(kLaterLongOptions) / sizeof(kLaterLongOptions[0])},
+    {kStringGraphLongOptions, sizeof(kStringGraphLongOptions) / sizeof(kStringGraphLongOptions[0])},
+    {kContainmentLongOptions, sizeof(kContainmentLongOptions) / sizeof(kContainmentLongOptions[0])},
+};
+
+constexpr size_t every_long_option_count()
+{
+    size_t n = 0;
+    for (const LongOptionTable &t : kLongOptionTables) n += t.count;
+    return n;
+}
+// row k of the tables laid end to end, k < every_long_option_count()
+constexpr const LongOption &every_long_option(size_t k)
+{
+    size_t t = 0;
+    while (k >= kLongOptionTables[t].count) k -= kLongOptionTables[t++].count;
+    return kLongOptionTables[t].rows[k];
+}
 
 // One long option as getopt found it (text: its argument, NULL for a flag).  false: the text is not what the option takes -- a
 // usage error, and the value is left alone.
@@ -410,12 +459,12 @@ inline bool set_long_option(const LongOption &o, const char *text, Options *p)
 // The options that mean nothing without another: --ends-min-ratio needs --overlap-ends; --best-overlaps needs it too (it takes its H
 // and F from it and its mask from that option's status bytes); --unitigs needs --best-overlaps, whose table it walks;
 // --fragment-paf-min needs --fragment-paf; --components needs --overlap-ends, whose H and F it classifies under, and so does
-// --string-graph; --string-graph-fuzz needs --string-graph.  false: a usage error.
+// --string-graph; --string-graph-fuzz needs --string-graph; --containment needs --overlap-ends for the same reason.  false: a usage error.
 inline bool usage_ok(const Options &o)
 {
     return (o.overlap_ends >= 0 || !o.ends_ratio_given) && (!o.best_overlaps || o.overlap_ends >= 0) && (!o.unitigs || o.best_overlaps) &&
            (o.fragment_paf || !o.fragment_paf_min_given) && (!o.components || o.overlap_ends >= 0) &&
-           (!o.string_graph || o.overlap_ends >= 0) && (o.string_graph || !o.string_graph_fuzz_given);
+           (!o.string_graph || o.overlap_ends >= 0) && (o.string_graph || !o.string_graph_fuzz_given) && (!o.containment || o.overlap_ends >= 0);
 }
 
 // What the options ask of the job between them, decided once (prepare: the group offsets and window records are made by the

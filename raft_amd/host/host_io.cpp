@@ -23,6 +23,7 @@
 #include "../../include/raft_host_lift.h"
 #include "../../include/raft_host_cc.h"
 #include "../../include/raft_host_sg.h"
+#include "../../include/raft_host_ctn.h"
 
 #include <emmintrin.h>
 #include <zlib.h>
@@ -1298,6 +1299,65 @@ int raft_host_write_components(const char *prefix, const raft_host_reads *reads,
                              o.push_back('\t'); put_num(o, comp_bases[k]);
                              o.push_back('\t'); put_num(o, comp_sides[k]);
                              o.push_back('\t'); o.append(reads->names.name(comp_first[k]), reads->names.name_len(comp_first[k]));
+                             o.push_back('\n');
+                         });
+}
+
+// PREFIX.containment.tsv (include/raft_host_ctn.h): one line per read.  A table that names a parent, a root or a unitig outside its
+// range is refused before anything is written.
+int raft_host_write_containment(const char *path, const raft_host_reads *reads, const int32_t *parent, const int32_t *pos, const int32_t *span,
+                                const int32_t *root, const int32_t *root_pos, const int32_t *depth, const int32_t *children, const uint8_t *flags,
+                                const int32_t *tree_reads, const int64_t *tree_bases, const int32_t *placed_unitig, const int64_t *start,
+                                const uint8_t *placed_orient)
+{
+    if (!path || !reads) return RAFT_HOST_ERR_ARG;
+    const long long n = (long long)reads->lens.size();
+    if (n > 0 && (!parent || !pos || !span || !root || !root_pos || !depth || !children || !flags || !tree_reads || !tree_bases)) return RAFT_HOST_ERR_ARG;
+    const bool placed = placed_unitig != nullptr;
+    if (placed != (start != nullptr) || placed != (placed_orient != nullptr)) return RAFT_HOST_ERR_ARG;
+    for (long long i = 0; i < n; ++i)
+        if (parent[i] < -1 || parent[i] >= n || root[i] < 0 || root[i] >= n || (placed && placed_unitig[i] < -1)) return RAFT_HOST_ERR_ARG;
+    const auto put_name = [&](std::string &o, int32_t r) { o.append(reads->names.name(r), reads->names.name_len(r)); };
+    return write_ordered(path, n, 1 << 16, [](long long) { return 1LL; },
+                         [&](long long i, std::string &o) {
+                             put_name(o, (int32_t)i);
+                             o.push_back('\t'); put_num(o, reads->lens[(size_t)i]);
+                             if (parent[i] >= 0) {
+                                 o.push_back('\t'); put_name(o, parent[i]);
+                                 o.push_back('\t'); o.push_back((flags[i] & 2u) ? '-' : '+');
+                                 o.push_back('\t'); put_num(o, pos[i]);
+                                 o.push_back('\t'); put_num(o, span[i]);
+                             } else o.append("\t*\t*\t0\t0");
+                             o.push_back('\t'); put_name(o, root[i]);
+                             o.push_back('\t'); o.push_back((flags[i] & 4u) ? '-' : '+');
+                             o.push_back('\t'); put_num(o, root_pos[i]);
+                             o.push_back('\t'); put_num(o, depth[i]);
+                             o.push_back('\t'); put_num(o, children[i]);
+                             o.push_back('\t'); put_num(o, tree_reads[i]);
+                             o.push_back('\t'); put_num(o, tree_bases[i]);
+                             if (placed && placed_unitig[i] >= 0) {
+                                 o.push_back('\t'); put_num(o, placed_unitig[i]);
+                                 o.push_back('\t'); put_num(o, start[i]);
+                                 o.push_back('\t'); o.push_back(placed_orient[i] ? '-' : '+');
+                             } else o.append("\t*\t0\t*");
+                             o.push_back('\n');
+                         });
+}
+
+// PREFIX.unitigs.depth.tsv (include/raft_host_ctn.h): one line per unitig.
+int raft_host_write_unitig_depth(const char *path, int64_t n_unitigs, const int32_t *utg_reads, const int64_t *utg_length, const int32_t *placed_reads,
+                                 const int64_t *placed_bases, const int64_t *depth_permille)
+{
+    if (!path || n_unitigs < 0) return RAFT_HOST_ERR_ARG;
+    if (n_unitigs > 0 && (!utg_reads || !utg_length || !placed_reads || !placed_bases || !depth_permille)) return RAFT_HOST_ERR_ARG;
+    return write_ordered(path, (long long)n_unitigs, 1 << 16, [](long long) { return 1LL; },
+                         [&](long long u, std::string &o) {
+                             put_num(o, u);
+                             o.push_back('\t'); put_num(o, utg_reads[u]);
+                             o.push_back('\t'); put_num(o, utg_length[u]);
+                             o.push_back('\t'); put_num(o, placed_reads[u]);
+                             o.push_back('\t'); put_num(o, placed_bases[u]);
+                             o.push_back('\t'); put_num(o, depth_permille[u]);
                              o.push_back('\n');
                          });
 }

@@ -35,6 +35,8 @@
 #include "../../include/raft_host_cc.h"
 #include "../../include/raft_hip_sg.h"
 #include "../../include/raft_host_sg.h"
+#include "../../include/raft_hip_ctn.h"
+#include "../../include/raft_host_ctn.h"
 #include "../../include/raft_host.h"
 #include "cli_plan.hpp"
 
@@ -83,6 +85,10 @@ struct UnitigOut { std::vector<int32_t> unitig, index, order, reads; std::vector
 struct ComponentsOut { std::vector<int32_t> component, degree, first, reads; std::vector<int64_t> bases, sides; raft_hip_cc_summary sum{}; };
 // --string-graph: per read end the arcs and the survivors, per read the flag byte; the surviving edges (nodes and span)
 struct StringGraphOut { std::vector<int32_t> arcs, kept, u, w, span; std::vector<uint8_t> flags; raft_hip_sg_summary sum{}; };
+// --containment: per read the parent with the place in it, the root with the place in it, the depth, the children, the flag byte; per root its tree
+struct ContainmentOut { std::vector<int32_t> parent, pos, span, root, root_pos, depth, children, tree_reads; std::vector<int64_t> tree_bases; std::vector<uint8_t> flags; raft_hip_ctn_summary sum{}; };
+// ... with --unitigs: per read the unitig, the start and the orientation; per unitig the reads, the bases and the depth
+struct PlaceOut { std::vector<int32_t> unitig, reads; std::vector<int64_t> start, bases, permille; std::vector<uint8_t> orient; raft_hip_place_summary sum{}; };
 struct LiftOut { std::vector<int32_t> col[6], src; std::vector<uint8_t> rev; raft_hip_lift_summary sum{}; };   // --fragment-paf: the eight columns of the lifted stream
 
 struct Job {
@@ -117,7 +123,7 @@ struct Job {
     std::vector<int32_t> qid_kept;                              // the query column as tokenised, where prepare_input writes over it (Request::keep_query_ids)
     // the optional outputs, in the order of kExtras
     FilterOut flt; ReadStatsOut rs; LowCovOut low; RepeatOverlapsOut ovl; FragmentOverlapsOut frag;
-    RepeatStatsOut rst; EndsOut ends; BestOut best; UnitigOut utg; ComponentsOut cc; StringGraphOut sg; LiftOut lift;
+    RepeatStatsOut rst; EndsOut ends; BestOut best; UnitigOut utg; ComponentsOut cc; StringGraphOut sg; ContainmentOut ctn; PlaceOut plc; LiftOut lift;
     // the arrays everything comes back in (made and page-locked on out_prep)
     raft_cli::Capacities cap;
     std::vector<int64_t> cov_off, rep_off, frag_off;
@@ -225,15 +231,15 @@ const char *const *names(Job &j)
 void parse_options(Job &j, int argc, char *argv[])
 {
     Options &p = j.p;
-    // (the short options and their quirks are the reference's; the long options are this program's own, the rows of cli_plan.hpp
-    // three tables, counted through by any_long_option(k): getopt_long returns 0 for them and says which row)
-    constexpr size_t n_long = raft_cli::any_long_option_count();
+    // (the short options and their quirks are the reference's; the long options are this program's own, the rows of cli_plan.hpp's
+    // list of tables, counted through by every_long_option(k): getopt_long returns 0 for them and says which row)
+    constexpr size_t n_long = raft_cli::every_long_option_count();
     struct option long_options[n_long + 1] = {};
-    for (size_t k = 0; k < n_long; ++k) long_options[k] = {raft_cli::any_long_option(k).name, raft_cli::any_long_option(k).parse ? required_argument : no_argument, nullptr, 0};
+    for (size_t k = 0; k < n_long; ++k) long_options[k] = {raft_cli::every_long_option(k).name, raft_cli::every_long_option(k).parse ? required_argument : no_argument, nullptr, 0};
     int option, row = 0;
     while ((option = getopt_long(argc, argv, "r:e:m:l:i:p:f:v:o:", long_options, &row)) != -1) {
         switch (option) {
-        case 0: if (!raft_cli::set_long_option(raft_cli::any_long_option((size_t)row), optarg, &p)) print_help(p); break;
+        case 0: if (!raft_cli::set_long_option(raft_cli::every_long_option((size_t)row), optarg, &p)) print_help(p); break;
         case 'r': p.reso = atoi(optarg); break;
         case 'e': p.auto_cov = strcmp(optarg, "auto") == 0; p.est_cov = p.auto_cov ? 0 : atoi(optarg); break;
         case 'm': p.cov_mul = std::stod(optarg); break;
@@ -752,6 +758,37 @@ void string_graph(Job &j)
     done(j, rc, bad_index, "string_graph");
 }
 
+// --containment: the forest of the contained reads (raft_hip_containment_host), behind string_graph(): on the first context over the same
+// whole stream as overlap_ends(), under its H and F and the job's symmetric flag.
+void containment(Job &j)
+{
+    ContainmentOut &o = j.ctn;
+    const size_t n = (size_t)j.n_reads;
+    o.parent.resize(n); o.pos.resize(n); o.span.resize(n); o.root.resize(n); o.root_pos.resize(n); o.depth.resize(n); o.children.resize(n);
+    o.flags.resize(n); o.tree_reads.resize(n); o.tree_bases.resize(n);
+    const raft_hip_records r = records(j);
+    int64_t bad_index = -1;
+    const int rc = raft_hip_containment_host(j.ctxs[0], j.n_reads, j.rl, r.n_rec, r.d_qid, r.d_qs, r.d_qe, r.d_tid, r.d_ts, r.d_te, j.strand,
+                                             j.p.overlap_ends, j.p.ends_min_ratio, j.sym ? 1 : 0, o.parent.data(), o.pos.data(), o.span.data(),
+                                             o.root.data(), o.root_pos.data(), o.depth.data(), o.children.data(), o.flags.data(), o.tree_reads.data(),
+                                             o.tree_bases.data(), nullptr, &o.sum, &bad_index, nullptr);
+    done(j, rc, bad_index, "containment");
+}
+
+// ... with --unitigs: that forest on the layout unitigs() holds (raft_hip_place_contained_host), directly behind containment().
+void place_contained(Job &j)
+{
+    PlaceOut &o = j.plc;
+    const size_t n = (size_t)j.n_reads, n_utg = (size_t)j.utg.sum.unitigs;
+    o.unitig.resize(n); o.start.resize(n); o.orient.resize(n); o.reads.resize(n_utg); o.bases.resize(n_utg); o.permille.resize(n_utg);
+    int64_t bad_index = -1;
+    const int rc = raft_hip_place_contained_host(j.ctxs[0], j.n_reads, j.rl, j.ctn.root.data(), j.ctn.root_pos.data(), j.ctn.flags.data(), j.utg.unitig.data(),
+                                                 j.utg.offset.data(), j.utg.orient.data(), (int32_t)n_utg, j.utg.length.data(), o.unitig.data(),
+                                                 o.start.data(), o.orient.data(), o.reads.data(), o.bases.data(), o.permille.data(), &o.sum, &bad_index,
+                                                 nullptr);
+    done(j, rc, bad_index, "place_contained");
+}
+
 // hifiasm writes its PAF grouped by query (reference README.md:36-38): a symmetric stream of at most four runs sorted by
 // read id is handed over in its grouped form -- per run, where every read's records begin -- and the query column stays
 // on the host (a third of the upload); any other stream goes up as it is.
@@ -1024,6 +1061,34 @@ std::string line_string_graph(const Job &j)
                                        s.reads_flagged, s.longest_row, j.n_reads);
 }
 
+// (the placed columns are there with --unitigs: place_contained() ran)
+int write_containment(Job &j)
+{
+    const ContainmentOut &o = j.ctn;
+    const bool placed = j.p.unitigs;
+    return raft_host_write_containment((j.p.prefix + ".containment.tsv").c_str(), j.reads, o.parent.data(), o.pos.data(), o.span.data(), o.root.data(),
+                                       o.root_pos.data(), o.depth.data(), o.children.data(), o.flags.data(), o.tree_reads.data(), o.tree_bases.data(),
+                                       placed ? j.plc.unitig.data() : nullptr, placed ? j.plc.start.data() : nullptr, placed ? j.plc.orient.data() : nullptr);
+}
+std::string line_containment(const Job &j)
+{
+    const raft_hip_ctn_summary &s = j.ctn.sum;
+    return raft_cli::containment_line(s.records, s.containment_views, s.views_not_longer, s.reads_with_parent, s.orphans, s.roots, s.roots_with_tree,
+                                      s.greatest_depth, s.largest_tree_reads, s.largest_tree_bases);
+}
+
+int write_unitig_depth(Job &j)
+{
+    const PlaceOut &o = j.plc;
+    return raft_host_write_unitig_depth((j.p.prefix + ".unitigs.depth.tsv").c_str(), j.utg.sum.unitigs, j.utg.reads.data(), j.utg.length.data(), o.reads.data(),
+                                        o.bases.data(), o.permille.data());
+}
+std::string line_place_contained(const Job &j)
+{
+    const raft_hip_place_summary &s = j.plc.sum;
+    return raft_cli::place_contained_line(s.n_unitigs, s.placed, s.unplaced, s.n_reads, s.unitigs_gained, s.greatest_depth_permille);
+}
+
 int write_fragment_paf(Job &j)
 {
     const LiftOut &o = j.lift;
@@ -1055,6 +1120,8 @@ const Extra kExtras[] = {
     {"unitigs", [](const Job &j) { return j.p.unitigs; }, Stage::stream, unitigs, write_unitigs, line_unitigs},
     {"components", [](const Job &j) { return j.p.components; }, Stage::stream, components, write_components, line_components},
     {"string_graph", [](const Job &j) { return j.p.string_graph; }, Stage::stream, string_graph, write_string_graph, line_string_graph},
+    {"containment", [](const Job &j) { return j.p.containment; }, Stage::stream, containment, write_containment, line_containment},
+    {"place_contained", [](const Job &j) { return j.p.containment && j.p.unitigs; }, Stage::stream, place_contained, write_unitig_depth, line_place_contained},
     {"fragment_paf", [](const Job &j) { return j.p.fragment_paf; }, Stage::results, fragment_paf, write_fragment_paf, line_fragment_paf},
 };
 

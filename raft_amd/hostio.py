@@ -98,6 +98,11 @@ CC_ABI = {
 SG_ABI = {
     "raft_host_write_string_graph": (C.c_int, [_str, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp]),
 }
+# ... and of include/raft_host_ctn.h
+CTN_ABI = {
+    "raft_host_write_containment": (C.c_int, [_str, _vp] + [_vp] * 13),
+    "raft_host_write_unitig_depth": (C.c_int, [_str, C.c_int64] + [_vp] * 5),
+}
 PAF_QUALITY, PAF_STRAND = 1, 2      # RAFT_HOST_PAF_*: the bits of ``columns``
 
 
@@ -117,7 +122,7 @@ def load_library():
         if not os.path.exists(_LIB_PATH):
             raise RuntimeError(f"{_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         lib = C.CDLL(_LIB_PATH)
-        for table in (ABI, LOW_ABI, OVL_ABI, FRAG_ABI, RST_ABI, FLT_ABI, END_ABI, BEST_ABI, UTG_ABI, LIFT_ABI, CC_ABI, SG_ABI):
+        for table in (ABI, LOW_ABI, OVL_ABI, FRAG_ABI, RST_ABI, FLT_ABI, END_ABI, BEST_ABI, UTG_ABI, LIFT_ABI, CC_ABI, SG_ABI, CTN_ABI):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -302,6 +307,33 @@ def write_string_graph(prefix: str, reads: Reads, res: dict):
                                                      ptr(edges[0]), ptr(edges[1]), ptr(edges[2]))
     if rc != OK:
         raise HostError(rc, prefix)
+
+
+def write_containment(path: str, reads: Reads, res: dict, placed: dict | None = None):
+    """raft_host_write_containment: PREFIX.containment.tsv from what ``Engine.containment`` returned and, where given, what
+    ``Engine.place_contained`` returned (``placed_unitig``, ``start``, ``placed_orient``); without it the last three columns are ``* 0 *``."""
+    i32 = [carray(res[k], np.int32) for k in ("parent", "pos", "span", "root", "root_pos", "depth", "children")]
+    flags, tree_reads, tree_bases = carray(res["flags"], np.uint8), carray(res["tree_reads"], np.int32), carray(res["tree_bases"], np.int64)
+    tail = [None, None, None] if placed is None else [carray(placed["placed_unitig"], np.int32), carray(placed["start"], np.int64),
+                                                      carray(placed["placed_orient"], np.uint8)]
+    if any(a.size != reads.n for a in (*i32, flags, tree_reads, tree_bases, *[a for a in tail if a is not None])):
+        raise ValueError("write_containment: every array is [n_reads]")
+    rc = load_library().raft_host_write_containment(path.encode(), reads._h, *[ptr(a) for a in i32], ptr(flags), ptr(tree_reads), ptr(tree_bases),
+                                                    *[ptr(a) for a in tail])
+    if rc != OK:
+        raise HostError(rc, path)
+
+
+def write_unitig_depth(path: str, utg_reads, utg_length, placed: dict):
+    """raft_host_write_unitig_depth: PREFIX.unitigs.depth.tsv from ``Engine.unitigs``' ``utg_reads`` and ``utg_length`` and what
+    ``Engine.place_contained`` returned (``placed_reads``, ``placed_bases``, ``depth_permille``)."""
+    arrays = [carray(utg_reads, np.int32), carray(utg_length, np.int64), carray(placed["placed_reads"], np.int32),
+              carray(placed["placed_bases"], np.int64), carray(placed["depth_permille"], np.int64)]
+    if any(a.size != arrays[0].size for a in arrays[1:]):
+        raise ValueError("write_unitig_depth: every array is [U]")
+    rc = load_library().raft_host_write_unitig_depth(path.encode(), arrays[0].size, *[ptr(a) for a in arrays])
+    if rc != OK:
+        raise HostError(rc, path)
 
 
 def write_unitigs(prefix: str, reads: Reads, res: dict):
