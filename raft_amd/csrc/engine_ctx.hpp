@@ -295,6 +295,7 @@ template <int N> struct DevBufSet {
 };
 constexpr int kSgBufs = 40;           // the buffers of raft_hip_string_graph_* (string_graph_lib.hip SgBuf)
 constexpr int kCtnBufs = 16;          // the buffers of raft_hip_containment_* and raft_hip_place_contained_* (containment_lib.hip CtnBuf)
+constexpr int kClnBufs = 29;         // the buffers of raft_hip_graph_clean_* (graph_clean_lib.hip ClnBuf)
 
 } // namespace raft
 
@@ -447,6 +448,10 @@ struct raft_hip_ctx {
     // slots with the flag words, the children and the per-root accumulators, the two halves of the pointer jumping's state, what goes
     // to the caller, the control words, the host forms' staging; containment_lib.hip names them (CtnBuf)
     DevBufSet<kCtnBufs> ctn{bufs};
+    // raft_hip_graph_clean_* (graph_clean_lib.hip): one entry for all of its buffers -- the items and the sort's pairs, the arcs with
+    // their rows and live bytes, the per-node and per-read tables, the two halves of the ranking's state, the chain records, what
+    // goes to the caller, the control words, the host form's staging of skip; graph_clean_lib.hip names them (ClnBuf)
+    DevBufSet<kClnBufs> cln{bufs};
     // raft_hip_census_*: counts and flag words per read, the flags as bytes, {first bad record, reads with a flag}; staging of the host form --
     // the census's own and not q_*: it lives in the engine library, whose chunk pool backs the columns (kBig), which the side libraries' must not be
     DevBuf cen_cnt{bufs}, cen_flags{bufs}, cen_out{bufs}, cen_ctl{bufs}, cen_len{bufs};

@@ -97,6 +97,23 @@ __global__ __launch_bounds__(kUtgThreads) void utg_jump_kernel(const UtgState *_
     }
 }
 
+// One ranking on stream st: the init kernel, then `rounds` rounds from one half of the state into the other, beginning with half[0].
+// Returns the half the last round wrote; with `count` the last round counts the half-edges still under way.  The kernels it
+// launched are added to *launches.  (unitig_lib.hip and graph_clean_lib.hip rank with it.)
+inline UtgState *utg_rank(hipStream_t st, int32_t n_reads, const int32_t *len, const int32_t *partner, const int32_t *span, const uint8_t *flags,
+                          const uint8_t *cut, UtgState *const (&half)[2], unsigned long long *ctl, int rounds, bool count, int64_t *launches)
+{
+    const long long n_half = 2 * (long long)n_reads;
+    hipLaunchKernelGGL(utg_init_kernel, dim3(utg_grid(n_reads)), dim3(kUtgThreads), 0, st, n_reads, len, partner, span, flags, cut, half[0], ctl);
+    const dim3 grid(utg_grid(n_half)), block(kUtgThreads);
+    for (int k = 0; k < rounds; ++k) {
+        if (count && k == rounds - 1) hipLaunchKernelGGL(utg_jump_kernel<true>, grid, block, 0, st, half[k & 1], half[(k + 1) & 1], n_half, ctl);
+        else hipLaunchKernelGGL(utg_jump_kernel<false>, grid, block, 0, st, half[k & 1], half[(k + 1) & 1], n_half, ctl);
+    }
+    *launches += 1 + rounds;
+    return half[rounds & 1];
+}
+
 __global__ __launch_bounds__(kUtgThreads) void utg_mark_kernel(const UtgState *__restrict__ state, int32_t n_reads, uint8_t *__restrict__ cut)
 {
     const long long stride = (long long)gridDim.x * blockDim.x;

@@ -39,17 +39,8 @@ int check_call(raft_hip_ctx *c, const UtgCall &a)
 void rank(raft_hip_ctx *c, const UtgCall &a, const uint8_t *cut, int rounds, bool count, UtgState **final_half, int64_t *launches)
 {
     const long long n_half = 2 * (long long)a.n_reads;
-    UtgState *half[2] = {c->ut_state.as<UtgState>(), c->ut_state.as<UtgState>() + n_half};
-    unsigned long long *ctl = c->ut_ctl.as<unsigned long long>();
-    hipLaunchKernelGGL(utg_init_kernel, dim3(utg_grid(a.n_reads)), dim3(kUtgThreads), 0, c->stream, a.n_reads, a.len, a.partner, a.span, a.flags, cut,
-                       half[0], ctl);
-    const dim3 grid(utg_grid(n_half)), block(kUtgThreads);
-    for (int k = 0; k < rounds; ++k) {
-        if (count && k == rounds - 1) hipLaunchKernelGGL(utg_jump_kernel<true>, grid, block, 0, c->stream, half[k & 1], half[(k + 1) & 1], n_half, ctl);
-        else hipLaunchKernelGGL(utg_jump_kernel<false>, grid, block, 0, c->stream, half[k & 1], half[(k + 1) & 1], n_half, ctl);
-    }
-    *final_half = half[rounds & 1];
-    *launches += 1 + rounds;
+    UtgState *const half[2] = {c->ut_state.as<UtgState>(), c->ut_state.as<UtgState>() + n_half};
+    *final_half = utg_rank(c->stream, a.n_reads, a.len, a.partner, a.span, a.flags, cut, half, c->ut_ctl.as<unsigned long long>(), rounds, count, launches);
 }
 
 // a: device arrays but for the outputs

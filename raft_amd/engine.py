@@ -101,6 +101,9 @@ _SgSummary = _counts_struct("_SgSummary", "records", "dovetail_views", "views_le
 _CtnSummary = _counts_struct("_CtnSummary", "records", "containment_views", "views_not_longer", "reads_with_parent", "orphans", "roots",
                              "roots_with_tree", "greatest_depth", "largest_tree_reads", "largest_tree_bases", "launches")
 _PlaceSummary = _counts_struct("_PlaceSummary", "n_reads", "n_unitigs", "placed", "unplaced", "unitigs_gained", "greatest_depth_permille")
+_ClnSummary = _counts_struct("_ClnSummary", "reads", "reads_flagged", "edges", "weak_arcs", "weak_edges", "rounds_run", "converged", "tips", "tip_reads",
+                             "tip_bases", "tip_edges", "candidates_kept", "isolated_short", "kept_edges", "ends_kept_one", "ends_kept_more",
+                             "ends_mutual", "ends_dead", "longest_row")
 
 
 class _FragTable(C.Structure):      # raft_hip_frag_table and raft_hip_frag_repeats: a count and the three arrays of a CSR table
@@ -301,6 +304,18 @@ CTN_PER_READ = (("parent", np.int32), ("pos", np.int32), ("span", np.int32), ("r
 PLACE_PER_READ = (("placed_unitig", np.int32), ("start", np.int64), ("placed_orient", np.uint8))
 PLACE_PER_UNITIG = (("placed_reads", np.int32), ("placed_bases", np.int64), ("depth_permille", np.int64))
 
+# ... and those of include/raft_hip_cln.h (libraft_hip_cln.so): load_side_library("cln") declares these
+# ctx, n_reads, read_len, skip, n_edges, the three edge columns, W, T, R, the fourteen outputs
+_CLN_CALL = [_vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32] + [_vp] * 10 + [_P(_ClnSummary), _P(_i64), _P(_f64), _P(_i64)]
+CLN_ABI = {
+    "raft_hip_cln_abi": (C.c_int, []),
+    "raft_hip_graph_clean_device": (C.c_int, _CLN_CALL),
+    "raft_hip_graph_clean_host": (C.c_int, _CLN_CALL),
+}
+CLN_WEAK_U, CLN_WEAK_W, CLN_TIP = 1, 2, 4                      # RAFT_HIP_CLN_*: the bits of ``edge_state``
+CLN_READ_STAYS, CLN_READ_TIP, CLN_READ_FLAGGED = 0, 1, 2      # RAFT_HIP_CLN_READ_*: ``read_state``
+CLN_MAX_ROUNDS = 64
+
 
 @dataclass
 class Summary:
@@ -390,14 +405,18 @@ _SIDE_THIRD = {
     "ctn": ("libraft_hip_ctn.so", CTN_ABI, "raft_hip_ctn_abi"),
 }
 _SIDE_TABLES = (_SIDE, _SIDE_LATER, _SIDE_THIRD)
+# Those three are closed.  _SIDE_OPEN is the open one: the next library is a row here, and nothing counts its rows.
+_SIDE_OPEN = {
+    "cln": ("libraft_hip_cln.so", CLN_ABI, "raft_hip_cln_abi"),
+}
 _side_libs: dict = {}
 
 
 def load_side_library(tag: str) -> C.CDLL:
-    """libraft_hip_<tag>.so of a table of ``_SIDE_TABLES`` (behind libraft_hip.so, whose contexts it takes) with every entry point
-    of include/raft_hip_<tag>.h declared; the two must have been built beside each other."""
+    """libraft_hip_<tag>.so of a table of ``_SIDE_TABLES`` or of ``_SIDE_OPEN`` (behind libraft_hip.so, whose contexts it takes) with
+    every entry point of include/raft_hip_<tag>.h declared; the two must have been built beside each other."""
     if tag not in _side_libs:
-        file, abi, abi_fn = next((t[tag] for t in _SIDE_TABLES[:-1] if tag in t), None) or _SIDE_TABLES[-1][tag]
+        file, abi, abi_fn = next((t[tag] for t in _SIDE_TABLES if tag in t), None) or _SIDE_OPEN[tag]
         main = load_library()
         p = os.path.join(os.path.dirname(_LIB_PATH), file)
         if not os.path.exists(p):
@@ -1404,6 +1423,43 @@ class Engine:
         self.last_place_contained_seconds = secs.value
         self._check(rc, err.value)
         return {**out, "summary": _summary_dict(sm), "kernel_seconds": secs.value}
+
+    # -- a string graph cleaned: the weak edges cut, the tips removed ----------------------------------------
+    last_graph_clean_seconds = 0.0       # device time of the launches of the last graph_clean()
+    last_graph_clean_launches = 0        # ... and how many there were
+
+    def graph_clean(self, read_len, edge_u, edge_w, edge_span, *, skip=None, min_ratio_permille: int = 500, max_tip_reads: int = 4,
+                    rounds: int = 3) -> dict:
+        """raft_hip_graph_clean_device / _host (libraft_hip_cln.so): the edge list of a string graph (node u = 2 * read + end; what
+        ``string_graph`` returned as ``edge_u``, ``edge_w``, ``edge_span`` is one) without the edges that are weak beside the best one
+        at the same end (span * 1000 < ``min_ratio_permille`` * the end's greatest span) and without the dead-end chains of at most
+        ``max_tip_reads`` reads that hang beside something greater, removed over at most ``rounds`` rounds, under the rule of
+        include/raft_hip_cln.h.  -> per edge, in the caller's order, ``edge_state`` (uint8, ``CLN_WEAK_U | CLN_WEAK_W | CLN_TIP``; 0:
+        stays) and ``edge_round`` (uint8); per read ``read_state`` (uint8, ``CLN_READ_*``) and ``read_round``; per read end ``arcs``,
+        ``weak``, ``kept`` (int32 [n_reads, 2]); the table ``unitigs`` takes: ``partner``, ``span`` (int32 [n_reads, 2]) and ``flags``
+        (uint8 [n_reads], ``BEST_*``); ``summary`` (the counts of raft_hip_cln_summary), ``kernel_seconds`` and ``launches``.  The
+        arrays are torch tensors on this engine's device (int32; skip uint8) or numpy arrays (staged by the library).  A bad edge
+        raises RaftError(ERR_READ_ID) with the smallest such edge as its index.  Independent of any pass."""
+        cols = [read_len, edge_u, edge_w, edge_span]
+        if any(x is None for x in cols):
+            raise ValueError("graph_clean needs read_len, edge_u, edge_w and edge_span")
+        cln = load_side_library("cln")
+        on_device, cols, (skip,), _, n, n_edges = self._record_query("graph_clean", cols, read_u8={"skip": skip})
+        fn = cln.raft_hip_graph_clean_device if on_device else cln.raft_hip_graph_clean_host
+        if skip is not None and M.count(skip) != n:
+            raise ValueError("graph_clean: skip is one byte per read")
+        per_edge = {k: np.zeros(n_edges, np.uint8) for k in ("edge_state", "edge_round")}
+        per_read = {k: np.zeros(n, np.uint8) for k in ("read_state", "read_round")}
+        per_end = {k: np.zeros((n, 2), np.int32) for k in ("arcs", "weak", "kept", "partner", "span")}
+        flags = np.zeros(n, np.uint8)
+        sm, err, secs, launches = _ClnSummary(), C.c_int64(-1), C.c_double(0.0), C.c_int64(0)
+        rc = fn(self._ctx, n, M.ptr(cols[0]), M.ptr(skip), n_edges, M.ptr(cols[1]), M.ptr(cols[2]), M.ptr(cols[3]), int(min_ratio_permille),
+                int(max_tip_reads), int(rounds), *[M.ptr(a) for a in (*per_edge.values(), *per_read.values(), *per_end.values(), flags)],
+                C.byref(sm), C.byref(err), C.byref(secs), C.byref(launches))
+        self.last_graph_clean_seconds, self.last_graph_clean_launches = secs.value, launches.value
+        self._check(rc, err.value)
+        return {**per_edge, **per_read, **per_end, "flags": flags, "summary": _summary_dict(sm), "kernel_seconds": secs.value,
+                "launches": launches.value}
 
     # -- the overlaps between the fragments ------------------------------------------------------------------
     last_lift_overlaps_seconds = 0.0     # device time of the launches of the last lift_overlaps()

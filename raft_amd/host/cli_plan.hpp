@@ -345,6 +345,40 @@ inline std::string place_contained_line(int64_t unitigs, int64_t placed, int64_t
            ", greatest depth = " + std::to_string(greatest_permille) + " per mille";
 }
 
+// --graph-clean: the string graph of --string-graph without its weak edges and its tips (raft_hip_graph_clean_host), and the unitigs of
+// what is left.  --clean-min-ratio W: W (min_ratio_permille) is a whole number written in digits alone, 0 .. 1000; without the option it
+// is miniasm's lower overlap drop ratio.  --clean-tip-reads T: T (max_tip_reads) is a whole number >= 0 in digits alone, at most
+// INT32_MAX; without the option it is miniasm's max_ext.  --clean-rounds R: R (rounds) is a whole number in digits alone, 1 .. 64.
+constexpr int32_t kCleanMinRatioDefault = 500, kCleanTipReadsDefault = 4, kCleanRoundsDefault = 3, kCleanRoundsMax = 64;
+inline bool parse_clean_min_ratio(const char *text, int32_t *permille) { return parse_ends_min_ratio(text, permille); }
+inline bool parse_clean_tip_reads(const char *text, int32_t *reads) { return parse_low_cov(text, reads); }
+inline bool parse_clean_rounds(const char *text, int32_t *rounds)
+{
+    int32_t v = 0;
+    if (!parse_low_cov(text, &v) || v < 1 || v > kCleanRoundsMax) return false;
+    *rounds = v;
+    return true;
+}
+
+// ... the option's two stdout lines, behind every other option's, from raft_hip_cln_summary's counts and from raft_hip_utg_summary's
+inline std::string graph_clean_line(int32_t min_ratio, int32_t tip_reads, int64_t rounds_run, int32_t rounds, int64_t converged, int64_t edges,
+                                    int64_t weak_edges, int64_t tips, int64_t tip_reads_fallen, int64_t tip_bases, int64_t tip_edges, int64_t kept_edges,
+                                    int64_t ends_more, int64_t ends_dead, int64_t isolated_short)
+{
+    return "INFO, graph_clean(), min_ratio = " + std::to_string(min_ratio) + " per mille, tip_reads = " + std::to_string(tip_reads) + ", rounds = " +
+           std::to_string(rounds_run) + " of " + std::to_string(rounds) + ", converged = " + std::to_string(converged) + ", edges = " + std::to_string(edges) +
+           ", weak edges = " + std::to_string(weak_edges) + ", tips = " + std::to_string(tips) + ", tip reads = " + std::to_string(tip_reads_fallen) +
+           ", tip bases = " + std::to_string(tip_bases) + ", tip edges = " + std::to_string(tip_edges) + ", kept edges = " + std::to_string(kept_edges) +
+           ", ends that branch = " + std::to_string(ends_more) + ", dead ends = " + std::to_string(ends_dead) + ", short isolated chains = " +
+           std::to_string(isolated_short);
+}
+inline std::string graph_clean_unitigs_line(int64_t reads, int64_t skipped, int64_t unitigs, int64_t singletons, int64_t circular, int64_t longest_reads,
+                                            int64_t longest_length, int64_t total_length, int64_t n50)
+{
+    const std::string fields = unitigs_line(reads, skipped, unitigs, singletons, circular, longest_reads, longest_length, total_length, n50);
+    return "INFO, graph_clean_unitigs()" + fields.substr(std::string("INFO, unitigs()").size());
+}
+
 // --fragment-paf: PREFIX.fragments.paf, the job's overlaps lifted onto its fragments (raft_hip_lift_overlaps_host).
 // --fragment-paf-min L: L (min_len of that call) is a whole number >= 1 written in digits alone, at most INT32_MAX; without the option it is
 constexpr int32_t kFragmentPafMinDefault = 1;
@@ -375,6 +409,9 @@ struct Options {
     int32_t string_graph_fuzz = kStringGraphFuzzDefault;
     bool string_graph_fuzz_given = false;
     bool containment = false;
+    bool graph_clean = false;
+    int32_t clean_min_ratio = kCleanMinRatioDefault, clean_tip_reads = kCleanTipReadsDefault, clean_rounds = kCleanRoundsDefault;
+    bool clean_min_ratio_given = false, clean_tip_reads_given = false, clean_rounds_given = false;
 };
 
 // The long options, one row each: the text's parser (none: a flag, which takes no argument), the value it writes, and the flag
@@ -447,6 +484,17 @@ constexpr const LongOption &every_long_option(size_t k)
     return kLongOptionTables[t].rows[k];
 }
 
+// Those four tables are what every_long_option counts through, and that stays so: 17 rows.  kOpenLongOptions is the open table: the
+// next option is a row here, and nothing counts its rows.  The command line lays it behind the seventeen: getopt's row k is
+// every_long_option(k) below every_long_option_count() and kOpenLongOptions[k - every_long_option_count()] from there on.
+inline constexpr LongOption kOpenLongOptions[] = {
+    {"graph-clean", nullptr, nullptr, &Options::graph_clean},               // PREFIX.clean.tsv, .clean.string_graph.*, .clean.unitigs.*: --string-graph's graph without weak edges and tips
+    {"clean-min-ratio", parse_clean_min_ratio, &Options::clean_min_ratio, &Options::clean_min_ratio_given},   // W, in per mille of the end's best span
+    {"clean-tip-reads", parse_clean_tip_reads, &Options::clean_tip_reads, &Options::clean_tip_reads_given},   // T: the longest chain that can be a tip
+    {"clean-rounds", parse_clean_rounds, &Options::clean_rounds, &Options::clean_rounds_given},               // R: at most that many tip rounds
+};
+constexpr size_t kOpenLongOptionCount = sizeof(kOpenLongOptions) / sizeof(kOpenLongOptions[0]);
+
 // One long option as getopt found it (text: its argument, NULL for a flag).  false: the text is not what the option takes -- a
 // usage error, and the value is left alone.
 inline bool set_long_option(const LongOption &o, const char *text, Options *p)
@@ -459,12 +507,15 @@ inline bool set_long_option(const LongOption &o, const char *text, Options *p)
 // The options that mean nothing without another: --ends-min-ratio needs --overlap-ends; --best-overlaps needs it too (it takes its H
 // and F from it and its mask from that option's status bytes); --unitigs needs --best-overlaps, whose table it walks;
 // --fragment-paf-min needs --fragment-paf; --components needs --overlap-ends, whose H and F it classifies under, and so does
-// --string-graph; --string-graph-fuzz needs --string-graph; --containment needs --overlap-ends for the same reason.  false: a usage error.
+// --string-graph; --string-graph-fuzz needs --string-graph; --containment needs --overlap-ends for the same reason; --graph-clean needs
+// --string-graph, whose edge list it takes, and --clean-min-ratio, --clean-tip-reads and --clean-rounds need --graph-clean.
+// false: a usage error.
 inline bool usage_ok(const Options &o)
 {
     return (o.overlap_ends >= 0 || !o.ends_ratio_given) && (!o.best_overlaps || o.overlap_ends >= 0) && (!o.unitigs || o.best_overlaps) &&
            (o.fragment_paf || !o.fragment_paf_min_given) && (!o.components || o.overlap_ends >= 0) &&
-           (!o.string_graph || o.overlap_ends >= 0) && (o.string_graph || !o.string_graph_fuzz_given) && (!o.containment || o.overlap_ends >= 0);
+           (!o.string_graph || o.overlap_ends >= 0) && (o.string_graph || !o.string_graph_fuzz_given) && (!o.containment || o.overlap_ends >= 0) &&
+           (!o.graph_clean || o.string_graph) && (o.graph_clean || !(o.clean_min_ratio_given || o.clean_tip_reads_given || o.clean_rounds_given));
 }
 
 // What the options ask of the job between them, decided once (prepare: the group offsets and window records are made by the

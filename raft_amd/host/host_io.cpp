@@ -24,6 +24,7 @@
 #include "../../include/raft_host_cc.h"
 #include "../../include/raft_host_sg.h"
 #include "../../include/raft_host_ctn.h"
+#include "../../include/raft_host_cln.h"
 
 #include <emmintrin.h>
 #include <zlib.h>
@@ -1404,6 +1405,31 @@ int raft_host_write_string_graph(const char *prefix, const raft_host_reads *read
                              o.push_back('\t'); put_num(o, reads->lens[(size_t)i]);
                              for (int k = 0; k < 2; ++k) {
                                  o.push_back('\t'); put_num(o, arcs[2 * i + k]);
+                                 o.push_back('\t'); put_num(o, kept[2 * i + k]);
+                             }
+                             o.push_back('\n');
+                         });
+}
+
+// PREFIX.clean.tsv (include/raft_host_cln.h): one line per read.  A state outside the three or a negative count is refused before
+// anything is written.
+int raft_host_write_graph_clean(const char *path, const raft_host_reads *reads, const uint8_t *read_state, const uint8_t *read_round,
+                                const int32_t *weak, const int32_t *kept)
+{
+    if (!path || !reads) return RAFT_HOST_ERR_ARG;
+    const long long n = (long long)reads->lens.size();
+    if (n > 0 && (!read_state || !read_round || !weak || !kept)) return RAFT_HOST_ERR_ARG;
+    for (long long i = 0; i < n; ++i)
+        if (read_state[i] > 2 || weak[2 * i] < 0 || weak[2 * i + 1] < 0 || kept[2 * i] < 0 || kept[2 * i + 1] < 0) return RAFT_HOST_ERR_ARG;
+    static const char *const kState[3] = {"kept", "tip", "flagged"};
+    return write_ordered(path, n, 1 << 16, [](long long) { return 1LL; },
+                         [&](long long i, std::string &o) {
+                             o.append(reads->names.name((int32_t)i), reads->names.name_len((int32_t)i));
+                             o.push_back('\t'); put_num(o, reads->lens[(size_t)i]);
+                             o.push_back('\t'); o.append(kState[read_state[i]]);
+                             o.push_back('\t'); put_num(o, (int)read_round[i]);
+                             for (int k = 0; k < 2; ++k) {
+                                 o.push_back('\t'); put_num(o, weak[2 * i + k]);
                                  o.push_back('\t'); put_num(o, kept[2 * i + k]);
                              }
                              o.push_back('\n');

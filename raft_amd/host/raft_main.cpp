@@ -37,6 +37,8 @@
 #include "../../include/raft_host_sg.h"
 #include "../../include/raft_hip_ctn.h"
 #include "../../include/raft_host_ctn.h"
+#include "../../include/raft_hip_cln.h"
+#include "../../include/raft_host_cln.h"
 #include "../../include/raft_host.h"
 #include "cli_plan.hpp"
 
@@ -89,6 +91,9 @@ struct StringGraphOut { std::vector<int32_t> arcs, kept, u, w, span; std::vector
 struct ContainmentOut { std::vector<int32_t> parent, pos, span, root, root_pos, depth, children, tree_reads; std::vector<int64_t> tree_bases; std::vector<uint8_t> flags; raft_hip_ctn_summary sum{}; };
 // ... with --unitigs: per read the unitig, the start and the orientation; per unitig the reads, the bases and the depth
 struct PlaceOut { std::vector<int32_t> unitig, reads; std::vector<int64_t> start, bases, permille; std::vector<uint8_t> orient; raft_hip_place_summary sum{}; };
+// --graph-clean: per edge of string_graph()'s list the state, per read the state and the round, per read end the degrees before, the arcs the
+// weak cut took and the degrees after, the cleaned table; the live edges; the unitigs of the cleaned table
+struct GraphCleanOut { std::vector<uint8_t> edge_state, read_state, read_round, flags; std::vector<int32_t> arcs, weak, kept, partner, span, u, w, edge_span; raft_hip_cln_summary sum{}; UnitigOut utg; };
 struct LiftOut { std::vector<int32_t> col[6], src; std::vector<uint8_t> rev; raft_hip_lift_summary sum{}; };   // --fragment-paf: the eight columns of the lifted stream
 
 struct Job {
@@ -123,7 +128,7 @@ struct Job {
     std::vector<int32_t> qid_kept;                              // the query column as tokenised, where prepare_input writes over it (Request::keep_query_ids)
     // the optional outputs, in the order of kExtras
     FilterOut flt; ReadStatsOut rs; LowCovOut low; RepeatOverlapsOut ovl; FragmentOverlapsOut frag;
-    RepeatStatsOut rst; EndsOut ends; BestOut best; UnitigOut utg; ComponentsOut cc; StringGraphOut sg; ContainmentOut ctn; PlaceOut plc; LiftOut lift;
+    RepeatStatsOut rst; EndsOut ends; BestOut best; UnitigOut utg; ComponentsOut cc; StringGraphOut sg; ContainmentOut ctn; PlaceOut plc; LiftOut lift; GraphCleanOut cln;
     // the arrays everything comes back in (made and page-locked on out_prep)
     raft_cli::Capacities cap;
     std::vector<int64_t> cov_off, rep_off, frag_off;
@@ -232,14 +237,16 @@ void parse_options(Job &j, int argc, char *argv[])
 {
     Options &p = j.p;
     // (the short options and their quirks are the reference's; the long options are this program's own, the rows of cli_plan.hpp's
-    // list of tables, counted through by every_long_option(k): getopt_long returns 0 for them and says which row)
-    constexpr size_t n_long = raft_cli::every_long_option_count();
+    // list of tables, counted through by every_long_option(k), and behind them the rows of its open table: getopt_long returns 0 for
+    // them and says which row)
+    constexpr size_t n_every = raft_cli::every_long_option_count(), n_long = n_every + raft_cli::kOpenLongOptionCount;
     struct option long_options[n_long + 1] = {};
-    for (size_t k = 0; k < n_long; ++k) long_options[k] = {raft_cli::every_long_option(k).name, raft_cli::every_long_option(k).parse ? required_argument : no_argument, nullptr, 0};
+    for (size_t k = 0; k < n_every; ++k) long_options[k] = {raft_cli::every_long_option(k).name, raft_cli::every_long_option(k).parse ? required_argument : no_argument, nullptr, 0};
+    for (size_t k = n_every; k < n_long; ++k) long_options[k] = {raft_cli::kOpenLongOptions[k - n_every].name, raft_cli::kOpenLongOptions[k - n_every].parse ? required_argument : no_argument, nullptr, 0};
     int option, row = 0;
     while ((option = getopt_long(argc, argv, "r:e:m:l:i:p:f:v:o:", long_options, &row)) != -1) {
         switch (option) {
-        case 0: if (!raft_cli::set_long_option(raft_cli::every_long_option((size_t)row), optarg, &p)) print_help(p); break;
+        case 0: if (!raft_cli::set_long_option((size_t)row < n_every ? raft_cli::every_long_option((size_t)row) : raft_cli::kOpenLongOptions[(size_t)row - n_every], optarg, &p)) print_help(p); break;
         case 'r': p.reso = atoi(optarg); break;
         case 'e': p.auto_cov = strcmp(optarg, "auto") == 0; p.est_cov = p.auto_cov ? 0 : atoi(optarg); break;
         case 'm': p.cov_mul = std::stod(optarg); break;
@@ -789,6 +796,42 @@ void place_contained(Job &j)
     done(j, rc, bad_index, "place_contained");
 }
 
+// --graph-clean: string_graph()'s surviving edges without the weak ones and the tips (raft_hip_graph_clean_host), behind every other
+// option of the stream: on the first context, under the same mask of contained reads.  The live edges are kept for the writer.
+void graph_clean(Job &j)
+{
+    GraphCleanOut &o = j.cln;
+    const StringGraphOut &g = j.sg;
+    const size_t n = (size_t)j.n_reads, m = g.u.size();
+    o.edge_state.resize(m); o.read_state.resize(n); o.read_round.resize(n); o.flags.resize(n);
+    o.arcs.resize(2 * n); o.weak.resize(2 * n); o.kept.resize(2 * n); o.partner.resize(2 * n); o.span.resize(2 * n);
+    const std::vector<uint8_t> skip = contained_reads(j);
+    int64_t bad_index = -1;
+    const int rc = raft_hip_graph_clean_host(j.ctxs[0], j.n_reads, j.rl, skip.data(), (int64_t)m, g.u.data(), g.w.data(), g.span.data(), j.p.clean_min_ratio,
+                                             j.p.clean_tip_reads, j.p.clean_rounds, o.edge_state.data(), nullptr, o.read_state.data(), o.read_round.data(),
+                                             o.arcs.data(), o.weak.data(), o.kept.data(), o.partner.data(), o.span.data(), o.flags.data(), &o.sum, &bad_index,
+                                             nullptr, nullptr);
+    done(j, rc, bad_index, "graph_clean");
+    for (size_t e = 0; e < m; ++e)
+        if (o.edge_state[e] == 0) { o.u.push_back(g.u[e]); o.w.push_back(g.w[e]); o.edge_span.push_back(g.span[e]); }
+}
+
+// ... and the unitigs of the cleaned table (raft_hip_unitigs_host), directly behind graph_clean().
+void graph_clean_unitigs(Job &j)
+{
+    const GraphCleanOut &c = j.cln;
+    UnitigOut &o = j.cln.utg;
+    const size_t n = (size_t)j.n_reads;
+    o.unitig.resize(n); o.index.resize(n); o.order.resize(n); o.reads.resize(n);
+    o.offset.resize(n); o.off.resize(n + 1); o.length.resize(n);
+    o.orient.resize(n); o.circular.resize(n);
+    int64_t bad_index = -1;
+    const int rc = raft_hip_unitigs_host(j.ctxs[0], j.n_reads, j.rl, c.partner.data(), c.span.data(), c.flags.data(), o.unitig.data(), o.index.data(),
+                                         o.offset.data(), o.orient.data(), o.order.data(), o.off.data(), o.reads.data(), o.length.data(), o.circular.data(),
+                                         &o.sum, &bad_index, nullptr, nullptr);
+    done(j, rc, bad_index, "graph_clean_unitigs");
+}
+
 // hifiasm writes its PAF grouped by query (reference README.md:36-38): a symmetric stream of at most four runs sorted by
 // read id is handed over in its grouped form -- per run, where every read's records begin -- and the query column stays
 // on the host (a third of the upload); any other stream goes up as it is.
@@ -1098,6 +1141,35 @@ int write_fragment_paf(Job &j)
 }
 std::string line_fragment_paf(const Job &j) { const auto &s = j.lift.sum; return raft_cli::fragment_paf_line(j.p.fragment_paf_min, s.n_records, s.n_out, s.records_cut, s.records_none, s.pairs_dropped, s.most_per_record); }
 
+// PREFIX.clean.tsv, and the cleaned graph through string_graph's writer under the prefix PREFIX.clean: arcs the degrees before, kept after
+int write_graph_clean(Job &j)
+{
+    const GraphCleanOut &o = j.cln;
+    const int rc = raft_host_write_graph_clean((j.p.prefix + ".clean.tsv").c_str(), j.reads, o.read_state.data(), o.read_round.data(), o.weak.data(), o.kept.data());
+    if (rc != RAFT_HOST_OK) return rc;
+    return raft_host_write_string_graph((j.p.prefix + ".clean").c_str(), j.reads, o.arcs.data(), o.kept.data(), o.flags.data(), (int64_t)o.u.size(), o.u.data(),
+                                        o.w.data(), o.edge_span.data());
+}
+std::string line_graph_clean(const Job &j)
+{
+    const raft_hip_cln_summary &s = j.cln.sum;
+    return raft_cli::graph_clean_line(j.p.clean_min_ratio, j.p.clean_tip_reads, s.rounds_run, j.p.clean_rounds, s.converged, s.edges, s.weak_edges, s.tips,
+                                      s.tip_reads, s.tip_bases, s.tip_edges, s.kept_edges, s.ends_kept_more, s.ends_dead, s.isolated_short);
+}
+
+int write_graph_clean_unitigs(Job &j)
+{
+    const UnitigOut &o = j.cln.utg;
+    return raft_host_write_unitigs((j.p.prefix + ".clean").c_str(), j.reads, o.sum.unitigs, o.unitig.data(), o.index.data(), o.offset.data(), o.orient.data(),
+                                   o.order.data(), o.off.data(), o.reads.data(), o.length.data(), o.circular.data());
+}
+std::string line_graph_clean_unitigs(const Job &j)
+{
+    const raft_hip_utg_summary &s = j.cln.utg.sum;
+    return raft_cli::graph_clean_unitigs_line(s.reads_in, s.reads_skipped, s.unitigs, s.singletons, s.circular, s.longest_reads, s.longest_length,
+                                              s.total_length, raft_cli::unitig_n50(j.cln.utg.length.data(), s.unitigs));
+}
+
 std::string line_filter_overlaps(const Job &j) { const auto &s = j.flt.sum; return raft_cli::filter_overlaps_line(j.p.min_identity, j.p.min_overlap, s.n_records, s.n_kept, s.below_identity, s.below_span); }
 
 // The optional outputs, one row each, in the one order in which they run, are written and report on stdout.  name: that of the row's
@@ -1123,6 +1195,8 @@ const Extra kExtras[] = {
     {"containment", [](const Job &j) { return j.p.containment; }, Stage::stream, containment, write_containment, line_containment},
     {"place_contained", [](const Job &j) { return j.p.containment && j.p.unitigs; }, Stage::stream, place_contained, write_unitig_depth, line_place_contained},
     {"fragment_paf", [](const Job &j) { return j.p.fragment_paf; }, Stage::results, fragment_paf, write_fragment_paf, line_fragment_paf},
+    {"graph_clean", [](const Job &j) { return j.p.graph_clean; }, Stage::stream, graph_clean, write_graph_clean, line_graph_clean},
+    {"graph_clean_unitigs", [](const Job &j) { return j.p.graph_clean; }, Stage::stream, graph_clean_unitigs, write_graph_clean_unitigs, line_graph_clean_unitigs},
 };
 
 void run_extras(Job &j, Stage stage)

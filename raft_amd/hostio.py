@@ -103,6 +103,10 @@ CTN_ABI = {
     "raft_host_write_containment": (C.c_int, [_str, _vp] + [_vp] * 13),
     "raft_host_write_unitig_depth": (C.c_int, [_str, C.c_int64] + [_vp] * 5),
 }
+# ... and of include/raft_host_cln.h
+CLN_ABI = {
+    "raft_host_write_graph_clean": (C.c_int, [_str, _vp] + [_vp] * 4),
+}
 PAF_QUALITY, PAF_STRAND = 1, 2      # RAFT_HOST_PAF_*: the bits of ``columns``
 
 
@@ -122,7 +126,7 @@ def load_library():
         if not os.path.exists(_LIB_PATH):
             raise RuntimeError(f"{_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         lib = C.CDLL(_LIB_PATH)
-        for table in (ABI, LOW_ABI, OVL_ABI, FRAG_ABI, RST_ABI, FLT_ABI, END_ABI, BEST_ABI, UTG_ABI, LIFT_ABI, CC_ABI, SG_ABI, CTN_ABI):
+        for table in (ABI, LOW_ABI, OVL_ABI, FRAG_ABI, RST_ABI, FLT_ABI, END_ABI, BEST_ABI, UTG_ABI, LIFT_ABI, CC_ABI, SG_ABI, CTN_ABI, CLN_ABI):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -320,6 +324,18 @@ def write_containment(path: str, reads: Reads, res: dict, placed: dict | None = 
         raise ValueError("write_containment: every array is [n_reads]")
     rc = load_library().raft_host_write_containment(path.encode(), reads._h, *[ptr(a) for a in i32], ptr(flags), ptr(tree_reads), ptr(tree_bases),
                                                     *[ptr(a) for a in tail])
+    if rc != OK:
+        raise HostError(rc, path)
+
+
+def write_graph_clean(path: str, reads: Reads, res: dict):
+    """raft_host_write_graph_clean: PREFIX.clean.tsv from what ``Engine.graph_clean`` returned (``read_state``, ``read_round``,
+    ``weak``, ``kept``)."""
+    state, rnd = carray(res["read_state"], np.uint8), carray(res["read_round"], np.uint8)
+    weak, kept = carray(res["weak"], np.int32), carray(res["kept"], np.int32)
+    if state.size != reads.n or rnd.size != reads.n or weak.size != 2 * reads.n or kept.size != 2 * reads.n:
+        raise ValueError("write_graph_clean: read_state and read_round are [n_reads], weak and kept [2 * n_reads]")
+    rc = load_library().raft_host_write_graph_clean(path.encode(), reads._h, ptr(state), ptr(rnd), ptr(weak), ptr(kept))
     if rc != OK:
         raise HostError(rc, path)
 
